@@ -31,7 +31,12 @@ Other BASELINE configs (--workload), each printed as its own JSON line of the sa
                          State diff is folded into HBM as it is reported, the checkpoint uploaded
                          at cycle start; reports the cycle close latency after the last report
 
-The default run (resnet18-fedavg) also carries configs 1, 3, 4 and 5 as sub-lines (`config1` ...
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps, writes the last
+step's outputs if --dump-outputs DIR is given, and prints the line.  Everything else is behind
+--full: the cpu_baseline, the live PMC passes behind roofline.traffic, the end-to-end and
+report-time closes beside the default line, and the sub-lines below.
+
+With --full the default run (resnet18-fedavg) also carries configs 1, 3, 4 and 5 as sub-lines (`config1` ...
 `config5`), each a fresh child run with a bit-exact check, and -- at N > 1 -- the one-process group
 over the same GPUs (`group`).  The whole run keeps to one deadline (--budget-s, under the driver's
 600 s): every child gets at most what is left after the headline's reserve, a child that runs out
@@ -122,7 +127,18 @@ def parse():
     ap.add_argument("--headline-reserve-s", type=float, default=None,
                     help="seconds of the budget kept for the headline world (default 150 at N = 1: its "
                          "end-to-end and report-time closes and cpu_baseline; 120 at N > 1)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else this script measures: the cpu_baseline, the live "
+                         "rocprofv3 --pmc passes, the config lines, the one-process group line at N > 1 and the "
+                         "end-to-end / report-time closes (each still has its --no-... switch).  Without it a run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left its caller as DIR/<name>.npy "
+                         "(float32 / float64; at most 64 MB in all: a larger output as a sample seeded by --seed)")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_live_traffic = args.no_config_lines = args.no_group_line = args.no_e2e = True
+    return args
 
 
 def main_group(ctx, args):

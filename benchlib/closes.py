@@ -9,7 +9,7 @@ import time
 from benchlib.baseline import cpu_model, in_reference_allocator
 from benchlib.common import RESNET18_P, ROOT
 from benchlib.roofline import roofline_of
-from benchlib.world import record
+from benchlib.world import dump_outputs, record, state_params
 
 
 def run_mnist_state(ctx, args, eng):
@@ -62,6 +62,7 @@ def run_mnist_state(ctx, args, eng):
         new = agg.average_plan_diffs({}, ck_pb, d_pb, avg_plan, plan_key=plan_key)
     el = time.perf_counter() - t0
     st = eng.stats()
+    dump_outputs(ctx, args, {"new_checkpoint": state_params(new)})
     P = sum(int(np.prod(s)) for s in MNIST_SHAPES)
     value = 4 * 3 * P * args.steps / el / 1e9
     cfg = {"workload": "mnist-state: MNIST 784-392-10 (P=311,650), 3 clients, non-iterative hosted avg_plan (the "
@@ -116,6 +117,7 @@ def run_resnet18_state(ctx, args, eng, N):
         new = agg.average_plan_diffs({}, ck_pb, d_pb)
     el = time.perf_counter() - t0
     st = eng.stats()
+    dump_outputs(ctx, args, {"new_checkpoint": state_params(new)})
     P = RESNET18_P
     value = 4 * N * P * args.steps / el / 1e9
     cfg = {"workload": f"resnet18-state: ResNet-18 (62 tensors, P={P}) x {N} clients, State protobuf bytes in host "
@@ -165,9 +167,10 @@ def run_resnet18_secagg_state(ctx, args, eng, N, S):
     eng.reset_stats()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     el = time.perf_counter() - t0
     st = eng.stats()
+    dump_outputs(ctx, args, {"share_sum": last[0], "decoded": last[1]})
     value = 8 * S * N * P * args.steps / el / 1e9
     cfg = {"workload": f"resnet18-secagg-state: ResNet-18 (62 tensors, P={P}) x {N} clients x {S} parties of int64 "
                        "shares as State bytes (packed varint) in host memory -> HBM -> GPU varint decode -> Z_2^64 "
@@ -254,6 +257,7 @@ def run_resnet18_report(ctx, args, eng, N):
         new = cycle()
     el = time.perf_counter() - t0
     st = eng.stats()
+    dump_outputs(ctx, args, {"new_checkpoint": state_params(new)})
     P = RESNET18_P
     nrep = len(reporters)
     value = 4 * nrep * P * args.steps / el / 1e9

@@ -92,7 +92,7 @@ def group_line(args, limit_s: int = 240) -> dict:
     over RCCL (distinct devices) or peer copies."""
     import subprocess
 
-    cmd = [sys.executable, str(BENCH), "--group", "--gpus", str(args.gpus), "--workload",
+    cmd = [sys.executable, str(BENCH), "--full", "--group", "--gpus", str(args.gpus), "--workload",
            args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup), "--seed", str(args.seed),
            "--no-cpu-baseline", "--no-live-traffic"]
     if args.dry_run:
@@ -161,7 +161,7 @@ def config_line(args, key: str) -> dict:
     workload, gpus, steps_cap, cpu, limit_s = CONFIG_LINES[key]
     gpus = gpus or args.gpus
     steps = min(args.steps, steps_cap) if steps_cap else args.steps
-    cmd = [sys.executable, str(BENCH), "--gpus", str(gpus), "--workload", workload,
+    cmd = [sys.executable, str(BENCH), "--full", "--gpus", str(gpus), "--workload", workload,
            "--steps", str(steps), "--warmup", str(1 if steps_cap else args.warmup), "--seed", str(args.seed),
            "--no-live-traffic", "--no-group-line", "--no-config-lines", "--check",
            "--cpu-seconds", str(args.cpu_seconds)]

@@ -3,7 +3,7 @@ group: one step = one fold of every client diff of the shard (plus the exchange 
 from __future__ import annotations
 
 from benchlib.roofline import roofline_of
-from benchlib.world import check_resident, check_sampled, record, timed
+from benchlib.world import check_resident, check_sampled, dump_outputs, record, timed
 
 
 def run_resident(ctx, args, eng, mode, dtype, N, parties, pg, P, lo, hi):
@@ -49,9 +49,10 @@ def run_resident(ctx, args, eng, mode, dtype, N, parties, pg, P, lo, hi):
         diff_bytes, dt, kernel = 8 * parties * N * pg, "int64", "k_secagg"
     torch.cuda.synchronize()
     el, st = timed(ctx, step, args.steps, args.warmup, eng)
+    full = og.assemble() if ctx.world > 1 else (out if dtype == 0 else d_out)
+    dump_outputs(ctx, args, {"new_checkpoint": full} if dtype == 0 else {"share_sum": s_out, "decoded": full})
     checked = None
     if args.check:
-        full = og.assemble() if ctx.world > 1 else (out if dtype == 0 else d_out)
         checked = check_resident(ctx, args, full, mode, dtype, N, parties, lo, hi, s_out if dtype == 1 else None)
     value = diff_bytes * ctx.world * args.steps / el / 1e9
     cfg = {"workload": f"{args.workload}: P_shard={pg} params/GPU x {N} clients"
@@ -85,6 +86,7 @@ def run_secagg_clients(ctx, args, eng, N, S, P):
         og.assemble()
     torch.cuda.synchronize()
     el, st = timed(ctx, step, args.steps, args.warmup, eng)
+    dump_outputs(ctx, args, {"decoded": og.assemble()})
     diff_bytes = 8 * S * N * P
     value = diff_bytes * ctx.world * args.steps / el / 1e9
     cfg = {"workload": f"secagg-clients: {N} clients/GPU x {S} parties int64 x P={P} (ResNet-18) on every rank, "
@@ -126,6 +128,7 @@ def run_c4(ctx, args, eng, N, pg, P):
         if ctx.world > 1:
             full[0] = gather_flat(out, P, ctx.world, ctx.rank)
     el, st = timed(ctx, step, args.steps, args.warmup, eng)
+    dump_outputs(ctx, args, {"new_checkpoint": full[0]})
     checked = None
     if args.check:
         def expected(idx):
@@ -189,6 +192,7 @@ def run_c5(ctx, args, eng, N, pg, P):
         if ctx.world > 1:
             full[0] = gather_flat(out, P, ctx.world, ctx.rank)
     el, st = timed(ctx, step, args.steps, args.warmup, eng)
+    dump_outputs(ctx, args, {"new_checkpoint": full[0]})
     checked = None
     if args.check:
         lo = eng.lo
@@ -258,6 +262,8 @@ def run_group_resident(ctx, args, eng, mode, dtype, N, parties, Pg):
             eng.secagg(10, 3, out_sum=bufs[0].array, out_dec=bufs[1].array)
         diff_bytes, dt, kernel = 8 * parties * N * P, "int64", "k_secagg"
     el, st = timed(ctx, step, args.steps, args.warmup, eng)
+    dump_outputs(ctx, args, {"new_checkpoint": eng.ckpt_download()} if dtype == 0
+                 else {"share_sum": bufs[0].array, "decoded": bufs[1].array})
     value = diff_bytes * args.steps / el / 1e9
     cfg = {"workload": f"{args.workload}: P_shard={Pg} params/GPU x {N} clients"
                        + (f" x {parties} parties int64" if dtype == 1 else " fp32") + ", resident in HBM",
@@ -291,6 +297,7 @@ def run_group_secagg_clients(ctx, args, eng, N, S, P):
     def step():
         eng.secagg(10, 3, out_sum=bufs[0].array, out_dec=bufs[1].array)
     el, st = timed(ctx, step, args.steps, args.warmup, eng)
+    dump_outputs(ctx, args, {"share_sum": bufs[0].array, "decoded": bufs[1].array})
     value = 8 * S * N * G * P * args.steps / el / 1e9
     cfg = {"workload": f"secagg-clients: {N} clients/GPU x {S} parties int64 x P={P} (ResNet-18), clients sharded "
                        "over the GPUs of one process, resident in HBM",

@@ -110,6 +110,46 @@ def record(ctx, args, name, value, el, dt, config, roofline, extra=None, step_is
     return rec
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files of one run together
+
+
+def state_params(pb):
+    """The params of State bytes as one flat float32 vector (--dump-outputs of the bytes -> bytes lines)."""
+    import numpy as np
+
+    from pygrid_amd.state_schema import parse_state
+
+    return np.concatenate([np.asarray(a, np.float32).reshape(-1) for a in parse_state(pb)])
+
+
+def dump_outputs(ctx, args, outputs: dict):
+    """``--dump-outputs DIR``: what the last timed step left its caller, written by rank 0 after the
+    timed region as ``DIR/<name>.npy`` -- float32 as it is, every other type (the int64 Z_2^64
+    sums) as float64.  The files of one run share DUMP_LIMIT_BYTES equally; an output over its
+    share is written as a sample: the elements at ``np.unique(default_rng(--seed).integers(0,
+    size, share))`` of the flat array, in index order -- the same elements in every run with the
+    same arguments, so two builds compare file by file."""
+    if not args.dump_outputs or ctx.rank != 0:
+        return
+    from pathlib import Path
+
+    import numpy as np
+
+    out = Path(args.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(outputs), 1)
+    for name, a in outputs.items():
+        flat = a.reshape(-1)
+        f32 = str(a.dtype).endswith("float32")
+        k = share // (4 if f32 else 8)
+        if flat.shape[0] > k:
+            idx = np.unique(np.random.default_rng(args.seed).integers(0, flat.shape[0], k))
+            flat = flat[idx if isinstance(flat, np.ndarray) else ctx.torch.from_numpy(idx).to(flat.device)]
+        if not isinstance(flat, np.ndarray):
+            flat = flat.cpu().numpy()
+        np.save(out / f"{name}.npy", np.ascontiguousarray(flat, np.float32 if f32 else np.float64))
+
+
 def check_sampled(ctx, args, full, lo: int, hi: int, expected, against: str = None) -> dict:
     """``--check``: a checker leg outside the timed region (like cpu_baseline, the only other place
     this script runs the oracle).  Every rank takes its share of a strided 4,096-param sample of

@@ -56,7 +56,7 @@ def test_plain_bench_forms_two_ranks():
     """The per-rank world's line, with the one-process group over the same GPUs (what the node
     deploys) run after the ranks exit, in a fresh child, under `group`, and
     the config-4 / config-5 worlds over the same GPUs under `config4` / `config5`."""
-    r = _run(["--gpus", "2", "--dry-run"])
+    r = _run(["--gpus", "2", "--dry-run", "--full"])
     assert r.returncode == 0, r.stderr
     rec = _json_line(r.stdout)
     _has(rec, {"dry_run": True, "n_gpus": 2, "backend": "gloo", "dist_backend": "gloo", "rccl_ranks": 0})
@@ -88,11 +88,62 @@ def test_plain_bench_forms_three_ranks():
 
 
 def test_single_rank_dry_run():
-    r = _run(["--dry-run"])
+    r = _run(["--dry-run", "--full"])
     assert r.returncode == 0, r.stderr
     rec = _json_line(r.stdout)
     assert rec["n_gpus"] == 1
     _config_lines(rec, 1)
+
+
+def test_plain_run_carries_no_child_lines():
+    """Without --full a run is its timed steps only: no config lines, no group line, no CPU baseline
+    (the stub list is left empty, so a cpu_baseline child would really run and show in the stages)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PGH_BENCH_STUB")}
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--dry-run"], cwd=str(ROOT), env=env,
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr
+    rec = _json_line(r.stdout)
+    _has(rec, {"dry_run": True, "n_gpus": 2, "dist_backend": "gloo"})
+    assert not any(k in rec for k in ("config1", "config3", "config4", "config5", "cpu_baseline"))
+    assert not isinstance(rec["group"], dict)
+    assert set(rec["budget"]["stages_s"]) <= {"headline"}
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays float32, int64 goes to float64, an output over its share of the
+    64 MB is a seeded sample (the same elements on every run), and only rank 0 writes."""
+    import importlib
+    import types
+
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    importlib.import_module("bench")
+    world = importlib.import_module("benchlib.world")
+    ctx = types.SimpleNamespace(torch=torch, rank=0)
+    small = torch.arange(1000, dtype=torch.float32).reshape(10, 100) * 0.5
+    sums = np.arange(-500, 500, dtype=np.int64)
+    args = types.SimpleNamespace(dump_outputs=str(tmp_path / "a"), seed=7)
+    world.dump_outputs(ctx, args, {"new_checkpoint": small, "share_sum": sums})
+    got = np.load(tmp_path / "a" / "new_checkpoint.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy().reshape(-1))
+    got = np.load(tmp_path / "a" / "share_sum.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, sums.astype(np.float64))
+    # over the limit (shrunk for the test): a sample, identical from run to run, taken in index order
+    monkeypatch.setattr(world, "DUMP_LIMIT_BYTES", 2 * 400)
+    for d in ("b", "c"):
+        args.dump_outputs = str(tmp_path / d)
+        world.dump_outputs(ctx, args, {"new_checkpoint": small, "share_sum": sums})
+    b, c = (np.load(tmp_path / d / "new_checkpoint.npy") for d in ("b", "c"))
+    assert b.dtype == np.float32 and 0 < b.size <= 100 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.all(np.isin(b, small.numpy()))
+    s = np.load(tmp_path / "b" / "share_sum.npy")
+    assert s.dtype == np.float64 and 0 < s.size <= 50 and np.all(np.diff(s) > 0)
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "b").iterdir()) <= 2 * 400
+    args.dump_outputs = str(tmp_path / "d")
+    world.dump_outputs(types.SimpleNamespace(torch=torch, rank=1), args, {"new_checkpoint": small})
+    assert not (tmp_path / "d").exists()
 
 
 def test_launcher_world_mismatch_fails_loudly():
@@ -107,7 +158,7 @@ def test_torchrun_launch_forms_two_ranks():
     env = _env()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29517", str(ROOT / "bench.py"),
-                        "--gpus", "2", "--dry-run"], cwd=str(ROOT), env=env, capture_output=True, text=True,
+                        "--gpus", "2", "--dry-run", "--full"], cwd=str(ROOT), env=env, capture_output=True, text=True,
                        timeout=240)
     assert r.returncode == 0, r.stderr
     rec = _json_line(r.stdout)
@@ -198,7 +249,7 @@ def test_headline_printed_inside_the_budget_when_a_child_overruns():
     t0 = time.time()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                         "--master-addr", "127.0.0.1", "--master-port", "29531", str(ROOT / "bench.py"),
-                        "--gpus", "8", "--dry-run", "--budget-s", str(budget), "--headline-reserve-s", "35"],
+                        "--gpus", "8", "--dry-run", "--full", "--budget-s", str(budget), "--headline-reserve-s", "35"],
                        cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=240)
     wall = time.time() - t0
     assert r.returncode == 0, r.stderr[-3000:]
@@ -227,7 +278,7 @@ def test_watchdog_prints_the_headline_line_when_the_headline_cannot_finish():
 def test_spawned_ranks_line_survives_a_hung_headline():
     """Without a launcher: the parent (no GPU) runs the child lines, spawns the ranks, and prints
     rank 0's watchdog line with the child lines merged in."""
-    r = _run(["--gpus", "2", "--dry-run", "--budget-s", "50", "--headline-reserve-s", "25"],
+    r = _run(["--gpus", "2", "--dry-run", "--full", "--budget-s", "50", "--headline-reserve-s", "25"],
              {"PGH_BENCH_STUB": "config1=0,config4=0,config5=0,config3=0,group=0,headline=300"}, timeout=150)
     assert r.returncode != 0
     rec = _json_line(r.stdout)
@@ -245,8 +296,8 @@ def test_cpu_baseline_on_the_n8_line():
     env.pop("PGH_BENCH_STUB", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                         "--master-addr", "127.0.0.1", "--master-port", "29533", str(ROOT / "bench.py"),
-                        "--gpus", "8", "--dry-run", "--no-config-lines", "--no-group-line", "--params", "20000",
-                        "--cpu-seconds", "1"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=240)
+                        "--gpus", "8", "--dry-run", "--full", "--no-config-lines", "--no-group-line",
+                        "--params", "20000", "--cpu-seconds", "1"], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)
     assert rec["n_gpus"] == 8 and rec["dist_backend"] == "gloo"

@@ -17,7 +17,7 @@ for s in $steps; do
             || { cat "$out/smoke.log"; exit 1; }
         tail -2 "$out/smoke.log" ;;
     bench)
-        timeout -k 10 620 python -u bench.py ${BENCH_ARGS:-} > "$out/bench.json" 2> "$out/bench.log" \
+        timeout -k 10 620 python -u bench.py --full ${BENCH_ARGS:-} > "$out/bench.json" 2> "$out/bench.log" \
             || { tail -20 "$out/bench.log"; exit 1; }
         tail -c 600 "$out/bench.json" ;;
     esac

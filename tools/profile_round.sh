@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${1:-round}
 PART=${2:-tests}
 mkdir -p $OUT
-b() { local name=$1 t=$2; shift 2; timeout -k 10 $t python -u bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; exit 1; }; echo "bench $name ok"; }
+b() { local name=$1 t=$2; shift 2; timeout -k 10 $t python -u bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; exit 1; }; echo "bench $name ok"; }
 if [ "$PART" = tests ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread > $OUT/gpu_tests.log 2>&1
   rc=$?; echo "pytest rc=$rc"; tail -2 $OUT/gpu_tests.log; [ $rc -eq 0 ] || exit $rc
@@ -29,7 +29,7 @@ if [ "$PART" = tests ]; then
   PGH_BENCH_DEVICES=0,0 b group2dev0-fedavg 300 --group --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline --no-e2e
   timeout -k 10 200 python tools/bench_b64.py > $OUT/b64.log 2>&1 || exit $?
 else
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_trace_default.json 2> $OUT/bench_trace_default.err || exit $?
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_trace_default.json 2> $OUT/bench_trace_default.err || exit $?
   for w in resnet18-iterative resnet18-secagg resnet18-report; do
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace_$w -o run --output-format csv -- python3 bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_trace_$w.json 2> $OUT/bench_trace_$w.err || exit $?
   done

@@ -21,7 +21,7 @@ devs() { local d=0; for ((i = 1; i < $1; i++)); do d="$d,0"; done; echo "$d"; }
 ranks() {  # ranks() N port config_clients: the driver's torchrun launch with N ranks on GPU 0
     PGH_DIST_BACKEND=gloo PGH_BENCH_DEVICE=0 PGH_BENCH_DEVICES=$(devs "$1") run "torchrun$1" python -u -m torch.distributed.run \
         --nnodes=1 --nproc-per-node "$1" --master-addr 127.0.0.1 --master-port "$2" bench.py --gpus "$1" --steps 5 \
-        --warmup 2 --clients 300 --config-clients "$3"
+        --warmup 2 --clients 300 --config-clients "$3" --full
 }
 if want group1; then run group1 python -u bench.py --group --gpus 1 --no-cpu-baseline --steps 10 --no-e2e || exit 1; fi
 if want group2_dev0; then
@@ -35,5 +35,5 @@ if want torchrun4; then ranks 4 29543 100 || exit 1; fi
 if want torchrun8; then ranks 8 29545 64 || exit 1; fi
 if want spawn8; then
     PGH_DIST_BACKEND=gloo PGH_BENCH_DEVICE=0 PGH_BENCH_DEVICES=$(devs 8) run spawn8 python -u bench.py --gpus 8 --steps 5 \
-        --warmup 2 --clients 300 --config-clients 64 || exit 1
+        --warmup 2 --clients 300 --config-clients 64 --full || exit 1
 fi
