@@ -45,8 +45,11 @@ typedef enum {
 /* Averaging mode.  PGH_MEAN: hard-coded path, cycle_manager.py:276-288.
  * PGH_ITERATIVE_MEAN: hosted iterative avg_plan, cycle_manager.py:266-269 with the plan of
  * examples/model-centric/01-Create-plan.ipynb:450-454.  PGH_WEIGHTED_MEAN: north_star's
- * weighted FedAvg (no reference counterpart; equals PGH_MEAN bit for bit at w == 1). */
-typedef enum { PGH_MEAN = 0, PGH_ITERATIVE_MEAN = 1, PGH_WEIGHTED_MEAN = 2 } pgh_mode;
+ * weighted FedAvg (no reference counterpart; equals PGH_MEAN bit for bit at w == 1).
+ * PGH_CLIPPED_MEAN: the mean of the diffs after each is scaled down to an L2 norm of at most the
+ * bound of pgh_set_clip_norm (norm-bounded FedAvg; no reference counterpart; equals PGH_MEAN bit for
+ * bit when no diff exceeds the bound). */
+typedef enum { PGH_MEAN = 0, PGH_ITERATIVE_MEAN = 1, PGH_WEIGHTED_MEAN = 2, PGH_CLIPPED_MEAN = 3 } pgh_mode;
 /* Stream kind for pgh_stream_begin besides the three averaging modes. */
 #define PGH_STREAM_SECAGG 16
 
@@ -172,6 +175,34 @@ int pgh_set_synth_kind(pgh_ctx* ctx, int kind);
 int pgh_synth_ingest(pgh_ctx* ctx, uint64_t seed, int client0, int n);
 /* Per-client weights for PGH_WEIGHTED_MEAN (n == clients ingested at reduction time). */
 int pgh_set_weights(pgh_ctx* ctx, const float* w, int n);
+
+/* ---- per-client L2 clipping (PGH_CLIPPED_MEAN) -----------------------------------------------
+ * out = ckpt - (sum_c s_c * d_c) / float(N), s_c = 1 when ||d_c|| <= C, else (float)(C / ||d_c||):
+ * each product rounded to f32, then added, in fold order (the weighted fold with the scales as
+ * weights and the divisor N).  ||d_c|| = sqrt(sumsq_c) in f64; sumsq_c is accumulated in f64 in ONE
+ * fixed order (tiles of 4,096 params, 256 lane partials, a shuffle tree per
+ * wave, the four wave sums left to right, the tile partials left to right), so results are
+ * bit-reproducible whatever the launch shape, slot or slab block width.  Non-finite diffs are not
+ * sanitised: a NaN norm gives a NaN scale, an infinite norm the scale 0, and the fold follows IEEE.
+ *
+ * c > 0 (finite) turns clipping on for later ingests and folds of this context, 0 turns it off.
+ * With clipping on, every ingest queues the row's norm pass behind its copy, and a fold in
+ * PGH_CLIPPED_MEAN computes the sums still missing in one batch, waits for them, and runs the
+ * weighted kernels; pgh_set_weights is not used.  PGH_CLIPPED_MEAN with clipping off is
+ * PGH_E_STATE.  PGH_E_UNSUPPORTED on a group context, a context whose shard is narrower than the
+ * layout (the norm needs the whole row), an int64 slab and a streaming context; pgh_stream_begin
+ * refuses PGH_CLIPPED_MEAN the same way. */
+int pgh_set_clip_norm(pgh_ctx* ctx, float c);
+/* Sums of squares (f64, the order above) of the diffs held by the n listed occupied slots (fp32
+ * RESIDENT slab of one GPU): computes the ones not cached since the slot's last ingest.  out
+ * non-NULL: waits and returns them (n doubles).  out NULL: only queues the work on the GPU. */
+int pgh_row_sumsq(pgh_ctx* ctx, const int32_t* slots, int n, double* out);
+/* The scale expression above, on the host (needs no GPU, ctx-free). */
+int pgh_clip_scale(double sumsq, float c, float* scale);
+/* Over the rows folded in PGH_CLIPPED_MEAN since the last pgh_reset / pgh_reserve (a row counts once
+ * per computation of its scale; pgh_fold_slots_restart drops the restarted rows): how many, how many
+ * got a scale other than 1, and the largest norm (NaN if any was NaN).  Each pointer may be NULL. */
+int pgh_clip_stats(pgh_ctx* ctx, int64_t* n_rows, int64_t* n_clipped, double* max_norm);
 
 /* ---- reduction ----------------------------------------------------------------------------
  * out = ckpt - avg(diffs), over this context's shard.  Host pointers, P_shard floats each. */

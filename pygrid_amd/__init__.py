@@ -15,9 +15,10 @@ Importing the package changes nothing in the host process; ``tune_process()`` is
 opt-in for the process-wide settings the engine benefits from (HIP hardware queues, glibc
 thresholds for 47 MB buffers).
 """
-from .exceptions import (AggregationError, EngineUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError,
-                         PyGridError, StateParseError)
-from .engine import F32, I64, ITERATIVE_MEAN, MEAN, STREAM_SECAGG, WEIGHTED_MEAN, Engine, PinnedBuffer, device_count
+from .exceptions import (AggregationError, ClipUnavailableError, EngineUnavailableError, ModelNotAcceleratedError,
+                         PlanNotAcceleratedError, PyGridError, StateParseError)
+from .engine import (CLIPPED_MEAN, F32, I64, ITERATIVE_MEAN, MEAN, STREAM_SECAGG, WEIGHTED_MEAN, Engine, PinnedBuffer,
+                     device_count)
 
 
 def tune_process(hw_queues: bool = True, malloc: bool = True) -> dict:
@@ -36,9 +37,9 @@ def tune_process(hw_queues: bool = True, malloc: bool = True) -> dict:
 
 
 __all__ = [
-    "AggregationError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
+    "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
     "StateParseError",
-    "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "F32", "I64",
+    "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "F32", "I64",
     "tune_process",
 ]
 __version__ = "0.3.0"

@@ -100,6 +100,10 @@ SIGNATURES = {
     "pgh_synth_fill": (_i, [_vp, _u64, _i]),
     "pgh_synth_ingest": (_i, [_vp, _u64, _i, _i]),
     "pgh_set_weights": (_i, [_vp, C.POINTER(C.c_float), _i]),
+    "pgh_set_clip_norm": (_i, [_vp, C.c_float]),
+    "pgh_row_sumsq": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
+    "pgh_clip_scale": (_i, [C.c_double, C.c_float, C.POINTER(C.c_float)]),
+    "pgh_clip_stats": (_i, [_vp, _P64, _P64, C.POINTER(C.c_double)]),
     "pgh_fedavg": (_i, [_vp, _i, _vp, _vp]),
     "pgh_fedavg_device": (_i, [_vp, _i, _vp, _vp, _vp]),
     "pgh_fedavg_device_range": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp]),

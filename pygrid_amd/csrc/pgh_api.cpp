@@ -133,6 +133,7 @@ void free_slab(pgh_ctx* c) {
     (void)hipFree(c->d_sum); c->d_sum = nullptr;
     (void)hipFree(c->d_dec); c->d_dec = nullptr;
     (void)hipFree(c->d_w); c->d_w = nullptr; c->w_cap = 0;
+    free_clip(c);
     c->slots = 0;
     c->slot_mode = -1;
     c->slot_client.clear();
@@ -867,6 +868,11 @@ float weight_total(const std::vector<float>& w, int64_t n) {  // left fold, floa
 // Fold slots holding clients [c0, c0 + n) (slot order may wrap) into the running state.
 // FIRST when c0 == 0; FINAL writes out (fedavg: ckpt - avg; secagg: sum/dec) instead of the state.
 int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const FinalArgs& fa, hipStream_t s) {
+    if (kind == PGH_CLIPPED_MEAN) {  // resident only: the weighted fold over the scales of clients [0, n)
+        if (c0 != 0 || !final) return fail(c, PGH_E_UNSUPPORTED, "a clipped mean folds a resident slab in one pass");
+        RC(resident_clip_scales(c, n));
+        kind = PGH_WEIGHTED_MEAN;
+    }
     RC(order_after_ingest(c, s));
     if (kind == PGH_WEIGHTED_MEAN && n > 0) {
         if ((int64_t)c->weights.size() < c0 + n)
@@ -968,6 +974,8 @@ int claim_slot(pgh_ctx* c, int64_t client, int* slot_out) {
         if (client >= c->slots)
             return fail(c, PGH_E_ARG, "client %lld outside slab capacity %d", (long long)client, c->slots);
         RC(order_slot_overwrite(c, (int)client));  // a fold issued earlier may still read the slot
+        c->sq_state[(size_t)client] = pgh_ctx::SQ_NONE;  // the cached sum of squares was the old diff's
+        c->clip_scales_valid = false;
         *slot_out = (int)client;
         return PGH_OK;
     }
@@ -1298,6 +1306,7 @@ void pgh_destroy(pgh_ctx* c) {
     for (auto e : c->rmark_pool) (void)hipEventDestroy(e);
     for (auto e : c->d2h_ev) (void)hipEventDestroy(e);
     for (auto e : c->rng_ev) (void)hipEventDestroy(e);
+    if (c->sq_ev) (void)hipEventDestroy(c->sq_ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->copy) (void)hipStreamDestroy(c->copy);
     if (c->aux) (void)hipStreamDestroy(c->aux);
@@ -1334,6 +1343,7 @@ int pgh_set_shard(pgh_ctx* c, int64_t lo, int64_t hi) {
     c->hi = hi;
     c->pg = hi - lo;
     c->pvec = std::max((c->pg + 63) & ~(int64_t)63, (c->vec_min + 63) & ~(int64_t)63);
+    if (c->pg != c->P) c->clip_c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
     c->st.p_shard = c->pg;
     return PGH_OK;
 }
@@ -1375,6 +1385,8 @@ int pgh_reserve(pgh_ctx* c, int max_clients, int dtype, int n_parties) {
     c->parties = n_parties;
     c->slot_client.assign((size_t)max_clients, -1);
     c->slot_read_seq.assign((size_t)max_clients, 0);
+    c->sq_state.assign((size_t)max_clients, (uint8_t)pgh_ctx::SQ_NONE);
+    c->sq_host.assign((size_t)max_clients, 0.0);
     c->weights.clear();
     c->weights_on_device = false;
     c->st.max_clients = max_clients;
@@ -1394,6 +1406,7 @@ int pgh_reset(pgh_ctx* c) {
     clear_marks(c);
     release_slot_fold_events(c);  // c->stream is idle (synchronised above)
     std::fill(c->slot_client.begin(), c->slot_client.end(), -1);
+    sumsq_forget(c);
     c->weights.clear();
     c->weights_on_device = false;
     c->streaming = false;
@@ -1421,7 +1434,7 @@ int pgh_effective_variant(pgh_ctx* c, int mode) {
     if (c->variant >= 0) return c->variant;
     if (mode == PGH_STREAM_SECAGG) return 14;  // SECAGG_AUTO_VARIANT in pgh_kernels.hip
     if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
-    return pgh::auto_variant(c->pg, mode);
+    return pgh::auto_variant(c->pg, kernel_mode(mode));
 }
 
 int pgh_stats(pgh_ctx* c, pgh_stats_t* out) {

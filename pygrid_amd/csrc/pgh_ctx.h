@@ -35,7 +35,10 @@
 
 namespace pgh_detail {
 
-constexpr int KIND_SECAGG = 3;  // stream kind besides the three fedavg modes
+constexpr int KIND_SECAGG = PGH_STREAM_SECAGG;  // fold kind besides the pgh_mode values (none of which it equals)
+static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KIND_SECAGG != PGH_WEIGHTED_MEAN &&
+                  KIND_SECAGG != PGH_CLIPPED_MEAN,
+              "the secagg fold kind must not collide with an averaging mode");
 
 // memcpy with non-temporal 16-byte stores for big copies into staging / output buffers (no
 // read-for-ownership of the destination, which is written once and then read by the DMA engine or
@@ -332,6 +335,27 @@ struct pgh_ctx {
     std::vector<float> weights;
     bool weights_on_device = false;
 
+    // Clipped FedAvg (pgh_set_clip_norm, PGH_CLIPPED_MEAN).  K7 (k_row_sumsq)
+    // runs on the copy stream -- behind the row's ingest, ahead of any later overwrite of the slot --
+    // and its sum comes back through h_sq in a small D2H on the same stream, followed by sq_ev.
+    // sq_state: NONE (no sum of the slot's present diff), QUEUED (K7 + D2H issued, value lands in
+    // h_sq before the latest sq_ev), VALID (sq_host holds it).  Any ingest into a slot resets it.
+    enum : uint8_t { SQ_NONE = 0, SQ_QUEUED = 1, SQ_VALID = 2 };
+    float clip_c = 0.f;               // the L2 bound; 0 = clipping off
+    std::vector<uint8_t> sq_state;    // per slot
+    std::vector<double> sq_host;      // per slot: the cached sum of squares
+    std::vector<int32_t> sq_queued;   // slots that went QUEUED since the last harvest
+    double* d_sq_part = nullptr;      // [slots][ceil(pg / SUMSQ_TILE)] tile partials
+    double* d_sq = nullptr;           // [slots]
+    double* h_sq = nullptr;           // pinned [slots]
+    hipEvent_t sq_ev = nullptr;
+    // the scales live in `weights` (fold order) and go to the device like weights.  Resident folds:
+    // clip_scales_valid says weights[0, n) are the scales of the slab as it is (range folds reuse them).
+    bool clip_scales_valid = false;
+    std::vector<double> clip_norms;   // slot folds of the running cycle, in fold order (beside weights)
+    int64_t clip_rows = 0, clip_clipped = 0;  // folds finished since pgh_reset / pgh_reserve
+    double clip_max_norm = 0.0;
+
     bool streaming = false;
     int slot_mode = -1;  // pgh_fold_slots: averaging mode of the cycle being folded slot by slot
     int kind = 0;
@@ -383,7 +407,13 @@ double now_ms();
 
 // ---- state checks and slab geometry -------------------------------------------------------------
 inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
-inline bool valid_mode(int m) { return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN; }
+inline bool valid_mode(int m) {
+    return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN;
+}
+// The kernels' mode: a clipped mean is the weighted fold with the scales as weights.
+inline int kernel_mode(int m) { return m == PGH_CLIPPED_MEAN ? PGH_WEIGHTED_MEAN : m; }
+// valid_mode, and PGH_CLIPPED_MEAN only with a bound set (PGH_E_STATE otherwise)
+int check_mode(pgh_ctx* c, int mode);
 int check_ready(pgh_ctx* c);
 int check_dtype(pgh_ctx* c, int dtype);
 int check_ckpt(pgh_ctx* c, const char* what);
@@ -502,6 +532,21 @@ int sync_weights(pgh_ctx* c, hipStream_t s);
 int ensure_recips(pgh_ctx* c, int64_t n, hipStream_t s);
 int fixed_point_divisor(pgh_ctx* c, int base, int prec, float* div);
 int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div);
+
+// ---- clipped FedAvg (pgh_reduce.cpp) ---------------------------------------------------------------
+inline bool clip_on(const pgh_ctx* c) { return c->clip_c > 0.f && c->dtype == PGH_F32 && !c->streaming; }
+// scale = norm <= C ? 1 : (float)(C / norm), norm = sqrt(sumsq) in f64 (IEEE: NaN -> NaN, inf -> 0)
+float clip_scale_of(double sumsq, float c);
+void sumsq_forget(pgh_ctx* c);             // every slot back to SQ_NONE (pgh_reset / pgh_reserve)
+void free_clip(pgh_ctx* c);                // the device / pinned buffers (free_slab)
+// K7 on the copy stream for those of `slots` that have no sum yet, and the D2H of the sums
+int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n);
+int sumsq_wait(pgh_ctx* c);                // the queued sums are in sq_host afterwards
+int sumsq_after_ingest(pgh_ctx* c, int slot);  // clipping on: queue the row's K7 behind its copy
+// weights[c0 + k] = the scale of slots[k] (waits for the sums); norms (nullable) receives sqrt(sumsq)
+int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms);
+int resident_clip_scales(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n)
+void clip_count(pgh_ctx* c, const float* scales, const double* norms, int64_t n);  // into the finished totals
 
 // What a FINAL fold pass writes (fedavg: ckpt - avg; secagg: sum/dec) and over which param range.
 struct FinalArgs {

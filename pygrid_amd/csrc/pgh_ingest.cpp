@@ -28,6 +28,7 @@ int pgh_ingest_raw(pgh_ctx* c, int client, const void* flat, size_t nbytes, int 
     const size_t first = nbytes == whole ? (size_t)c->lo : 0;
     for (int s = 0; s < c->parties; ++s)
         RC(stage_h2d(c, row_dest(c, slot, s), src + ((size_t)s * row_elems + first) * es, (size_t)c->pg * es, pinned));
+    RC(sumsq_after_ingest(c, slot));
     return mark_ingested(c, client, slot);
 }
 
@@ -61,6 +62,7 @@ int pgh_ingest_state(pgh_ctx* c, int client, const uint8_t* pb, size_t n) {
         const double t0 = now_ms();
         RC(pinned_gather_ingest(c, pb, pieces, slot, ranged));
         c->st.h2d_ms_total += now_ms() - t0;
+        RC(sumsq_after_ingest(c, slot));
         return mark_ingested(c, client, slot);
     }
     if (n && is_pinned(pb)) {
@@ -76,6 +78,7 @@ int pgh_ingest_state(pgh_ctx* c, int client, const uint8_t* pb, size_t n) {
         CK(c, hipStreamSynchronize(c->copy));
         c->st.h2d_ms_total += now_ms() - t0;
         c->st.h2d_bytes_total += off;
+        RC(sumsq_after_ingest(c, slot));
         return mark_ingested(c, client, slot);
     }
     size_t total = 0;
@@ -84,6 +87,7 @@ int pgh_ingest_state(pgh_ctx* c, int client, const uint8_t* pb, size_t n) {
         RC(stage_pieces_h2d_ranged(c, row_dest(c, slot, 0), pieces, total));
     else
         RC(stage_pieces_h2d(c, row_dest(c, slot, 0), pieces));
+    RC(sumsq_after_ingest(c, slot));
     return mark_ingested(c, client, slot);
 }
 
@@ -438,6 +442,7 @@ int pgh_synth_ingest(pgh_ctx* c, uint64_t seed, int client0, int n) {
         for (int j = 0; j < run; ++j) {
             if (c->slot_client[(size_t)(slot + j)] != client + j) c->st.n_clients += 1;
             c->slot_client[(size_t)(slot + j)] = client + j;
+            c->sq_state[(size_t)(slot + j)] = pgh_ctx::SQ_NONE;  // a clipped fold sums these rows in one batch
         }
         if (c->streaming) RC(maybe_fold(c, false));
         k += run;
@@ -505,6 +510,7 @@ int pgh_set_weights(pgh_ctx* c, const float* w, int n) {
     }
     c->weights.assign(w, w + n);
     c->weights_on_device = false;
+    c->clip_scales_valid = false;
     return PGH_OK;
 }
 

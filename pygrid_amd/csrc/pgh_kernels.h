@@ -124,6 +124,25 @@ struct GChunk {
 hipError_t launch_gather_f32(const uint8_t* bytes, const GChunk* chunks, int n_chunks, float* row, const SlabMap& m,
                              hipStream_t s);
 
+// K7: per-row sum of squares in f64, in the fixed order of DESIGN.md "Clipped FedAvg": tiles of
+// SUMSQ_TILE params, 256 lane partials per tile (lane l adds the squares of its four 16-byte columns
+// 4(l + 256j) .. + 3, j = 0 .. 3, in index order), a shuffle tree per wave, ((w0 + w1) + w2) + w3,
+// then a left fold of the row's tile partials.  Params at or past p count as +0.0.  The launch
+// covers n_rows slab rows (row0 .. row0 + n_rows - 1, or tab->rows[0 .. n_rows) with tab set;
+// n_rows <= ROWTAB_MAX then), writes part[row * ntiles + t] and then sumsq[row] (row = slab row).
+constexpr int SUMSQ_TILE = 4096;
+struct SumsqArgs {
+    const float* slab;   // the slab at row 0
+    SlabMap map;         // map.off = 0
+    int64_t p;           // params in the shard
+    int64_t ntiles;      // ceil(p / SUMSQ_TILE)
+    int row0;
+    int n_rows;
+    double* part;        // [slab rows][ntiles]
+    double* sumsq;       // [slab rows]
+};
+hipError_t launch_row_sumsq(const SumsqArgs& a, const RowTab* tab, hipStream_t s);
+
 constexpr uint64_t STREAM_DIFF = 0, STREAM_CKPT = 1, STREAM_SECRET = 2, STREAM_SHARE = 3;
 constexpr float DIFF_SCALE = 2.6429e-7f;
 constexpr float CKPT_SCALE = 1.32145e-6f;

@@ -7,6 +7,8 @@
 //       restates cycle_manager.py:266-269 + 01-Create-plan.ipynb:450-454
 // K3  k_secagg                 Z_2^64 wrap-sum over [clients*parties][P] int64 + fixed-point
 //       decode float32(int64)/10^prec (PySyft 0.2.9 semantics)
+// K7  k_row_sumsq              sumsq_c = sum_i (double)d_c[i]^2 along a client's row, in one fixed
+//       order (build-owned: the norms of PGH_CLIPPED_MEAN)
 //
 // Design (DESIGN.md "Kernels"): every kernel is a single streaming pass over the slab held in
 // HBM, column-blocked (SlabMap in pgh_kernels.h: blocks of ld columns, each block all rows,
@@ -711,6 +713,90 @@ __global__ __launch_bounds__(256) void k_varint_decode(const uint8_t* bytes, con
     }
 }
 
+// K7: sums of squares along slab rows (the clipping norm), the one reduction here that runs along
+// a client's row instead of down a param column.  One workgroup per tile of SUMSQ_TILE params and
+// group of RB rows: every lane issues its four 16-byte columns of all RB rows (4 RB non-temporal
+// loads in flight) before it squares any, then each row is reduced on its own in the fixed order of
+// pgh_kernels.h (lane partial -> shuffle tree per wave -> four wave sums through LDS).  The squares
+// are exact in f64, so the fma below is the rounded add of the definition.  Addresses past the
+// shard clamp to its last column and are masked to +0.0 (the slab's padding columns hold stale
+// bytes); a launch's last row group repeats its last row instead of branching around the loads.
+constexpr int SUMSQ_RB = 4;
+
+template <bool IDX>
+__device__ __forceinline__ void row_sumsq_tile(const SumsqArgs& a, const RowTab* tab) {
+    __shared__ double wsum[SUMSQ_RB][4];
+    const int lane = threadIdx.x, wave = lane >> 6;
+    const int64_t t = blockIdx.x, base = t * SUMSQ_TILE;
+    const int r0 = (int)blockIdx.y * SUMSQ_RB;
+    const int nr = min(SUMSQ_RB, a.n_rows - r0);
+    const bool full = base + SUMSQ_TILE <= a.p;
+    const int64_t last4 = (a.p - 1) & ~int64_t(3);
+    int64_t idx[4], off[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        idx[j] = base + 4 * (lane + BLOCK * j);
+        off[j] = a.map.at(full ? idx[j] : min(idx[j], last4));
+    }
+    size_t row[SUMSQ_RB];
+#pragma unroll
+    for (int rr = 0; rr < SUMSQ_RB; ++rr) {
+        const int r = r0 + min(rr, nr - 1);
+        row[rr] = IDX ? (size_t)(uint32_t)tab->rows[r] : (size_t)(a.row0 + r);
+    }
+    f32x4 v[SUMSQ_RB][4];
+#pragma unroll
+    for (int rr = 0; rr < SUMSQ_RB; ++rr)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[rr][j] = ld4<true>(a.slab + row[rr] * (size_t)a.map.ld + off[j]);
+#pragma unroll
+    for (int rr = 0; rr < SUMSQ_RB; ++rr) {
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double x = (full || idx[j] + e < a.p) ? (double)v[rr][j][e] : 0.0;
+                acc = __builtin_fma(x, x, acc);
+            }
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) acc += __shfl_down(acc, h, 64);
+        if ((lane & 63) == 0) wsum[rr][wave] = acc;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < SUMSQ_RB; ++rr)
+        if (lane == rr && rr < nr)
+            a.part[row[rr] * (size_t)a.ntiles + (size_t)t] = ((wsum[rr][0] + wsum[rr][1]) + wsum[rr][2]) + wsum[rr][3];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq(SumsqArgs a) { row_sumsq_tile<false>(a, nullptr); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_rows(SumsqArgs a, RowTab tab) { row_sumsq_tile<true>(a, &tab); }
+
+// The row's tile partials, left-folded in ascending tile order by one lane; the workgroup brings
+// them into LDS 1,024 at a time (coalesced) so the serial chain reads LDS, not HBM.
+constexpr int SUMSQ_FOLD_CHUNK = 4 * BLOCK;
+
+template <bool IDX>
+__device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const RowTab* tab) {
+    __shared__ double buf[SUMSQ_FOLD_CHUNK];
+    const size_t row = IDX ? (size_t)(uint32_t)tab->rows[blockIdx.x] : (size_t)(a.row0 + (int)blockIdx.x);
+    const double* part = a.part + row * (size_t)a.ntiles;
+    double acc = 0.0;  // + 0.0 + partial 0 is partial 0 (partials are never -0.0)
+    for (int64_t c0 = 0; c0 < a.ntiles; c0 += SUMSQ_FOLD_CHUNK) {
+        const int m = (int)min((int64_t)SUMSQ_FOLD_CHUNK, a.ntiles - c0);
+        for (int k = threadIdx.x; k < m; k += BLOCK) buf[k] = part[c0 + k];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < m; ++k) acc += buf[k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.sumsq[row] = acc;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold(SumsqArgs a) { row_sumsq_fold<false>(a, nullptr); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold_rows(SumsqArgs a, RowTab tab) { row_sumsq_fold<true>(a, &tab); }
+
 int cu_count() {
     static int cached[64] = {0};
     int dev = 0;
@@ -1023,6 +1109,32 @@ hipError_t launch_secagg_decode(const int64_t* sum, float* dec, int64_t n, float
     if (g > 8192) g = 8192;
     k_secagg_decode<<<(unsigned)g, BLOCK, 0, s>>>(sum, dec, n, divisor);
     return hipGetLastError();
+}
+
+hipError_t launch_row_sumsq(const SumsqArgs& a, const RowTab* tab, hipStream_t s) {
+    if (a.p <= 0 || a.n_rows < 0 || a.row0 < 0 || a.map.off != 0 || !valid_map(a.map, a.p) ||
+        a.ntiles != (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE || a.ntiles > 0x7fffffff)
+        return hipErrorInvalidValue;
+    if (a.n_rows == 0) return hipSuccess;
+    if (!a.slab || !a.part || !a.sumsq || (reinterpret_cast<uintptr_t>(a.slab) & 15)) return hipErrorInvalidValue;
+    if (tab && a.n_rows > ROWTAB_MAX) return hipErrorInvalidValue;
+    const int max_rows = 65535 * SUMSQ_RB;  // grid rows of one launch
+    for (int done = 0; done < a.n_rows; done += max_rows) {
+        SumsqArgs b = a;
+        b.row0 = a.row0 + done;
+        b.n_rows = std::min(max_rows, a.n_rows - done);
+        const dim3 grid((unsigned)b.ntiles, (unsigned)((b.n_rows + SUMSQ_RB - 1) / SUMSQ_RB));
+        if (tab) {
+            k_row_sumsq_rows<<<grid, BLOCK, 0, s>>>(b, *tab);
+            k_row_sumsq_fold_rows<<<(unsigned)b.n_rows, BLOCK, 0, s>>>(b, *tab);
+        } else {
+            k_row_sumsq<<<grid, BLOCK, 0, s>>>(b);
+            k_row_sumsq_fold<<<(unsigned)b.n_rows, BLOCK, 0, s>>>(b);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_synth_shares(int64_t* out, const SlabMap& m, int64_t ncols, int n_clients, int n_parties,

@@ -5,16 +5,241 @@
 // (struct pgh_ctx and the shared helpers: pgh_ctx.h)
 #include "pgh_ctx.h"
 
+#include <cmath>
+
 using namespace pgh_detail;
 
 // (the public entry points take their C linkage from include/pgh_api.h)
+
+// ---- clipped FedAvg: per-row sums of squares (K7), their host cache, the scales --------------------
+
+namespace pgh_detail {
+
+int check_mode(pgh_ctx* c, int mode) {
+    if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
+    if (mode == PGH_CLIPPED_MEAN && !(c->clip_c > 0.f))
+        return fail(c, PGH_E_STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first");
+    return PGH_OK;
+}
+
+float clip_scale_of(double sumsq, float c) {
+    const double norm = std::sqrt(sumsq);
+    return norm <= (double)c ? 1.0f : (float)((double)c / norm);
+}
+
+void sumsq_forget(pgh_ctx* c) {
+    std::fill(c->sq_state.begin(), c->sq_state.end(), (uint8_t)pgh_ctx::SQ_NONE);
+    c->sq_queued.clear();
+    c->clip_scales_valid = false;
+    c->clip_norms.clear();
+    c->clip_rows = c->clip_clipped = 0;
+    c->clip_max_norm = 0.0;
+}
+
+void free_clip(pgh_ctx* c) {  // the copy stream is idle (free_slab synchronised it)
+    (void)hipFree(c->d_sq_part); c->d_sq_part = nullptr;
+    (void)hipFree(c->d_sq); c->d_sq = nullptr;
+    if (c->h_sq) (void)hipHostFree(c->h_sq);
+    c->h_sq = nullptr;
+    c->sq_state.clear();
+    c->sq_host.clear();
+    sumsq_forget(c);
+}
+
+namespace {
+int ensure_sumsq_buffers(pgh_ctx* c) {
+    if (c->d_sq_part) return PGH_OK;
+    const size_t ntiles = (size_t)((c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE);
+    const size_t rows = (size_t)c->slots;
+    if (!c->sq_ev) CK(c, hipEventCreateWithFlags(&c->sq_ev, hipEventDisableTiming));
+    if (hipMalloc((void**)&c->d_sq_part, 8 * rows * ntiles) != hipSuccess ||
+        hipMalloc((void**)&c->d_sq, 8 * rows) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_sq, 8 * rows, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(c->d_sq_part); c->d_sq_part = nullptr;
+        (void)hipFree(c->d_sq); c->d_sq = nullptr;
+        c->h_sq = nullptr;
+        return fail(c, PGH_E_OOM, "allocation of the clipping sums (%zu rows x %zu tiles) failed", rows, ntiles);
+    }
+    return PGH_OK;
+}
+}  // namespace
+
+int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n) {
+    std::vector<int32_t> todo;
+    for (int k = 0; k < n; ++k)
+        if (c->sq_state[(size_t)slots[k]] == pgh_ctx::SQ_NONE) todo.push_back(slots[k]);
+    if (todo.empty()) return PGH_OK;
+    RC(ensure_sumsq_buffers(c));
+    pgh::SumsqArgs a{};
+    a.slab = (const float*)c->d_slab;
+    a.map = slab_map(c);
+    a.p = c->pg;
+    a.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
+    a.part = c->d_sq_part;
+    a.sumsq = c->d_sq;
+    const hipStream_t s = c->copy;
+    bool run = true;  // consecutive slots: one launch over contiguous rows
+    int32_t lo = todo[0], hi = todo[0];
+    for (size_t k = 0; k < todo.size(); ++k) {
+        run = run && todo[k] == todo[0] + (int32_t)k;
+        lo = std::min(lo, todo[k]);
+        hi = std::max(hi, todo[k]);
+    }
+    const auto bytes = [&](size_t rows) { return rows * (4ull * (uint64_t)c->pg + 8ull * (uint64_t)a.ntiles); };
+    if (run) {
+        a.row0 = todo[0];
+        a.n_rows = (int)todo.size();
+        RC(timed_launch(c, s, bytes(todo.size()), [&] { return pgh::launch_row_sumsq(a, nullptr, s); }));
+    } else {
+        for (size_t done = 0; done < todo.size(); done += pgh::ROWTAB_MAX) {
+            const size_t m = std::min(todo.size() - done, (size_t)pgh::ROWTAB_MAX);
+            pgh::RowTab tab;
+            for (size_t k = 0; k < m; ++k) tab.rows[k] = todo[done + k];
+            a.n_rows = (int)m;
+            RC(timed_launch(c, s, bytes(m), [&] { return pgh::launch_row_sumsq(a, &tab, s); }));
+        }
+    }
+    // entries of other slots inside [lo, hi] are rewritten with what the device holds for them: the
+    // same value an earlier copy brought (same stream), or one nobody reads
+    CK(c, hipMemcpyAsync(c->h_sq + lo, c->d_sq + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
+    CK(c, hipEventRecord(c->sq_ev, s));
+    for (int32_t sl : todo) {
+        c->sq_state[(size_t)sl] = pgh_ctx::SQ_QUEUED;
+        c->sq_queued.push_back(sl);
+    }
+    return PGH_OK;
+}
+
+int sumsq_wait(pgh_ctx* c) {
+    if (c->sq_queued.empty()) return PGH_OK;
+    CK(c, hipEventSynchronize(c->sq_ev));
+    for (int32_t sl : c->sq_queued)
+        if (c->sq_state[(size_t)sl] == pgh_ctx::SQ_QUEUED) {
+            c->sq_host[(size_t)sl] = c->h_sq[sl];
+            c->sq_state[(size_t)sl] = pgh_ctx::SQ_VALID;
+        }
+    c->sq_queued.clear();
+    return PGH_OK;
+}
+
+int sumsq_after_ingest(pgh_ctx* c, int slot) {
+    if (!clip_on(c)) return PGH_OK;
+    const int32_t sl = slot;
+    return sumsq_queue(c, &sl, 1);
+}
+
+int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms) {
+    RC(sumsq_queue(c, slots, n));
+    RC(sumsq_wait(c));
+    c->weights.resize((size_t)(c0 + n));
+    if (norms) norms->resize((size_t)(c0 + n));
+    for (int k = 0; k < n; ++k) {
+        const double ss = c->sq_host[(size_t)slots[k]];
+        c->weights[(size_t)(c0 + k)] = clip_scale_of(ss, c->clip_c);
+        if (norms) (*norms)[(size_t)(c0 + k)] = std::sqrt(ss);
+    }
+    c->weights_on_device = false;
+    return PGH_OK;
+}
+
+void clip_count(pgh_ctx* c, const float* scales, const double* norms, int64_t n) {
+    for (int64_t k = 0; k < n; ++k) {
+        c->clip_rows += 1;
+        c->clip_clipped += scales[k] == 1.0f ? 0 : 1;
+        if (!std::isnan(c->clip_max_norm) && (std::isnan(norms[k]) || norms[k] > c->clip_max_norm))
+            c->clip_max_norm = norms[k];
+    }
+}
+
+}  // namespace pgh_detail
+
+// Resident folds in PGH_CLIPPED_MEAN: the scales of clients [0, n) (slot k holds client k), computed
+// once per state of the slab -- the range form and repeated folds reuse them.
+int pgh_detail::resident_clip_scales(pgh_ctx* c, int64_t n) {
+    if (c->clip_scales_valid && (int64_t)c->weights.size() == n) return PGH_OK;
+    std::vector<int32_t> slots((size_t)n);
+    for (int64_t k = 0; k < n; ++k) slots[(size_t)k] = (int32_t)k;
+    std::vector<double> norms;
+    RC(clip_set_scales(c, slots.data(), (int)n, 0, &norms));
+    clip_count(c, c->weights.data(), norms.data(), n);
+    c->clip_scales_valid = true;
+    return PGH_OK;
+}
+
+namespace {
+int check_clip_ctx(pgh_ctx* c, const char* what) {
+    if (!c) return fail(nullptr, PGH_E_ARG, "null context");
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s: a group's shards each hold part of a row (the sums would need an all-reduce)", what);
+    if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
+    if (c->pg != c->P) return fail(c, PGH_E_UNSUPPORTED, "%s: the shard [%lld,%lld) is narrower than the model", what, (long long)c->lo, (long long)c->hi);
+    if (c->d_slab && c->dtype != PGH_F32) return fail(c, PGH_E_UNSUPPORTED, "%s: the slab holds int64 shares", what);
+    if (c->streaming) return fail(c, PGH_E_UNSUPPORTED, "%s: the context is streaming", what);
+    return PGH_OK;
+}
+}  // namespace
+
+int pgh_set_clip_norm(pgh_ctx* c, float bound) {
+    if (!c) return PGH_E_ARG;
+    if (bound == 0.f) {  // off: always possible (a group never clips)
+        c->clip_c = 0.f;
+        c->clip_scales_valid = false;
+        return PGH_OK;
+    }
+    RC(check_clip_ctx(c, "pgh_set_clip_norm"));
+    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(c, PGH_E_ARG, "the clipping bound must be finite and > 0, or 0 for off");
+    if (bound != c->clip_c) c->clip_scales_valid = false;
+    c->clip_c = bound;
+    return PGH_OK;
+}
+
+int pgh_row_sumsq(pgh_ctx* c, const int32_t* slots, int n, double* out) {
+    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_row_sumsq: a group's shards each hold part of a row");
+    RC(check_dtype(c, PGH_F32));
+    if (c->streaming) return fail(c, PGH_E_UNSUPPORTED, "pgh_row_sumsq: the context is streaming");
+    if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
+    for (int k = 0; k < n; ++k) {
+        if (slots[k] < 0 || slots[k] >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", slots[k], c->slots);
+        if (c->slot_client[(size_t)slots[k]] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", slots[k]);
+    }
+    DeviceGuard g(c->device);
+    RC(sumsq_queue(c, slots, n));
+    if (!out) return PGH_OK;
+    RC(sumsq_wait(c));
+    for (int k = 0; k < n; ++k) out[k] = c->sq_host[(size_t)slots[k]];
+    return PGH_OK;
+}
+
+int pgh_clip_scale(double sumsq, float bound, float* scale) {
+    if (!scale) return fail(nullptr, PGH_E_ARG, "scale is NULL");
+    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(nullptr, PGH_E_ARG, "the clipping bound must be finite and > 0");
+    *scale = clip_scale_of(sumsq, bound);
+    return PGH_OK;
+}
+
+int pgh_clip_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_clipped, double* max_norm) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_clip_stats: group contexts do not clip");
+    // the finished folds, and the slot folds of the running cycle on top
+    const int64_t rows0 = c->clip_rows, cl0 = c->clip_clipped;
+    const double mx0 = c->clip_max_norm;
+    const int64_t m = std::min<int64_t>((int64_t)c->clip_norms.size(), (int64_t)c->weights.size());
+    clip_count(c, c->weights.data(), c->clip_norms.data(), m);
+    if (n_rows) *n_rows = c->clip_rows;
+    if (n_clipped) *n_clipped = c->clip_clipped;
+    if (max_norm) *max_norm = c->clip_max_norm;
+    c->clip_rows = rows0;
+    c->clip_clipped = cl0;
+    c->clip_max_norm = mx0;
+    return PGH_OK;
+}
 
 // ---- RESIDENT reductions -------------------------------------------------------------------------
 
 int pgh_fedavg_device(pgh_ctx* c, int mode, const float* d_ckpt, float* d_out, void* stream) {
     if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s takes device pointers, which name one GPU: call it on pgh_group_child", __func__);
     RC(check_dtype(c, PGH_F32));
-    if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
+    RC(check_mode(c, mode));
     if (!d_ckpt || !d_out) return fail(c, PGH_E_ARG, "d_ckpt / d_out is NULL");
     if (((uintptr_t)d_ckpt | (uintptr_t)d_out) & 15) return fail(c, PGH_E_ARG, "device buffers must be 16-byte aligned");
     DeviceGuard g(c->device);
@@ -32,7 +257,7 @@ int pgh_fedavg_device_range(pgh_ctx* c, int mode, int64_t off, int64_t len, cons
                             void* stream) {
     if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s takes device pointers, which name one GPU: call it on pgh_group_child", __func__);
     RC(check_dtype(c, PGH_F32));
-    if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
+    RC(check_mode(c, mode));
     if (!d_ckpt || !d_out || (((uintptr_t)d_ckpt | (uintptr_t)d_out) & 15))
         return fail(c, PGH_E_ARG, "d_ckpt / d_out must be 16-byte aligned device pointers");
     DeviceGuard g(c->device);
@@ -48,8 +273,10 @@ int pgh_fedavg_device_range(pgh_ctx* c, int mode, int64_t off, int64_t len, cons
 }
 
 int pgh_fedavg(pgh_ctx* c, int mode, const float* ckpt, float* out) {
+    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
     if (c && c->grp) return pgh_group_api::fedavg(c, mode, ckpt, out);
     RC(check_dtype(c, PGH_F32));
+    RC(check_mode(c, mode));
     if (!ckpt || !out) return fail(c, PGH_E_ARG, "ckpt / out is NULL");
     DeviceGuard g(c->device);
     const double t0 = now_ms();
@@ -108,10 +335,11 @@ int pgh_ckpt_upload_state(pgh_ctx* c, const uint8_t* pb, size_t n) {
 }
 
 int pgh_fedavg_resident(pgh_ctx* c, int mode) {
+    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
     if (c && c->grp) return pgh_group_api::fedavg_resident(c, mode);
     RC(check_dtype(c, PGH_F32));
     RC(check_ckpt(c, "pgh_fedavg_resident"));
-    if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
+    RC(check_mode(c, mode));
     DeviceGuard g(c->device);
     const double t0 = now_ms();
     clear_final_marks(c);
@@ -252,6 +480,7 @@ int pgh_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, float* dec_out)
 // ---- STREAM reductions ---------------------------------------------------------------------------
 
 int pgh_stream_begin(pgh_ctx* c, int kind, int fold_batch) {
+    if (c && kind == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not clip: a scale needs the whole row of every client");
     if (c && c->grp) return pgh_group_api::stream_begin(c, kind, fold_batch);
     RC(check_ready(c));
     if (kind == PGH_STREAM_SECAGG) {

@@ -12,7 +12,7 @@ using namespace pgh_detail;
 namespace {
 int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     RC(check_dtype(c, PGH_F32));
-    if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
+    RC(check_mode(c, mode));
     if (c->streaming) return fail(c, PGH_E_STATE, "context is streaming: slot folds need a RESIDENT slab");
     if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
     if (c->slot_mode >= 0 && c->slot_mode != mode)
@@ -38,10 +38,17 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     const hipStream_t s = c->stream;
     // a close right behind a ranged ingest (pgh_set_ingest_ranges) orders each FINAL range after the
     // chunk of the last report it reads instead of after the whole copy stream
-    const bool ranged = final && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && ranged_ingest_valid(c);
+    // (never a clipped pass: a scale needs the last report's whole row, so it takes the whole-stream wait)
+    const bool clipped = mode == PGH_CLIPPED_MEAN;
+    const bool ranged = final && !clipped && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && ranged_ingest_valid(c);
+    if (clipped && n > 0) {  // the sums still missing in one batch, then the scales in fold order
+        if (c0 == 0) c->clip_norms.clear();
+        c->clip_scales_valid = false;
+        RC(clip_set_scales(c, slots, n, c0, &c->clip_norms));
+    }
     if (!ranged) RC(order_after_ingest(c, s));
     else if (c->dec_last) CK(c, hipStreamWaitEvent(s, c->dec_last, 0));  // the copy stream: per range below
-    if (mode == PGH_WEIGHTED_MEAN && n > 0) {
+    if (kernel_mode(mode) == PGH_WEIGHTED_MEAN && n > 0) {
         if ((int64_t)c->weights.size() < total)
             return fail(c, PGH_E_STATE, "weighted mean: %zu weights for %lld clients", c->weights.size(),
                         (long long)total);
@@ -68,7 +75,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         a.out = c->d_out;
         a.divisor = fa.divisor;
         a.flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
-        a.mode = mode;
+        a.mode = kernel_mode(mode);
         a.variant = c->variant;
         // The FINAL pass of a report-time close (a short fold of the rows left) as ranges of 4 MiB of
         // output, one after another on one stream, a mark behind every second one: each 8 MiB D2H
@@ -131,18 +138,25 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         c->pre_d2h_valid = prequeued && c->pre_d2h.src == (const uint8_t*)c->d_ckpt;
         c->folded = 0;  // the next cycle folds from scratch
         c->slot_mode = -1;
+        if (clipped) {  // the cycle's rows join the finished totals (pgh_clip_stats)
+            const int64_t m = std::min<int64_t>((int64_t)c->clip_norms.size(), (int64_t)c->weights.size());
+            clip_count(c, c->weights.data(), c->clip_norms.data(), m);
+            c->clip_norms.clear();
+        }
     }
     return PGH_OK;
 }
 }  // namespace
 
 int pgh_fold_slots(pgh_ctx* c, int mode, const int32_t* slots, int n) {
+    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
     if (c && c->grp) return pgh_group_api::fold_slots(c, mode, slots, n, false);
     if (!c) return PGH_E_ARG;
     return slot_fold(c, mode, slots, n, false);
 }
 
 int pgh_fold_slots_finish_resident(pgh_ctx* c, int mode, const int32_t* slots, int n) {
+    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
     if (c && c->grp) return pgh_group_api::fold_slots(c, mode, slots, n, true);
     if (!c) return PGH_E_ARG;
     const double t0 = now_ms();
@@ -168,7 +182,8 @@ int pgh_fold_slots_restart(pgh_ctx* c) {
     c->folded = 0;
     c->st.n_folded = 0;
     c->slot_mode = -1;
-    c->weights.clear();
+    c->weights.clear();  // (a clipped cycle's scales among them)
+    c->clip_norms.clear();
     c->weights_on_device = false;
     return PGH_OK;
 }

@@ -27,8 +27,38 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import state as state_codec
-from .engine import ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
-from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
+from .engine import CLIPPED_MEAN, ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
+from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
+    StateParseError
+
+CLIP_KEY = "diff_clip_norm"  # optional server_config key: the per-client L2 bound (no reference counterpart)
+
+
+def clip_norm_of(server_config: dict) -> Optional[float]:
+    """The FL process's per-client L2 bound, ``server_config["diff_clip_norm"]``: a finite number
+    > 0, or None when the key is absent or None (clipping off).  Anything else -- another type
+    (bools included), NaN, an infinity, 0, a negative value -- raises ``AggregationError``: a
+    mistyped bound must not quietly mean "no clipping"."""
+    c = server_config.get(CLIP_KEY, None)
+    if c is None:
+        return None
+    if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)):
+        raise AggregationError(f"{CLIP_KEY} must be a finite number > 0, not {c!r}")
+    c = float(c)
+    with np.errstate(over="ignore", under="ignore"):
+        c32 = np.float32(c)  # the engine takes the bound as a float32
+    if not np.isfinite(c) or c <= 0 or not np.isfinite(c32) or c32 <= 0:
+        raise AggregationError(f"{CLIP_KEY} must be a finite float32 > 0, not {c!r}")
+    return c
+
+
+_NO_CLIP = object()  # "take the bound from server_config"
+
+
+def _clip_arg(server_config: dict, clip_norm):
+    if clip_norm is _NO_CLIP:
+        return clip_norm_of(server_config)
+    return None if clip_norm is None else clip_norm_of({CLIP_KEY: clip_norm})
 
 
 def ready_to_average(server_config: dict, received_diffs: int, cycle_end=None, now=None) -> bool:
@@ -177,7 +207,28 @@ def cached_mode(server_config: dict, plan_key, mean_plans: Optional[str] = None)
 
 
 def select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
-                mean_plans: Optional[str] = None, shapes=None, n_clients=None) -> int:
+                mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None) -> int:
+    """The dispatch rule below; with ``clip_norm`` set: ``CLIPPED_MEAN`` exactly where the rule gives
+    ``MEAN`` (no hosted plan, or a plan probed equal to the mean), ``ClipUnavailableError`` everywhere
+    else -- weights, the iterative plan, a plan the engine declines -- so that the caller cannot fall
+    back to an average that does not clip."""
+    if clip_norm is None:
+        return _select_mode(server_config, avg_plan, weights, plan_key, mean_plans, shapes, n_clients)
+    if weights is not None:
+        raise ClipUnavailableError(f"{CLIP_KEY} cannot be combined with aggregation weights")
+    try:
+        mode = _select_mode(server_config, avg_plan, None, plan_key, mean_plans, shapes, n_clients)
+    except PlanNotAcceleratedError as e:
+        raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine does not run this avg plan ({e}); the node's "
+                                   "own averaging does not clip") from e
+    if mode != MEAN:
+        raise ClipUnavailableError(f"{CLIP_KEY} is set but the hosted avg plan is the iterative mean, which the "
+                                   "engine does not clip")
+    return CLIPPED_MEAN
+
+
+def _select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
+                 mean_plans: Optional[str] = None, shapes=None, n_clients=None) -> int:
     """Dispatch rule (module docstring).  ``plan_key`` -- the hosted plan's serialized bytes
     (``avg_plan_rec.value``, cycle_manager.py:256) -- caches the probe's verdict: a node's avg plan
     is fixed for its FL process, and probing a non-iterative plan costs ~2.6 ms of torch calls,
@@ -222,6 +273,23 @@ def _probe_mode(server_config: dict, avg_plan: Callable, mean_plans=None, shapes
     if not is_canonical_iterative_plan(avg_plan):
         raise PlanNotAcceleratedError("iterative avg plan is not (avg * num + item) / (num + 1)")
     return ITERATIVE_MEAN
+
+
+def _engine_clip(engine, clip_norm: Optional[float]):
+    """Set (or clear) the engine's bound before a cycle's first ingest: an engine shared across FL
+    processes never carries one over.  An engine that cannot clip fails the cycle."""
+    if clip_norm is None:
+        if hasattr(engine, "set_clip_norm"):
+            engine.set_clip_norm(0.0)
+        return
+    try:
+        engine.set_clip_norm(clip_norm)
+    except AttributeError as e:
+        raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine has no clipping") from e
+    except AggregationError as e:
+        if e.status == -6:  # PGH_E_UNSUPPORTED: a multi-GPU group, a sub-range shard
+            raise ClipUnavailableError(f"{CLIP_KEY} is set but this engine cannot clip: {e}") from e
+        raise
 
 
 def _decline_non_float32(pb: bytes, what: str):
@@ -284,7 +352,7 @@ class CycleAggregator:
     # ---- bytes in / bytes out: the replaceable slice cycle_manager.py:240-303 -------------------
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
-                           plan_key=None) -> bytes:
+                           plan_key=None, clip_norm=_NO_CLIP) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -294,14 +362,26 @@ class CycleAggregator:
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
+        clip = _clip_arg(server_config, clip_norm)
+        try:
+            return self._average_plan_diffs(server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key,
+                                            clip)
+        except PlanNotAcceleratedError as e:
+            if clip is None:
+                raise
+            raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine cannot average this cycle ({e}); the "
+                                       "node's own averaging does not clip") from e
+
+    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, clip):
         mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
-                           shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs))
+                           shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), clip_norm=clip)
         try:
             numel = state_codec.tensor_numels(checkpoint)  # :240
         except StateParseError:
             _decline_non_float32(checkpoint, "the checkpoint")
             raise
         self._prepare(numel, len(diffs))
+        _engine_clip(self.engine, clip)  # before the first ingest: each diff's norm pass rides behind its copy
         if checkpoint is not self._resident or self.engine.ckpt_owner is not self:
             self.engine.ckpt_upload_state(checkpoint)  # else: the last cycle's output is still in HBM
         for i, d in enumerate(diffs):  # :247-250
@@ -327,14 +407,16 @@ class CycleAggregator:
     # ---- tensor lists in / out (what the reference holds after unserialize) ---------------------
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
-                       weights=None) -> List[np.ndarray]:
+                       weights=None, clip_norm=_NO_CLIP) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
+        clip = _clip_arg(server_config, clip_norm)
         shapes = [np.shape(p) for p in model_params]
         mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
-                           n_clients=len(diffs))
+                           n_clients=len(diffs), clip_norm=clip)
         numel = [int(np.prod(s)) for s in shapes]
         self._prepare(numel, len(diffs))
+        _engine_clip(self.engine, clip)
         for i, d in enumerate(diffs):
             if len(d) != len(numel):
                 raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
@@ -405,12 +487,16 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
         with gate() if gate is not None else contextlib.nullcontext():
             reports = self._worker_cycles.query(cycle_id=cycle.id, is_completed=True)
             diffs = [r.diff for r in reports]  # what :247-250 reads, at the query
+        clip = clip_norm_of(server_config)  # a malformed bound fails the close
         try:
             avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
                                              getattr(aggregator, "mean_plans", None))
             new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,
                                                      plan_key=plan_key, framing=framing)
         except PlanNotAcceleratedError as e:
+            if clip is not None:  # fail closed: the node's own averaging does not clip
+                raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine does not average this cycle ({e})") \
+                    from e
             logging.info("engine declined (%s): running the reference averaging", e)
             return original(self, server_config, cycle)
         finish_cycle(self, server_config, cycle, model_manager, _model.id, new_ckpt)

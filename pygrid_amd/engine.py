@@ -15,11 +15,12 @@ import numpy as np
 from . import _lib
 from .exceptions import AggregationError, EngineUnavailableError, StateParseError
 
-MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN = 0, 1, 2
+MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN = 0, 1, 2, 3
 STREAM_SECAGG = 16
 DEFAULT_VARIANT = -1  # PGH_DEFAULT_VARIANT: auto by shard size
 F32, I64 = 0, 1
-MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean"}
+MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
+              CLIPPED_MEAN: "clipped_mean"}
 
 
 def device_count() -> int:
@@ -257,6 +258,40 @@ class Engine:
         a = np.ascontiguousarray(w, dtype=np.float32)
         self._check(self._lib.pgh_set_weights(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.size),
                     "set_weights")
+
+    # ---- per-client L2 clipping (CLIPPED_MEAN) ---------------------------------------------------
+    def set_clip_norm(self, c: float):
+        """The L2 bound for later ingests and CLIPPED_MEAN folds (finite, > 0); 0 turns clipping off.
+        Refused (status PGH_E_UNSUPPORTED) on a group, a sub-range shard, an int64 slab, a stream."""
+        self._check(self._lib.pgh_set_clip_norm(self._h, C.c_float(float(c))), "set_clip_norm")
+
+    def row_sumsq(self, slots: Sequence[int], wait: bool = True) -> Optional[np.ndarray]:
+        """float64 sums of squares of the diffs in ``slots`` (the fixed order of DESIGN.md section 5).
+        ``wait=False`` only queues the norm passes still missing on the GPU and returns None."""
+        a = np.ascontiguousarray(slots, dtype=np.int32)
+        out = np.empty(a.size, dtype=np.float64) if wait else None
+        self._check(self._lib.pgh_row_sumsq(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
+                                            out.ctypes.data_as(C.POINTER(C.c_double)) if wait else None),
+                    "row_sumsq")
+        return out
+
+    @staticmethod
+    def clip_scale(sumsq: float, c: float) -> np.float32:
+        """``1`` if ``sqrt(sumsq) <= c`` else ``float32(c / sqrt(sumsq))`` (host arithmetic; no GPU)."""
+        lib = _lib.load()
+        s = C.c_float(0)
+        rc = lib.pgh_clip_scale(C.c_double(float(sumsq)), C.c_float(float(c)), C.byref(s))
+        if rc != 0:
+            raise AggregationError(f"clip_scale: {_lib.STATUS_NAMES.get(rc, rc)}: "
+                                   f"{lib.pgh_last_error(None).decode(errors='replace')}", status=rc)
+        return np.float32(s.value)
+
+    def clip_stats(self) -> dict:
+        """Rows folded in CLIPPED_MEAN since the last reset / reserve: ``rows``, ``clipped`` (scale
+        other than 1) and ``max_norm``."""
+        n, k, m = C.c_int64(0), C.c_int64(0), C.c_double(0)
+        self._check(self._lib.pgh_clip_stats(self._h, C.byref(n), C.byref(k), C.byref(m)), "clip_stats")
+        return {"rows": n.value, "clipped": k.value, "max_norm": m.value}
 
     # ---- reduction -----------------------------------------------------------------------------
     def fedavg(self, mode: int, ckpt: np.ndarray) -> np.ndarray:

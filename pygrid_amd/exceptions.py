@@ -35,6 +35,14 @@ class PlanNotAcceleratedError(PyGridError):
     keeps running the reference's own CPU path for it."""
 
 
+class ClipUnavailableError(AggregationError):
+    """The FL process asks for per-client L2 clipping (``server_config["diff_clip_norm"]``) and the
+    engine cannot clip this cycle: a hosted iterative or unaccelerated plan, a non-float32 model, a
+    multi-GPU group engine, or aggregation weights given together with the bound.  Deliberately NOT
+    a ``PlanNotAcceleratedError``: the node's own averaging does not clip, so falling back to it
+    would silently drop the defence the operator configured -- the close fails instead."""
+
+
 class ModelNotAcceleratedError(PlanNotAcceleratedError):
     """The checkpoint or a diff holds well-formed tensors that are not float32 (another dtype, or a
     serializer other than syft's "all").  The reference averages them with torch's type promotion;

@@ -65,8 +65,8 @@ import threading
 from typing import Callable, Dict, Hashable, List, Optional, Sequence
 
 from . import state as state_codec
-from .engine import F32, MEAN, WEIGHTED_MEAN, Engine
-from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
+from .engine import CLIPPED_MEAN, F32, MEAN, WEIGHTED_MEAN, Engine
+from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, StateParseError
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
 MAX_DEFAULT_SLOTS = 4096
@@ -81,9 +81,21 @@ def default_slots(P: int, budget: int = DEFAULT_HBM_BUDGET) -> int:
 class IncrementalCycle:
     def __init__(self, engine: Engine, numel, mode: int = MEAN, slots: Optional[int] = None, fold_batch: int = 8,
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
-                 early_fold: bool = True):
+                 early_fold: bool = True, clip_norm: Optional[float] = None):
+        """``clip_norm``: the FL process's per-client L2 bound (``cycle.clip_norm_of``).  ``mode`` must
+        then be MEAN; every fold runs as CLIPPED_MEAN, each diff's norm pass is queued right behind
+        its ingest (off the close), and a cycle the engine cannot clip raises
+        ``ClipUnavailableError`` instead of being handed back to the node's unclipped averaging."""
         self.engine = engine
         self.mode = mode
+        from .cycle import _engine_clip, clip_norm_of
+
+        self.clip_norm = None
+        if clip_norm is not None:
+            self.clip_norm = clip_norm_of({"diff_clip_norm": clip_norm})
+            if mode != MEAN or weights_by_worker is not None:
+                raise ClipUnavailableError("diff_clip_norm applies to the plain mean only (no weights, no iterative plan)")
+        self._fold_mode = CLIPPED_MEAN if self.clip_norm is not None else mode
         self._numel = tuple(int(n) for n in numel)
         P = sum(self._numel)
         self.slots = int(slots) if slots else default_slots(P)
@@ -128,6 +140,10 @@ class IncrementalCycle:
         if hasattr(engine, "set_ingest_ranges"):
             # the close overlaps the tail of the last report's copy (pgh_set_ingest_ranges)
             engine.set_ingest_ranges(os.environ.get("PGH_INGEST_RANGES", "1") != "0")
+        if self.clip_norm is not None:  # (an engine without the method is only touched when a bound is set)
+            _engine_clip(engine, self.clip_norm)
+        elif hasattr(engine, "set_clip_norm"):
+            engine.set_clip_norm(0.0)  # a shared engine never carries another process's bound over
         self._ckpt: Optional[bytes] = None  # checkpoint bytes whose payloads are resident in HBM
         if checkpoint is not None and getattr(engine, "ckpt_owner", None) is not None \
                 and getattr(engine, "ckpt_bytes", None) is checkpoint:
@@ -139,7 +155,7 @@ class IncrementalCycle:
             try:
                 engine.ckpt_upload_state(checkpoint)
             except StateParseError:
-                _raise_if_not_float32(checkpoint, "the checkpoint")
+                self._raise_if_not_float32(checkpoint, "the checkpoint")
                 raise
             engine.ckpt_owner = self
             self._ckpt = checkpoint
@@ -224,6 +240,7 @@ class IncrementalCycle:
         """Store ``diff`` as the worker's latest: over its old slot, in a free slot, or parked."""
         if worker in self._slot_of:  # re-report before the fold: same slot (parse first, then DMA)
             self.engine.ingest_state(self._slot_of[worker], diff)
+            self._queue_norm(self._slot_of[worker])
             return
         # a diff that cannot fold yet leaves one slot free for the fold front
         if self._free and (len(self._free) > 1 or self._is_front(worker)):
@@ -264,6 +281,20 @@ class IncrementalCycle:
             self._free.append(slot)
             raise
         self._slot_of[worker] = slot
+        self._queue_norm(slot)
+
+    def _queue_norm(self, slot: int):
+        """Clipping: the row's norm pass goes to the GPU now, behind its copy, not at the close."""
+        if self.clip_norm is not None:
+            self.engine.row_sumsq([slot], wait=False)
+
+    def _raise_if_not_float32(self, pb: bytes, what: str):
+        try:
+            _raise_if_not_float32(pb, what)
+        except ModelNotAcceleratedError as e:
+            if self.clip_norm is None:
+                raise
+            raise ClipUnavailableError(f"diff_clip_norm is set but {e}; the node's own averaging does not clip") from e
 
     def _held(self, worker) -> bool:
         return worker in self._slot_of or worker in self._parked
@@ -318,7 +349,7 @@ class IncrementalCycle:
         if self.mode == WEIGHTED_MEAN and self._weights_by_worker is not None:
             self._weights.extend(float(self._weights_by_worker[w]) for w in ws)
             self.engine.set_weights(self._weights)
-        self.engine.fold_slots(self.mode, slots)
+        self.engine.fold_slots(self._fold_mode, slots)
         for w in ws:
             del self._slot_of[w]
         self._free.extend(reversed(slots))
@@ -351,6 +382,8 @@ class IncrementalCycle:
                 raise AggregationError("cycle already closed")
             self._closed = True
             if self._declined:
+                if self.clip_norm is not None:  # fail closed: the node's own averaging does not clip
+                    raise ClipUnavailableError(f"diff_clip_norm is set but {self._declined}")
                 raise ModelNotAcceleratedError(self._declined)
             if order is None:
                 if self._stale or self._bad:
@@ -422,6 +455,11 @@ class IncrementalCycle:
             del stats["db_rows"]
             stats.update(refold=bool(refold), reason=refold or None, early=k, n=len(order),
                          folded_before_close=folded_before)
+            if self.clip_norm is not None:  # the engine was reset when this cycle took it: its rows only
+                cs = self.engine.clip_stats()
+                stats.update(clipped=int(cs["clipped"]), max_norm=float(cs["max_norm"]))
+            else:
+                stats.update(clipped=0, max_norm=None)
             self.last_close = stats
             new = (state_codec.fresh_checkpoint(self.engine, checkpoint, prepared=prep) if framing == "fresh"
                    else self.engine.ckpt_patch_state(checkpoint))
@@ -448,9 +486,9 @@ class IncrementalCycle:
                 if self._weights:
                     self.engine.set_weights(self._weights)
             if final:
-                self.engine.fold_slots_finish_resident(self.mode, slots)
+                self.engine.fold_slots_finish_resident(self._fold_mode, slots)
             else:
-                self.engine.fold_slots(self.mode, slots)
+                self.engine.fold_slots(self._fold_mode, slots)
         free.extend(reversed(slots))
         return slots
 

@@ -72,9 +72,9 @@ from typing import Callable, Dict, Optional, Sequence
 
 from . import state as state_codec
 from .checkpoints import Checkpoint, CheckpointStore
-from .cycle import CycleAggregator, finish_cycle, hosted_plan, make_average_plan_diffs, select_mode
-from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, PyGridError, \
-    StateParseError
+from .cycle import CycleAggregator, clip_norm_of, finish_cycle, hosted_plan, make_average_plan_diffs, select_mode
+from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
+    PyGridError, StateParseError
 from .incremental import IncrementalCycle
 from .trigger import CycleCloseTrigger
 
@@ -314,6 +314,18 @@ class NodeEngine:
 
     def _new_cycle(self, cm, cycle, fresh: bool = False) -> IncrementalCycle:
         server_config, _ = self.process_manager.get_configs(id=cycle.fl_process_id)
+        clip = clip_norm_of(server_config)  # the process's diff_clip_norm (a malformed one raises)
+        if clip is None:
+            return self._new_cycle_for(cm, cycle, server_config, None, fresh)
+        try:
+            return self._new_cycle_for(cm, cycle, server_config, clip, fresh)
+        except PlanNotAcceleratedError as e:
+            # not _DECLINED: the node's own averaging does not clip.  The close-time path refuses
+            # the cycle again, loudly, when it closes.
+            raise ClipUnavailableError(f"diff_clip_norm is set but the engine does not average this cycle ({e})") \
+                from e
+
+    def _new_cycle_for(self, cm, cycle, server_config, clip, fresh: bool) -> IncrementalCycle:
         avg_plan, plan_key = hosted_plan(server_config, cycle, self.process_manager, self.plan_manager,
                                          self.aggregator.mean_plans)
         model = self.model_manager.get(fl_process_id=cycle.fl_process_id)
@@ -325,11 +337,13 @@ class NodeEngine:
 
             _decline_non_float32(ckpt, "the checkpoint")
             raise
+        select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
+                    shapes=lambda: _shapes(ckpt), clip_norm=clip)  # with a bound: MEAN-able, or ClipUnavailableError
         mode = select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
                            shapes=lambda: _shapes(ckpt))
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
         inc = IncrementalCycle(self.engine, numel, mode=mode, slots=self.slots, fold_batch=self.fold_batch,
-                               checkpoint=ckpt)
+                               checkpoint=ckpt, clip_norm=clip)
         if not fresh:  # after a restart: the rows assigned before it (a cycle just created has none;
             # an assignment that lands while this state is built is recorded from _pending_assign)
             for row in _rows(cm, cycle_id=cycle.id):
@@ -407,6 +421,9 @@ class NodeEngine:
     def average_plan_diffs(self, cm, server_config, cycle, close_time: Callable, original: Callable):
         """The close (executor thread).  Holds the engine lock throughout, the report gate only for
         the snapshot of the completed rows (see the module docstring)."""
+        clip = clip_norm_of(server_config)  # a malformed bound fails the close
+        if clip is not None:
+            original = _refuse_unclipped(cycle.id)  # fail closed: the node's own averaging does not clip
         with self._engine_for_close():
             model = ckpt = None
             if isinstance(self._cycles.get(cycle.id), IncrementalCycle):
@@ -470,6 +487,10 @@ class NodeEngine:
                 self.stats["closes_close_time"] += 1
                 return close_time(cm, server_config, cycle)
             self.stats["closes_report_time"] += 1
+            if clip is not None:
+                log.info("cycle %s closed with diff_clip_norm=%g: %d of %d diffs clipped, max norm %g", cycle.id, clip,
+                         st.last_close.get("clipped", 0), st.last_close.get("n", 0),
+                         st.last_close.get("max_norm") or 0.0)
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)
             self.aggregator._resident = None
@@ -515,6 +536,14 @@ class NodeEngine:
         for k in self._assigned_keys.pop(cycle_id, ()):
             if self._assigned.get(k, (None, None))[1] == cycle_id:
                 del self._assigned[k]
+
+
+def _refuse_unclipped(cycle_id):
+    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for clipping."""
+    def original(*_a, **_k):
+        raise ClipUnavailableError(f"cycle {cycle_id}: diff_clip_norm is set and the engine does not average this "
+                                   "cycle; not falling back to the node's unclipped averaging")
+    return original
 
 
 def _only(blobs: dict):
