@@ -1,18 +1,20 @@
 // The single-GPU context (struct pgh_ctx) and the helpers its entry points share.  Not installed;
 // the public surface is include/pgh_api.h.
 //
-// The context's entry points are split by what they do:
-//   pgh_api.cpp     lifecycle (create / layout / reserve / reset / destroy), page-locked host blocks,
-//                   observability, the shared helpers below, the group driver's internals
+// The context's code is split by what it does:
+//   pgh_api.cpp     lifecycle, errors and state checks, observability, the group driver's internals
+//   pgh_host.cpp    host code free of HIP (pgh_host.h): non-temporal copy, copy pool, pre-faulting
+//   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks
+//   pgh_order.cpp   which stream waits for what, and the timing events
 //   pgh_ingest.cpp  host bytes -> HBM slab rows (raw, State messages, int64 shares, synthetic)
-//   pgh_reduce.cpp  RESIDENT and STREAM folds, the resident checkpoint, secagg
+//   pgh_reduce.cpp  fold_run, RESIDENT and STREAM folds, the resident checkpoint, secagg, clipping
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order)
+// The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -20,7 +22,6 @@
 #include <cstring>
 #include <deque>
 #include <functional>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -29,8 +30,10 @@
 #include <vector>
 
 #include "../../include/pgh_api.h"
+#include "pgh_host.h"
 #include "pgh_internal.h"
 #include "pgh_kernels.h"
+#include "pgh_res.h"
 #include "pgh_state.h"
 
 namespace pgh_detail {
@@ -40,133 +43,10 @@ static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KI
                   KIND_SECAGG != PGH_CLIPPED_MEAN,
               "the secagg fold kind must not collide with an averaging mode");
 
-// memcpy with non-temporal 16-byte stores for big copies into staging / output buffers (no
-// read-for-ownership of the destination, which is written once and then read by the DMA engine or
-// handed to the caller; r01ab).
-void copy_stream(uint8_t* dst, const uint8_t* src, size_t n);
-// Bind the calling thread to `cpus` (no-op when empty or refused).
-void bind_thread(const std::vector<int>& cpus);
 // CPUs on the GPU's own socket (its PCI device's local_cpulist) that this process may run on; empty
 // when unknown.  Staging copies and pinned buffers there keep the host side of every H2D / D2H off
 // the socket interconnect (a 2-socket node: GPUs 0-3 on one socket, 4-7 on the other).
 std::vector<int> gpu_local_cpus(int device);
-
-// Host copy engine: a persistent pool that splits one batch of (dst, src, n) segments evenly
-// by bytes across its threads (the caller's thread takes the first share).  Used to fill and
-// drain the pinned staging slots, where payload pieces are many and mostly small.
-class CopyPool {
-  public:
-    struct Seg {
-        uint8_t* dst;
-        const uint8_t* src;
-        size_t n;
-    };
-    explicit CopyPool(int threads, std::vector<int> cpus = {}) : nthreads_(std::max(1, threads)) {
-        for (int t = 1; t < nthreads_; ++t)
-            workers_.emplace_back([this, t, cpus] {
-                bind_thread(cpus);
-                loop(t);
-            });
-    }
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            stop_ = true;
-            ++gen_;
-        }
-        cv_.notify_all();
-        for (auto& w : workers_) w.join();
-    }
-    int threads() const { return nthreads_; }
-    void run(const std::vector<Seg>& segs) {
-        size_t total = 0;
-        for (auto& sg : segs) total += sg.n;
-        if (total < (4u << 20) || nthreads_ == 1) { copy_range(segs, 0, total); return; }
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            segs_ = &segs;
-            total_ = total;
-            pending_ = nthreads_ - 1;
-            ++gen_;
-        }
-        cv_.notify_all();
-        copy_range(segs, 0, share(total, 0));
-        std::unique_lock<std::mutex> lk(m_);
-        done_cv_.wait(lk, [this] { return pending_ == 0; });
-        segs_ = nullptr;
-    }
-
-    // f(i) for every i in [0, n), items split into contiguous runs over the threads (the caller's
-    // thread takes the first run).  Small jobs stay on the caller's thread.
-    void run_items(int n, bool parallel, const std::function<void(int)>& f) {
-        if (!parallel || nthreads_ == 1 || n < 2) { for (int i = 0; i < n; ++i) f(i); return; }
-        const int per = (n + nthreads_ - 1) / nthreads_;
-        std::function<void(int)> job = [&](int t) {
-            for (int i = t * per; i < std::min(n, (t + 1) * per); ++i) f(i);
-        };
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            fn_ = &job;
-            pending_ = nthreads_ - 1;
-            ++gen_;
-        }
-        cv_.notify_all();
-        job(0);
-        std::unique_lock<std::mutex> lk(m_);
-        done_cv_.wait(lk, [this] { return pending_ == 0; });
-        fn_ = nullptr;
-    }
-
-  private:
-    size_t share(size_t total, int t) const {  // [begin, end) of thread t, 4 KiB granules
-        const size_t per = ((total + nthreads_ - 1) / nthreads_ + 4095) & ~(size_t)4095;
-        return std::min(total, per * (size_t)(t + 1));
-    }
-    static void copy_range(const std::vector<Seg>& segs, size_t a, size_t b) {
-        size_t base = 0;
-        for (auto& sg : segs) {
-            const size_t lo = std::max(a, base), hi = std::min(b, base + sg.n);
-            if (lo < hi) copy_stream(sg.dst + (lo - base), sg.src + (lo - base), hi - lo);
-            base += sg.n;
-            if (base >= b) break;
-        }
-    }
-    void loop(int t) {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::vector<Seg>* segs;
-            const std::function<void(int)>* fn;
-            size_t total;
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return gen_ != seen; });
-                seen = gen_;
-                if (stop_) return;
-                segs = segs_;
-                fn = fn_;
-                total = total_;
-            }
-            if (fn) {
-                (*fn)(t);
-            } else {
-                const size_t a = t == 0 ? 0 : share(total, t - 1);
-                copy_range(*segs, std::min(a, total), share(total, t));
-            }
-            std::lock_guard<std::mutex> lk(m_);
-            if (--pending_ == 0) done_cv_.notify_one();
-        }
-    }
-    int nthreads_;
-    std::vector<std::thread> workers_;
-    std::mutex m_;
-    std::condition_variable cv_, done_cv_;
-    const std::vector<Seg>* segs_ = nullptr;
-    const std::function<void(int)>* fn_ = nullptr;
-    size_t total_ = 0;
-    int pending_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
 
 }  // namespace pgh_detail
 
@@ -174,12 +54,18 @@ struct pgh_ctx {
     using CopyPool = pgh_detail::CopyPool;
     pgh_group* grp = nullptr;  // set: a multi-GPU group (pgh_create_group); the rest is unused
     int device = 0;
-    hipStream_t stream = nullptr;  // reductions
-    hipStream_t copy = nullptr;    // ingest H2D and on-device synthetic fill
-    hipEvent_t copy_done = nullptr;
-    hipEvent_t xsync = nullptr;    // caller-stream <-> context-stream ordering
-    hipStream_t aux = nullptr;     // second reduction stream: alternate ranges of a split FINAL pass
-    hipEvent_t aux_ev = nullptr;
+    using Event = pgh_detail::Event; using Stream = pgh_detail::Stream;
+    using DeviceBuf = pgh_detail::DeviceBuf; using PinnedBuf = pgh_detail::PinnedBuf;
+    Stream stream;  // reductions
+    Stream copy;    // ingest H2D and on-device synthetic fill
+    Event copy_done;
+    Event xsync;    // caller-stream <-> context-stream ordering
+    Stream aux;     // second reduction stream: alternate ranges of a split FINAL pass
+    Event aux_ev;
+    // Every ordering event that comes and goes (fold_evs, slab_evs, slot_ring, marks, final_marks,
+    // d2h_ev, rng_ev) is lent by ev_pool; the timing pairs (pending) by timing_pool, whose events
+    // keep hipEventDisableSystemFence (take_event).
+    pgh_detail::EventPool ev_pool{hipEventDisableTiming}, timing_pool{hipEventDisableSystemFence};
     // The last fold issued on each stream (folds may run on several caller streams at once, e.g.
     // the param ranges of the multi-GPU overlap): the copy stream waits on all before it
     // overwrites slots, and then forgets them (later copies are ordered after those waits).
@@ -192,12 +78,10 @@ struct pgh_ctx {
     std::vector<int64_t> slot_read_seq;                     // per slot; 0 = not read by a slot fold
     std::deque<std::pair<int64_t, hipEvent_t>> slot_ring;  // recent slot folds on c->stream, in order
     int64_t slot_seq = 0;
-    std::vector<hipEvent_t> fold_ev_pool;
     // STREAM: one event per fold with the fold front after it, so overwriting a slot waits only
     // for the fold that consumed the slot's previous client (not for the latest fold).
     struct FoldMark { hipEvent_t ev; int64_t upto; };
     std::deque<FoldMark> marks;
-    std::vector<hipEvent_t> mark_pool;
 
     std::vector<int64_t> numel;
     int64_t P = 0, lo = 0, hi = 0, pg = 0;
@@ -211,31 +95,24 @@ struct pgh_ctx {
     int synth_kind = 0;        // pgh_set_synth_kind: generator of synthetic diffs (0 Irwin-Hall, 1 fast)
 
     int slots = 0, dtype = PGH_F32, parties = 1;
-    void* d_slab = nullptr;
-    size_t slab_bytes = 0;
-    float* d_ckpt = nullptr;
-    float* d_out = nullptr;
+    DeviceBuf d_slab;
+    DeviceBuf d_ckpt, d_out;  // float [pvec]
     // d_ckpt holds a checkpoint (uploaded, or the output of a resident fold); a fresh slab's is
     // uninitialised memory, which a resident fold / download / patch must refuse to read
     bool ckpt_valid = false;
-    float* d_acc = nullptr;
-    uint64_t* d_uacc = nullptr;
-    int64_t* d_sum = nullptr;
-    float* d_dec = nullptr;
-    float* d_w = nullptr;
-    size_t w_cap = 0;
+    DeviceBuf d_acc, d_uacc, d_sum, d_dec;  // [pvec]: float, uint64, int64, float
+    DeviceBuf d_w;                          // float per client
     // iterative plan: rec[k] = 1 / (double)(float)(k + 1), grown on demand, kept for the context's
     // life (a superseded table may still be read by an in-flight fold: freed at destroy)
-    double* d_rec = nullptr;
-    int64_t rec_cap = 0;
-    std::vector<double*> rec_old;
+    DeviceBuf d_rec;  // double per client
+    std::vector<DeviceBuf> rec_old;
 
-    uint8_t* h_pin[2] = {nullptr, nullptr};
+    PinnedBuf h_pin[2];
     size_t pin_slot = 0;
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
+    Event pin_ev[2];
     bool pin_used[2] = {false, false};
     int pin_next = 0;
-    std::vector<hipEvent_t> d2h_ev;  // one per ring cell of a staged D2H (stage_d2h_pieces)
+    std::vector<hipEvent_t> d2h_ev;  // one per ring cell of a staged D2H (stage_d2h_pieces); ev_pool's
     // A staged D2H through the pinned ring: pieces of `piece` bytes of [src, src + total) into the
     // cells of the free pinned slots, each followed by d2h_ev[cell].  piped: src is a fold's result
     // with range marks; each piece is issued (on the copy stream) once the host sees every mark
@@ -248,7 +125,7 @@ struct pgh_ctx {
         int n_free = 0;
         hipStream_t s = nullptr;
         bool piped = false;
-        uint8_t* base = nullptr;  // the cells of a piped ring: h_d2h (own_d2h), else the free pinned slots
+        uint8_t* base = nullptr;  // (not owned) the cells of a piped ring: h_d2h (own_d2h), else the free pinned slots
     };
     // The new checkpoint's D2H as the FINAL pass of a report-time close starts it: the pieces whose
     // ranges finished while the later ranges were still being issued (pgh_slots.cpp); the patch /
@@ -265,9 +142,8 @@ struct pgh_ctx {
     // stream, it read ranges that had not run yet -- profiles/r06s/.)
     bool own_d2h = true;
     int d2h_mode = 1;
-    hipStream_t d2h = nullptr;
-    uint8_t* h_d2h = nullptr;
-    size_t d2h_cap = 0;
+    Stream d2h;
+    PinnedBuf h_d2h;
     int copy_threads = 8;
     std::vector<int> local_cpus;  // PGH_NUMA (default on): the GPU's socket, for the copy pool + pinned ring
     std::unique_ptr<CopyPool> pool_copy;
@@ -277,32 +153,27 @@ struct pgh_ctx {
     // DMA does not queue behind it; the HBM bytes and chunk table alternate between two buffers (the
     // DMA of one message beside the decode of the one before).
     struct VarintBuf {
-        uint8_t* bytes = nullptr;
-        size_t cap = 0;
-        pgh::VChunk* tab = nullptr;
-        size_t tab_cap = 0;
-        hipEvent_t done = nullptr;  // the last decode that read this buffer
+        DeviceBuf bytes;
+        DeviceBuf tab;  // pgh::VChunk
+        Event done;     // the last decode that read this buffer
         bool used = false;
     };
     VarintBuf vbuf[2];
     int vbuf_next = 0;
-    hipStream_t dec = nullptr;
-    hipEvent_t dec_in = nullptr;     // copy stream -> dec: a message's bytes and table have landed
-    hipEvent_t dec_last = nullptr;   // the last decode issued: folds wait for it (order_after_ingest)
-    pgh::VChunk* h_vtab = nullptr;   // pinned host image of a chunk table
-    size_t vtab_cap = 0;
-    hipEvent_t vtab_ev = nullptr;    // the last table upload (h_vtab reusable after it)
+    Stream dec;                      // made on first use: a context's fifth stream
+    Event dec_in;                    // copy stream -> dec: a message's bytes and table have landed
+    hipEvent_t dec_last = nullptr;   // (a vbuf's `done`, not owned) the last decode issued: folds wait for it
+    PinnedBuf h_vtab;                // host image of a chunk table (pgh::VChunk)
+    Event vtab_ev;                   // the last table upload (h_vtab reusable after it)
     bool vtab_used = false;
     // page-locked fp32 State messages (below) stage through this buffer
-    uint8_t* d_vbytes = nullptr;
-    size_t vbytes_cap = 0;
+    DeviceBuf d_vbytes;
     // page-locked fp32 State messages (pgh_ingest_state): DMA'd whole into d_vbytes, gathered into the
     // slab row by k_gather_f32 with this chunk table (PGH_PINNED_GATHER=0: one DMA per payload piece)
-    pgh::GChunk* d_gtab = nullptr;
-    pgh::GChunk* h_gtab = nullptr;  // pinned
-    size_t gtab_cap = 0;
-    hipEvent_t gtab_ev = nullptr;    // the last table upload (h_gtab reusable after it)
-    hipEvent_t gdma_ev = nullptr;    // the last message DMA (the caller's buffer is free after it)
+    DeviceBuf d_gtab;  // pgh::GChunk
+    PinnedBuf h_gtab;
+    Event gtab_ev;     // the last table upload (h_gtab reusable after it)
+    Event gdma_ev;     // the last message DMA (the caller's buffer is free after it)
     bool gtab_used = false;
     bool pinned_gather = true;
     // Ranged report ingest (pgh_set_ingest_ranges): a State diff goes to HBM in chunks of
@@ -312,7 +183,7 @@ struct pgh_ctx {
     // the copy stream; the ranged close applies only while rng_seq == copy_seq (nothing issued on
     // the copy stream since the latest ranged ingest) and rng_n chunks cover the shard.
     bool ingest_ranges = false;
-    std::vector<hipEvent_t> rng_ev;
+    std::vector<hipEvent_t> rng_ev;  // ev_pool's
     uint64_t copy_seq = 0, rng_seq = ~0ull;
     int rng_n = 0;
     bool warmup_skipped = false;  // pgh_create's warm-up failed (e.g. no device memory left): skipped
@@ -323,7 +194,6 @@ struct pgh_ctx {
     // (PGH_FINAL_RANGES, shards of >= 1 M params; opt-in, see final_split below).
     struct RangeMark { int64_t end; hipEvent_t ev; };
     std::vector<RangeMark> final_marks;
-    std::vector<hipEvent_t> rmark_pool;
     // PGH_FINAL_RANGES (opt-in): split the FINAL pass of resident folds into this many param ranges
     // with marks, so a following D2H starts behind the first range.  Off by default: each extra
     // launch costs its drain (ResNet-18 fold 7.45 ms as 4 ranges on two streams vs 6.91 ms as one,
@@ -345,10 +215,10 @@ struct pgh_ctx {
     std::vector<uint8_t> sq_state;    // per slot
     std::vector<double> sq_host;      // per slot: the cached sum of squares
     std::vector<int32_t> sq_queued;   // slots that went QUEUED since the last harvest
-    double* d_sq_part = nullptr;      // [slots][ceil(pg / SUMSQ_TILE)] tile partials
-    double* d_sq = nullptr;           // [slots]
-    double* h_sq = nullptr;           // pinned [slots]
-    hipEvent_t sq_ev = nullptr;
+    DeviceBuf d_sq_part;              // double [slots][ceil(pg / SUMSQ_TILE)] tile partials
+    DeviceBuf d_sq;                   // double [slots]
+    PinnedBuf h_sq;                   // double [slots]
+    Event sq_ev;
     // the scales live in `weights` (fold order) and go to the device like weights.  Resident folds:
     // clip_scales_valid says weights[0, n) are the scales of the slab as it is (range folds reuse them).
     bool clip_scales_valid = false;
@@ -365,7 +235,6 @@ struct pgh_ctx {
     int variant = PGH_DEFAULT_VARIANT;
     struct Timed { hipEvent_t a, b; uint64_t bytes; };
     std::vector<Timed> pending;
-    std::vector<hipEvent_t> pool;
     pgh_stats_t st{};
     std::string err;
 };
@@ -423,7 +292,7 @@ void free_slab(pgh_ctx* c);
 inline pgh::SlabMap slab_map(const pgh_ctx* c) { return pgh::SlabMap{c->bw, c->bstride, c->bshift, c->bmask, 0}; }
 inline uint8_t* slot_row(pgh_ctx* c, int slot, int party) {
     const size_t row = (size_t)slot * c->parties + party;
-    return (uint8_t*)c->d_slab + row * (size_t)c->bw * esize(c->dtype);
+    return c->d_slab.as<uint8_t>() + row * (size_t)c->bw * esize(c->dtype);
 }
 
 // Where host bytes land: a slab row (blocked) or a [p] vector (one block).
@@ -451,7 +320,7 @@ int timed_launch(pgh_ctx* c, hipStream_t s, uint64_t bytes, F&& launch) {
     CK(c, hipEventRecord(a, s));
     hipError_t e = launch();
     if (e != hipSuccess) {
-        c->pool.push_back(a); c->pool.push_back(b);
+        c->timing_pool.give(a); c->timing_pool.give(b);
         return fail(c, PGH_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     }
     CK(c, hipEventRecord(b, s));
@@ -460,15 +329,6 @@ int timed_launch(pgh_ctx* c, hipStream_t s, uint64_t bytes, F&& launch) {
 }
 
 // ---- host <-> HBM --------------------------------------------------------------------------------
-struct Piece {
-    const uint8_t* src;
-    size_t n;
-};
-struct OutPiece {
-    uint8_t* dst;
-    size_t n;
-};
-
 // HBM -> host results move in pieces of at most D2H_PIECE, the later pieces' DMAs beside the host
 // copy-out of the earlier ones (r01ac: 4, 8, 16 MiB within the noise of the 47 MB report-time close;
 // with the parallel pre-fault, r01ak, 8 MiB pieces closed in 2.3-2.4 ms vs 2.6-2.7 for one piece).
@@ -488,9 +348,6 @@ int stage_pieces_h2d(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& piec
 int stage_pieces_h2d_ranged(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& pieces, size_t total);
 bool ranged_ingest_valid(const pgh_ctx* c);
 int stage_h2d(pgh_ctx* c, const Dest& dst, const uint8_t* src, size_t n, bool pinned_src);
-void scatter_out(const uint8_t* src, size_t off, size_t len, const std::vector<OutPiece>& pieces, CopyPool& pool);
-void prefault_small_any(uint8_t* p, size_t n);
-void prefault_parallel(uint8_t* p, size_t n, CopyPool& pool);
 int stage_d2h_pieces(pgh_ctx* c, const uint8_t* src, const std::vector<OutPiece>& pieces, hipStream_t s,
                      const std::function<void()>& overlap = nullptr, bool marks = false);
 // may_wait = false: both pinned slots still busy -> r->n_free == 0 (nothing set up) instead of waiting
@@ -507,11 +364,11 @@ int host_dma_queued(pgh_ctx* c, const void* p, size_t n, hipStream_t s);
 // ---- ordering between ingest copies and folds -----------------------------------------------------
 int order_after_ingest(pgh_ctx* c, hipStream_t s);
 void release_slot_fold_events(pgh_ctx* c);
-int record_slab_fold(pgh_ctx* c, hipStream_t s);
 int record_slot_fold(pgh_ctx* c, const int32_t* slots, int n);
 int order_slot_overwrite(pgh_ctx* c, int slot);
 int order_before_overwrite(pgh_ctx* c);
-int record_fold(pgh_ctx* c, hipStream_t s);
+// the fold just issued on stream s joins `evs`: fold_evs, or slab_evs for one reading every slab row
+int record_fold(pgh_ctx* c, std::vector<std::pair<hipStream_t, hipEvent_t>>& evs, hipStream_t s);
 void clear_marks(pgh_ctx* c);
 int order_stream_overwrite(pgh_ctx* c, int64_t last_client);
 int record_mark(pgh_ctx* c, hipStream_t s, int64_t upto);

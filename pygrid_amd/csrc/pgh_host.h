@@ -1,0 +1,153 @@
+// HIP-free host code of libpygrid_hip (not installed): the non-temporal copy, the copy pool, the
+// scatter out of a landed piece, page pre-faulting, the CPU count.  Nothing here may include HIP.
+#pragma once
+#include <algorithm>
+#include <condition_variable>
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+namespace pgh_int { int usable_cpus(); }  // (documented in pgh_internal.h)
+
+namespace pgh_detail {
+
+// memcpy with non-temporal 16-byte stores for big copies into staging / output buffers (no
+// read-for-ownership of the destination, which is written once and then read by the DMA engine or
+// handed to the caller; r01ab).
+void copy_stream(uint8_t* dst, const uint8_t* src, size_t n);
+// Bind the calling thread to `cpus` (no-op when empty or refused).
+void bind_thread(const std::vector<int>& cpus);
+
+// Host copy engine: a persistent pool that splits one batch of (dst, src, n) segments evenly
+// by bytes across its threads (the caller's thread takes the first share).  Used to fill and
+// drain the pinned staging slots, where payload pieces are many and mostly small.
+class CopyPool {
+  public:
+    struct Seg {
+        uint8_t* dst;
+        const uint8_t* src;
+        size_t n;
+    };
+    explicit CopyPool(int threads, std::vector<int> cpus = {}) : nthreads_(std::max(1, threads)) {
+        for (int t = 1; t < nthreads_; ++t)
+            workers_.emplace_back([this, t, cpus] {
+                bind_thread(cpus);
+                loop(t);
+            });
+    }
+    ~CopyPool() {
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            stop_ = true;
+            ++gen_;
+        }
+        cv_.notify_all();
+        for (auto& w : workers_) w.join();
+    }
+    int threads() const { return nthreads_; }
+    void run(const std::vector<Seg>& segs) {
+        size_t total = 0;
+        for (auto& sg : segs) total += sg.n;
+        if (total < (4u << 20) || nthreads_ == 1) { copy_range(segs, 0, total); return; }
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            segs_ = &segs;
+            total_ = total;
+            pending_ = nthreads_ - 1;
+            ++gen_;
+        }
+        cv_.notify_all();
+        copy_range(segs, 0, share(total, 0));
+        std::unique_lock<std::mutex> lk(m_);
+        done_cv_.wait(lk, [this] { return pending_ == 0; });
+        segs_ = nullptr;
+    }
+
+    // f(i) for every i in [0, n), items split into contiguous runs over the threads (the caller's
+    // thread takes the first run).  Small jobs stay on the caller's thread.
+    void run_items(int n, bool parallel, const std::function<void(int)>& f) {
+        if (!parallel || nthreads_ == 1 || n < 2) { for (int i = 0; i < n; ++i) f(i); return; }
+        const int per = (n + nthreads_ - 1) / nthreads_;
+        std::function<void(int)> job = [&](int t) {
+            for (int i = t * per; i < std::min(n, (t + 1) * per); ++i) f(i);
+        };
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            fn_ = &job;
+            pending_ = nthreads_ - 1;
+            ++gen_;
+        }
+        cv_.notify_all();
+        job(0);
+        std::unique_lock<std::mutex> lk(m_);
+        done_cv_.wait(lk, [this] { return pending_ == 0; });
+        fn_ = nullptr;
+    }
+
+  private:
+    size_t share(size_t total, int t) const {  // [begin, end) of thread t, 4 KiB granules
+        const size_t per = ((total + nthreads_ - 1) / nthreads_ + 4095) & ~(size_t)4095;
+        return std::min(total, per * (size_t)(t + 1));
+    }
+    static void copy_range(const std::vector<Seg>& segs, size_t a, size_t b) {
+        size_t base = 0;
+        for (auto& sg : segs) {
+            const size_t lo = std::max(a, base), hi = std::min(b, base + sg.n);
+            if (lo < hi) copy_stream(sg.dst + (lo - base), sg.src + (lo - base), hi - lo);
+            base += sg.n;
+            if (base >= b) break;
+        }
+    }
+    void loop(int t) {
+        uint64_t seen = 0;
+        for (;;) {
+            const std::vector<Seg>* segs;
+            const std::function<void(int)>* fn;
+            size_t total;
+            {
+                std::unique_lock<std::mutex> lk(m_);
+                cv_.wait(lk, [&] { return gen_ != seen; });
+                seen = gen_;
+                if (stop_) return;
+                segs = segs_;
+                fn = fn_;
+                total = total_;
+            }
+            if (fn) {
+                (*fn)(t);
+            } else {
+                const size_t a = t == 0 ? 0 : share(total, t - 1);
+                copy_range(*segs, std::min(a, total), share(total, t));
+            }
+            std::lock_guard<std::mutex> lk(m_);
+            if (--pending_ == 0) done_cv_.notify_one();
+        }
+    }
+    int nthreads_;
+    std::vector<std::thread> workers_;
+    std::mutex m_;
+    std::condition_variable cv_, done_cv_;
+    const std::vector<Seg>* segs_ = nullptr;
+    const std::function<void(int)>* fn_ = nullptr;
+    size_t total_ = 0;
+    int pending_ = 0;
+    uint64_t gen_ = 0;
+    bool stop_ = false;
+};
+
+struct Piece {
+    const uint8_t* src;
+    size_t n;
+};
+struct OutPiece {
+    uint8_t* dst;
+    size_t n;
+};
+void scatter_out(const uint8_t* src, size_t off, size_t len, const std::vector<OutPiece>& pieces, CopyPool& pool);
+void prefault_small_any(uint8_t* p, size_t n);
+void prefault_parallel(uint8_t* p, size_t n, CopyPool& pool);
+
+}  // namespace pgh_detail

@@ -168,21 +168,6 @@ int check_share_msg(pgh_ctx* c, ShareMsg* m, int client, int party) {
     return PGH_OK;
 }
 
-int grow_device(pgh_ctx* c, void** p, size_t* cap, size_t need, const char* what) {
-    if (need <= *cap) return PGH_OK;
-    const size_t sz = std::max(need, *cap * 3 / 2);
-    CK(c, hipStreamSynchronize(c->copy));  // an earlier decode may still read the old buffer
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, sz) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PGH_E_OOM, "%s: device allocation of %zu bytes failed", what, sz);
-    }
-    *cap = sz;
-    return PGH_OK;
-}
-
 // Stage one party message: chunk bytes -> pinned ring (copied and counted by the pool threads)
 // -> its region of the HBM byte buffer `dev`, on the copy stream.  Nothing is decoded yet.
 int stage_share_msg(pgh_ctx* c, ShareMsg& m, uint8_t* dev) {
@@ -197,7 +182,7 @@ int stage_share_msg(pgh_ctx* c, ShareMsg& m, uint8_t* dev) {
         size_t k1 = k;
         while (k1 < nk && (size_t)m.chunks[k1].off + (size_t)m.chunks[k1].n - s0 <= cap) ++k1;
         if (k1 == k) return fail(c, PGH_E_STATE, "pinned slot smaller than one varint chunk");
-        uint8_t* pin = c->h_pin[ps];
+        uint8_t* pin = c->h_pin[ps].as<uint8_t>();
         const size_t fill = (size_t)m.chunks[k1 - 1].off + (size_t)m.chunks[k1 - 1].n - s0;
         c->pool_copy->run_items((int)(k1 - k), fill >= (4u << 20), [&](int i) {
             const size_t q = k + (size_t)i;
@@ -240,52 +225,43 @@ int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>
     }
     ranged = ranged && dst == c->pg;
     if (tab.empty()) return PGH_OK;
-    RC(grow_device(c, (void**)&c->d_vbytes, &c->vbytes_cap, b - a + 16, "pinned message buffer"));
     const size_t tb = tab.size() * sizeof(pgh::GChunk);
-    if (!c->gtab_ev) CK(c, hipEventCreateWithFlags(&c->gtab_ev, hipEventDisableTiming));
-    if (!c->gdma_ev) CK(c, hipEventCreateWithFlags(&c->gdma_ev, hipEventDisableTiming));
+    // regrown only behind the copy stream: an earlier gather may still read the old buffers
+    if (b - a + 16 > c->d_vbytes.cap() || tb > c->d_gtab.cap()) CK(c, hipStreamSynchronize(c->copy));
+    if (!c->d_vbytes.reserve_geometric(b - a + 16))
+        return fail(c, PGH_E_OOM, "pinned message buffer: device allocation of %zu bytes failed", b - a + 16);
     if (c->gtab_used) CK(c, hipEventSynchronize(c->gtab_ev));  // the previous table upload read h_gtab
-    if (tb > c->gtab_cap) {
-        if (c->h_gtab) (void)hipHostFree(c->h_gtab);
-        c->h_gtab = nullptr;
-        size_t cap = 0;
-        void* d = c->d_gtab;
-        RC(grow_device(c, &d, &cap, tb, "gather chunk table"));
-        c->d_gtab = (pgh::GChunk*)d;
-        if (hipHostMalloc((void**)&c->h_gtab, cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            c->gtab_cap = 0;
-            return fail(c, PGH_E_OOM, "pinned gather table of %zu bytes failed", cap);
+    if (tb > c->d_gtab.cap()) {
+        if (!c->d_gtab.reserve(tb) || !c->h_gtab.reserve(tb)) {
+            c->d_gtab.reset();  // (the test above: both or neither)
+            return fail(c, PGH_E_OOM, "gather chunk table of %zu bytes failed", tb);
         }
-        c->gtab_cap = cap;
         c->gtab_used = false;
     }
-    std::memcpy(c->h_gtab, tab.data(), tb);
+    pgh::GChunk* const d_gtab = c->d_gtab.as<pgh::GChunk>();
+    uint8_t* const d_vbytes = c->d_vbytes.as<uint8_t>();
+    std::memcpy(c->h_gtab.as<void>(), tab.data(), tb);
     ++c->copy_seq;
-    CK(c, hipMemcpyAsync(c->d_gtab, c->h_gtab, tb, hipMemcpyHostToDevice, c->copy));
+    CK(c, hipMemcpyAsync(d_gtab, c->h_gtab.as<void>(), tb, hipMemcpyHostToDevice, c->copy));
     CK(c, hipEventRecord(c->gtab_ev, c->copy));
     c->gtab_used = true;
     const Dest d = row_dest(c, slot, 0);
     const bool async = host_async(pb + a, b - a);
     if (ranged) {
         const int K = (int)((c->pg + INGEST_CHUNK - 1) / INGEST_CHUNK);
-        while ((int)c->rng_ev.size() < K) {
-            hipEvent_t ev = nullptr;
-            CK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            c->rng_ev.push_back(ev);
-        }
+        if (!c->ev_pool.fill(c->rng_ev, (size_t)K)) return fail(c, PGH_E_HIP, "hipEventCreate failed");
         size_t e0 = 0;
         for (int k = 0; k < K; ++k) {
             size_t e1 = e0;
             while (e1 < tab.size() && tab[e1].dst < (int64_t)(k + 1) * INGEST_CHUNK) ++e1;
             if (e1 > e0) {
                 const size_t lo = (size_t)tab[e0].src, hi = (size_t)tab[e1 - 1].src + 4 * (size_t)tab[e1 - 1].n;
-                CK(c, hipMemcpyAsync(c->d_vbytes + lo, pb + a + lo, hi - lo, hipMemcpyHostToDevice, c->copy));
+                CK(c, hipMemcpyAsync(d_vbytes + lo, pb + a + lo, hi - lo, hipMemcpyHostToDevice, c->copy));
                 if (e1 == tab.size()) {  // the message's last DMA: the host block is read once this is done
                     if (async) RC(host_dma_queued(c, pb + a, b - a, c->copy));
                     else CK(c, hipEventRecord(c->gdma_ev, c->copy));
                 }
-                const hipError_t e = pgh::launch_gather_f32(c->d_vbytes, c->d_gtab + e0, (int)(e1 - e0),
+                const hipError_t e = pgh::launch_gather_f32(d_vbytes, d_gtab + e0, (int)(e1 - e0),
                                                             (float*)d.base, d.map, c->copy);
                 if (e != hipSuccess) return fail(c, PGH_E_HIP, "gather launch failed: %s", hipGetErrorString(e));
             }
@@ -295,10 +271,10 @@ int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>
         c->rng_seq = c->copy_seq;
         c->rng_n = K;
     } else {
-        CK(c, hipMemcpyAsync(c->d_vbytes, pb + a, b - a, hipMemcpyHostToDevice, c->copy));
+        CK(c, hipMemcpyAsync(d_vbytes, pb + a, b - a, hipMemcpyHostToDevice, c->copy));
         if (async) RC(host_dma_queued(c, pb + a, b - a, c->copy));  // the block's owner waits (pgh_host_wait)
         else CK(c, hipEventRecord(c->gdma_ev, c->copy));
-        const hipError_t e = pgh::launch_gather_f32(c->d_vbytes, c->d_gtab, (int)tab.size(), (float*)d.base, d.map,
+        const hipError_t e = pgh::launch_gather_f32(d_vbytes, d_gtab, (int)tab.size(), (float*)d.base, d.map,
                                                     c->copy);
         if (e != hipSuccess) return fail(c, PGH_E_HIP, "gather launch failed: %s", hipGetErrorString(e));
     }
@@ -308,18 +284,15 @@ int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>
 }
 
 // A varint buffer holding `bytes` of messages and a table of `tab_bytes` (grown when short, after
-// the decode that last read it).  The dec stream and its events are made on the first use.
+// the decode that last read it).  The dec stream is made on the first use.
 int prepare_vbuf(pgh_ctx* c, pgh_ctx::VarintBuf& b, size_t bytes, size_t tab_bytes) {
-    if (!c->dec) {
-        CK(c, hipStreamCreateWithFlags(&c->dec, hipStreamNonBlocking));
-        CK(c, hipEventCreateWithFlags(&c->dec_in, hipEventDisableTiming));
-        for (auto& x : c->vbuf) CK(c, hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
+    if (!c->dec) CK(c, c->dec.make());
+    if (bytes > b.bytes.cap() || tab_bytes > b.tab.cap()) {  // regrown behind its last decode and the copy stream
+        if (b.used) CK(c, hipEventSynchronize(b.done));
+        CK(c, hipStreamSynchronize(c->copy));
+        if (!b.bytes.reserve_geometric(bytes) || !b.tab.reserve_geometric(tab_bytes))
+            return fail(c, PGH_E_OOM, "share payload buffer / varint chunk table: device allocation failed");
     }
-    if ((bytes > b.cap || tab_bytes > b.tab_cap) && b.used) CK(c, hipEventSynchronize(b.done));
-    RC(grow_device(c, (void**)&b.bytes, &b.cap, bytes, "share payload buffer"));
-    void* t = b.tab;
-    RC(grow_device(c, &t, &b.tab_cap, tab_bytes, "varint chunk table"));
-    b.tab = (pgh::VChunk*)t;
     // the copy stream's DMAs into this buffer wait for the decode that last read it (two messages ago)
     if (b.used) CK(c, hipStreamWaitEvent(c->copy, b.done, 0));
     return PGH_OK;
@@ -332,27 +305,20 @@ int decode_share_msgs(pgh_ctx* c, std::vector<ShareMsg>& msgs, int slot, pgh_ctx
     for (auto& m : msgs) nk += m.chunks.size();
     if (nk == 0) return PGH_OK;  // every tensor empty
     const size_t tb = nk * sizeof(pgh::VChunk);
-    if (!c->vtab_ev) CK(c, hipEventCreateWithFlags(&c->vtab_ev, hipEventDisableTiming));
     if (c->vtab_used) CK(c, hipEventSynchronize(c->vtab_ev));  // the previous table upload read h_vtab
-    if (tb > c->vtab_cap) {
-        if (c->h_vtab) (void)hipHostFree(c->h_vtab);
-        c->h_vtab = nullptr;
-        c->vtab_cap = 0;
-        if (hipHostMalloc((void**)&c->h_vtab, b.tab_cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            c->h_vtab = nullptr;
-            return fail(c, PGH_E_OOM, "pinned chunk table of %zu bytes failed", b.tab_cap);
-        }
-        c->vtab_cap = b.tab_cap;
+    if (tb > c->h_vtab.cap()) {
+        if (!c->h_vtab.reserve(b.tab.cap())) return fail(c, PGH_E_OOM, "pinned chunk table of %zu bytes failed", b.tab.cap());
         c->vtab_used = false;
     }
+    pgh::VChunk* const h_vtab = c->h_vtab.as<pgh::VChunk>();
+    pgh::VChunk* const d_tab = b.tab.as<pgh::VChunk>();
     size_t at = 0;
     for (auto& m : msgs) {
-        std::memcpy(c->h_vtab + at, m.chunks.data(), m.chunks.size() * sizeof(pgh::VChunk));
+        std::memcpy(h_vtab + at, m.chunks.data(), m.chunks.size() * sizeof(pgh::VChunk));
         at += m.chunks.size();
     }
     ++c->copy_seq;
-    CK(c, hipMemcpyAsync(b.tab, c->h_vtab, tb, hipMemcpyHostToDevice, c->copy));
+    CK(c, hipMemcpyAsync(d_tab, h_vtab, tb, hipMemcpyHostToDevice, c->copy));
     CK(c, hipEventRecord(c->vtab_ev, c->copy));
     c->vtab_used = true;
     CK(c, hipEventRecord(c->dec_in, c->copy));
@@ -360,7 +326,7 @@ int decode_share_msgs(pgh_ctx* c, std::vector<ShareMsg>& msgs, int slot, pgh_ctx
     at = 0;
     for (size_t s = 0; s < msgs.size(); ++s) {
         const int n = (int)msgs[s].chunks.size();
-        const hipError_t e = pgh::launch_varint_decode(b.bytes, b.tab + at, n, (int64_t*)slot_row(c, slot, (int)s),
+        const hipError_t e = pgh::launch_varint_decode(b.bytes.as<uint8_t>(), d_tab + at, n, (int64_t*)slot_row(c, slot, (int)s),
                                                        slab_map(c), c->lo, c->hi, c->dec);
         if (e != hipSuccess) return fail(c, PGH_E_HIP, "varint decode launch failed: %s", hipGetErrorString(e));
         at += (size_t)n;
@@ -396,7 +362,7 @@ int pgh_ingest_state_shares(pgh_ctx* c, int client, int n_parties, const uint8_t
     pgh_ctx::VarintBuf& b = c->vbuf[c->vbuf_next];
     c->vbuf_next ^= 1;
     RC(prepare_vbuf(c, b, total + 16, std::max<size_t>(nk, 1) * sizeof(pgh::VChunk)));
-    for (auto& m : msgs) RC(stage_share_msg(c, m, b.bytes));
+    for (auto& m : msgs) RC(stage_share_msg(c, m, b.bytes.as<uint8_t>()));
     for (int s = 0; s < n_parties; ++s) RC(check_share_msg(c, &msgs[(size_t)s], client, s));
     RC(decode_share_msgs(c, msgs, slot, b));
     return mark_ingested(c, client, slot);
@@ -491,10 +457,10 @@ int pgh_synth_ckpt_device(pgh_ctx* c, uint64_t seed, float* d_ckpt, void* stream
     if (!c->d_ckpt) return fail(c, PGH_E_STATE, "pgh_reserve has not been called");
     c->ckpt_valid = false;  // the resident checkpoint is used as scratch here
     clear_final_marks(c);
-    hipError_t e = pgh::launch_synth_f32(c->d_ckpt, pgh::single_block(c->pvec), c->pvec, 1, c->pg, seed,
+    hipError_t e = pgh::launch_synth_f32(c->d_ckpt.as<float>(), pgh::single_block(c->pvec), c->pvec, 1, c->pg, seed,
                                          pgh::STREAM_CKPT, 0, c->lo, pgh::CKPT_SCALE, s);
     if (e != hipSuccess) return fail(c, PGH_E_HIP, "synthetic checkpoint failed: %s", hipGetErrorString(e));
-    CK(c, hipMemcpyAsync(d_ckpt, c->d_ckpt, sizeof(float) * c->pg, hipMemcpyDeviceToDevice, s));
+    CK(c, hipMemcpyAsync(d_ckpt, c->d_ckpt.as<float>(), sizeof(float) * c->pg, hipMemcpyDeviceToDevice, s));
     return PGH_OK;
 }
 

@@ -1,4 +1,4 @@
-// libpygrid_hip: RESIDENT folds (every ingested client in one launch, repeatable), the resident
+// libpygrid_hip: fold_run and its bookkeeping, RESIDENT folds (every ingested client in one launch, repeatable), the resident
 // checkpoint kept in HBM across cycles, secure aggregation (Z_2^64 share sum + fixed-point decode) and
 // STREAM folds (a ring of slots folded in client order while ingest continues).  Reference:
 // cycle_manager.py:252-296 (fedavg), test_basic_syft_operations.py:417-424 (secagg).
@@ -10,6 +10,207 @@
 using namespace pgh_detail;
 
 // (the public entry points take their C linkage from include/pgh_api.h)
+
+// ---- the fold itself, its weights and divisors, the STREAM / RESIDENT bookkeeping -------------------
+
+namespace pgh_detail {
+
+int sync_weights(pgh_ctx* c, hipStream_t s) {
+    if (c->weights_on_device || c->weights.empty()) return PGH_OK;
+    if (!c->d_w.reserve(sizeof(float) * c->weights.size())) return fail(c, PGH_E_OOM, "weight vector allocation failed");
+    CK(c, hipMemcpyAsync(c->d_w.as<float>(), c->weights.data(), sizeof(float) * c->weights.size(), hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // c->weights may change after return
+    c->weights_on_device = true;
+    return PGH_OK;
+}
+
+// Reciprocal table covering clients [0, n) for the iterative fold's division (div_by_count in
+// pgh_kernels.hip).  Grows geometrically; the upload is ordered before stream `s`'s next fold.
+int ensure_recips(pgh_ctx* c, int64_t n, hipStream_t s) {
+    const int64_t have = (int64_t)(c->d_rec.cap() / sizeof(double));
+    if (n <= have) return PGH_OK;
+    const int64_t cap = std::max<int64_t>({n, 2 * have, 4096});
+    std::vector<double> h((size_t)cap);
+    for (int64_t k = 0; k < cap; ++k) h[(size_t)k] = 1.0 / (double)(float)(k + 1);  // y as the plan sees it
+    pgh_ctx::DeviceBuf d;
+    if (!d.reserve(sizeof(double) * (size_t)cap)) return fail(c, PGH_E_OOM, "reciprocal table allocation failed");
+    CK(c, hipMemcpyAsync(d.as<void>(), h.data(), sizeof(double) * (size_t)cap, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // h is freed on return
+    std::swap(c->d_rec, d);
+    if (d) c->rec_old.push_back(std::move(d));  // an in-flight fold may read it: kept until pgh_destroy
+    return PGH_OK;
+}
+
+int fixed_point_divisor(pgh_ctx* c, int base, int prec, float* div) {
+    if (base < 2 || prec < 0 || prec > 18) return fail(c, PGH_E_ARG, "bad fixed-point base %d / precision %d", base, prec);
+    long double scale = 1;
+    for (int k = 0; k < prec; ++k) scale *= base;
+    if (scale > 9.2e18L) return fail(c, PGH_E_ARG, "base**prec overflows int64");
+    *div = (float)(int64_t)scale;  // python int base**prec, promoted to float32 by the division
+    return PGH_OK;
+}
+
+float weight_total(const std::vector<float>& w, int64_t n) {  // left fold, float32
+    float t = w[0];
+    for (int64_t k = 1; k < n; ++k) t = t + w[k];
+    return t;
+}
+
+// Fold slots holding clients [c0, c0 + n) (slot order may wrap) into the running state.
+// FIRST when c0 == 0; FINAL writes out (fedavg: ckpt - avg; secagg: sum/dec) instead of the state.
+int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const FinalArgs& fa, hipStream_t s) {
+    if (kind == PGH_CLIPPED_MEAN) {  // resident only: the weighted fold over the scales of clients [0, n)
+        if (c0 != 0 || !final) return fail(c, PGH_E_UNSUPPORTED, "a clipped mean folds a resident slab in one pass");
+        RC(resident_clip_scales(c, n));
+        kind = PGH_WEIGHTED_MEAN;
+    }
+    RC(order_after_ingest(c, s));
+    if (kind == PGH_WEIGHTED_MEAN && n > 0) {
+        if ((int64_t)c->weights.size() < c0 + n)
+            return fail(c, PGH_E_STATE, "weighted mean: %zu weights for %lld clients", c->weights.size(),
+                        (long long)(c0 + n));
+        RC(sync_weights(c, s));
+    }
+    if (kind == PGH_ITERATIVE_MEAN && n > 0) RC(ensure_recips(c, c0 + n, s));
+    const int R = c->slots;
+    const int64_t off = fa.off;
+    const int64_t len = fa.len < 0 ? c->pg - off : fa.len;
+    if (off < 0 || (off & 3) || len <= 0 || off + len > c->pg)
+        return fail(c, PGH_E_ARG, "param range [%lld,+%lld) outside the shard or not 4-aligned", (long long)off,
+                    (long long)len);
+    int64_t done = 0;
+    do {
+        const int slot = (int)((c0 + done) % R);
+        const int64_t seg = std::min<int64_t>(n - done, (int64_t)(R - slot));
+        const bool first = (c0 + done == 0);
+        const bool last = (done + seg == n);
+        const int flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
+        const uint64_t pg = (uint64_t)len;
+        if (kind == KIND_SECAGG) {
+            pgh::SecaggArgs a{};
+            a.shares = (const int64_t*)slot_row(c, slot, 0);
+            a.map = slab_map(c);
+            a.map.off = off;
+            a.n_rows = (int)(seg * c->parties);
+            a.p = len;
+            a.acc = c->d_uacc.as<uint64_t>() + off;
+            a.sum_out = fa.sum ? fa.sum + off : nullptr;
+            a.dec_out = fa.dec ? fa.dec + off : nullptr;
+            a.divisor = fa.divisor;
+            a.flags = flags;
+            a.variant = c->variant;
+            const uint64_t bytes = 8ull * (uint64_t)a.n_rows * pg + (first ? 0 : 8 * pg) +
+                                   ((flags & pgh::FL_FINAL) ? (fa.sum ? 8 * pg : 0) + (fa.dec ? 4 * pg : 0) : 8 * pg);
+            RC(timed_launch(c, s, bytes, [&] { return pgh::launch_secagg(a, s); }));
+        } else {
+            pgh::FedavgArgs a{};
+            a.diffs = (const float*)slot_row(c, slot, 0);
+            a.map = slab_map(c);
+            a.map.off = off;
+            a.n_rows = (int)seg;
+            a.client0 = c0 + done;
+            a.p = len;
+            a.weights = c->d_w ? c->d_w.as<float>() + (c0 + done) : nullptr;
+            a.recips = c->d_rec ? c->d_rec.as<double>() + (c0 + done) : nullptr;
+            a.acc = c->d_acc.as<float>() + off;
+            a.ckpt = fa.ckpt ? fa.ckpt + off : nullptr;
+            a.out = fa.out ? fa.out + off : nullptr;
+            a.divisor = fa.divisor;
+            a.flags = flags;
+            a.mode = kind;
+            a.variant = c->variant;
+            const uint64_t bytes = 4ull * (uint64_t)seg * pg + (first ? 0 : 4 * pg) +
+                                   ((flags & pgh::FL_FINAL) ? 8 * pg : 4 * pg);
+            RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
+        }
+        done += seg;
+    } while (done < n);
+    RC(record_fold(c, c->fold_evs, s));
+    return record_fold(c, c->slab_evs, s);  // it read every slab row
+}
+
+// Length of the run of ingested clients starting at `from` (slot ring order).
+int64_t ready_run(pgh_ctx* c, int64_t from) {
+    int64_t n = 0;
+    while (n < c->slots && c->slot_client[(size_t)((from + n) % c->slots)] == from + n) ++n;
+    return n;
+}
+
+// Every ingested client must belong to the contiguous run starting at `from`.
+int check_no_gaps(pgh_ctx* c, int64_t from, int64_t run) {
+    for (int s = 0; s < c->slots; ++s) {
+        const int64_t k = c->slot_client[(size_t)s];
+        if (k >= 0 && (k < from || k >= from + run))
+            return fail(c, PGH_E_STATE, "client %lld is missing but client %lld was ingested",
+                        (long long)(from + run), (long long)k);
+    }
+    return PGH_OK;
+}
+
+// STREAM: fold the ready run when it reaches the batch size (or always, when forced).
+int maybe_fold(pgh_ctx* c, bool force) {
+    const int64_t run = ready_run(c, c->folded);
+    if (run == 0 || (!force && run < c->fold_batch)) return PGH_OK;
+    RC(fold_run(c, c->kind, c->folded, run, false, FinalArgs{}, c->stream));
+    for (int64_t k = 0; k < run; ++k) c->slot_client[(size_t)((c->folded + k) % c->slots)] = -1;
+    c->folded += run;
+    c->st.n_folded = c->folded;
+    return record_mark(c, c->stream, c->folded);
+}
+
+// Claim the slot for `client` (both modes) before bytes are written to it.
+int claim_slot(pgh_ctx* c, int64_t client, int* slot_out) {
+    if (client < 0) return fail(c, PGH_E_ARG, "negative client index");
+    if (!c->streaming) {
+        if (client >= c->slots)
+            return fail(c, PGH_E_ARG, "client %lld outside slab capacity %d", (long long)client, c->slots);
+        RC(order_slot_overwrite(c, (int)client));  // a fold issued earlier may still read the slot
+        c->sq_state[(size_t)client] = pgh_ctx::SQ_NONE;  // the cached sum of squares was the old diff's
+        c->clip_scales_valid = false;
+        *slot_out = (int)client;
+        return PGH_OK;
+    }
+    if (client < c->folded) return fail(c, PGH_E_STATE, "client %lld was already folded", (long long)client);
+    const int slot = (int)(client % c->slots);
+    const int64_t held = c->slot_client[(size_t)slot];
+    if (held >= 0 && held != client)
+        return fail(c, PGH_E_STATE, "ring full: slot %d still holds unfolded client %lld (fold front %lld)", slot,
+                    (long long)held, (long long)c->folded);
+    RC(order_stream_overwrite(c, client));
+    *slot_out = slot;
+    return PGH_OK;
+}
+
+int mark_ingested(pgh_ctx* c, int64_t client, int slot) {
+    if (c->slot_client[(size_t)slot] != client) c->st.n_clients += 1;
+    c->slot_client[(size_t)slot] = client;
+    return c->streaming ? maybe_fold(c, false) : PGH_OK;
+}
+
+// RESIDENT: clients [0, n) all present, nothing else.
+int resident_count(pgh_ctx* c, int64_t* n_out) {
+    if (c->streaming) return fail(c, PGH_E_STATE, "context is streaming: finish with pgh_stream_finish*");
+    int64_t n = ready_run(c, 0);
+    RC(check_no_gaps(c, 0, n));
+    if (n == 0) return fail(c, PGH_E_STATE, "no diffs ingested");
+    *n_out = n;
+    return PGH_OK;
+}
+
+int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
+    if (mode == PGH_WEIGHTED_MEAN) {
+        if ((int64_t)c->weights.size() < n)
+            return fail(c, PGH_E_STATE, "weighted mean needs %lld weights, have %zu", (long long)n, c->weights.size());
+        const float t = weight_total(c->weights, n);
+        if (!(t != 0.f)) return fail(c, PGH_E_ARG, "sum of weights is zero");
+        *div = t;
+    } else {
+        *div = (float)n;  // th.div(sum, len(diffs)), cycle_manager.py:288
+    }
+    return PGH_OK;
+}
+
+}  // namespace pgh_detail
 
 // ---- clipped FedAvg: per-row sums of squares (K7), their host cache, the scales --------------------
 
@@ -37,10 +238,9 @@ void sumsq_forget(pgh_ctx* c) {
 }
 
 void free_clip(pgh_ctx* c) {  // the copy stream is idle (free_slab synchronised it)
-    (void)hipFree(c->d_sq_part); c->d_sq_part = nullptr;
-    (void)hipFree(c->d_sq); c->d_sq = nullptr;
-    if (c->h_sq) (void)hipHostFree(c->h_sq);
-    c->h_sq = nullptr;
+    c->d_sq_part.reset();
+    c->d_sq.reset();
+    c->h_sq.reset();
     c->sq_state.clear();
     c->sq_host.clear();
     sumsq_forget(c);
@@ -51,14 +251,8 @@ int ensure_sumsq_buffers(pgh_ctx* c) {
     if (c->d_sq_part) return PGH_OK;
     const size_t ntiles = (size_t)((c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE);
     const size_t rows = (size_t)c->slots;
-    if (!c->sq_ev) CK(c, hipEventCreateWithFlags(&c->sq_ev, hipEventDisableTiming));
-    if (hipMalloc((void**)&c->d_sq_part, 8 * rows * ntiles) != hipSuccess ||
-        hipMalloc((void**)&c->d_sq, 8 * rows) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_sq, 8 * rows, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(c->d_sq_part); c->d_sq_part = nullptr;
-        (void)hipFree(c->d_sq); c->d_sq = nullptr;
-        c->h_sq = nullptr;
+    if (!c->d_sq_part.reserve(8 * rows * ntiles) || !c->d_sq.reserve(8 * rows) || !c->h_sq.reserve(8 * rows)) {
+        c->d_sq_part.reset();  // (the test above: all three or none)
         return fail(c, PGH_E_OOM, "allocation of the clipping sums (%zu rows x %zu tiles) failed", rows, ntiles);
     }
     return PGH_OK;
@@ -72,12 +266,12 @@ int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n) {
     if (todo.empty()) return PGH_OK;
     RC(ensure_sumsq_buffers(c));
     pgh::SumsqArgs a{};
-    a.slab = (const float*)c->d_slab;
+    a.slab = c->d_slab.as<float>();
     a.map = slab_map(c);
     a.p = c->pg;
     a.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
-    a.part = c->d_sq_part;
-    a.sumsq = c->d_sq;
+    a.part = c->d_sq_part.as<double>();
+    a.sumsq = c->d_sq.as<double>();
     const hipStream_t s = c->copy;
     bool run = true;  // consecutive slots: one launch over contiguous rows
     int32_t lo = todo[0], hi = todo[0];
@@ -102,7 +296,7 @@ int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n) {
     }
     // entries of other slots inside [lo, hi] are rewritten with what the device holds for them: the
     // same value an earlier copy brought (same stream), or one nobody reads
-    CK(c, hipMemcpyAsync(c->h_sq + lo, c->d_sq + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
+    CK(c, hipMemcpyAsync(c->h_sq.as<double>() + lo, c->d_sq.as<double>() + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
     CK(c, hipEventRecord(c->sq_ev, s));
     for (int32_t sl : todo) {
         c->sq_state[(size_t)sl] = pgh_ctx::SQ_QUEUED;
@@ -116,7 +310,7 @@ int sumsq_wait(pgh_ctx* c) {
     CK(c, hipEventSynchronize(c->sq_ev));
     for (int32_t sl : c->sq_queued)
         if (c->sq_state[(size_t)sl] == pgh_ctx::SQ_QUEUED) {
-            c->sq_host[(size_t)sl] = c->h_sq[sl];
+            c->sq_host[(size_t)sl] = c->h_sq.as<double>()[sl];
             c->sq_state[(size_t)sl] = pgh_ctx::SQ_VALID;
         }
     c->sq_queued.clear();
@@ -284,14 +478,14 @@ int pgh_fedavg(pgh_ctx* c, int mode, const float* ckpt, float* out) {
     RC(order_before_overwrite(c));
     c->ckpt_valid = false;
     clear_final_marks(c);
-    RC(stage_h2d(c, vec_dest(c->d_ckpt, c->pvec, 4), (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
+    RC(stage_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
     c->ckpt_valid = true;
-    RC(pgh_fedavg_device(c, mode, c->d_ckpt, c->d_out, c->stream));
+    RC(pgh_fedavg_device(c, mode, c->d_ckpt.as<float>(), c->d_out.as<float>(), c->stream));
     if (is_pinned(out)) {
-        CK(c, hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+        CK(c, hipMemcpyAsync(out, c->d_out.as<float>(), bytes, hipMemcpyDeviceToHost, c->stream));
         CK(c, hipStreamSynchronize(c->stream));
     } else {
-        RC(stage_d2h_pieces(c, (const uint8_t*)c->d_out, {OutPiece{(uint8_t*)out, bytes}}, c->stream));
+        RC(stage_d2h_pieces(c, c->d_out.as<uint8_t>(), {OutPiece{(uint8_t*)out, bytes}}, c->stream));
     }
     c->st.close_ms_last = now_ms() - t0;
     return collect_timings(c);
@@ -312,7 +506,7 @@ int pgh_ckpt_upload(pgh_ctx* c, const float* ckpt, size_t nbytes) {
     const uint8_t* src = (const uint8_t*)ckpt + (nbytes == whole ? 4 * (size_t)c->lo : 0);
     c->ckpt_valid = false;
     clear_final_marks(c);
-    RC(stage_h2d(c, vec_dest(c->d_ckpt, c->pvec, 4), src, shard, is_pinned(ckpt)));
+    RC(stage_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), src, shard, is_pinned(ckpt)));
     c->ckpt_valid = true;
     return PGH_OK;
 }
@@ -329,7 +523,7 @@ int pgh_ckpt_upload_state(pgh_ctx* c, const uint8_t* pb, size_t n) {
     RC(order_before_overwrite(c));
     c->ckpt_valid = false;
     clear_final_marks(c);
-    RC(stage_pieces_h2d(c, vec_dest(c->d_ckpt, c->pvec, 4), pieces));
+    RC(stage_pieces_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), pieces));
     c->ckpt_valid = true;
     return PGH_OK;
 }
@@ -345,13 +539,13 @@ int pgh_fedavg_resident(pgh_ctx* c, int mode) {
     clear_final_marks(c);
     const int K = final_ranges(c);
     if (K == 1) {
-        RC(pgh_fedavg_device(c, mode, c->d_ckpt, c->d_out, c->stream));
+        RC(pgh_fedavg_device(c, mode, c->d_ckpt.as<float>(), c->d_out.as<float>(), c->stream));
     } else {  // the same fold as K range launches, each followed by its mark (pipelined close)
         int64_t n = 0;
         RC(resident_count(c, &n));
         FinalArgs fa;
-        fa.ckpt = c->d_ckpt;
-        fa.out = c->d_out;
+        fa.ckpt = c->d_ckpt.as<float>();
+        fa.out = c->d_out.as<float>();
         RC(fedavg_divisor(c, mode, n, &fa.divisor));
         RC(fork_aux(c, c->stream));
         for (int k = 0; k < K; ++k) {
@@ -377,10 +571,10 @@ int pgh_ckpt_download(pgh_ctx* c, float* out) {
     const size_t bytes = 4 * (size_t)c->pg;
     RC(order_after_ingest(c, c->stream));
     if (is_pinned(out)) {
-        CK(c, hipMemcpyAsync(out, c->d_ckpt, bytes, hipMemcpyDeviceToHost, c->stream));
+        CK(c, hipMemcpyAsync(out, c->d_ckpt.as<float>(), bytes, hipMemcpyDeviceToHost, c->stream));
         CK(c, hipStreamSynchronize(c->stream));
     } else {
-        RC(stage_d2h_pieces(c, (const uint8_t*)c->d_ckpt, {OutPiece{(uint8_t*)out, bytes}}, c->stream, nullptr, true));
+        RC(stage_d2h_pieces(c, c->d_ckpt.as<uint8_t>(), {OutPiece{(uint8_t*)out, bytes}}, c->stream, nullptr, true));
     }
     return collect_timings(c);
 }
@@ -413,7 +607,7 @@ int pgh_ckpt_patch_state(pgh_ctx* c, const uint8_t* tmpl, size_t n, uint8_t* out
     }
     // the framing copy and the pre-fault of the output run while the first slot's DMA flies (in
     // place, out == tmpl, is how a freshly framed checkpoint is filled: its pages are fresh too)
-    RC(stage_d2h_pieces(c, (const uint8_t*)c->d_ckpt, pieces, c->stream, [&] {
+    RC(stage_d2h_pieces(c, c->d_ckpt.as<uint8_t>(), pieces, c->stream, [&] {
         prefault_parallel(out, n, *c->pool_copy);
         if (!gaps.empty()) c->pool_copy->run(gaps);
     }, true));
@@ -469,9 +663,9 @@ int pgh_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, float* dec_out)
     RC(check_dtype(c, PGH_I64));
     DeviceGuard g(c->device);
     const double t0 = now_ms();
-    RC(pgh_secagg_device(c, base, prec, sum_out ? c->d_sum : nullptr, dec_out ? c->d_dec : nullptr, c->stream));
-    if (sum_out) CK(c, hipMemcpyAsync(sum_out, c->d_sum, 8ull * c->pg, hipMemcpyDeviceToHost, c->stream));
-    if (dec_out) CK(c, hipMemcpyAsync(dec_out, c->d_dec, 4ull * c->pg, hipMemcpyDeviceToHost, c->stream));
+    RC(pgh_secagg_device(c, base, prec, sum_out ? c->d_sum.as<int64_t>() : nullptr, dec_out ? c->d_dec.as<float>() : nullptr, c->stream));
+    if (sum_out) CK(c, hipMemcpyAsync(sum_out, c->d_sum.as<int64_t>(), 8ull * c->pg, hipMemcpyDeviceToHost, c->stream));
+    if (dec_out) CK(c, hipMemcpyAsync(dec_out, c->d_dec.as<float>(), 4ull * c->pg, hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     c->st.close_ms_last = now_ms() - t0;
     return collect_timings(c);
@@ -542,7 +736,7 @@ int pgh_stream_finish_resident(pgh_ctx* c) {
     DeviceGuard g(c->device);
     clear_final_marks(c);
     const double t0 = now_ms();
-    RC(pgh_stream_finish_device(c, c->d_ckpt, c->d_out, c->stream));
+    RC(pgh_stream_finish_device(c, c->d_ckpt.as<float>(), c->d_out.as<float>(), c->stream));
     std::swap(c->d_ckpt, c->d_out);  // the new checkpoint is the next cycle's input
     c->st.close_ms_last = now_ms() - t0;
     return PGH_OK;
@@ -561,10 +755,10 @@ int pgh_stream_finish(pgh_ctx* c, const float* ckpt, float* out) {
     RC(order_before_overwrite(c));
     c->ckpt_valid = false;
     clear_final_marks(c);
-    RC(stage_h2d(c, vec_dest(c->d_ckpt, c->pvec, 4), (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
+    RC(stage_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
     c->ckpt_valid = true;
-    RC(pgh_stream_finish_device(c, c->d_ckpt, c->d_out, c->stream));
-    CK(c, hipMemcpyAsync(out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    RC(pgh_stream_finish_device(c, c->d_ckpt.as<float>(), c->d_out.as<float>(), c->stream));
+    CK(c, hipMemcpyAsync(out, c->d_out.as<float>(), bytes, hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     c->st.close_ms_last = now_ms() - t0;
     return collect_timings(c);
@@ -586,10 +780,10 @@ int pgh_stream_finish_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, f
     RC(check_dtype(c, PGH_I64));
     DeviceGuard g(c->device);
     const double t0 = now_ms();
-    RC(pgh_stream_finish_secagg_device(c, base, prec, sum_out ? c->d_sum : nullptr, dec_out ? c->d_dec : nullptr,
+    RC(pgh_stream_finish_secagg_device(c, base, prec, sum_out ? c->d_sum.as<int64_t>() : nullptr, dec_out ? c->d_dec.as<float>() : nullptr,
                                        c->stream));
-    if (sum_out) CK(c, hipMemcpyAsync(sum_out, c->d_sum, 8ull * c->pg, hipMemcpyDeviceToHost, c->stream));
-    if (dec_out) CK(c, hipMemcpyAsync(dec_out, c->d_dec, 4ull * c->pg, hipMemcpyDeviceToHost, c->stream));
+    if (sum_out) CK(c, hipMemcpyAsync(sum_out, c->d_sum.as<int64_t>(), 8ull * c->pg, hipMemcpyDeviceToHost, c->stream));
+    if (dec_out) CK(c, hipMemcpyAsync(dec_out, c->d_dec.as<float>(), 4ull * c->pg, hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     c->st.close_ms_last = now_ms() - t0;
     return collect_timings(c);

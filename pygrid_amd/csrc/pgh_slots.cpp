@@ -63,16 +63,16 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         for (int k = 0; k < m; ++k) tab.rows[k] = slots[done + k] * c->parties;
         const bool first = (c0 + done == 0), last = (done + m == n);
         pgh::FedavgArgs a{};
-        a.diffs = (const float*)c->d_slab;
+        a.diffs = c->d_slab.as<float>();
         a.map = slab_map(c);
         a.n_rows = m;
         a.client0 = c0 + done;
         a.p = c->pg;
-        a.weights = c->d_w ? c->d_w + (c0 + done) : nullptr;
-        a.recips = c->d_rec ? c->d_rec + (c0 + done) : nullptr;
-        a.acc = c->d_acc;
-        a.ckpt = c->d_ckpt;
-        a.out = c->d_out;
+        a.weights = c->d_w ? c->d_w.as<float>() + (c0 + done) : nullptr;
+        a.recips = c->d_rec ? c->d_rec.as<double>() + (c0 + done) : nullptr;
+        a.acc = c->d_acc.as<float>();
+        a.ckpt = c->d_ckpt.as<float>();
+        a.out = c->d_out.as<float>();
         a.divisor = fa.divisor;
         a.flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
         a.mode = kernel_mode(mode);
@@ -92,7 +92,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         pgh_ctx::D2HRing& pre = c->pre_d2h;
         bool prequeue = false;
         if (K > 1 && (a.flags & pgh::FL_FINAL)) {
-            RC(d2h_ring_begin(c, &pre, (const uint8_t*)c->d_out, 4 * (size_t)c->pg, s, true, false));
+            RC(d2h_ring_begin(c, &pre, c->d_out.as<uint8_t>(), 4 * (size_t)c->pg, s, true, false));
             prequeue = pre.base || pre.n_free > 0;  // own cells, or a free staging slot
         }
         for (int r = 0; r < K; ++r) {
@@ -107,9 +107,9 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
             pgh::FedavgArgs ar = a;
             ar.map.off = lo;
             ar.p = hi - lo;
-            ar.acc = c->d_acc + lo;
-            ar.ckpt = c->d_ckpt + lo;
-            ar.out = c->d_out + lo;
+            ar.acc = c->d_acc.as<float>() + lo;
+            ar.ckpt = c->d_ckpt.as<float>() + lo;
+            ar.out = c->d_out.as<float>() + lo;
             const uint64_t rp = (uint64_t)(hi - lo);
             const uint64_t bytes = 4ull * (uint64_t)m * rp + (first ? 0 : 4 * rp) + ((a.flags & pgh::FL_FINAL) ? 8 * rp : 4 * rp);
             RC(timed_launch(c, rs, bytes, [&] { return pgh::launch_fedavg_rows(ar, tab, rs); }));
@@ -127,7 +127,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         prequeued = prequeued || prequeue;
         done += m;
     } while (done < n);
-    RC(record_fold(c, s));
+    RC(record_fold(c, c->fold_evs, s));
     RC(record_slot_fold(c, slots, n));
     for (int k = 0; k < n; ++k) c->slot_client[(size_t)slots[k]] = -1;  // free for the next ingests
     c->folded = total;
@@ -135,7 +135,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     c->slot_mode = mode;
     if (final) {
         std::swap(c->d_ckpt, c->d_out);  // the new checkpoint is the next cycle's input
-        c->pre_d2h_valid = prequeued && c->pre_d2h.src == (const uint8_t*)c->d_ckpt;
+        c->pre_d2h_valid = prequeued && c->pre_d2h.src == c->d_ckpt.as<uint8_t>();
         c->folded = 0;  // the next cycle folds from scratch
         c->slot_mode = -1;
         if (clipped) {  // the cycle's rows join the finished totals (pgh_clip_stats)
