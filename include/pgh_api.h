@@ -48,8 +48,17 @@ typedef enum {
  * weighted FedAvg (no reference counterpart; equals PGH_MEAN bit for bit at w == 1).
  * PGH_CLIPPED_MEAN: the mean of the diffs after each is scaled down to an L2 norm of at most the
  * bound of pgh_set_clip_norm (norm-bounded FedAvg; no reference counterpart; equals PGH_MEAN bit for
- * bit when no diff exceeds the bound). */
-typedef enum { PGH_MEAN = 0, PGH_ITERATIVE_MEAN = 1, PGH_WEIGHTED_MEAN = 2, PGH_CLIPPED_MEAN = 3 } pgh_mode;
+ * bit when no diff exceeds the bound).
+ * PGH_TRIMMED_MEAN: per parameter, the mean of the N reported values without the b largest and the
+ * b smallest (coordinate-wise trimmed mean, Yin et al. 2018; b from pgh_set_trim; no reference
+ * counterpart). */
+typedef enum {
+    PGH_MEAN = 0,
+    PGH_ITERATIVE_MEAN = 1,
+    PGH_WEIGHTED_MEAN = 2,
+    PGH_CLIPPED_MEAN = 3,
+    PGH_TRIMMED_MEAN = 4
+} pgh_mode;
 /* Stream kind for pgh_stream_begin besides the three averaging modes. */
 #define PGH_STREAM_SECAGG 16
 
@@ -204,6 +213,34 @@ int pgh_clip_scale(double sumsq, float c, float* scale);
  * got a scale other than 1, and the largest norm (NaN if any was NaN).  Each pointer may be NULL. */
 int pgh_clip_stats(pgh_ctx* ctx, int64_t* n_rows, int64_t* n_clipped, double* max_norm);
 
+/* ---- coordinate-wise trimmed mean (PGH_TRIMMED_MEAN) ----------------------------------------
+ * Per parameter: drop the b largest and the b smallest of the N values, average the other N - 2b.
+ * Up to b arbitrary rows (NaN, infinities, 1e30) then cannot move any parameter outside the range
+ * of the others' values.  The definition is a streaming one, so the result
+ * does not depend on the launch shape, the slots or how the rows are split over launches:
+ *   values are ordered by the int32 key(x) = bits(x) ^ ((bits(x) >> 31) & 0x7fffffff) (arithmetic
+ *   shift, signed compare: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN; unkey = key);
+ *   state per parameter: lo[0..b) = INT32_MAX, hi[0..b) = INT32_MIN, acc (f32);
+ *   fold client k = 0, 1, ... (fold order): e = key(x_k);
+ *     for j < b: t = max(lo[j], e), lo[j] = min(lo[j], e), e = t;      stop if k < b;
+ *     for j < b: t = min(hi[j], e), hi[j] = max(hi[j], e), e = t;      stop if k < 2b;
+ *     v = unkey(e);  acc = v when k == 2b, else acc + v (f32);
+ *   close: out = ckpt - acc / float(N - 2b), an IEEE f32 division; it needs N >= 2b + 1.
+ * The kept multiset is sort(values)[b : N - b] whatever the order; only the f32 additions follow
+ * the fold order.
+ *
+ * pgh_set_trim: b = 0 turns trimming off, 1 .. PGH_TRIM_MAX turns it on, anything else is
+ * PGH_E_ARG; changing b while slot folds of a cycle are under way is PGH_E_STATE.  A group hands b
+ * to its children.  PGH_TRIMMED_MEAN with trimming off is PGH_E_STATE, and so is a closing fold of
+ * fewer than 2b + 1 diffs (nothing is launched; the context stays usable).  Every RESIDENT fold
+ * and slot fold accepts the mode, on shards and groups too (nothing in it looks along a row);
+ * pgh_stream_begin refuses it (PGH_E_UNSUPPORTED).  A fold that is not a whole cycle in one launch
+ * keeps lo, hi and acc in 2b + 1 planes of P_shard words in HBM.  pgh_set_variant does not affect
+ * trimmed folds: PGH_TRIM_VEC=4|1 (read by pgh_create) forces 16-byte columns or one parameter
+ * per lane, and pgh_effective_variant(ctx, PGH_TRIMMED_MEAN) reports 40 or 41 for them. */
+#define PGH_TRIM_MAX 8
+int pgh_set_trim(pgh_ctx* ctx, int b);
+
 /* ---- reduction ----------------------------------------------------------------------------
  * out = ckpt - avg(diffs), over this context's shard.  Host pointers, P_shard floats each. */
 int pgh_fedavg(pgh_ctx* ctx, int mode, const float* ckpt, float* out);
@@ -279,7 +316,8 @@ int pgh_synth_ckpt_device(pgh_ctx* ctx, uint64_t seed, float* d_ckpt, void* stre
  * After pgh_stream_begin, every run of >= fold_batch consecutive clients at the fold front is
  * folded into the running state (same op order as RESIDENT: bit-identical results) and its slots
  * are freed; H2D of later clients overlaps those folds.  kind = a pgh_mode or PGH_STREAM_SECAGG;
- * fold_batch <= 0 means half the slots.  Clients may arrive out of order within the ring. */
+ * fold_batch <= 0 means half the slots.  Clients may arrive out of order within the ring.
+ * PGH_CLIPPED_MEAN and PGH_TRIMMED_MEAN are refused (PGH_E_UNSUPPORTED). */
 int pgh_stream_begin(pgh_ctx* ctx, int kind, int fold_batch);
 int pgh_stream_flush(pgh_ctx* ctx);               /* fold the ready run now */
 /* Fold what is left and write out = ckpt - avg (all clients [0, n) must have arrived). */

@@ -16,9 +16,9 @@ opt-in for the process-wide settings the engine benefits from (HIP hardware queu
 thresholds for 47 MB buffers).
 """
 from .exceptions import (AggregationError, ClipUnavailableError, EngineUnavailableError, ModelNotAcceleratedError,
-                         PlanNotAcceleratedError, PyGridError, StateParseError)
-from .engine import (CLIPPED_MEAN, F32, I64, ITERATIVE_MEAN, MEAN, STREAM_SECAGG, WEIGHTED_MEAN, Engine, PinnedBuffer,
-                     device_count)
+                         PlanNotAcceleratedError, PyGridError, StateParseError, TrimUnavailableError)
+from .engine import (CLIPPED_MEAN, F32, I64, ITERATIVE_MEAN, MEAN, MODE_NAMES, STREAM_SECAGG, TRIMMED_MEAN, TRIM_MAX,
+                     WEIGHTED_MEAN, Engine, PinnedBuffer, device_count)
 
 
 def tune_process(hw_queues: bool = True, malloc: bool = True) -> dict:
@@ -38,8 +38,9 @@ def tune_process(hw_queues: bool = True, malloc: bool = True) -> dict:
 
 __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
-    "StateParseError",
-    "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "F32", "I64",
+    "StateParseError", "TrimUnavailableError",
+    "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
+    "TRIM_MAX", "MODE_NAMES", "F32", "I64",
     "tune_process",
 ]
 __version__ = "0.3.0"

@@ -104,6 +104,7 @@ SIGNATURES = {
     "pgh_row_sumsq": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
     "pgh_clip_scale": (_i, [C.c_double, C.c_float, C.POINTER(C.c_float)]),
     "pgh_clip_stats": (_i, [_vp, _P64, _P64, C.POINTER(C.c_double)]),
+    "pgh_set_trim": (_i, [_vp, _i]),
     "pgh_fedavg": (_i, [_vp, _i, _vp, _vp]),
     "pgh_fedavg_device": (_i, [_vp, _i, _vp, _vp, _vp]),
     "pgh_fedavg_device_range": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp]),

@@ -7,7 +7,7 @@
 //   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks
 //   pgh_order.cpp   which stream waits for what, and the timing events
 //   pgh_ingest.cpp  host bytes -> HBM slab rows (raw, State messages, int64 shares, synthetic)
-//   pgh_reduce.cpp  fold_run, RESIDENT and STREAM folds, the resident checkpoint, secagg, clipping
+//   pgh_reduce.cpp  fold_run, RESIDENT and STREAM folds, the resident checkpoint, secagg, clipping, trimming
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order)
 // The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
@@ -40,7 +40,7 @@ namespace pgh_detail {
 
 constexpr int KIND_SECAGG = PGH_STREAM_SECAGG;  // fold kind besides the pgh_mode values (none of which it equals)
 static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KIND_SECAGG != PGH_WEIGHTED_MEAN &&
-                  KIND_SECAGG != PGH_CLIPPED_MEAN,
+                  KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN,
               "the secagg fold kind must not collide with an averaging mode");
 
 // CPUs on the GPU's own socket (its PCI device's local_cpulist) that this process may run on; empty
@@ -226,6 +226,14 @@ struct pgh_ctx {
     int64_t clip_rows = 0, clip_clipped = 0;  // folds finished since pgh_reset / pgh_reserve
     double clip_max_norm = 0.0;
 
+    // Trimmed-mean FedAvg (pgh_set_trim, PGH_TRIMMED_MEAN).  A fold that is a
+    // whole cycle in one launch keeps K8's selection state in registers; any other keeps it in HBM
+    // between launches: 2 trim_b planes of pvec int32 keys here (lo, then hi) and the running sum in
+    // d_acc -- (2b + 1) x 4 x pvec bytes, allocated by the first launch that needs them.
+    int trim_b = 0;    // values dropped per side; 0 = trimming off
+    int trim_vec = 0;  // PGH_TRIM_VEC: 4 or 1 forces K8's column width, 0 = by shard size
+    DeviceBuf d_trim;
+
     bool streaming = false;
     int slot_mode = -1;  // pgh_fold_slots: averaging mode of the cycle being folded slot by slot
     int kind = 0;
@@ -277,11 +285,14 @@ double now_ms();
 // ---- state checks and slab geometry -------------------------------------------------------------
 inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
 inline bool valid_mode(int m) {
-    return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN;
+    return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN ||
+           m == PGH_TRIMMED_MEAN;
 }
+static_assert(PGH_TRIMMED_MEAN == pgh::MODE_TRIMMED && PGH_TRIM_MAX == pgh::TRIM_MAX, "the kernels' numbering");
 // The kernels' mode: a clipped mean is the weighted fold with the scales as weights.
 inline int kernel_mode(int m) { return m == PGH_CLIPPED_MEAN ? PGH_WEIGHTED_MEAN : m; }
-// valid_mode, and PGH_CLIPPED_MEAN only with a bound set (PGH_E_STATE otherwise)
+// valid_mode, and PGH_CLIPPED_MEAN only with a bound set, PGH_TRIMMED_MEAN only with a trim count
+// (PGH_E_STATE otherwise)
 int check_mode(pgh_ctx* c, int mode);
 int check_ready(pgh_ctx* c);
 int check_dtype(pgh_ctx* c, int dtype);
@@ -404,6 +415,16 @@ int sumsq_after_ingest(pgh_ctx* c, int slot);  // clipping on: queue the row's K
 int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms);
 int resident_clip_scales(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n)
 void clip_count(pgh_ctx* c, const float* scales, const double* norms, int64_t n);  // into the finished totals
+
+// ---- trimmed-mean FedAvg (pgh_reduce.cpp) -----------------------------------------------------------
+// K8's arguments on top of a filled FedavgArgs (map.off = the launch's first shard param): the mode,
+// b, the column width and -- unless the launch is FIRST and FINAL -- the state planes, allocated here.
+int trim_args(pgh_ctx* c, pgh::FedavgArgs* a);
+// HBM bytes of K8's state a launch with these flags moves over rp params
+inline uint64_t trim_state_bytes(const pgh_ctx* c, int flags, uint64_t rp) {
+    const uint64_t planes = 2ull * (uint64_t)c->trim_b;  // (the acc plane is counted like the other modes')
+    return ((flags & pgh::FL_FIRST) ? 0 : 4 * planes * rp) + ((flags & pgh::FL_FINAL) ? 0 : 4 * planes * rp);
+}
 
 // What a FINAL fold pass writes (fedavg: ckpt - avg; secagg: sum/dec) and over which param range.
 struct FinalArgs {

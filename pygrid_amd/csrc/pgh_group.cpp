@@ -727,6 +727,10 @@ int set_weights(pgh_ctx* c, const float* w, int n) {
     return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_weights(k, w, n); });
 }
 
+int set_trim(pgh_ctx* c, int b) {
+    return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_trim(k, b); }, (int)G(c)->kids.size());
+}
+
 int fedavg(pgh_ctx* c, int mode, const float* ckpt, float* out) {
     pgh_group* g = G(c);
     RC(need_slab(c));

@@ -8,7 +8,9 @@
 namespace pgh {
 
 // fedavg modes (same numbering as PGH_MEAN / PGH_ITERATIVE_MEAN / PGH_WEIGHTED_MEAN)
-enum { MODE_MEAN = 0, MODE_ITERATIVE = 1, MODE_WEIGHTED = 2 };
+// (3, PGH_CLIPPED_MEAN, reaches the kernels as MODE_WEIGHTED over the scales)
+enum { MODE_MEAN = 0, MODE_ITERATIVE = 1, MODE_WEIGHTED = 2, MODE_TRIMMED = 4 };
+constexpr int TRIM_MAX = 8;
 // flags for a chunked (client-streaming) reduction
 enum { FL_FIRST = 1, FL_FINAL = 2 };
 
@@ -49,7 +51,18 @@ struct FedavgArgs {
     int flags;
     int mode;
     int variant;            // kernel variant (table in pgh_kernels.hip); < 0 = auto by shard size
+    // MODE_TRIMMED (K8, the streaming definition in include/pgh_api.h): b = trim_b values dropped per
+    // side; divisor = float(N - 2b); client0 + r is the fold index k of row r.  The selection state
+    // of a param lives in registers for the launch; a launch without FL_FIRST reads it and a launch
+    // without FL_FINAL writes it: lo[j] in plane j and hi[j] in plane b + j of tstate (int32 keys,
+    // planes tplane elements apart, each indexed like acc), the running sum in acc.
+    int trim_b;             // 1 .. TRIM_MAX
+    int trim_vec;           // 4: 16-byte columns, 1: one param per lane, 0: auto_trim_vec
+    int32_t* tstate;        // [2 b][tplane] at this launch's column 0; unused when FL_FIRST | FL_FINAL
+    int64_t tplane;
 };
+// The column width K8 takes for a shard of p params at b (variant ids 40: 16-byte, 41: one param).
+int auto_trim_vec(int64_t p, int b);
 hipError_t launch_fedavg(const FedavgArgs& a, hipStream_t s);
 
 // Slab rows of one fold launch given by index instead of contiguous from `diffs`: row r of the

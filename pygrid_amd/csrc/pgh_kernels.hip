@@ -7,6 +7,8 @@
 //       restates cycle_manager.py:266-269 + 01-Create-plan.ipynb:450-454
 // K3  k_secagg                 Z_2^64 wrap-sum over [clients*parties][P] int64 + fixed-point
 //       decode float32(int64)/10^prec (PySyft 0.2.9 semantics)
+// K8  k_fedavg_trim            per param, the mean without the b largest and b smallest values
+//       (build-owned: PGH_TRIMMED_MEAN, a register-resident selection network)
 // K7  k_row_sumsq              sumsq_c = sum_i (double)d_c[i]^2 along a client's row, in one fixed
 //       order (build-owned: the norms of PGH_CLIPPED_MEAN)
 //
@@ -344,6 +346,153 @@ __global__ __launch_bounds__(TB) void k_fedavg(FedavgArgs a, int64_t ncol) {
 template <int MODE, int U, int W, bool NT, int TB, int VEC>
 __global__ __launch_bounds__(TB) void k_fedavg_rows(FedavgArgs a, int64_t ncol, RowTab tab) {
     fedavg_tiles<MODE, U, W, NT, TB, VEC, true>(a, &tab, ncol);
+}
+
+// K8: coordinate-wise trimmed mean (MODE_TRIMMED; the definition is in include/pgh_api.h).  The same
+// walk as fedavg_columns -- one lane down the client rows of its column, U non-temporal loads in
+// flight -- with a selection network in registers beside the stream: per param B keys `lo` (the B
+// smallest so far), B keys `hi` (the B largest of what lo evicted) and the f32 sum of what hi
+// evicted.  Keys are int32 (v_min_i32 / v_max_i32 / v_med3_i32), converted on load and back on
+// eviction (op count: trim_step).  No LDS and no second pass.
+__device__ __forceinline__ int trim_key(int b) { return b ^ ((b >> 31) & 0x7fffffff); }  // its own inverse
+
+__device__ __forceinline__ float lane_get(float v, int) { return v; }
+__device__ __forceinline__ float lane_get(const f32x4& v, int e) { return v[e]; }
+__device__ __forceinline__ void lane_put(float& v, int, float x) { v = x; }
+__device__ __forceinline__ void lane_put(f32x4& v, int e, float x) { v[e] = x; }
+
+template <int B, int VEC>
+struct TrimState {
+    int lo[B][VEC], hi[B][VEC];
+    float acc[VEC];
+};
+
+// The median of three as min / max (hipcc selects v_med3_i32 for this shape).
+__device__ __forceinline__ int med3i(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }
+
+// One row.  k = its fold index, the same in every lane.  The definition's compare-exchange chain
+// (t = max(lo[j], e); lo[j] = min(lo[j], e); e = t) is an insertion into a list that stays sorted
+// (lo ascending, hi descending; the sentinels and a state read back from HBM are sorted too), so
+// entry j of the new list is the median of its two old neighbours and the new key, and the evicted
+// key the max (min) of the old last entry and the new key: the same values bit for bit -- keys are
+// totally ordered and equal keys are equal bits -- in B + 1 independent ops instead of a chain of 2B.
+// Per float: 3 (key) + (B + 1) + (B + 1) + 3 (unkey) + 1 (add) = 2B + 9 VALU ops.
+// STEADY: k > 2B is known, so the fill phase's branches (k < B: lo still filling; k < 2B: hi still
+// filling; k == 2B: the sum starts at the first kept value, not at 0, so that -0 survives) are
+// compiled out.
+template <int B, int VEC, bool STEADY, class T>
+__device__ __forceinline__ void trim_step(TrimState<B, VEC>& s, const T& v, int64_t k) {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        int x = trim_key(__float_as_int(lane_get(v, e)));
+        const int up = max(s.lo[B - 1][e], x);  // the largest of lo and x leaves lo
+#pragma unroll
+        for (int j = B - 1; j > 0; --j) s.lo[j][e] = med3i(s.lo[j - 1][e], s.lo[j][e], x);
+        s.lo[0][e] = min(s.lo[0][e], x);
+        if (!STEADY && k < B) continue;
+        const int down = min(s.hi[B - 1][e], up);  // the smallest of hi and it leaves hi: a kept value
+#pragma unroll
+        for (int j = B - 1; j > 0; --j) s.hi[j][e] = med3i(s.hi[j - 1][e], s.hi[j][e], up);
+        s.hi[0][e] = max(s.hi[0][e], up);
+        if (!STEADY && k < 2 * B) continue;
+        const float kept = __int_as_float(trim_key(down));
+        s.acc[e] = (!STEADY && k == 2 * B) ? kept : s.acc[e] + kept;
+    }
+}
+
+// A state plane is indexed like acc: [p] words from the launch's column 0, the last column ragged.
+template <int VEC>
+__device__ __forceinline__ void trim_plane_load(const int32_t* plane, int64_t q, int64_t p, int (&dst)[VEC]) {
+    const auto v = Lane<VEC>::load_tail(reinterpret_cast<const float*>(plane), q, p);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) dst[e] = __float_as_int(lane_get(v, e));
+}
+template <int VEC>
+__device__ __forceinline__ void trim_plane_store(int32_t* plane, int64_t q, int64_t p, const int (&src)[VEC]) {
+    typename Lane<VEC>::T v;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) lane_put(v, e, __int_as_float(src[e]));
+    Lane<VEC>::store_tail(reinterpret_cast<float*>(plane), q, p, v);
+}
+
+template <int B, int U, int VEC, bool IDX>
+__device__ __forceinline__ void trim_column(const FedavgArgs& a, const RowTab* tab, int64_t q) {
+    using L = Lane<VEC>;
+    using T = typename L::T;
+    const int n = a.n_rows;
+    const int64_t ld = a.map.ld;
+    const float* col = a.diffs + a.map.at(VEC * q);
+    TrimState<B, VEC> s;
+    if (a.flags & FL_FIRST) {
+#pragma unroll
+        for (int j = 0; j < B; ++j)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                s.lo[j][e] = 0x7fffffff;
+                s.hi[j][e] = (int)0x80000000;
+            }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s.acc[e] = 0.f;  // replaced at k == 2B
+    } else {
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            trim_plane_load<VEC>(a.tstate + (int64_t)j * a.tplane, q, a.p, s.lo[j]);
+            trim_plane_load<VEC>(a.tstate + (int64_t)(B + j) * a.tplane, q, a.p, s.hi[j]);
+        }
+        const T v = L::load_tail(a.acc_in, q, a.p);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s.acc[e] = lane_get(v, e);
+    }
+    // Full batches past the fill phase take the branch-free step; the batches of the fill phase
+    // (k <= 2B: a prologue of at most ceil((2B + 1) / U) + 1 batches) and the last partial one take
+    // the general step, whose branches are wave-uniform.
+    for (int r = 0; r < n;) {
+        const int nv = min(U, n - r);
+        const int64_t k0 = a.client0 + r;
+        T v[U];
+        if (nv == U && k0 > 2 * B) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) v[u] = L::template load<true>(col + row_at<IDX>(tab, r + u) * ld);
+#pragma unroll
+            for (int u = 0; u < U; ++u) trim_step<B, VEC, true>(s, v[u], k0 + u);
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (u < nv) v[u] = L::template load<true>(col + row_at<IDX>(tab, r + u) * ld);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (u < nv) trim_step<B, VEC, false>(s, v[u], k0 + u);
+        }
+        r += nv;
+    }
+    if (a.flags & FL_FINAL) {
+        T avg;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) lane_put(avg, e, s.acc[e] / a.divisor);
+        L::store_tail(a.out, q, a.p, L::load_tail(a.ckpt, q, a.p) - avg);
+    } else {
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            trim_plane_store<VEC>(a.tstate + (int64_t)j * a.tplane, q, a.p, s.lo[j]);
+            trim_plane_store<VEC>(a.tstate + (int64_t)(B + j) * a.tplane, q, a.p, s.hi[j]);
+        }
+        T v;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) lane_put(v, e, s.acc[e]);
+        L::store_tail(a.acc, q, a.p, v);
+    }
+}
+
+template <int B, int U, int TB, int VEC>
+__global__ __launch_bounds__(TB) void k_fedavg_trim(FedavgArgs a, int64_t ncol) {
+    const int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (q < ncol) trim_column<B, U, VEC, false>(a, nullptr, q);
+}
+
+template <int B, int U, int TB, int VEC>
+__global__ __launch_bounds__(TB) void k_fedavg_trim_rows(FedavgArgs a, int64_t ncol, RowTab tab) {
+    const int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (q < ncol) trim_column<B, U, VEC, true>(a, &tab, q);
 }
 
 // Z_2^64 lane element: VEC = 2 (16-byte column of 2 int64) or 1 (one int64 per lane).
@@ -912,7 +1061,42 @@ hipError_t dispatch_fedavg(const FedavgArgs& a, int variant, hipStream_t s) {
     }
 }
 
+// K8 shapes: 16-byte columns in 256-thread blocks with 8 rows in flight (the mean's big-shard shape,
+// variant 0), or one param per lane in 64-thread blocks with 32 rows in flight (its small-shard
+// shape, variant 14).  Registers per lane: (2B + 1) VEC of state + U VEC of rows.
+template <int B, int VEC>
+hipError_t go_trim(const FedavgArgs& a, const RowTab* t, hipStream_t s) {
+    constexpr int TB = VEC == 4 ? 256 : 64, U = VEC == 4 ? 8 : 32;
+    const int64_t ncol = (a.p + VEC - 1) / VEC;
+    const unsigned grid = grid_for(ncol, TB, false);
+    if (t) k_fedavg_trim_rows<B, U, TB, VEC><<<grid, TB, 0, s>>>(a, ncol, *t);
+    else k_fedavg_trim<B, U, TB, VEC><<<grid, TB, 0, s>>>(a, ncol);
+    return hipGetLastError();
+}
+
+template <int VEC>
+hipError_t dispatch_trim(const FedavgArgs& a, const RowTab* t, hipStream_t s) {
+    switch (a.trim_b) {
+    case 1: return go_trim<1, VEC>(a, t, s);
+    case 2: return go_trim<2, VEC>(a, t, s);
+    case 3: return go_trim<3, VEC>(a, t, s);
+    case 4: return go_trim<4, VEC>(a, t, s);
+    case 5: return go_trim<5, VEC>(a, t, s);
+    case 6: return go_trim<6, VEC>(a, t, s);
+    case 7: return go_trim<7, VEC>(a, t, s);
+    case 8: return go_trim<8, VEC>(a, t, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace
+
+// K8's column width: the mean's threshold between one param per lane and 16-byte columns (below
+// ~360 K params the 16-byte columns leave CUs without lanes, auto_variant).
+int auto_trim_vec(int64_t p, int b) {
+    (void)b;
+    return p < 360000 ? 1 : 4;
+}
 
 // Measured on MI355X, column-blocked slab (r01l, tools/sweep_r01l.sh; GB/s of algorithmic bytes):
 //   P = 11.69M x 1K:     mean v0 6930 / v6 6921 / v15 6882 / v11 6861 / v14 6576
@@ -972,6 +1156,18 @@ bool valid_map(const SlabMap& m, int64_t p) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// MODE_TRIMMED behind the common checks of launch_fedavg / launch_fedavg_rows.
+static hipError_t launch_trim(const FedavgArgs& a, const RowTab* t, hipStream_t s) {
+    if (a.trim_b < 1 || a.trim_b > TRIM_MAX || a.client0 < 0) return hipErrorInvalidValue;
+    if (a.trim_vec != 0 && a.trim_vec != 1 && a.trim_vec != 4) return hipErrorInvalidValue;
+    if ((a.flags & (FL_FIRST | FL_FINAL)) != (FL_FIRST | FL_FINAL) &&
+        (!a.tstate || !aligned16(a.tstate) || a.tplane < a.p || (a.tplane & 3)))
+        return hipErrorInvalidValue;
+    if ((a.flags & FL_FIRST) && a.client0 != 0) return hipErrorInvalidValue;
+    const int vec = a.trim_vec ? a.trim_vec : auto_trim_vec(a.p, a.trim_b);
+    return vec == 4 ? dispatch_trim<4>(a, t, s) : dispatch_trim<1>(a, t, s);
+}
+
 hipError_t launch_fedavg(const FedavgArgs& a_, hipStream_t s) {
     FedavgArgs a = a_;
     if (!a.acc_in) a.acc_in = a.acc;
@@ -986,6 +1182,7 @@ hipError_t launch_fedavg(const FedavgArgs& a_, hipStream_t s) {
         return hipErrorInvalidValue;
     if (a.mode == MODE_WEIGHTED && a.n_rows > 0 && !a.weights) return hipErrorInvalidValue;
     if (a.mode == MODE_ITERATIVE && a.n_rows > 0 && !a.recips) return hipErrorInvalidValue;
+    if (a.mode == MODE_TRIMMED) return launch_trim(a, nullptr, s);
     const int v = a.variant < 0 ? auto_variant(a.p, a.mode) : a.variant;
     switch (a.mode) {
     case MODE_MEAN: return dispatch_fedavg<MODE_MEAN>(a, v, s);
@@ -1010,6 +1207,7 @@ hipError_t launch_fedavg_rows(const FedavgArgs& a_, const RowTab& t, hipStream_t
         return hipErrorInvalidValue;
     if (a.mode == MODE_WEIGHTED && a.n_rows > 0 && !a.weights) return hipErrorInvalidValue;
     if (a.mode == MODE_ITERATIVE && a.n_rows > 0 && !a.recips) return hipErrorInvalidValue;
+    if (a.mode == MODE_TRIMMED) return launch_trim(a, &t, s);
     int v = auto_variant(a.p, a.mode);
     if (a.variant == 0 || a.variant == 11 || a.variant == 14 || a.variant == 17) v = a.variant;
     switch (a.mode) {

@@ -119,8 +119,12 @@ int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const Fina
             a.flags = flags;
             a.mode = kind;
             a.variant = c->variant;
-            const uint64_t bytes = 4ull * (uint64_t)seg * pg + (first ? 0 : 4 * pg) +
-                                   ((flags & pgh::FL_FINAL) ? 8 * pg : 4 * pg);
+            uint64_t bytes = 4ull * (uint64_t)seg * pg + (first ? 0 : 4 * pg) +
+                             ((flags & pgh::FL_FINAL) ? 8 * pg : 4 * pg);
+            if (kind == PGH_TRIMMED_MEAN) {
+                RC(trim_args(c, &a));
+                bytes += trim_state_bytes(c, flags, pg);
+            }
             RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
         }
         done += seg;
@@ -198,7 +202,12 @@ int resident_count(pgh_ctx* c, int64_t* n_out) {
 }
 
 int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
-    if (mode == PGH_WEIGHTED_MEAN) {
+    if (mode == PGH_TRIMMED_MEAN) {  // b dropped per side; at least one value must be left
+        if (n < 2 * (int64_t)c->trim_b + 1)
+            return fail(c, PGH_E_STATE, "trimmed mean with b = %d needs at least %d diffs, have %lld", c->trim_b,
+                        2 * c->trim_b + 1, (long long)n);
+        *div = (float)(n - 2 * (int64_t)c->trim_b);
+    } else if (mode == PGH_WEIGHTED_MEAN) {
         if ((int64_t)c->weights.size() < n)
             return fail(c, PGH_E_STATE, "weighted mean needs %lld weights, have %zu", (long long)n, c->weights.size());
         const float t = weight_total(c->weights, n);
@@ -220,6 +229,22 @@ int check_mode(pgh_ctx* c, int mode) {
     if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
     if (mode == PGH_CLIPPED_MEAN && !(c->clip_c > 0.f))
         return fail(c, PGH_E_STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first");
+    if (mode == PGH_TRIMMED_MEAN && c->trim_b == 0)
+        return fail(c, PGH_E_STATE, "PGH_TRIMMED_MEAN needs a trim count: call pgh_set_trim first");
+    return PGH_OK;
+}
+
+int trim_args(pgh_ctx* c, pgh::FedavgArgs* a) {
+    a->mode = pgh::MODE_TRIMMED;
+    a->trim_b = c->trim_b;
+    a->trim_vec = c->trim_vec;
+    if ((a->flags & (pgh::FL_FIRST | pgh::FL_FINAL)) == (pgh::FL_FIRST | pgh::FL_FINAL)) return PGH_OK;
+    // (a buffer left from a larger b serves; one too small is only ever replaced before a cycle's
+    // first launch -- pgh_set_trim -- and hipFree waits for the launches that still use it)
+    if (!c->d_trim.reserve(2 * (size_t)c->trim_b * 4 * (size_t)c->pvec))
+        return fail(c, PGH_E_OOM, "allocation of the trimmed mean's %d state planes failed", 2 * c->trim_b);
+    a->tstate = c->d_trim.as<int32_t>() + a->map.off;
+    a->tplane = c->pvec;
     return PGH_OK;
 }
 
@@ -384,6 +409,17 @@ int pgh_set_clip_norm(pgh_ctx* c, float bound) {
     if (!(bound > 0.f) || !std::isfinite(bound)) return fail(c, PGH_E_ARG, "the clipping bound must be finite and > 0, or 0 for off");
     if (bound != c->clip_c) c->clip_scales_valid = false;
     c->clip_c = bound;
+    return PGH_OK;
+}
+
+int pgh_set_trim(pgh_ctx* c, int b) {
+    if (!c) return PGH_E_ARG;
+    if (b < 0 || b > PGH_TRIM_MAX) return fail(c, PGH_E_ARG, "trim count %d outside [0,%d]", b, PGH_TRIM_MAX);
+    if (c->grp) return pgh_group_api::set_trim(c, b);
+    if (b != c->trim_b && c->folded > 0 && !c->streaming)
+        return fail(c, PGH_E_STATE, "trim count changed from %d to %d with %lld diffs of the cycle folded", c->trim_b, b,
+                    (long long)c->folded);
+    c->trim_b = b;
     return PGH_OK;
 }
 
@@ -675,6 +711,7 @@ int pgh_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, float* dec_out)
 
 int pgh_stream_begin(pgh_ctx* c, int kind, int fold_batch) {
     if (c && kind == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not clip: a scale needs the whole row of every client");
+    if (c && kind == PGH_TRIMMED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not trim: fold a RESIDENT slab or slots");
     if (c && c->grp) return pgh_group_api::stream_begin(c, kind, fold_batch);
     RC(check_ready(c));
     if (kind == PGH_STREAM_SECAGG) {

@@ -111,7 +111,11 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
             ar.ckpt = c->d_ckpt.as<float>() + lo;
             ar.out = c->d_out.as<float>() + lo;
             const uint64_t rp = (uint64_t)(hi - lo);
-            const uint64_t bytes = 4ull * (uint64_t)m * rp + (first ? 0 : 4 * rp) + ((a.flags & pgh::FL_FINAL) ? 8 * rp : 4 * rp);
+            uint64_t bytes = 4ull * (uint64_t)m * rp + (first ? 0 : 4 * rp) + ((a.flags & pgh::FL_FINAL) ? 8 * rp : 4 * rp);
+            if (mode == PGH_TRIMMED_MEAN) {
+                RC(trim_args(c, &ar));
+                bytes += trim_state_bytes(c, a.flags, rp);
+            }
             RC(timed_launch(c, rs, bytes, [&] { return pgh::launch_fedavg_rows(ar, tab, rs); }));
             if (K > 1 && (hi % (2 * RF) == 0 || hi == c->pg)) {
                 RC(add_final_mark(c, rs, hi));

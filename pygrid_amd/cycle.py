@@ -27,9 +27,9 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import state as state_codec
-from .engine import CLIPPED_MEAN, ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
+from .engine import CLIPPED_MEAN, ITERATIVE_MEAN, MEAN, TRIMMED_MEAN, TRIM_MAX, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
-    StateParseError
+    StateParseError, TrimUnavailableError
 
 CLIP_KEY = "diff_clip_norm"  # optional server_config key: the per-client L2 bound (no reference counterpart)
 
@@ -52,7 +52,41 @@ def clip_norm_of(server_config: dict) -> Optional[float]:
     return c
 
 
+TRIM_KEY = "diff_trim_count"  # optional server_config key: values dropped per side and parameter (no reference counterpart)
+
+
+def trim_count_of(server_config: dict) -> Optional[int]:
+    """The FL process's trim count, ``server_config["diff_trim_count"]``: an int in 1 .. 8, or None
+    when the key is absent or None (no trimming).  Anything else -- a bool, a float with a fraction,
+    0, a negative value, more than 8, another type -- raises ``AggregationError``: a mistyped count
+    must not quietly mean "no trimming"."""
+    b = server_config.get(TRIM_KEY, None)
+    if b is None:
+        return None
+    if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)):
+        raise AggregationError(f"{TRIM_KEY} must be an integer in 1..{TRIM_MAX}, not {b!r}")
+    if isinstance(b, (float, np.floating)) and not (np.isfinite(b) and float(b) == int(b)):
+        raise AggregationError(f"{TRIM_KEY} must be an integer in 1..{TRIM_MAX}, not {b!r}")
+    if not 1 <= int(b) <= TRIM_MAX:
+        raise AggregationError(f"{TRIM_KEY} must be an integer in 1..{TRIM_MAX}, not {b!r}")
+    return int(b)
+
+
+def check_trim_count(trim_count: int, n_diffs: int):
+    """A trimmed close needs at least ``2 b + 1`` diffs (one value must be left per parameter)."""
+    if n_diffs < 2 * trim_count + 1:
+        raise TrimUnavailableError(f"{TRIM_KEY} = {trim_count} needs at least {2 * trim_count + 1} diffs, the cycle "
+                                   f"has {n_diffs}")
+
+
 _NO_CLIP = object()  # "take the bound from server_config"
+_NO_TRIM = _NO_CLIP  # "take the trim count from server_config"
+
+
+def _trim_arg(server_config: dict, trim_count):
+    if trim_count is _NO_TRIM:
+        return trim_count_of(server_config)
+    return None if trim_count is None else trim_count_of({TRIM_KEY: trim_count})
 
 
 def _clip_arg(server_config: dict, clip_norm):
@@ -207,11 +241,27 @@ def cached_mode(server_config: dict, plan_key, mean_plans: Optional[str] = None)
 
 
 def select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
-                mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None) -> int:
+                mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None,
+                trim_count=None) -> int:
     """The dispatch rule below; with ``clip_norm`` set: ``CLIPPED_MEAN`` exactly where the rule gives
     ``MEAN`` (no hosted plan, or a plan probed equal to the mean), ``ClipUnavailableError`` everywhere
     else -- weights, the iterative plan, a plan the engine declines -- so that the caller cannot fall
-    back to an average that does not clip."""
+    back to an average that does not clip.  ``trim_count`` likewise: ``TRIMMED_MEAN`` where the rule
+    gives ``MEAN``, ``TrimUnavailableError`` everywhere else and together with ``clip_norm``."""
+    if trim_count is not None:
+        if clip_norm is not None:
+            raise TrimUnavailableError(f"{TRIM_KEY} cannot be combined with {CLIP_KEY}")
+        if weights is not None:
+            raise TrimUnavailableError(f"{TRIM_KEY} cannot be combined with aggregation weights")
+        try:
+            mode = _select_mode(server_config, avg_plan, None, plan_key, mean_plans, shapes, n_clients)
+        except PlanNotAcceleratedError as e:
+            raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine does not run this avg plan ({e}); the "
+                                       "node's own averaging does not trim") from e
+        if mode != MEAN:
+            raise TrimUnavailableError(f"{TRIM_KEY} is set but the hosted avg plan is the iterative mean, which "
+                                       "the engine does not trim")
+        return TRIMMED_MEAN
     if clip_norm is None:
         return _select_mode(server_config, avg_plan, weights, plan_key, mean_plans, shapes, n_clients)
     if weights is not None:
@@ -292,6 +342,19 @@ def _engine_clip(engine, clip_norm: Optional[float]):
         raise
 
 
+def _engine_trim(engine, trim_count: Optional[int]):
+    """Set (or clear) the engine's trim count before a cycle's first fold: an engine shared across
+    FL processes never carries one over.  An engine that cannot trim fails the cycle."""
+    if trim_count is None:
+        if hasattr(engine, "set_trim"):
+            engine.set_trim(0)
+        return
+    try:
+        engine.set_trim(trim_count)
+    except AttributeError as e:
+        raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine has no trimmed mean") from e
+
+
 def _decline_non_float32(pb: bytes, what: str):
     """After the State walker refused ``pb``: well-formed bytes holding non-float32 tensors are a
     model the engine does not implement (``ModelNotAcceleratedError``: the node averages it with
@@ -352,7 +415,7 @@ class CycleAggregator:
     # ---- bytes in / bytes out: the replaceable slice cycle_manager.py:240-303 -------------------
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
-                           plan_key=None, clip_norm=_NO_CLIP) -> bytes:
+                           plan_key=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -363,18 +426,26 @@ class CycleAggregator:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         clip = _clip_arg(server_config, clip_norm)
+        trim = _trim_arg(server_config, trim_count)
         try:
             return self._average_plan_diffs(server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key,
-                                            clip)
+                                            clip, trim)
         except PlanNotAcceleratedError as e:
+            if trim is not None:
+                raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine cannot average this cycle ({e}); the "
+                                           "node's own averaging does not trim") from e
             if clip is None:
                 raise
             raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine cannot average this cycle ({e}); the "
                                        "node's own averaging does not clip") from e
 
-    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, clip):
+    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, clip,
+                            trim=None):
         mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
-                           shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), clip_norm=clip)
+                           shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), clip_norm=clip,
+                           trim_count=trim)
+        if trim is not None:
+            check_trim_count(trim, len(diffs))
         try:
             numel = state_codec.tensor_numels(checkpoint)  # :240
         except StateParseError:
@@ -382,6 +453,7 @@ class CycleAggregator:
             raise
         self._prepare(numel, len(diffs))
         _engine_clip(self.engine, clip)  # before the first ingest: each diff's norm pass rides behind its copy
+        _engine_trim(self.engine, trim)
         if checkpoint is not self._resident or self.engine.ckpt_owner is not self:
             self.engine.ckpt_upload_state(checkpoint)  # else: the last cycle's output is still in HBM
         for i, d in enumerate(diffs):  # :247-250
@@ -407,16 +479,25 @@ class CycleAggregator:
     # ---- tensor lists in / out (what the reference holds after unserialize) ---------------------
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
-                       weights=None, clip_norm=_NO_CLIP) -> List[np.ndarray]:
+                       weights=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         clip = _clip_arg(server_config, clip_norm)
+        trim = _trim_arg(server_config, trim_count)
         shapes = [np.shape(p) for p in model_params]
-        mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
-                           n_clients=len(diffs), clip_norm=clip)
+        try:
+            mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
+                               n_clients=len(diffs), clip_norm=clip, trim_count=trim)
+        except PlanNotAcceleratedError as e:
+            if trim is None:
+                raise
+            raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine cannot average this cycle ({e})") from e
+        if trim is not None:
+            check_trim_count(trim, len(diffs))
         numel = [int(np.prod(s)) for s in shapes]
         self._prepare(numel, len(diffs))
         _engine_clip(self.engine, clip)
+        _engine_trim(self.engine, trim)
         for i, d in enumerate(diffs):
             if len(d) != len(numel):
                 raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
@@ -488,12 +569,16 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
             reports = self._worker_cycles.query(cycle_id=cycle.id, is_completed=True)
             diffs = [r.diff for r in reports]  # what :247-250 reads, at the query
         clip = clip_norm_of(server_config)  # a malformed bound fails the close
+        trim = trim_count_of(server_config)  # and so does a malformed trim count
         try:
             avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
                                              getattr(aggregator, "mean_plans", None))
             new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,
                                                      plan_key=plan_key, framing=framing)
         except PlanNotAcceleratedError as e:
+            if trim is not None:  # fail closed: the node's own averaging does not trim
+                raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine does not average this cycle ({e})") \
+                    from e
             if clip is not None:  # fail closed: the node's own averaging does not clip
                 raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine does not average this cycle ({e})") \
                     from e

@@ -15,12 +15,13 @@ import numpy as np
 from . import _lib
 from .exceptions import AggregationError, EngineUnavailableError, StateParseError
 
-MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN = 0, 1, 2, 3
+MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN = 0, 1, 2, 3, 4
+TRIM_MAX = 8  # PGH_TRIM_MAX
 STREAM_SECAGG = 16
 DEFAULT_VARIANT = -1  # PGH_DEFAULT_VARIANT: auto by shard size
 F32, I64 = 0, 1
 MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
-              CLIPPED_MEAN: "clipped_mean"}
+              CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean"}
 
 
 def device_count() -> int:
@@ -293,6 +294,12 @@ class Engine:
         self._check(self._lib.pgh_clip_stats(self._h, C.byref(n), C.byref(k), C.byref(m)), "clip_stats")
         return {"rows": n.value, "clipped": k.value, "max_norm": m.value}
 
+    # ---- coordinate-wise trimmed mean (TRIMMED_MEAN) ----------------------------------------------
+    def set_trim(self, b: int):
+        """Values dropped per side and parameter by later TRIMMED_MEAN folds (1 .. TRIM_MAX); 0 turns
+        trimming off.  Refused (PGH_E_STATE) while slot folds of a cycle are under way."""
+        self._check(self._lib.pgh_set_trim(self._h, int(b)), "set_trim")
+
     # ---- reduction -----------------------------------------------------------------------------
     def fedavg(self, mode: int, ckpt: np.ndarray) -> np.ndarray:
         """``ckpt - avg(diffs)`` over this shard (host arrays of p_shard floats)."""
@@ -454,7 +461,7 @@ class Engine:
 
     def effective_variant(self, mode: int = MEAN) -> int:
         """Kernel variant the next fold runs for ``mode`` (MEAN / ITERATIVE_MEAN / WEIGHTED_MEAN /
-        STREAM_SECAGG)."""
+        STREAM_SECAGG; TRIMMED_MEAN: 40 for 16-byte columns, 41 for one parameter per lane)."""
         v = self._lib.pgh_effective_variant(self._h, int(mode))
         self._check(min(v, 0), "effective_variant")
         return v

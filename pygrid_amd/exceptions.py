@@ -43,6 +43,14 @@ class ClipUnavailableError(AggregationError):
     would silently drop the defence the operator configured -- the close fails instead."""
 
 
+class TrimUnavailableError(AggregationError):
+    """The FL process asks for the coordinate-wise trimmed mean (``server_config["diff_trim_count"]``)
+    and the engine cannot trim this cycle: a hosted iterative or unaccelerated plan, a non-float32
+    model, aggregation weights or ``diff_clip_norm`` given together with it, or fewer than
+    ``2 b + 1`` diffs at the close.  Like ``ClipUnavailableError`` it is NOT a
+    ``PlanNotAcceleratedError``: the node's own averaging does not trim, so the close fails closed."""
+
+
 class ModelNotAcceleratedError(PlanNotAcceleratedError):
     """The checkpoint or a diff holds well-formed tensors that are not float32 (another dtype, or a
     serializer other than syft's "all").  The reference averages them with torch's type promotion;

@@ -65,8 +65,9 @@ import threading
 from typing import Callable, Dict, Hashable, List, Optional, Sequence
 
 from . import state as state_codec
-from .engine import CLIPPED_MEAN, F32, MEAN, WEIGHTED_MEAN, Engine
-from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, StateParseError
+from .engine import CLIPPED_MEAN, F32, MEAN, TRIMMED_MEAN, WEIGHTED_MEAN, Engine
+from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, StateParseError, \
+    TrimUnavailableError
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
 MAX_DEFAULT_SLOTS = 4096
@@ -81,21 +82,34 @@ def default_slots(P: int, budget: int = DEFAULT_HBM_BUDGET) -> int:
 class IncrementalCycle:
     def __init__(self, engine: Engine, numel, mode: int = MEAN, slots: Optional[int] = None, fold_batch: int = 8,
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
-                 early_fold: bool = True, clip_norm: Optional[float] = None):
-        """``clip_norm``: the FL process's per-client L2 bound (``cycle.clip_norm_of``).  ``mode`` must
+                 early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None):
+        """``trim_count``: the FL process's trim count b (``cycle.trim_count_of``).  ``mode`` must then
+        be MEAN, without weights and without ``clip_norm``; every fold runs as TRIMMED_MEAN (early
+        folds as they are: the selection state travels between them on the GPU), and a cycle the
+        engine cannot trim -- fewer than ``2 b + 1`` diffs at the close among them -- raises
+        ``TrimUnavailableError`` instead of being handed back to the node's untrimmed averaging.
+
+        ``clip_norm``: the FL process's per-client L2 bound (``cycle.clip_norm_of``).  ``mode`` must
         then be MEAN; every fold runs as CLIPPED_MEAN, each diff's norm pass is queued right behind
         its ingest (off the close), and a cycle the engine cannot clip raises
         ``ClipUnavailableError`` instead of being handed back to the node's unclipped averaging."""
         self.engine = engine
         self.mode = mode
-        from .cycle import _engine_clip, clip_norm_of
+        from .cycle import _engine_clip, _engine_trim, clip_norm_of, trim_count_of
 
+        self.trim_count = None
+        if trim_count is not None:
+            self.trim_count = trim_count_of({"diff_trim_count": trim_count})
+            if mode != MEAN or weights_by_worker is not None or clip_norm is not None:
+                raise TrimUnavailableError("diff_trim_count applies to the plain mean only (no weights, no iterative "
+                                           "plan, no diff_clip_norm)")
         self.clip_norm = None
         if clip_norm is not None:
             self.clip_norm = clip_norm_of({"diff_clip_norm": clip_norm})
             if mode != MEAN or weights_by_worker is not None:
                 raise ClipUnavailableError("diff_clip_norm applies to the plain mean only (no weights, no iterative plan)")
-        self._fold_mode = CLIPPED_MEAN if self.clip_norm is not None else mode
+        self._fold_mode = (TRIMMED_MEAN if self.trim_count is not None else
+                           CLIPPED_MEAN if self.clip_norm is not None else mode)
         self._numel = tuple(int(n) for n in numel)
         P = sum(self._numel)
         self.slots = int(slots) if slots else default_slots(P)
@@ -144,6 +158,8 @@ class IncrementalCycle:
             _engine_clip(engine, self.clip_norm)
         elif hasattr(engine, "set_clip_norm"):
             engine.set_clip_norm(0.0)  # a shared engine never carries another process's bound over
+        if self.trim_count is not None or hasattr(engine, "set_trim"):
+            _engine_trim(engine, self.trim_count)  # (the engine was reset above: no slot folds under way)
         self._ckpt: Optional[bytes] = None  # checkpoint bytes whose payloads are resident in HBM
         if checkpoint is not None and getattr(engine, "ckpt_owner", None) is not None \
                 and getattr(engine, "ckpt_bytes", None) is checkpoint:
@@ -292,6 +308,9 @@ class IncrementalCycle:
         try:
             _raise_if_not_float32(pb, what)
         except ModelNotAcceleratedError as e:
+            if self.trim_count is not None:
+                raise TrimUnavailableError(f"diff_trim_count is set but {e}; the node's own averaging does not "
+                                           "trim") from e
             if self.clip_norm is None:
                 raise
             raise ClipUnavailableError(f"diff_clip_norm is set but {e}; the node's own averaging does not clip") from e
@@ -382,6 +401,8 @@ class IncrementalCycle:
                 raise AggregationError("cycle already closed")
             self._closed = True
             if self._declined:
+                if self.trim_count is not None:  # fail closed: the node's own averaging does not trim
+                    raise TrimUnavailableError(f"diff_trim_count is set but {self._declined}")
                 if self.clip_norm is not None:  # fail closed: the node's own averaging does not clip
                     raise ClipUnavailableError(f"diff_clip_norm is set but {self._declined}")
                 raise ModelNotAcceleratedError(self._declined)
@@ -398,6 +419,10 @@ class IncrementalCycle:
                 raise AggregationError("the completed-WorkerCycle order lists a worker twice")
             if not order:
                 raise AggregationError("no diffs to average")
+            if self.trim_count is not None:
+                from .cycle import check_trim_count
+
+                check_trim_count(self.trim_count, len(order))
             if self._weights_by_worker is not None:
                 missing = [w for w in order if w not in self._weights_by_worker]
                 if missing:
@@ -460,6 +485,7 @@ class IncrementalCycle:
                 stats.update(clipped=int(cs["clipped"]), max_norm=float(cs["max_norm"]))
             else:
                 stats.update(clipped=0, max_norm=None)
+            stats.update(trim=self.trim_count)
             self.last_close = stats
             new = (state_codec.fresh_checkpoint(self.engine, checkpoint, prepared=prep) if framing == "fresh"
                    else self.engine.ckpt_patch_state(checkpoint))

@@ -72,8 +72,10 @@ from typing import Callable, Dict, Optional, Sequence
 
 from . import state as state_codec
 from .checkpoints import Checkpoint, CheckpointStore
-from .cycle import CycleAggregator, clip_norm_of, finish_cycle, hosted_plan, make_average_plan_diffs, select_mode
+from .cycle import CycleAggregator, clip_norm_of, finish_cycle, hosted_plan, make_average_plan_diffs, select_mode, \
+    trim_count_of
 from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
+    TrimUnavailableError, \
     PyGridError, StateParseError
 from .incremental import IncrementalCycle
 from .trigger import CycleCloseTrigger
@@ -315,6 +317,13 @@ class NodeEngine:
     def _new_cycle(self, cm, cycle, fresh: bool = False) -> IncrementalCycle:
         server_config, _ = self.process_manager.get_configs(id=cycle.fl_process_id)
         clip = clip_norm_of(server_config)  # the process's diff_clip_norm (a malformed one raises)
+        trim = trim_count_of(server_config)  # and its diff_trim_count
+        if trim is not None:
+            try:
+                return self._new_cycle_for(cm, cycle, server_config, clip, fresh, trim)
+            except PlanNotAcceleratedError as e:  # not _DECLINED: the node's own averaging does not trim
+                raise TrimUnavailableError(f"diff_trim_count is set but the engine does not average this cycle "
+                                           f"({e})") from e
         if clip is None:
             return self._new_cycle_for(cm, cycle, server_config, None, fresh)
         try:
@@ -325,7 +334,7 @@ class NodeEngine:
             raise ClipUnavailableError(f"diff_clip_norm is set but the engine does not average this cycle ({e})") \
                 from e
 
-    def _new_cycle_for(self, cm, cycle, server_config, clip, fresh: bool) -> IncrementalCycle:
+    def _new_cycle_for(self, cm, cycle, server_config, clip, fresh: bool, trim=None) -> IncrementalCycle:
         avg_plan, plan_key = hosted_plan(server_config, cycle, self.process_manager, self.plan_manager,
                                          self.aggregator.mean_plans)
         model = self.model_manager.get(fl_process_id=cycle.fl_process_id)
@@ -338,12 +347,13 @@ class NodeEngine:
             _decline_non_float32(ckpt, "the checkpoint")
             raise
         select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
-                    shapes=lambda: _shapes(ckpt), clip_norm=clip)  # with a bound: MEAN-able, or ClipUnavailableError
+                    shapes=lambda: _shapes(ckpt), clip_norm=clip,
+                    trim_count=trim)  # with a bound or a trim count: MEAN-able, or Clip- / TrimUnavailableError
         mode = select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
                            shapes=lambda: _shapes(ckpt))
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
         inc = IncrementalCycle(self.engine, numel, mode=mode, slots=self.slots, fold_batch=self.fold_batch,
-                               checkpoint=ckpt, clip_norm=clip)
+                               checkpoint=ckpt, clip_norm=clip, trim_count=trim)
         if not fresh:  # after a restart: the rows assigned before it (a cycle just created has none;
             # an assignment that lands while this state is built is recorded from _pending_assign)
             for row in _rows(cm, cycle_id=cycle.id):
@@ -422,8 +432,11 @@ class NodeEngine:
         """The close (executor thread).  Holds the engine lock throughout, the report gate only for
         the snapshot of the completed rows (see the module docstring)."""
         clip = clip_norm_of(server_config)  # a malformed bound fails the close
+        trim = trim_count_of(server_config)  # and so does a malformed trim count
         if clip is not None:
             original = _refuse_unclipped(cycle.id)  # fail closed: the node's own averaging does not clip
+        if trim is not None:
+            original = _refuse_untrimmed(cycle.id)  # nor does it trim
         with self._engine_for_close():
             model = ckpt = None
             if isinstance(self._cycles.get(cycle.id), IncrementalCycle):
@@ -491,6 +504,9 @@ class NodeEngine:
                 log.info("cycle %s closed with diff_clip_norm=%g: %d of %d diffs clipped, max norm %g", cycle.id, clip,
                          st.last_close.get("clipped", 0), st.last_close.get("n", 0),
                          st.last_close.get("max_norm") or 0.0)
+            if trim is not None:
+                log.info("cycle %s closed with diff_trim_count=%d: per parameter %d of %d values kept", cycle.id, trim,
+                         st.last_close.get("n", 0) - 2 * trim, st.last_close.get("n", 0))
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)
             self.aggregator._resident = None
@@ -543,6 +559,14 @@ def _refuse_unclipped(cycle_id):
     def original(*_a, **_k):
         raise ClipUnavailableError(f"cycle {cycle_id}: diff_clip_norm is set and the engine does not average this "
                                    "cycle; not falling back to the node's unclipped averaging")
+    return original
+
+
+def _refuse_untrimmed(cycle_id):
+    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for a trimmed mean."""
+    def original(*_a, **_k):
+        raise TrimUnavailableError(f"cycle {cycle_id}: diff_trim_count is set and the engine does not average this "
+                                   "cycle; not falling back to the node's untrimmed averaging")
     return original
 
 
