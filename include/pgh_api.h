@@ -51,13 +51,16 @@ typedef enum {
  * bit when no diff exceeds the bound).
  * PGH_TRIMMED_MEAN: per parameter, the mean of the N reported values without the b largest and the
  * b smallest (coordinate-wise trimmed mean, Yin et al. 2018; b from pgh_set_trim; no reference
- * counterpart). */
+ * counterpart).
+ * PGH_MEDIAN: per parameter, the median of the N reported values (coordinate-wise median, Yin et al.
+ * 2018; no parameter; no reference counterpart; defined below, before the reductions). */
 typedef enum {
     PGH_MEAN = 0,
     PGH_ITERATIVE_MEAN = 1,
     PGH_WEIGHTED_MEAN = 2,
     PGH_CLIPPED_MEAN = 3,
-    PGH_TRIMMED_MEAN = 4
+    PGH_TRIMMED_MEAN = 4,
+    PGH_MEDIAN = 5
 } pgh_mode;
 /* Stream kind for pgh_stream_begin besides the three averaging modes. */
 #define PGH_STREAM_SECAGG 16
@@ -241,6 +244,30 @@ int pgh_clip_stats(pgh_ctx* ctx, int64_t* n_rows, int64_t* n_clipped, double* ma
 #define PGH_TRIM_MAX 8
 int pgh_set_trim(pgh_ctx* ctx, int b);
 
+/* ---- coordinate-wise median (PGH_MEDIAN) -------------------------------------------------------
+ * Per parameter, with the trimmed mean's total order on bit patterns (key above; unkey = key; equal
+ * keys are identical bits, so ties need no rule) and s = sort(keys of the N reported values):
+ *   N odd:  m = unkey(s[(N - 1) / 2]);
+ *   N even: a = unkey(s[N / 2 - 1]), b = unkey(s[N / 2]), m = 0.5f * a + 0.5f * b -- two f32
+ *           products, each rounded, added once in f32, no FMA (two middles of 3e38 give 3e38; a -inf
+ *           and a +inf middle give NaN);
+ *   out = ckpt - m, one f32 subtraction.
+ * Fewer than ceil(N / 2) rows of arbitrary content cannot move a parameter outside the range of the
+ * others' values; a majority of NaNs of one sign leaves a NaN.  The median is pure selection: the
+ * result does not depend on the order of the rows, the slots, the launch shape, the slab's block
+ * width, the range split or the kernel path.
+ * The mode takes every row of the cycle in one call: pgh_fedavg, pgh_fedavg_device[_range],
+ * pgh_fedavg_resident and pgh_fold_slots_finish_resident (any n up to the slab's capacity, no
+ * earlier slot fold in the cycle: PGH_E_STATE otherwise) accept it, on shards and groups too
+ * (nothing in it looks along a row).  pgh_fold_slots and pgh_stream_begin refuse it
+ * (PGH_E_UNSUPPORTED): nothing can be folded before every row is there.
+ * Two kernel paths with the same results: up to PGH_MEDIAN_NCHIP rows the selection runs on chip in
+ * one pass over the slab (K9); more rows, or PGH_MEDIAN_PATH=passes (read by pgh_create), take one
+ * pass per key bit with a plane of P_shard words in HBM (K9p).  pgh_effective_variant(ctx,
+ * PGH_MEDIAN) reports 50 or 51 for the diffs currently held; pgh_set_variant does not affect
+ * median folds. */
+#define PGH_MEDIAN_NCHIP 1024
+
 /* ---- reduction ----------------------------------------------------------------------------
  * out = ckpt - avg(diffs), over this context's shard.  Host pointers, P_shard floats each. */
 int pgh_fedavg(pgh_ctx* ctx, int mode, const float* ckpt, float* out);
@@ -317,7 +344,7 @@ int pgh_synth_ckpt_device(pgh_ctx* ctx, uint64_t seed, float* d_ckpt, void* stre
  * folded into the running state (same op order as RESIDENT: bit-identical results) and its slots
  * are freed; H2D of later clients overlaps those folds.  kind = a pgh_mode or PGH_STREAM_SECAGG;
  * fold_batch <= 0 means half the slots.  Clients may arrive out of order within the ring.
- * PGH_CLIPPED_MEAN and PGH_TRIMMED_MEAN are refused (PGH_E_UNSUPPORTED). */
+ * PGH_CLIPPED_MEAN, PGH_TRIMMED_MEAN and PGH_MEDIAN are refused (PGH_E_UNSUPPORTED). */
 int pgh_stream_begin(pgh_ctx* ctx, int kind, int fold_batch);
 int pgh_stream_flush(pgh_ctx* ctx);               /* fold the ready run now */
 /* Fold what is left and write out = ckpt - avg (all clients [0, n) must have arrived). */

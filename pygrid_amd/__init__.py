@@ -15,9 +15,11 @@ Importing the package changes nothing in the host process; ``tune_process()`` is
 opt-in for the process-wide settings the engine benefits from (HIP hardware queues, glibc
 thresholds for 47 MB buffers).
 """
-from .exceptions import (AggregationError, ClipUnavailableError, EngineUnavailableError, ModelNotAcceleratedError,
+from .exceptions import (AggregationError, ClipUnavailableError, EngineUnavailableError, MedianUnavailableError,
+                         ModelNotAcceleratedError,
                          PlanNotAcceleratedError, PyGridError, StateParseError, TrimUnavailableError)
-from .engine import (CLIPPED_MEAN, F32, I64, ITERATIVE_MEAN, MEAN, MODE_NAMES, STREAM_SECAGG, TRIMMED_MEAN, TRIM_MAX,
+from .engine import (CLIPPED_MEAN, F32, I64, ITERATIVE_MEAN, MEAN, MEDIAN, MEDIAN_NCHIP, MODE_NAMES, STREAM_SECAGG,
+                     TRIMMED_MEAN, TRIM_MAX,
                      WEIGHTED_MEAN, Engine, PinnedBuffer, device_count)
 
 
@@ -38,9 +40,9 @@ def tune_process(hw_queues: bool = True, malloc: bool = True) -> dict:
 
 __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
-    "StateParseError", "TrimUnavailableError",
+    "StateParseError", "TrimUnavailableError", "MedianUnavailableError",
     "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
-    "TRIM_MAX", "MODE_NAMES", "F32", "I64",
+    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "MODE_NAMES", "F32", "I64",
     "tune_process",
 ]
 __version__ = "0.3.0"

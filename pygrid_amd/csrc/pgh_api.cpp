@@ -92,7 +92,7 @@ static void sync_work(pgh_ctx* c) {
 
 void free_slab(pgh_ctx* c) {
     sync_work(c);
-    for (auto* v : {&c->d_slab, &c->d_ckpt, &c->d_out, &c->d_acc, &c->d_uacc, &c->d_sum, &c->d_dec, &c->d_w, &c->d_trim}) v->reset();
+    for (auto* v : {&c->d_slab, &c->d_ckpt, &c->d_out, &c->d_acc, &c->d_uacc, &c->d_sum, &c->d_dec, &c->d_w, &c->d_trim, &c->d_med, &c->d_rowidx}) v->reset();
     c->ckpt_valid = false;
     clear_final_marks(c);
     free_clip(c);
@@ -188,6 +188,7 @@ int pgh_create(int device, size_t pinned_bytes, pgh_ctx** out) {
     if (const char* e = std::getenv("PGH_PINNED_GATHER")) c->pinned_gather = std::atoi(e) != 0;
     if (const char* e = std::getenv("PGH_BLOCK_BYTES")) c->block_bytes = (size_t)std::max(0LL, std::atoll(e));
     if (const char* e = std::getenv("PGH_TRIM_VEC")) c->trim_vec = std::atoi(e) == 4 ? 4 : std::atoi(e) == 1 ? 1 : 0;
+    if (const char* e = std::getenv("PGH_MEDIAN_PATH")) c->median_passes = std::strcmp(e, "passes") == 0;
     if (const char* e = std::getenv("PGH_FINAL_RANGES")) c->final_split = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("PGH_D2H_STREAM")) c->d2h_mode = std::max(0, std::min(1, std::atoi(e)));
     c->own_d2h = c->d2h_mode > 0;
@@ -374,6 +375,11 @@ int pgh_effective_variant(pgh_ctx* c, int mode) {
     if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
     if (mode == PGH_TRIMMED_MEAN)  // K8's two column widths, whatever pgh_set_variant says
         return (c->trim_vec ? c->trim_vec : pgh::auto_trim_vec(c->pg, c->trim_b)) == 4 ? 40 : 41;
+    if (mode == PGH_MEDIAN) {  // K9 or K9p by the diffs held now, whatever pgh_set_variant says
+        int64_t n = 0;
+        for (int64_t k : c->slot_client) n += k >= 0 ? 1 : 0;
+        return median_variant(c, n);
+    }
     if (c->variant >= 0) return c->variant;
     if (mode == PGH_STREAM_SECAGG) return 14;  // SECAGG_AUTO_VARIANT in pgh_kernels.hip
     if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);

@@ -7,7 +7,7 @@
 //   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks
 //   pgh_order.cpp   which stream waits for what, and the timing events
 //   pgh_ingest.cpp  host bytes -> HBM slab rows (raw, State messages, int64 shares, synthetic)
-//   pgh_reduce.cpp  fold_run, RESIDENT and STREAM folds, the resident checkpoint, secagg, clipping, trimming
+//   pgh_reduce.cpp  fold_run, RESIDENT and STREAM folds, the resident checkpoint, secagg, clipping, trimming, the median
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order)
 // The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
@@ -40,7 +40,7 @@ namespace pgh_detail {
 
 constexpr int KIND_SECAGG = PGH_STREAM_SECAGG;  // fold kind besides the pgh_mode values (none of which it equals)
 static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KIND_SECAGG != PGH_WEIGHTED_MEAN &&
-                  KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN,
+                  KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN && KIND_SECAGG != PGH_MEDIAN,
               "the secagg fold kind must not collide with an averaging mode");
 
 // CPUs on the GPU's own socket (its PCI device's local_cpulist) that this process may run on; empty
@@ -234,6 +234,13 @@ struct pgh_ctx {
     int trim_vec = 0;  // PGH_TRIM_VEC: 4 or 1 forces K8's column width, 0 = by shard size
     DeviceBuf d_trim;
 
+    // Median FedAvg (PGH_MEDIAN).  K9 keeps everything on chip; K9p keeps the
+    // bisection's prefix in a plane of pvec words between its launches, and a slot list longer than
+    // a RowTab goes to the kernels as a device table: both allocated by the first fold that needs them.
+    bool median_passes = false;  // PGH_MEDIAN_PATH=passes: K9p whatever the row count
+    DeviceBuf d_med;             // uint32 [pvec]
+    DeviceBuf d_rowidx;          // int32 [slots]
+
     bool streaming = false;
     int slot_mode = -1;  // pgh_fold_slots: averaging mode of the cycle being folded slot by slot
     int kind = 0;
@@ -286,9 +293,10 @@ double now_ms();
 inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
 inline bool valid_mode(int m) {
     return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN ||
-           m == PGH_TRIMMED_MEAN;
+           m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN;
 }
 static_assert(PGH_TRIMMED_MEAN == pgh::MODE_TRIMMED && PGH_TRIM_MAX == pgh::TRIM_MAX, "the kernels' numbering");
+static_assert(PGH_MEDIAN == pgh::MODE_MEDIAN && PGH_MEDIAN_NCHIP == pgh::MEDIAN_NCHIP, "the kernels' numbering");
 // The kernels' mode: a clipped mean is the weighted fold with the scales as weights.
 inline int kernel_mode(int m) { return m == PGH_CLIPPED_MEAN ? PGH_WEIGHTED_MEAN : m; }
 // valid_mode, and PGH_CLIPPED_MEAN only with a bound set, PGH_TRIMMED_MEAN only with a trim count
@@ -425,6 +433,16 @@ inline uint64_t trim_state_bytes(const pgh_ctx* c, int flags, uint64_t rp) {
     const uint64_t planes = 2ull * (uint64_t)c->trim_b;  // (the acc plane is counted like the other modes')
     return ((flags & pgh::FL_FIRST) ? 0 : 4 * planes * rp) + ((flags & pgh::FL_FINAL) ? 0 : 4 * planes * rp);
 }
+
+// ---- median FedAvg (pgh_reduce.cpp) ------------------------------------------------------------------
+// The path a median fold of n rows takes: 50 (K9, on chip) or 51 (K9p, one pass per bit).
+inline int median_variant(const pgh_ctx* c, int64_t n) { return c->median_passes || n > pgh::MEDIAN_NCHIP ? 51 : 50; }
+// The whole median fold of a filled FedavgArgs (diffs, map, n_rows, p, ckpt, out; every row of the
+// cycle) on stream s: K9's one launch or K9p's 32 or 33.  The rows: tab, else d_rows (a device table
+// of n_rows entries), else contiguous from a.diffs.
+int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s);
+// slots[k] * parties for k < n, uploaded to d_rowidx on stream s (waits for the copy)
+int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s);
 
 // What a FINAL fold pass writes (fedavg: ckpt - avg; secagg: sum/dec) and over which param range.
 struct FinalArgs {

@@ -9,7 +9,7 @@ namespace pgh {
 
 // fedavg modes (same numbering as PGH_MEAN / PGH_ITERATIVE_MEAN / PGH_WEIGHTED_MEAN)
 // (3, PGH_CLIPPED_MEAN, reaches the kernels as MODE_WEIGHTED over the scales)
-enum { MODE_MEAN = 0, MODE_ITERATIVE = 1, MODE_WEIGHTED = 2, MODE_TRIMMED = 4 };
+enum { MODE_MEAN = 0, MODE_ITERATIVE = 1, MODE_WEIGHTED = 2, MODE_TRIMMED = 4, MODE_MEDIAN = 5 };
 constexpr int TRIM_MAX = 8;
 // flags for a chunked (client-streaming) reduction
 enum { FL_FIRST = 1, FL_FINAL = 2 };
@@ -75,6 +75,36 @@ struct RowTab {
     int32_t rows[ROWTAB_MAX];
 };
 hipError_t launch_fedavg_rows(const FedavgArgs& a, const RowTab& t, hipStream_t s);
+
+// MODE_MEDIAN (the definition is in include/pgh_api.h): out = ckpt - median over the launch's rows,
+// per param.  Values are compared as u = key(x) ^ 0x80000000 (unsigned order = the key's signed
+// order); the element of rank (n - 1) / 2 is found by bisection on u, most significant bit first:
+// T = prefix | 1 << bit; prefix = T when #{u < T} <= rank.  An even n also needs the next element:
+// with c = #{u <= lower} it is lower when c >= n / 2 + 1 and min{u > lower} otherwise.
+// The rows: tab (at most ROWTAB_MAX, by value), else rowidx (a device table of n_rows slab rows),
+// else n_rows contiguous rows from diffs.
+// K9 launch_median: one pass over HBM.  The rows of a tile of 64 columns come on chip as keys in
+// registers, one column per lane: up to 64 rows in one lane (8 / 16 / 32 / 64 keys), more rows split
+// over the 2 / 4 / 8 / MEDIAN_WAVES waves of a workgroup (64 keys per lane, wave w holding rows w,
+// w + W, ...), whose per-bit counts meet in LDS.  n_rows <= MEDIAN_NCHIP.
+// K9p launch_median_pass: any n_rows.  One launch per bit (31 .. 0) and one more (bit = -1) for the
+// upper middle of an even n; one lane walks down its column and counts.  The prefix of a param
+// lives in `prefix` ([p] words at the launch's column 0) between the launches: bit 31 starts it,
+// the last launch (bit 0 for an odd n, -1 for an even one) writes out instead.
+constexpr int MEDIAN_WAVES = 16;
+constexpr int MEDIAN_NCHIP = 64 * MEDIAN_WAVES;
+struct MedianArgs {
+    const float* diffs;      // the slab at row 0 (tab / rowidx) or at the first row
+    SlabMap map;             // map.off = shard param of local column 0
+    int n_rows;
+    int64_t p;               // params of the launch
+    const int32_t* rowidx;   // device, [n_rows]; nullptr = contiguous rows (or tab)
+    const float* ckpt;       // [p]
+    float* out;              // [p]
+    uint32_t* prefix;        // [p], K9p only
+};
+hipError_t launch_median(const MedianArgs& a, const RowTab* tab, hipStream_t s);
+hipError_t launch_median_pass(const MedianArgs& a, const RowTab* tab, int bit, hipStream_t s);
 
 struct SecaggArgs {
     const int64_t* shares;  // slab at the first row (rows = clients x parties)

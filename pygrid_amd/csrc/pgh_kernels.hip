@@ -9,6 +9,9 @@
 //       decode float32(int64)/10^prec (PySyft 0.2.9 semantics)
 // K8  k_fedavg_trim            per param, the mean without the b largest and b smallest values
 //       (build-owned: PGH_TRIMMED_MEAN, a register-resident selection network)
+// K9  k_median / k_median_pass per param, the median of the N values: a bisection on the key, the
+//       rows of a 64-column tile on chip (K9) or one pass over the slab per bit (K9p)
+//       (build-owned: PGH_MEDIAN)
 // K7  k_row_sumsq              sumsq_c = sum_i (double)d_c[i]^2 along a client's row, in one fixed
 //       order (build-owned: the norms of PGH_CLIPPED_MEAN)
 //
@@ -19,7 +22,9 @@
 // client rows in index order, so the fp32 fold order is exactly the reference's left fold
 // (bit-exact, no tree/shuffle reordering).  U rows are issued before they are consumed to keep
 // U loads per lane in flight.  No LDS: there is no reuse to stage, and no MFMA: this is a
-// 0.25 flop/byte reduction, bound by HBM bandwidth.
+// 0.25 flop/byte reduction, bound by HBM bandwidth.  (K9, the median, is the exception: it holds
+// the rows of a tile on chip, a column's rows shared by the waves of a workgroup past 64 rows, whose
+// per-bit counts meet in 1 KiB of LDS.)
 //
 // Build flags matter for parity: -ffp-contract=off (no a*k+d -> FMA), no fast-math, f32
 // denormals kept, IEEE (correctly rounded) f32 division.
@@ -493,6 +498,161 @@ template <int B, int U, int TB, int VEC>
 __global__ __launch_bounds__(TB) void k_fedavg_trim_rows(FedavgArgs a, int64_t ncol, RowTab tab) {
     const int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x;
     if (q < ncol) trim_column<B, U, VEC, true>(a, &tab, q);
+}
+
+// K9 / K9p: coordinate-wise median (MODE_MEDIAN; the definition is in include/pgh_api.h, the
+// bisection in pgh_kernels.h).  Values are compared as u = key ^ 0x80000000, unsigned.
+__device__ __forceinline__ uint32_t med_ukey(uint32_t b) { return b ^ (uint32_t)(((int)b >> 31) | (int)0x80000000); }
+__device__ __forceinline__ float med_value(uint32_t u) { return __int_as_float(trim_key((int)(u ^ 0x80000000u))); }
+// m = lower for an odd n, 0.5f * lower + 0.5f * upper (two rounded products, one rounded sum) for an even one
+__device__ __forceinline__ float med_mid(uint32_t lower, uint32_t upper, bool even) {
+    const float a = med_value(lower);
+    return even ? __fadd_rn(__fmul_rn(0.5f, a), __fmul_rn(0.5f, med_value(upper))) : a;
+}
+
+// Slab row of the launch's row r (wave-uniform): SRC 0 contiguous, 1 the RowTab, 2 the device table.
+template <int SRC>
+__device__ __forceinline__ size_t med_row(const MedianArgs& a, const RowTab* t, int r) {
+    if constexpr (SRC == 1) return (size_t)(uint32_t)t->rows[r];
+    else if constexpr (SRC == 2) return (size_t)(uint32_t)a.rowidx[r];
+    else return (size_t)r;
+}
+
+// K9.  A tile = 64 consecutive columns; lane l of a wave owns column l of its tile, so a wave-wide
+// load reads 256 contiguous bytes of one row.  The rows of a tile are split over the W waves of a
+// workgroup (wave w holds rows w, w + W, ...: KPL keys per lane in registers), all KPL loads of a
+// lane issued before the first use.  Places past n_rows hold the largest u, which no rank below
+// n_rows reaches; lanes past p hold only those and store nothing (the slab's padding columns are
+// never read).
+// Per bit every lane counts its keys below T (v_cmp_lt_u32 + v_addc per key); with W > 1 the W
+// counts of a column meet in LDS -- one ds_add per lane into one of three 64-word buffers used in
+// turn (wave 0 clears the one of the bit before, so a bit costs one barrier), one read back -- and
+// every lane of the column takes the same branch.  Per float: 3 (key) + 32 x 2 ops; per lane and
+// bit two LDS operations on top.  W = 1 (up to 64 rows): a lane holds its whole column, no LDS and no
+// barrier, four independent tiles per 256-thread workgroup.
+template <int W, int KPL, int SRC>
+__device__ __forceinline__ void median_tile(const MedianArgs& a, const RowTab* tab) {
+    __shared__ uint32_t s_cnt[3][64];
+    __shared__ uint32_t s_min[64];
+    const int lane = threadIdx.x & 63;
+    const int w = W == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t q = W == 1 ? (int64_t)blockIdx.x * blockDim.x + threadIdx.x : (int64_t)blockIdx.x * 64 + lane;
+    const bool live = q < a.p;
+    const int n = a.n_rows;
+    const int64_t ld = a.map.ld;
+    const uint32_t* col = reinterpret_cast<const uint32_t*>(a.diffs) + a.map.at(live ? q : 0);
+    uint32_t k[KPL];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        const int r = w + W * j;
+        k[j] = 0x7fffffffu;  // bits of the largest key
+        if (r < n && live) k[j] = __builtin_nontemporal_load(col + med_row<SRC>(a, tab, r) * ld);
+    }
+    if constexpr (W > 1) {
+        if (w == 0) {
+            s_cnt[0][lane] = s_cnt[1][lane] = s_cnt[2][lane] = 0;
+            s_min[lane] = 0xffffffffu;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) k[j] = med_ukey(k[j]);
+    const uint32_t rank = (uint32_t)(n - 1) >> 1;
+    uint32_t pre = 0;
+    int buf = 0;  // s_cnt[buf]: all zero here; s_cnt[buf + 2 (mod 3)] was read a barrier ago
+#pragma unroll 1
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t T = pre | (1u << bit);
+        uint32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < KPL; ++j) c += k[j] < T ? 1u : 0u;
+        if constexpr (W > 1) {
+            __hip_atomic_fetch_add(&s_cnt[buf][lane], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __syncthreads();
+            c = s_cnt[buf][lane];
+            const int old = buf == 0 ? 2 : buf - 1;
+            if (w == 0) s_cnt[old][lane] = 0;  // every wave read it before this bit's barrier
+            buf = buf == 2 ? 0 : buf + 1;
+        }
+        if (c <= rank) pre = T;
+    }
+    const bool even = !(n & 1);
+    uint32_t upper = pre;
+    if (even) {  // (uniform)
+        uint32_t c = 0, mn = 0xffffffffu;
+#pragma unroll
+        for (int j = 0; j < KPL; ++j) {
+            c += k[j] <= pre ? 1u : 0u;
+            mn = k[j] > pre ? min(mn, k[j]) : mn;
+        }
+        if constexpr (W > 1) {
+            __hip_atomic_fetch_add(&s_cnt[buf][lane], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_min(&s_min[lane], mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __syncthreads();
+            c = s_cnt[buf][lane];
+            mn = s_min[lane];
+        }
+        upper = c >= (uint32_t)(n / 2 + 1) ? pre : mn;
+    }
+    if (w == 0 && live) a.out[q] = a.ckpt[q] - med_mid(pre, upper, even);
+}
+
+template <int W, int KPL, int SRC>
+__global__ __launch_bounds__(W == 1 ? BLOCK : 64 * W) void k_median(MedianArgs a) {
+    median_tile<W, KPL, SRC>(a, nullptr);
+}
+template <int W, int KPL>
+__global__ __launch_bounds__(W == 1 ? BLOCK : 64 * W) void k_median_tab(MedianArgs a, RowTab tab) {
+    median_tile<W, KPL, 1>(a, &tab);
+}
+
+// K9p: one step of the same bisection with the prefix in HBM: the K1 walk (one lane down its
+// column, U loads in flight) counting instead of adding.  3 (key) + 2 ops per float and pass.
+template <int SRC, int U>
+__device__ __forceinline__ void median_pass(const MedianArgs& a, const RowTab* tab, int bit) {
+    const int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= a.p) return;
+    const int n = a.n_rows;
+    const int64_t ld = a.map.ld;
+    const uint32_t* col = reinterpret_cast<const uint32_t*>(a.diffs) + a.map.at(q);
+    const uint32_t pre = bit == 31 ? 0u : a.prefix[q];
+    const bool upper_pass = bit < 0;
+    const uint32_t T = upper_pass ? pre : pre | (1u << bit);
+    uint32_t c = 0, mn = 0xffffffffu;
+    for (int r = 0; r < n; r += U) {
+        const int nv = min(U, n - r);
+        uint32_t x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (u < nv) x[u] = __builtin_nontemporal_load(col + med_row<SRC>(a, tab, r + u) * ld);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (u < nv) {
+                const uint32_t key = med_ukey(x[u]);
+                if (upper_pass) {
+                    c += key <= T ? 1u : 0u;
+                    mn = key > T ? min(mn, key) : mn;
+                } else {
+                    c += key < T ? 1u : 0u;
+                }
+            }
+    }
+    const bool even = !(n & 1);
+    if (upper_pass) {
+        a.out[q] = a.ckpt[q] - med_mid(pre, c >= (uint32_t)(n / 2 + 1) ? pre : mn, true);
+        return;
+    }
+    const uint32_t next = c <= ((uint32_t)(n - 1) >> 1) ? T : pre;
+    if (bit == 0 && !even) a.out[q] = a.ckpt[q] - med_mid(next, next, false);
+    else a.prefix[q] = next;
+}
+
+template <int SRC>
+__global__ __launch_bounds__(BLOCK) void k_median_pass(MedianArgs a, int bit) {
+    median_pass<SRC, 16>(a, nullptr, bit);
+}
+__global__ __launch_bounds__(BLOCK) void k_median_pass_tab(MedianArgs a, int bit, RowTab tab) {
+    median_pass<1, 16>(a, &tab, bit);
 }
 
 // Z_2^64 lane element: VEC = 2 (16-byte column of 2 int64) or 1 (one int64 per lane).
@@ -1216,6 +1376,46 @@ hipError_t launch_fedavg_rows(const FedavgArgs& a_, const RowTab& t, hipStream_t
     case MODE_WEIGHTED: return dispatch_fedavg_rows<MODE_WEIGHTED>(a, t, v, s);
     default: return hipErrorInvalidValue;
     }
+}
+
+static bool valid_median(const MedianArgs& a, const RowTab* t) {
+    if (a.p <= 0 || a.n_rows < 1 || !valid_map(a.map, a.p)) return false;
+    if (!a.diffs || !aligned16(a.diffs) || !a.ckpt || !a.out) return false;
+    return !t || a.n_rows <= ROWTAB_MAX;
+}
+
+template <int W, int KPL>
+static hipError_t go_median(const MedianArgs& a, const RowTab* t, hipStream_t s) {
+    constexpr int TB = W == 1 ? BLOCK : 64 * W;
+    const unsigned grid = grid_for(a.p, W == 1 ? BLOCK : 64, false);
+    if (t) k_median_tab<W, KPL><<<grid, TB, 0, s>>>(a, *t);
+    else if (a.rowidx) k_median<W, KPL, 2><<<grid, TB, 0, s>>>(a);
+    else k_median<W, KPL, 0><<<grid, TB, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// K9's tiers (waves per tile x keys per lane): up to 64 rows a lane holds its whole column, in 8, 16,
+// 32 or 64 registers; up to 128 / 256 / 512 / 1,024 rows 2 / 4 / 8 / 16 waves hold 64 keys per lane.
+hipError_t launch_median(const MedianArgs& a, const RowTab* t, hipStream_t s) {
+    if (!valid_median(a, t) || a.n_rows > MEDIAN_NCHIP) return hipErrorInvalidValue;
+    if (a.n_rows <= 8) return go_median<1, 8>(a, t, s);
+    if (a.n_rows <= 16) return go_median<1, 16>(a, t, s);
+    if (a.n_rows <= 32) return go_median<1, 32>(a, t, s);
+    if (a.n_rows <= 64) return go_median<1, 64>(a, t, s);
+    if (a.n_rows <= 128) return go_median<2, 64>(a, t, s);
+    if (a.n_rows <= 256) return go_median<4, 64>(a, t, s);
+    if (a.n_rows <= 512) return go_median<8, 64>(a, t, s);
+    return go_median<MEDIAN_WAVES, 64>(a, t, s);
+}
+
+hipError_t launch_median_pass(const MedianArgs& a, const RowTab* t, int bit, hipStream_t s) {
+    if (!valid_median(a, t) || !a.prefix || bit < -1 || bit > 31) return hipErrorInvalidValue;
+    if (bit < 0 && (a.n_rows & 1)) return hipErrorInvalidValue;  // an odd n closes at bit 0
+    const unsigned grid = grid_for(a.p, BLOCK, false);
+    if (t) k_median_pass_tab<<<grid, BLOCK, 0, s>>>(a, bit, *t);
+    else if (a.rowidx) k_median_pass<2><<<grid, BLOCK, 0, s>>>(a, bit);
+    else k_median_pass<0><<<grid, BLOCK, 0, s>>>(a, bit);
+    return hipGetLastError();
 }
 
 hipError_t launch_secagg(const SecaggArgs& a, hipStream_t s) {

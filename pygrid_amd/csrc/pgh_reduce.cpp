@@ -64,6 +64,8 @@ int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const Fina
         RC(resident_clip_scales(c, n));
         kind = PGH_WEIGHTED_MEAN;
     }
+    if (kind == PGH_MEDIAN && (c0 != 0 || !final || n > c->slots))
+        return fail(c, PGH_E_UNSUPPORTED, "a median folds every row of a resident slab in one call");
     RC(order_after_ingest(c, s));
     if (kind == PGH_WEIGHTED_MEAN && n > 0) {
         if ((int64_t)c->weights.size() < c0 + n)
@@ -125,7 +127,8 @@ int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const Fina
                 RC(trim_args(c, &a));
                 bytes += trim_state_bytes(c, flags, pg);
             }
-            RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
+            if (kind == PGH_MEDIAN) RC(median_fold(c, a, nullptr, nullptr, s));  // (its own launches and bytes)
+            else RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
         }
         done += seg;
     } while (done < n);
@@ -245,6 +248,42 @@ int trim_args(pgh_ctx* c, pgh::FedavgArgs* a) {
         return fail(c, PGH_E_OOM, "allocation of the trimmed mean's %d state planes failed", 2 * c->trim_b);
     a->tstate = c->d_trim.as<int32_t>() + a->map.off;
     a->tplane = c->pvec;
+    return PGH_OK;
+}
+
+int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s) {
+    if (!c->d_rowidx.reserve(sizeof(int32_t) * (size_t)c->slots))
+        return fail(c, PGH_E_OOM, "allocation of the median's row table (%d rows) failed", c->slots);
+    std::vector<int32_t> rows((size_t)n);
+    for (int k = 0; k < n; ++k) rows[(size_t)k] = slots[k] * c->parties;
+    // (an earlier fold that still reads the table runs on c->stream too, or has been waited for)
+    CK(c, hipMemcpyAsync(c->d_rowidx.as<int32_t>(), rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // rows is freed on return
+    return PGH_OK;
+}
+
+int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s) {
+    pgh::MedianArgs m{};
+    m.diffs = a.diffs;
+    m.map = a.map;
+    m.n_rows = a.n_rows;
+    m.p = a.p;
+    m.rowidx = tab ? nullptr : d_rows;
+    m.ckpt = a.ckpt;
+    m.out = a.out;
+    const uint64_t rows = 4ull * (uint64_t)a.n_rows * (uint64_t)a.p, rp = (uint64_t)a.p;
+    if (median_variant(c, a.n_rows) == 50)  // K9: the slab once, ckpt in, out
+        return timed_launch(c, s, rows + 8 * rp, [&] { return pgh::launch_median(m, tab, s); });
+    if (!c->d_med.reserve(sizeof(uint32_t) * (size_t)c->pvec))
+        return fail(c, PGH_E_OOM, "allocation of the median's prefix plane failed");
+    m.prefix = c->d_med.as<uint32_t>() + a.map.off;
+    // K9p: bits 31 .. 0, then the upper middle of an even count; each launch reads the rows, reads
+    // the prefix plane (not the first) and writes it, or ckpt in and out (the last)
+    const int last = (a.n_rows & 1) ? 0 : -1;
+    for (int bit = 31; bit >= last; --bit) {
+        const uint64_t bytes = rows + (bit == 31 ? 0 : 4 * rp) + (bit == last ? 8 * rp : 4 * rp);
+        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_median_pass(m, tab, bit, s); }));
+    }
     return PGH_OK;
 }
 
@@ -712,6 +751,7 @@ int pgh_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, float* dec_out)
 int pgh_stream_begin(pgh_ctx* c, int kind, int fold_batch) {
     if (c && kind == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not clip: a scale needs the whole row of every client");
     if (c && kind == PGH_TRIMMED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not trim: fold a RESIDENT slab or slots");
+    if (c && kind == PGH_MEDIAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no median: it needs every row at once");
     if (c && c->grp) return pgh_group_api::stream_begin(c, kind, fold_batch);
     RC(check_ready(c));
     if (kind == PGH_STREAM_SECAGG) {

@@ -25,6 +25,10 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         if (seen[(size_t)sl]) return fail(c, PGH_E_ARG, "slot %d listed twice", sl);
         seen[(size_t)sl] = 1;
     }
+    const bool median = mode == PGH_MEDIAN;  // every row of the cycle in this one call
+    if (median && !final) return fail(c, PGH_E_UNSUPPORTED, "a median needs every row at once: nothing can be folded early");
+    if (median && c->folded > 0)
+        return fail(c, PGH_E_STATE, "a median closes a cycle without earlier slot folds (%lld diffs folded)", (long long)c->folded);
     const int64_t c0 = c->folded, total = c0 + n;
     FinalArgs fa;
     if (final) {
@@ -55,12 +59,13 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         RC(sync_weights(c, s));
     }
     if (mode == PGH_ITERATIVE_MEAN && n > 0) RC(ensure_recips(c, total, s));
+    if (median && n > pgh::ROWTAB_MAX) RC(median_row_table(c, slots, n, s));  // more rows than a RowTab carries
     int done = 0;
     bool prequeued = false;
     do {
-        const int m = std::min(n - done, pgh::ROWTAB_MAX);
+        const int m = median ? n : std::min(n - done, pgh::ROWTAB_MAX);
         pgh::RowTab tab;
-        for (int k = 0; k < m; ++k) tab.rows[k] = slots[done + k] * c->parties;
+        for (int k = 0; k < std::min(m, pgh::ROWTAB_MAX); ++k) tab.rows[k] = slots[done + k] * c->parties;
         const bool first = (c0 + done == 0), last = (done + m == n);
         pgh::FedavgArgs a{};
         a.diffs = c->d_slab.as<float>();
@@ -116,7 +121,8 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
                 RC(trim_args(c, &ar));
                 bytes += trim_state_bytes(c, a.flags, rp);
             }
-            RC(timed_launch(c, rs, bytes, [&] { return pgh::launch_fedavg_rows(ar, tab, rs); }));
+            if (median) RC(median_fold(c, ar, m <= pgh::ROWTAB_MAX ? &tab : nullptr, c->d_rowidx.as<int32_t>(), rs));
+            else RC(timed_launch(c, rs, bytes, [&] { return pgh::launch_fedavg_rows(ar, tab, rs); }));
             if (K > 1 && (hi % (2 * RF) == 0 || hi == c->pg)) {
                 RC(add_final_mark(c, rs, hi));
                 const size_t before = prequeue ? pre.queued : 0;
@@ -153,6 +159,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
 }  // namespace
 
 int pgh_fold_slots(pgh_ctx* c, int mode, const int32_t* slots, int n) {
+    if (c && mode == PGH_MEDIAN) return fail(c, PGH_E_UNSUPPORTED, "%s: a median needs every row at once, nothing can be folded early", __func__);
     if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
     if (c && c->grp) return pgh_group_api::fold_slots(c, mode, slots, n, false);
     if (!c) return PGH_E_ARG;

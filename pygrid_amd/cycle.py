@@ -27,9 +27,9 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import state as state_codec
-from .engine import CLIPPED_MEAN, ITERATIVE_MEAN, MEAN, TRIMMED_MEAN, TRIM_MAX, WEIGHTED_MEAN, F32, I64, Engine
+from .engine import CLIPPED_MEAN, ITERATIVE_MEAN, MEAN, MEDIAN, TRIMMED_MEAN, TRIM_MAX, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
-    StateParseError, TrimUnavailableError
+    MedianUnavailableError, StateParseError, TrimUnavailableError
 
 CLIP_KEY = "diff_clip_norm"  # optional server_config key: the per-client L2 bound (no reference counterpart)
 
@@ -79,8 +79,31 @@ def check_trim_count(trim_count: int, n_diffs: int):
                                    f"has {n_diffs}")
 
 
+MEDIAN_KEY = "diff_median"  # optional server_config key: True = the coordinate-wise median (no reference counterpart)
+
+
+def median_of(server_config: dict) -> bool:
+    """Whether the FL process asks for the coordinate-wise median, ``server_config["diff_median"]``:
+    ``True`` turns it on; absent, ``None`` or ``False`` leaves it off.  Anything else -- an int, a
+    string, a float -- raises ``AggregationError``: a mistyped switch must not quietly mean "the
+    plain mean"."""
+    m = server_config.get(MEDIAN_KEY, None)
+    if m is None:
+        return False
+    if isinstance(m, (bool, np.bool_)):
+        return bool(m)
+    raise AggregationError(f"{MEDIAN_KEY} must be True or False, not {m!r}")
+
+
 _NO_CLIP = object()  # "take the bound from server_config"
 _NO_TRIM = _NO_CLIP  # "take the trim count from server_config"
+_NO_MEDIAN = _NO_CLIP  # "take the switch from server_config"
+
+
+def _median_arg(server_config: dict, median) -> bool:
+    if median is _NO_MEDIAN:
+        return median_of(server_config)
+    return median_of({MEDIAN_KEY: median})
 
 
 def _trim_arg(server_config: dict, trim_count):
@@ -242,12 +265,30 @@ def cached_mode(server_config: dict, plan_key, mean_plans: Optional[str] = None)
 
 def select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
                 mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None,
-                trim_count=None) -> int:
+                trim_count=None, median: bool = False) -> int:
     """The dispatch rule below; with ``clip_norm`` set: ``CLIPPED_MEAN`` exactly where the rule gives
     ``MEAN`` (no hosted plan, or a plan probed equal to the mean), ``ClipUnavailableError`` everywhere
     else -- weights, the iterative plan, a plan the engine declines -- so that the caller cannot fall
     back to an average that does not clip.  ``trim_count`` likewise: ``TRIMMED_MEAN`` where the rule
-    gives ``MEAN``, ``TrimUnavailableError`` everywhere else and together with ``clip_norm``."""
+    gives ``MEAN``, ``TrimUnavailableError`` everywhere else and together with ``clip_norm``.
+    ``median`` likewise: ``MEDIAN`` where the rule gives ``MEAN``, ``MedianUnavailableError``
+    everywhere else and together with ``clip_norm`` or ``trim_count``."""
+    if median:
+        if clip_norm is not None:
+            raise MedianUnavailableError(f"{MEDIAN_KEY} cannot be combined with {CLIP_KEY}")
+        if trim_count is not None:
+            raise MedianUnavailableError(f"{MEDIAN_KEY} cannot be combined with {TRIM_KEY}")
+        if weights is not None:
+            raise MedianUnavailableError(f"{MEDIAN_KEY} cannot be combined with aggregation weights")
+        try:
+            mode = _select_mode(server_config, avg_plan, None, plan_key, mean_plans, shapes, n_clients)
+        except PlanNotAcceleratedError as e:
+            raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine does not run this avg plan ({e}); the "
+                                         "node's own averaging takes no median") from e
+        if mode != MEAN:
+            raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the hosted avg plan is the iterative mean, of "
+                                         "which the engine takes no median")
+        return MEDIAN
     if trim_count is not None:
         if clip_norm is not None:
             raise TrimUnavailableError(f"{TRIM_KEY} cannot be combined with {CLIP_KEY}")
@@ -415,7 +456,7 @@ class CycleAggregator:
     # ---- bytes in / bytes out: the replaceable slice cycle_manager.py:240-303 -------------------
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
-                           plan_key=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM) -> bytes:
+                           plan_key=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM, median=_NO_MEDIAN) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -427,10 +468,14 @@ class CycleAggregator:
             raise AggregationError("no diffs to average")
         clip = _clip_arg(server_config, clip_norm)
         trim = _trim_arg(server_config, trim_count)
+        med = _median_arg(server_config, median)
         try:
             return self._average_plan_diffs(server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key,
-                                            clip, trim)
+                                            clip, trim, med)
         except PlanNotAcceleratedError as e:
+            if med:
+                raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine cannot average this cycle ({e}); "
+                                             "the node's own averaging takes no median") from e
             if trim is not None:
                 raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine cannot average this cycle ({e}); the "
                                            "node's own averaging does not trim") from e
@@ -440,10 +485,10 @@ class CycleAggregator:
                                        "node's own averaging does not clip") from e
 
     def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, clip,
-                            trim=None):
+                            trim=None, median=False):
         mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                            shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), clip_norm=clip,
-                           trim_count=trim)
+                           trim_count=trim, median=median)
         if trim is not None:
             check_trim_count(trim, len(diffs))
         try:
@@ -479,16 +524,20 @@ class CycleAggregator:
     # ---- tensor lists in / out (what the reference holds after unserialize) ---------------------
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
-                       weights=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM) -> List[np.ndarray]:
+                       weights=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM, median=_NO_MEDIAN) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         clip = _clip_arg(server_config, clip_norm)
         trim = _trim_arg(server_config, trim_count)
+        med = _median_arg(server_config, median)
         shapes = [np.shape(p) for p in model_params]
         try:
             mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
-                               n_clients=len(diffs), clip_norm=clip, trim_count=trim)
+                               n_clients=len(diffs), clip_norm=clip, trim_count=trim, median=med)
         except PlanNotAcceleratedError as e:
+            if med:
+                raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine cannot average this cycle ({e})") \
+                    from e
             if trim is None:
                 raise
             raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine cannot average this cycle ({e})") from e
@@ -570,12 +619,16 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
             diffs = [r.diff for r in reports]  # what :247-250 reads, at the query
         clip = clip_norm_of(server_config)  # a malformed bound fails the close
         trim = trim_count_of(server_config)  # and so does a malformed trim count
+        med = median_of(server_config)  # or a malformed median switch
         try:
             avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
                                              getattr(aggregator, "mean_plans", None))
             new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,
                                                      plan_key=plan_key, framing=framing)
         except PlanNotAcceleratedError as e:
+            if med:  # fail closed: the node's own averaging takes no median
+                raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine does not average this cycle ({e})") \
+                    from e
             if trim is not None:  # fail closed: the node's own averaging does not trim
                 raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine does not average this cycle ({e})") \
                     from e

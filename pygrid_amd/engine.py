@@ -15,13 +15,14 @@ import numpy as np
 from . import _lib
 from .exceptions import AggregationError, EngineUnavailableError, StateParseError
 
-MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN = 0, 1, 2, 3, 4
+MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN = 0, 1, 2, 3, 4, 5
 TRIM_MAX = 8  # PGH_TRIM_MAX
+MEDIAN_NCHIP = 1024  # PGH_MEDIAN_NCHIP: rows the on-chip median kernel takes
 STREAM_SECAGG = 16
 DEFAULT_VARIANT = -1  # PGH_DEFAULT_VARIANT: auto by shard size
 F32, I64 = 0, 1
 MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
-              CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean"}
+              CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean", MEDIAN: "median"}
 
 
 def device_count() -> int:
@@ -461,7 +462,8 @@ class Engine:
 
     def effective_variant(self, mode: int = MEAN) -> int:
         """Kernel variant the next fold runs for ``mode`` (MEAN / ITERATIVE_MEAN / WEIGHTED_MEAN /
-        STREAM_SECAGG; TRIMMED_MEAN: 40 for 16-byte columns, 41 for one parameter per lane)."""
+        STREAM_SECAGG; TRIMMED_MEAN: 40 for 16-byte columns, 41 for one parameter per lane; MEDIAN: 50
+        for the on-chip kernel, 51 for one pass per key bit, by the diffs held now)."""
         v = self._lib.pgh_effective_variant(self._h, int(mode))
         self._check(min(v, 0), "effective_variant")
         return v

@@ -51,6 +51,15 @@ class TrimUnavailableError(AggregationError):
     ``PlanNotAcceleratedError``: the node's own averaging does not trim, so the close fails closed."""
 
 
+class MedianUnavailableError(AggregationError):
+    """The FL process asks for the coordinate-wise median (``server_config["diff_median"]``) and the
+    engine cannot take it this cycle: a hosted iterative or unaccelerated plan, a non-float32 model,
+    aggregation weights, ``diff_clip_norm`` or ``diff_trim_count`` given together with it, or more
+    diffs at the close than the slab has slots.  Like ``ClipUnavailableError`` and
+    ``TrimUnavailableError`` it is NOT a ``PlanNotAcceleratedError``: the node's own averaging takes
+    no median, so the close fails closed."""
+
+
 class ModelNotAcceleratedError(PlanNotAcceleratedError):
     """The checkpoint or a diff holds well-formed tensors that are not float32 (another dtype, or a
     serializer other than syft's "all").  The reference averages them with torch's type promotion;

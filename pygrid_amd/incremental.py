@@ -65,9 +65,9 @@ import threading
 from typing import Callable, Dict, Hashable, List, Optional, Sequence
 
 from . import state as state_codec
-from .engine import CLIPPED_MEAN, F32, MEAN, TRIMMED_MEAN, WEIGHTED_MEAN, Engine
-from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, StateParseError, \
-    TrimUnavailableError
+from .engine import CLIPPED_MEAN, F32, MEAN, MEDIAN, TRIMMED_MEAN, WEIGHTED_MEAN, Engine
+from .exceptions import AggregationError, ClipUnavailableError, MedianUnavailableError, ModelNotAcceleratedError, \
+    StateParseError, TrimUnavailableError
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
 MAX_DEFAULT_SLOTS = 4096
@@ -82,8 +82,18 @@ def default_slots(P: int, budget: int = DEFAULT_HBM_BUDGET) -> int:
 class IncrementalCycle:
     def __init__(self, engine: Engine, numel, mode: int = MEAN, slots: Optional[int] = None, fold_batch: int = 8,
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
-                 early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None):
-        """``trim_count``: the FL process's trim count b (``cycle.trim_count_of``).  ``mode`` must then
+                 early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
+                 median: bool = False):
+        """``median``: the FL process asks for the coordinate-wise median (``cycle.median_of``).  ``mode``
+        must then be MEAN, without weights, ``clip_norm`` or ``trim_count``.  A median needs every row
+        at once, so nothing is folded early whatever ``early_fold`` says: reports still go to HBM
+        slots as they arrive (every slot may be taken: there is no fold front to keep one for), and
+        the close is one MEDIAN finish over every held slot, diffs held elsewhere (parked, or read
+        through ``fetch``) ingested into free slots first.  The result does not depend on the order
+        of the rows, so no close order can be stale.  A close with more diffs than the slab has slots
+        raises ``MedianUnavailableError`` before anything is folded or any slot given up.
+
+        ``trim_count``: the FL process's trim count b (``cycle.trim_count_of``).  ``mode`` must then
         be MEAN, without weights and without ``clip_norm``; every fold runs as TRIMMED_MEAN (early
         folds as they are: the selection state travels between them on the GPU), and a cycle the
         engine cannot trim -- fewer than ``2 b + 1`` diffs at the close among them -- raises
@@ -97,6 +107,11 @@ class IncrementalCycle:
         self.mode = mode
         from .cycle import _engine_clip, _engine_trim, clip_norm_of, trim_count_of
 
+        self.median = bool(median)
+        if self.median and (mode != MEAN or weights_by_worker is not None or clip_norm is not None
+                            or trim_count is not None):
+            raise MedianUnavailableError("diff_median applies to the plain mean only (no weights, no iterative plan, "
+                                         "no diff_clip_norm, no diff_trim_count)")
         self.trim_count = None
         if trim_count is not None:
             self.trim_count = trim_count_of({"diff_trim_count": trim_count})
@@ -108,7 +123,7 @@ class IncrementalCycle:
             self.clip_norm = clip_norm_of({"diff_clip_norm": clip_norm})
             if mode != MEAN or weights_by_worker is not None:
                 raise ClipUnavailableError("diff_clip_norm applies to the plain mean only (no weights, no iterative plan)")
-        self._fold_mode = (TRIMMED_MEAN if self.trim_count is not None else
+        self._fold_mode = (MEDIAN if self.median else TRIMMED_MEAN if self.trim_count is not None else
                            CLIPPED_MEAN if self.clip_norm is not None else mode)
         self._numel = tuple(int(n) for n in numel)
         P = sum(self._numel)
@@ -116,7 +131,7 @@ class IncrementalCycle:
         if self.slots < 2:
             raise AggregationError("report-time aggregation needs at least 2 HBM slots")
         self.fold_batch = max(1, int(fold_batch))
-        self.early_fold = bool(early_fold)
+        self.early_fold = bool(early_fold) and not self.median
         self._seq = itertools.count()
         self._order: List[object] = []      # assigned workers, sorted by assignment key
         self._keys: List[tuple] = []        # their keys (sorted, parallel to _order)
@@ -259,7 +274,7 @@ class IncrementalCycle:
             self._queue_norm(self._slot_of[worker])
             return
         # a diff that cannot fold yet leaves one slot free for the fold front
-        if self._free and (len(self._free) > 1 or self._is_front(worker)):
+        if self._free and (self.median or len(self._free) > 1 or self._is_front(worker)):
             self._to_hbm(worker, diff)  # raises StateParseError on a malformed diff: nothing recorded
             self._parked.pop(worker, None)
         else:
@@ -308,6 +323,9 @@ class IncrementalCycle:
         try:
             _raise_if_not_float32(pb, what)
         except ModelNotAcceleratedError as e:
+            if self.median:
+                raise MedianUnavailableError(f"diff_median is set but {e}; the node's own averaging takes no "
+                                             "median") from e
             if self.trim_count is not None:
                 raise TrimUnavailableError(f"diff_trim_count is set but {e}; the node's own averaging does not "
                                            "trim") from e
@@ -401,6 +419,8 @@ class IncrementalCycle:
                 raise AggregationError("cycle already closed")
             self._closed = True
             if self._declined:
+                if self.median:  # fail closed: the node's own averaging takes no median
+                    raise MedianUnavailableError(f"diff_median is set but {self._declined}")
                 if self.trim_count is not None:  # fail closed: the node's own averaging does not trim
                     raise TrimUnavailableError(f"diff_trim_count is set but {self._declined}")
                 if self.clip_norm is not None:  # fail closed: the node's own averaging does not clip
@@ -423,6 +443,9 @@ class IncrementalCycle:
                 from .cycle import check_trim_count
 
                 check_trim_count(self.trim_count, len(order))
+            if self.median and len(order) > self.slots:  # every row at once: no partial fold, no slot given up
+                raise MedianUnavailableError(f"diff_median is set and the cycle has {len(order)} diffs, the slab "
+                                             f"{self.slots} slots: a median needs every diff in HBM at once")
             if self._weights_by_worker is not None:
                 missing = [w for w in order if w not in self._weights_by_worker]
                 if missing:
@@ -485,7 +508,7 @@ class IncrementalCycle:
                 stats.update(clipped=int(cs["clipped"]), max_norm=float(cs["max_norm"]))
             else:
                 stats.update(clipped=0, max_norm=None)
-            stats.update(trim=self.trim_count)
+            stats.update(trim=self.trim_count, median=self.median)
             self.last_close = stats
             new = (state_codec.fresh_checkpoint(self.engine, checkpoint, prepared=prep) if framing == "fresh"
                    else self.engine.ckpt_patch_state(checkpoint))
@@ -547,6 +570,8 @@ class IncrementalCycle:
                     diff = fetch(w)
             else:
                 from_host += 1
+            if not free and self.median:  # (seal refused a close with more diffs than slots)
+                raise MedianUnavailableError("diff_median is set and no slot is free for a diff of the close")
             if not free:
                 if batch:
                     self._fold(batch, False, slot_of, free, dry)

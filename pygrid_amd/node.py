@@ -72,10 +72,10 @@ from typing import Callable, Dict, Optional, Sequence
 
 from . import state as state_codec
 from .checkpoints import Checkpoint, CheckpointStore
-from .cycle import CycleAggregator, clip_norm_of, finish_cycle, hosted_plan, make_average_plan_diffs, select_mode, \
-    trim_count_of
+from .cycle import CycleAggregator, clip_norm_of, finish_cycle, hosted_plan, make_average_plan_diffs, median_of, \
+    select_mode, trim_count_of
 from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
-    TrimUnavailableError, \
+    MedianUnavailableError, TrimUnavailableError, \
     PyGridError, StateParseError
 from .incremental import IncrementalCycle
 from .trigger import CycleCloseTrigger
@@ -318,6 +318,13 @@ class NodeEngine:
         server_config, _ = self.process_manager.get_configs(id=cycle.fl_process_id)
         clip = clip_norm_of(server_config)  # the process's diff_clip_norm (a malformed one raises)
         trim = trim_count_of(server_config)  # and its diff_trim_count
+        med = median_of(server_config)  # and its diff_median
+        if med:
+            try:
+                return self._new_cycle_for(cm, cycle, server_config, clip, fresh, trim, med)
+            except PlanNotAcceleratedError as e:  # not _DECLINED: the node's own averaging takes no median
+                raise MedianUnavailableError(f"diff_median is set but the engine does not average this cycle "
+                                             f"({e})") from e
         if trim is not None:
             try:
                 return self._new_cycle_for(cm, cycle, server_config, clip, fresh, trim)
@@ -334,7 +341,8 @@ class NodeEngine:
             raise ClipUnavailableError(f"diff_clip_norm is set but the engine does not average this cycle ({e})") \
                 from e
 
-    def _new_cycle_for(self, cm, cycle, server_config, clip, fresh: bool, trim=None) -> IncrementalCycle:
+    def _new_cycle_for(self, cm, cycle, server_config, clip, fresh: bool, trim=None,
+                       median: bool = False) -> IncrementalCycle:
         avg_plan, plan_key = hosted_plan(server_config, cycle, self.process_manager, self.plan_manager,
                                          self.aggregator.mean_plans)
         model = self.model_manager.get(fl_process_id=cycle.fl_process_id)
@@ -348,12 +356,13 @@ class NodeEngine:
             raise
         select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
                     shapes=lambda: _shapes(ckpt), clip_norm=clip,
-                    trim_count=trim)  # with a bound or a trim count: MEAN-able, or Clip- / TrimUnavailableError
+                    trim_count=trim, median=median)  # with a bound, a trim count or the median: MEAN-able, or
+        # Clip- / Trim- / MedianUnavailableError
         mode = select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
                            shapes=lambda: _shapes(ckpt))
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
         inc = IncrementalCycle(self.engine, numel, mode=mode, slots=self.slots, fold_batch=self.fold_batch,
-                               checkpoint=ckpt, clip_norm=clip, trim_count=trim)
+                               checkpoint=ckpt, clip_norm=clip, trim_count=trim, median=median)
         if not fresh:  # after a restart: the rows assigned before it (a cycle just created has none;
             # an assignment that lands while this state is built is recorded from _pending_assign)
             for row in _rows(cm, cycle_id=cycle.id):
@@ -437,6 +446,8 @@ class NodeEngine:
             original = _refuse_unclipped(cycle.id)  # fail closed: the node's own averaging does not clip
         if trim is not None:
             original = _refuse_untrimmed(cycle.id)  # nor does it trim
+        if median_of(server_config):  # (a malformed switch fails the close too)
+            original = _refuse_no_median(cycle.id)  # nor does it take a median
         with self._engine_for_close():
             model = ckpt = None
             if isinstance(self._cycles.get(cycle.id), IncrementalCycle):
@@ -507,6 +518,9 @@ class NodeEngine:
             if trim is not None:
                 log.info("cycle %s closed with diff_trim_count=%d: per parameter %d of %d values kept", cycle.id, trim,
                          st.last_close.get("n", 0) - 2 * trim, st.last_close.get("n", 0))
+            if st.last_close.get("median"):
+                log.info("cycle %s closed with diff_median: the median of %d diffs per parameter", cycle.id,
+                         st.last_close.get("n", 0))
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)
             self.aggregator._resident = None
@@ -567,6 +581,14 @@ def _refuse_untrimmed(cycle_id):
     def original(*_a, **_k):
         raise TrimUnavailableError(f"cycle {cycle_id}: diff_trim_count is set and the engine does not average this "
                                    "cycle; not falling back to the node's untrimmed averaging")
+    return original
+
+
+def _refuse_no_median(cycle_id):
+    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for the median."""
+    def original(*_a, **_k):
+        raise MedianUnavailableError(f"cycle {cycle_id}: diff_median is set and the engine does not average this "
+                                     "cycle; not falling back to the node's own averaging, which takes no median")
     return original
 
 
