@@ -27,95 +27,10 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import state as state_codec
-from .engine import CLIPPED_MEAN, ITERATIVE_MEAN, MEAN, MEDIAN, TRIMMED_MEAN, TRIM_MAX, WEIGHTED_MEAN, F32, I64, Engine
-from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
-    MedianUnavailableError, StateParseError, TrimUnavailableError
-
-CLIP_KEY = "diff_clip_norm"  # optional server_config key: the per-client L2 bound (no reference counterpart)
-
-
-def clip_norm_of(server_config: dict) -> Optional[float]:
-    """The FL process's per-client L2 bound, ``server_config["diff_clip_norm"]``: a finite number
-    > 0, or None when the key is absent or None (clipping off).  Anything else -- another type
-    (bools included), NaN, an infinity, 0, a negative value -- raises ``AggregationError``: a
-    mistyped bound must not quietly mean "no clipping"."""
-    c = server_config.get(CLIP_KEY, None)
-    if c is None:
-        return None
-    if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)):
-        raise AggregationError(f"{CLIP_KEY} must be a finite number > 0, not {c!r}")
-    c = float(c)
-    with np.errstate(over="ignore", under="ignore"):
-        c32 = np.float32(c)  # the engine takes the bound as a float32
-    if not np.isfinite(c) or c <= 0 or not np.isfinite(c32) or c32 <= 0:
-        raise AggregationError(f"{CLIP_KEY} must be a finite float32 > 0, not {c!r}")
-    return c
-
-
-TRIM_KEY = "diff_trim_count"  # optional server_config key: values dropped per side and parameter (no reference counterpart)
-
-
-def trim_count_of(server_config: dict) -> Optional[int]:
-    """The FL process's trim count, ``server_config["diff_trim_count"]``: an int in 1 .. 8, or None
-    when the key is absent or None (no trimming).  Anything else -- a bool, a float with a fraction,
-    0, a negative value, more than 8, another type -- raises ``AggregationError``: a mistyped count
-    must not quietly mean "no trimming"."""
-    b = server_config.get(TRIM_KEY, None)
-    if b is None:
-        return None
-    if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)):
-        raise AggregationError(f"{TRIM_KEY} must be an integer in 1..{TRIM_MAX}, not {b!r}")
-    if isinstance(b, (float, np.floating)) and not (np.isfinite(b) and float(b) == int(b)):
-        raise AggregationError(f"{TRIM_KEY} must be an integer in 1..{TRIM_MAX}, not {b!r}")
-    if not 1 <= int(b) <= TRIM_MAX:
-        raise AggregationError(f"{TRIM_KEY} must be an integer in 1..{TRIM_MAX}, not {b!r}")
-    return int(b)
-
-
-def check_trim_count(trim_count: int, n_diffs: int):
-    """A trimmed close needs at least ``2 b + 1`` diffs (one value must be left per parameter)."""
-    if n_diffs < 2 * trim_count + 1:
-        raise TrimUnavailableError(f"{TRIM_KEY} = {trim_count} needs at least {2 * trim_count + 1} diffs, the cycle "
-                                   f"has {n_diffs}")
-
-
-MEDIAN_KEY = "diff_median"  # optional server_config key: True = the coordinate-wise median (no reference counterpart)
-
-
-def median_of(server_config: dict) -> bool:
-    """Whether the FL process asks for the coordinate-wise median, ``server_config["diff_median"]``:
-    ``True`` turns it on; absent, ``None`` or ``False`` leaves it off.  Anything else -- an int, a
-    string, a float -- raises ``AggregationError``: a mistyped switch must not quietly mean "the
-    plain mean"."""
-    m = server_config.get(MEDIAN_KEY, None)
-    if m is None:
-        return False
-    if isinstance(m, (bool, np.bool_)):
-        return bool(m)
-    raise AggregationError(f"{MEDIAN_KEY} must be True or False, not {m!r}")
-
-
-_NO_CLIP = object()  # "take the bound from server_config"
-_NO_TRIM = _NO_CLIP  # "take the trim count from server_config"
-_NO_MEDIAN = _NO_CLIP  # "take the switch from server_config"
-
-
-def _median_arg(server_config: dict, median) -> bool:
-    if median is _NO_MEDIAN:
-        return median_of(server_config)
-    return median_of({MEDIAN_KEY: median})
-
-
-def _trim_arg(server_config: dict, trim_count):
-    if trim_count is _NO_TRIM:
-        return trim_count_of(server_config)
-    return None if trim_count is None else trim_count_of({TRIM_KEY: trim_count})
-
-
-def _clip_arg(server_config: dict, clip_norm):
-    if clip_norm is _NO_CLIP:
-        return clip_norm_of(server_config)
-    return None if clip_norm is None else clip_norm_of({CLIP_KEY: clip_norm})
+from .engine import ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
+from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
+from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, check_trim_count, clip_norm_of, failing_closed, median_of, \
+    rule_kwargs, rule_of, set_on_engine, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
 
 
 def ready_to_average(server_config: dict, received_diffs: int, cycle_end=None, now=None) -> bool:
@@ -266,56 +181,22 @@ def cached_mode(server_config: dict, plan_key, mean_plans: Optional[str] = None)
 def select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
                 mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None,
                 trim_count=None, median: bool = False) -> int:
-    """The dispatch rule below; with ``clip_norm`` set: ``CLIPPED_MEAN`` exactly where the rule gives
-    ``MEAN`` (no hosted plan, or a plan probed equal to the mean), ``ClipUnavailableError`` everywhere
-    else -- weights, the iterative plan, a plan the engine declines -- so that the caller cannot fall
-    back to an average that does not clip.  ``trim_count`` likewise: ``TRIMMED_MEAN`` where the rule
-    gives ``MEAN``, ``TrimUnavailableError`` everywhere else and together with ``clip_norm``.
-    ``median`` likewise: ``MEDIAN`` where the rule gives ``MEAN``, ``MedianUnavailableError``
-    everywhere else and together with ``clip_norm`` or ``trim_count``."""
-    if median:
-        if clip_norm is not None:
-            raise MedianUnavailableError(f"{MEDIAN_KEY} cannot be combined with {CLIP_KEY}")
-        if trim_count is not None:
-            raise MedianUnavailableError(f"{MEDIAN_KEY} cannot be combined with {TRIM_KEY}")
-        if weights is not None:
-            raise MedianUnavailableError(f"{MEDIAN_KEY} cannot be combined with aggregation weights")
-        try:
-            mode = _select_mode(server_config, avg_plan, None, plan_key, mean_plans, shapes, n_clients)
-        except PlanNotAcceleratedError as e:
-            raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine does not run this avg plan ({e}); the "
-                                         "node's own averaging takes no median") from e
-        if mode != MEAN:
-            raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the hosted avg plan is the iterative mean, of "
-                                         "which the engine takes no median")
-        return MEDIAN
-    if trim_count is not None:
-        if clip_norm is not None:
-            raise TrimUnavailableError(f"{TRIM_KEY} cannot be combined with {CLIP_KEY}")
-        if weights is not None:
-            raise TrimUnavailableError(f"{TRIM_KEY} cannot be combined with aggregation weights")
-        try:
-            mode = _select_mode(server_config, avg_plan, None, plan_key, mean_plans, shapes, n_clients)
-        except PlanNotAcceleratedError as e:
-            raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine does not run this avg plan ({e}); the "
-                                       "node's own averaging does not trim") from e
-        if mode != MEAN:
-            raise TrimUnavailableError(f"{TRIM_KEY} is set but the hosted avg plan is the iterative mean, which "
-                                       "the engine does not trim")
-        return TRIMMED_MEAN
-    if clip_norm is None:
+    """The dispatch rule below; under a rule (``robust.rule_of`` of ``clip_norm``, ``trim_count`` and
+    ``median``, parsed values; ``server_config``'s own keys are not read): the rule's mode --
+    ``CLIPPED_MEAN``, ``TRIMMED_MEAN``, ``MEDIAN`` -- exactly where the dispatch gives ``MEAN`` (no
+    hosted plan, or a plan probed equal to the mean) and the rule's error everywhere else -- weights,
+    the iterative plan, a plan the engine declines -- so that the caller cannot fall back to an
+    average that does not apply the rule."""
+    rule = rule_of(server_config, clip_norm=clip_norm, trim_count=trim_count, median=median)
+    if rule is None:
         return _select_mode(server_config, avg_plan, weights, plan_key, mean_plans, shapes, n_clients)
     if weights is not None:
-        raise ClipUnavailableError(f"{CLIP_KEY} cannot be combined with aggregation weights")
-    try:
+        raise rule.refuse("cannot be combined with aggregation weights")
+    with failing_closed(rule, "the engine does not run this avg plan"):
         mode = _select_mode(server_config, avg_plan, None, plan_key, mean_plans, shapes, n_clients)
-    except PlanNotAcceleratedError as e:
-        raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine does not run this avg plan ({e}); the node's "
-                                   "own averaging does not clip") from e
     if mode != MEAN:
-        raise ClipUnavailableError(f"{CLIP_KEY} is set but the hosted avg plan is the iterative mean, which the "
-                                   "engine does not clip")
-    return CLIPPED_MEAN
+        raise rule.refuse("is set but the hosted avg plan is the iterative mean, to which the engine does not apply it")
+    return rule.mode
 
 
 def _select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
@@ -366,36 +247,6 @@ def _probe_mode(server_config: dict, avg_plan: Callable, mean_plans=None, shapes
     return ITERATIVE_MEAN
 
 
-def _engine_clip(engine, clip_norm: Optional[float]):
-    """Set (or clear) the engine's bound before a cycle's first ingest: an engine shared across FL
-    processes never carries one over.  An engine that cannot clip fails the cycle."""
-    if clip_norm is None:
-        if hasattr(engine, "set_clip_norm"):
-            engine.set_clip_norm(0.0)
-        return
-    try:
-        engine.set_clip_norm(clip_norm)
-    except AttributeError as e:
-        raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine has no clipping") from e
-    except AggregationError as e:
-        if e.status == -6:  # PGH_E_UNSUPPORTED: a multi-GPU group, a sub-range shard
-            raise ClipUnavailableError(f"{CLIP_KEY} is set but this engine cannot clip: {e}") from e
-        raise
-
-
-def _engine_trim(engine, trim_count: Optional[int]):
-    """Set (or clear) the engine's trim count before a cycle's first fold: an engine shared across
-    FL processes never carries one over.  An engine that cannot trim fails the cycle."""
-    if trim_count is None:
-        if hasattr(engine, "set_trim"):
-            engine.set_trim(0)
-        return
-    try:
-        engine.set_trim(trim_count)
-    except AttributeError as e:
-        raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine has no trimmed mean") from e
-
-
 def _decline_non_float32(pb: bytes, what: str):
     """After the State walker refused ``pb``: well-formed bytes holding non-float32 tensors are a
     model the engine does not implement (``ModelNotAcceleratedError``: the node averages it with
@@ -409,6 +260,11 @@ def _decline_non_float32(pb: bytes, what: str):
         return
     if bad:
         raise ModelNotAcceleratedError(f"{what} holds non-float32 tensors {bad[:8]} (the engine is fp32-only)")
+
+
+def _check_diff_count(rule, n_diffs: int):
+    if rule is not None and rule.key == TRIM_KEY:
+        check_trim_count(rule.value, n_diffs)
 
 
 def _shapes_or_none(pb: bytes):
@@ -456,7 +312,7 @@ class CycleAggregator:
     # ---- bytes in / bytes out: the replaceable slice cycle_manager.py:240-303 -------------------
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
-                           plan_key=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM, median=_NO_MEDIAN) -> bytes:
+                           plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -466,39 +322,22 @@ class CycleAggregator:
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        clip = _clip_arg(server_config, clip_norm)
-        trim = _trim_arg(server_config, trim_count)
-        med = _median_arg(server_config, median)
-        try:
+        rule = rule_of(server_config, clip_norm, trim_count, median)
+        with failing_closed(rule, "the engine cannot average this cycle"):
             return self._average_plan_diffs(server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key,
-                                            clip, trim, med)
-        except PlanNotAcceleratedError as e:
-            if med:
-                raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine cannot average this cycle ({e}); "
-                                             "the node's own averaging takes no median") from e
-            if trim is not None:
-                raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine cannot average this cycle ({e}); the "
-                                           "node's own averaging does not trim") from e
-            if clip is None:
-                raise
-            raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine cannot average this cycle ({e}); the "
-                                       "node's own averaging does not clip") from e
+                                            rule)
 
-    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, clip,
-                            trim=None, median=False):
+    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, rule):
         mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
-                           shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), clip_norm=clip,
-                           trim_count=trim, median=median)
-        if trim is not None:
-            check_trim_count(trim, len(diffs))
+                           shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), **rule_kwargs(rule))
+        _check_diff_count(rule, len(diffs))
         try:
             numel = state_codec.tensor_numels(checkpoint)  # :240
         except StateParseError:
             _decline_non_float32(checkpoint, "the checkpoint")
             raise
         self._prepare(numel, len(diffs))
-        _engine_clip(self.engine, clip)  # before the first ingest: each diff's norm pass rides behind its copy
-        _engine_trim(self.engine, trim)
+        set_on_engine(self.engine, rule)  # before the first ingest: each diff's norm pass rides behind its copy
         if checkpoint is not self._resident or self.engine.ckpt_owner is not self:
             self.engine.ckpt_upload_state(checkpoint)  # else: the last cycle's output is still in HBM
         for i, d in enumerate(diffs):  # :247-250
@@ -524,43 +363,32 @@ class CycleAggregator:
     # ---- tensor lists in / out (what the reference holds after unserialize) ---------------------
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
-                       weights=None, clip_norm=_NO_CLIP, trim_count=_NO_TRIM, median=_NO_MEDIAN) -> List[np.ndarray]:
+                       weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        clip = _clip_arg(server_config, clip_norm)
-        trim = _trim_arg(server_config, trim_count)
-        med = _median_arg(server_config, median)
-        shapes = [np.shape(p) for p in model_params]
-        try:
+        rule = rule_of(server_config, clip_norm, trim_count, median)
+        with failing_closed(rule, "the engine cannot average this cycle"):
+            shapes = [np.shape(p) for p in model_params]
             mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
-                               n_clients=len(diffs), clip_norm=clip, trim_count=trim, median=med)
-        except PlanNotAcceleratedError as e:
-            if med:
-                raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine cannot average this cycle ({e})") \
-                    from e
-            if trim is None:
-                raise
-            raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine cannot average this cycle ({e})") from e
-        if trim is not None:
-            check_trim_count(trim, len(diffs))
-        numel = [int(np.prod(s)) for s in shapes]
-        self._prepare(numel, len(diffs))
-        _engine_clip(self.engine, clip)
-        _engine_trim(self.engine, trim)
-        for i, d in enumerate(diffs):
-            if len(d) != len(numel):
-                raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
-            self.engine.ingest(i, np.concatenate([np.asarray(t, np.float32).reshape(-1) for t in d]))
-        if mode == WEIGHTED_MEAN:
-            self.engine.set_weights(weights)
-        flat = np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in model_params])
-        self._resident = None  # the host-buffer fold overwrites the resident checkpoint
-        out = self.engine.fedavg(mode, flat)
-        res, off = [], 0
-        for s, n in zip(shapes, numel):
-            res.append(out[off:off + n].reshape(s))
-            off += n
-        return res
+                               n_clients=len(diffs), **rule_kwargs(rule))
+            _check_diff_count(rule, len(diffs))
+            numel = [int(np.prod(s)) for s in shapes]
+            self._prepare(numel, len(diffs))
+            set_on_engine(self.engine, rule)
+            for i, d in enumerate(diffs):
+                if len(d) != len(numel):
+                    raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
+                self.engine.ingest(i, np.concatenate([np.asarray(t, np.float32).reshape(-1) for t in d]))
+            if mode == WEIGHTED_MEAN:
+                self.engine.set_weights(weights)
+            flat = np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in model_params])
+            self._resident = None  # the host-buffer fold overwrites the resident checkpoint
+            out = self.engine.fedavg(mode, flat)
+            res, off = [], 0
+            for s, n in zip(shapes, numel):
+                res.append(out[off:off + n].reshape(s))
+                off += n
+            return res
 
     # ---- secure aggregation (PySyft share add + get + float_prec) ------------------------------
     def secure_aggregate(self, shares: np.ndarray, base: int = 10, precision_fractional: int = 3):
@@ -617,24 +445,14 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
         with gate() if gate is not None else contextlib.nullcontext():
             reports = self._worker_cycles.query(cycle_id=cycle.id, is_completed=True)
             diffs = [r.diff for r in reports]  # what :247-250 reads, at the query
-        clip = clip_norm_of(server_config)  # a malformed bound fails the close
-        trim = trim_count_of(server_config)  # and so does a malformed trim count
-        med = median_of(server_config)  # or a malformed median switch
+        rule = rule_of(server_config)  # a malformed setting fails the close
         try:
-            avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
-                                             getattr(aggregator, "mean_plans", None))
-            new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,
-                                                     plan_key=plan_key, framing=framing)
+            with failing_closed(rule):
+                avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
+                                                 getattr(aggregator, "mean_plans", None))
+                new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,
+                                                         plan_key=plan_key, framing=framing)
         except PlanNotAcceleratedError as e:
-            if med:  # fail closed: the node's own averaging takes no median
-                raise MedianUnavailableError(f"{MEDIAN_KEY} is set but the engine does not average this cycle ({e})") \
-                    from e
-            if trim is not None:  # fail closed: the node's own averaging does not trim
-                raise TrimUnavailableError(f"{TRIM_KEY} is set but the engine does not average this cycle ({e})") \
-                    from e
-            if clip is not None:  # fail closed: the node's own averaging does not clip
-                raise ClipUnavailableError(f"{CLIP_KEY} is set but the engine does not average this cycle ({e})") \
-                    from e
             logging.info("engine declined (%s): running the reference averaging", e)
             return original(self, server_config, cycle)
         finish_cycle(self, server_config, cycle, model_manager, _model.id, new_ckpt)

@@ -65,9 +65,10 @@ import threading
 from typing import Callable, Dict, Hashable, List, Optional, Sequence
 
 from . import state as state_codec
-from .engine import CLIPPED_MEAN, F32, MEAN, MEDIAN, TRIMMED_MEAN, WEIGHTED_MEAN, Engine
-from .exceptions import AggregationError, ClipUnavailableError, MedianUnavailableError, ModelNotAcceleratedError, \
-    StateParseError, TrimUnavailableError
+from .cycle import _decline_non_float32
+from .engine import F32, MEAN, WEIGHTED_MEAN, Engine
+from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
+from .robust import check_trim_count, failing_closed, rule_of, set_on_engine
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
 MAX_DEFAULT_SLOTS = 4096
@@ -105,26 +106,13 @@ class IncrementalCycle:
         ``ClipUnavailableError`` instead of being handed back to the node's unclipped averaging."""
         self.engine = engine
         self.mode = mode
-        from .cycle import _engine_clip, _engine_trim, clip_norm_of, trim_count_of
-
-        self.median = bool(median)
-        if self.median and (mode != MEAN or weights_by_worker is not None or clip_norm is not None
-                            or trim_count is not None):
-            raise MedianUnavailableError("diff_median applies to the plain mean only (no weights, no iterative plan, "
-                                         "no diff_clip_norm, no diff_trim_count)")
-        self.trim_count = None
-        if trim_count is not None:
-            self.trim_count = trim_count_of({"diff_trim_count": trim_count})
-            if mode != MEAN or weights_by_worker is not None or clip_norm is not None:
-                raise TrimUnavailableError("diff_trim_count applies to the plain mean only (no weights, no iterative "
-                                           "plan, no diff_clip_norm)")
-        self.clip_norm = None
-        if clip_norm is not None:
-            self.clip_norm = clip_norm_of({"diff_clip_norm": clip_norm})
-            if mode != MEAN or weights_by_worker is not None:
-                raise ClipUnavailableError("diff_clip_norm applies to the plain mean only (no weights, no iterative plan)")
-        self._fold_mode = (MEDIAN if self.median else TRIMMED_MEAN if self.trim_count is not None else
-                           CLIPPED_MEAN if self.clip_norm is not None else mode)
+        self._rule = rule = rule_of({}, clip_norm=clip_norm, trim_count=trim_count, median=bool(median))
+        if rule is not None and (mode != MEAN or weights_by_worker is not None):
+            raise rule.refuse("applies to the plain mean only (no weights, no iterative plan)")
+        self.clip_norm, self.trim_count, self.median = None, None, False
+        if rule is not None:
+            setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
+        self._fold_mode = rule.mode if rule else mode
         self._numel = tuple(int(n) for n in numel)
         P = sum(self._numel)
         self.slots = int(slots) if slots else default_slots(P)
@@ -169,12 +157,7 @@ class IncrementalCycle:
         if hasattr(engine, "set_ingest_ranges"):
             # the close overlaps the tail of the last report's copy (pgh_set_ingest_ranges)
             engine.set_ingest_ranges(os.environ.get("PGH_INGEST_RANGES", "1") != "0")
-        if self.clip_norm is not None:  # (an engine without the method is only touched when a bound is set)
-            _engine_clip(engine, self.clip_norm)
-        elif hasattr(engine, "set_clip_norm"):
-            engine.set_clip_norm(0.0)  # a shared engine never carries another process's bound over
-        if self.trim_count is not None or hasattr(engine, "set_trim"):
-            _engine_trim(engine, self.trim_count)  # (the engine was reset above: no slot folds under way)
+        set_on_engine(engine, rule)  # (the engine was reset above: no slot folds under way)
         self._ckpt: Optional[bytes] = None  # checkpoint bytes whose payloads are resident in HBM
         if checkpoint is not None and getattr(engine, "ckpt_owner", None) is not None \
                 and getattr(engine, "ckpt_bytes", None) is checkpoint:
@@ -254,7 +237,7 @@ class IncrementalCycle:
                 self._take(worker, diff)
             except StateParseError:
                 try:
-                    _raise_if_not_float32(diff, f"worker {worker!r}'s diff")
+                    _decline_non_float32(diff, f"worker {worker!r}'s diff")
                 except ModelNotAcceleratedError as e:
                     self._declined = str(e)
                     self._parked.clear()
@@ -320,18 +303,8 @@ class IncrementalCycle:
             self.engine.row_sumsq([slot], wait=False)
 
     def _raise_if_not_float32(self, pb: bytes, what: str):
-        try:
-            _raise_if_not_float32(pb, what)
-        except ModelNotAcceleratedError as e:
-            if self.median:
-                raise MedianUnavailableError(f"diff_median is set but {e}; the node's own averaging takes no "
-                                             "median") from e
-            if self.trim_count is not None:
-                raise TrimUnavailableError(f"diff_trim_count is set but {e}; the node's own averaging does not "
-                                           "trim") from e
-            if self.clip_norm is None:
-                raise
-            raise ClipUnavailableError(f"diff_clip_norm is set but {e}; the node's own averaging does not clip") from e
+        with failing_closed(self._rule):
+            _decline_non_float32(pb, what)
 
     def _held(self, worker) -> bool:
         return worker in self._slot_of or worker in self._parked
@@ -419,13 +392,8 @@ class IncrementalCycle:
                 raise AggregationError("cycle already closed")
             self._closed = True
             if self._declined:
-                if self.median:  # fail closed: the node's own averaging takes no median
-                    raise MedianUnavailableError(f"diff_median is set but {self._declined}")
-                if self.trim_count is not None:  # fail closed: the node's own averaging does not trim
-                    raise TrimUnavailableError(f"diff_trim_count is set but {self._declined}")
-                if self.clip_norm is not None:  # fail closed: the node's own averaging does not clip
-                    raise ClipUnavailableError(f"diff_clip_norm is set but {self._declined}")
-                raise ModelNotAcceleratedError(self._declined)
+                with failing_closed(self._rule):
+                    raise ModelNotAcceleratedError(self._declined)
             if order is None:
                 if self._stale or self._bad:
                     what = self._stale or ", ".join(f"{w!r}: {why}" for w, why in self._bad.items())
@@ -440,12 +408,10 @@ class IncrementalCycle:
             if not order:
                 raise AggregationError("no diffs to average")
             if self.trim_count is not None:
-                from .cycle import check_trim_count
-
                 check_trim_count(self.trim_count, len(order))
             if self.median and len(order) > self.slots:  # every row at once: no partial fold, no slot given up
-                raise MedianUnavailableError(f"diff_median is set and the cycle has {len(order)} diffs, the slab "
-                                             f"{self.slots} slots: a median needs every diff in HBM at once")
+                raise self._rule.refuse(f"is set and the cycle has {len(order)} diffs, the slab {self.slots} slots: a "
+                                        "median needs every diff in HBM at once")
             if self._weights_by_worker is not None:
                 missing = [w for w in order if w not in self._weights_by_worker]
                 if missing:
@@ -571,7 +537,7 @@ class IncrementalCycle:
             else:
                 from_host += 1
             if not free and self.median:  # (seal refused a close with more diffs than slots)
-                raise MedianUnavailableError("diff_median is set and no slot is free for a diff of the close")
+                raise self._rule.refuse("is set and no slot is free for a diff of the close")
             if not free:
                 if batch:
                     self._fold(batch, False, slot_of, free, dry)
@@ -632,8 +598,3 @@ def _common_prefix(a: Sequence, b: Sequence) -> int:
         i += 1
     return i
 
-
-def _raise_if_not_float32(pb: bytes, what: str):
-    from .cycle import _decline_non_float32
-
-    _decline_non_float32(pb, what)

@@ -72,12 +72,12 @@ from typing import Callable, Dict, Optional, Sequence
 
 from . import state as state_codec
 from .checkpoints import Checkpoint, CheckpointStore
-from .cycle import CycleAggregator, clip_norm_of, finish_cycle, hosted_plan, make_average_plan_diffs, median_of, \
-    select_mode, trim_count_of
-from .exceptions import AggregationError, ClipUnavailableError, ModelNotAcceleratedError, PlanNotAcceleratedError, \
-    MedianUnavailableError, TrimUnavailableError, \
-    PyGridError, StateParseError
+from .cycle import CycleAggregator, _decline_non_float32, finish_cycle, hosted_plan, make_average_plan_diffs, \
+    select_mode
+from .engine import MEAN
+from .exceptions import AggregationError, PlanNotAcceleratedError, PyGridError, StateParseError
 from .incremental import IncrementalCycle
+from .robust import failing_closed, rule_kwargs, rule_of
 from .trigger import CycleCloseTrigger
 
 log = logging.getLogger(__name__)
@@ -316,33 +316,13 @@ class NodeEngine:
 
     def _new_cycle(self, cm, cycle, fresh: bool = False) -> IncrementalCycle:
         server_config, _ = self.process_manager.get_configs(id=cycle.fl_process_id)
-        clip = clip_norm_of(server_config)  # the process's diff_clip_norm (a malformed one raises)
-        trim = trim_count_of(server_config)  # and its diff_trim_count
-        med = median_of(server_config)  # and its diff_median
-        if med:
-            try:
-                return self._new_cycle_for(cm, cycle, server_config, clip, fresh, trim, med)
-            except PlanNotAcceleratedError as e:  # not _DECLINED: the node's own averaging takes no median
-                raise MedianUnavailableError(f"diff_median is set but the engine does not average this cycle "
-                                             f"({e})") from e
-        if trim is not None:
-            try:
-                return self._new_cycle_for(cm, cycle, server_config, clip, fresh, trim)
-            except PlanNotAcceleratedError as e:  # not _DECLINED: the node's own averaging does not trim
-                raise TrimUnavailableError(f"diff_trim_count is set but the engine does not average this cycle "
-                                           f"({e})") from e
-        if clip is None:
-            return self._new_cycle_for(cm, cycle, server_config, None, fresh)
-        try:
-            return self._new_cycle_for(cm, cycle, server_config, clip, fresh)
-        except PlanNotAcceleratedError as e:
-            # not _DECLINED: the node's own averaging does not clip.  The close-time path refuses
-            # the cycle again, loudly, when it closes.
-            raise ClipUnavailableError(f"diff_clip_norm is set but the engine does not average this cycle ({e})") \
-                from e
+        rule = rule_of(server_config)  # the process's robust-aggregation rule (a malformed setting raises)
+        # under a rule a cycle the engine does not run is not _DECLINED -- the node's own averaging does not
+        # apply the rule: the close-time path refuses the cycle again, loudly, when it closes
+        with failing_closed(rule):
+            return self._new_cycle_for(cm, cycle, server_config, rule, fresh)
 
-    def _new_cycle_for(self, cm, cycle, server_config, clip, fresh: bool, trim=None,
-                       median: bool = False) -> IncrementalCycle:
+    def _new_cycle_for(self, cm, cycle, server_config, rule, fresh: bool) -> IncrementalCycle:
         avg_plan, plan_key = hosted_plan(server_config, cycle, self.process_manager, self.plan_manager,
                                          self.aggregator.mean_plans)
         model = self.model_manager.get(fl_process_id=cycle.fl_process_id)
@@ -350,19 +330,14 @@ class NodeEngine:
         try:
             numel = state_codec.tensor_numels(ckpt)
         except StateParseError:
-            from .cycle import _decline_non_float32
-
             _decline_non_float32(ckpt, "the checkpoint")
             raise
-        select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
-                    shapes=lambda: _shapes(ckpt), clip_norm=clip,
-                    trim_count=trim, median=median)  # with a bound, a trim count or the median: MEAN-able, or
-        # Clip- / Trim- / MedianUnavailableError
+        # under a rule: the rule's mode where the plan dispatches to MEAN, the rule's error everywhere else
         mode = select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
-                           shapes=lambda: _shapes(ckpt))
+                           shapes=lambda: _shapes(ckpt), **rule_kwargs(rule))
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
-        inc = IncrementalCycle(self.engine, numel, mode=mode, slots=self.slots, fold_batch=self.fold_batch,
-                               checkpoint=ckpt, clip_norm=clip, trim_count=trim, median=median)
+        inc = IncrementalCycle(self.engine, numel, mode=MEAN if rule else mode, slots=self.slots,
+                               fold_batch=self.fold_batch, checkpoint=ckpt, **rule_kwargs(rule))
         if not fresh:  # after a restart: the rows assigned before it (a cycle just created has none;
             # an assignment that lands while this state is built is recorded from _pending_assign)
             for row in _rows(cm, cycle_id=cycle.id):
@@ -440,14 +415,9 @@ class NodeEngine:
     def average_plan_diffs(self, cm, server_config, cycle, close_time: Callable, original: Callable):
         """The close (executor thread).  Holds the engine lock throughout, the report gate only for
         the snapshot of the completed rows (see the module docstring)."""
-        clip = clip_norm_of(server_config)  # a malformed bound fails the close
-        trim = trim_count_of(server_config)  # and so does a malformed trim count
-        if clip is not None:
-            original = _refuse_unclipped(cycle.id)  # fail closed: the node's own averaging does not clip
-        if trim is not None:
-            original = _refuse_untrimmed(cycle.id)  # nor does it trim
-        if median_of(server_config):  # (a malformed switch fails the close too)
-            original = _refuse_no_median(cycle.id)  # nor does it take a median
+        rule = rule_of(server_config)  # a malformed setting, or two rules at once, fails the close
+        if rule is not None:
+            original = _refuse(rule, cycle.id)  # fail closed: the node's own averaging does not apply the rule
         with self._engine_for_close():
             model = ckpt = None
             if isinstance(self._cycles.get(cycle.id), IncrementalCycle):
@@ -511,16 +481,10 @@ class NodeEngine:
                 self.stats["closes_close_time"] += 1
                 return close_time(cm, server_config, cycle)
             self.stats["closes_report_time"] += 1
-            if clip is not None:
-                log.info("cycle %s closed with diff_clip_norm=%g: %d of %d diffs clipped, max norm %g", cycle.id, clip,
-                         st.last_close.get("clipped", 0), st.last_close.get("n", 0),
-                         st.last_close.get("max_norm") or 0.0)
-            if trim is not None:
-                log.info("cycle %s closed with diff_trim_count=%d: per parameter %d of %d values kept", cycle.id, trim,
-                         st.last_close.get("n", 0) - 2 * trim, st.last_close.get("n", 0))
-            if st.last_close.get("median"):
-                log.info("cycle %s closed with diff_median: the median of %d diffs per parameter", cycle.id,
-                         st.last_close.get("n", 0))
+            if rule is not None:
+                log.info("cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)", cycle.id, rule.key,
+                         rule.value, st.last_close.get("n", 0), st.last_close.get("clipped", 0),
+                         st.last_close.get("max_norm"))
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)
             self.aggregator._resident = None
@@ -568,27 +532,11 @@ class NodeEngine:
                 del self._assigned[k]
 
 
-def _refuse_unclipped(cycle_id):
-    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for clipping."""
+def _refuse(rule, cycle_id):
+    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for a rule."""
     def original(*_a, **_k):
-        raise ClipUnavailableError(f"cycle {cycle_id}: diff_clip_norm is set and the engine does not average this "
-                                   "cycle; not falling back to the node's unclipped averaging")
-    return original
-
-
-def _refuse_untrimmed(cycle_id):
-    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for a trimmed mean."""
-    def original(*_a, **_k):
-        raise TrimUnavailableError(f"cycle {cycle_id}: diff_trim_count is set and the engine does not average this "
-                                   "cycle; not falling back to the node's untrimmed averaging")
-    return original
-
-
-def _refuse_no_median(cycle_id):
-    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for the median."""
-    def original(*_a, **_k):
-        raise MedianUnavailableError(f"cycle {cycle_id}: diff_median is set and the engine does not average this "
-                                     "cycle; not falling back to the node's own averaging, which takes no median")
+        raise rule.refuse(f"is set and the engine does not average cycle {cycle_id}; not falling back to the node's "
+                          f"own averaging, which {rule.lacks}")
     return original
 
 
