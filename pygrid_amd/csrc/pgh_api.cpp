@@ -381,7 +381,7 @@ int pgh_effective_variant(pgh_ctx* c, int mode) {
         return median_variant(c, n);
     }
     if (c->variant >= 0) return c->variant;
-    if (mode == PGH_STREAM_SECAGG) return 14;  // SECAGG_AUTO_VARIANT in pgh_kernels.hip
+    if (mode == PGH_STREAM_SECAGG) return pgh::SECAGG_AUTO_VARIANT;
     if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
     return pgh::auto_variant(c->pg, kernel_mode(mode));
 }
@@ -451,6 +451,7 @@ pgh_ctx* new_group_ctx(pgh_group* g, int device) {
 void free_group_ctx(pgh_ctx* c) { delete c; }
 int device_of(const pgh_ctx* c) { return c->device; }
 hipStream_t stream_of(const pgh_ctx* c) { return c->stream; }
+int fixed_point_divisor(pgh_ctx* c, int base, int prec, float* div) { return pgh_detail::fixed_point_divisor(c, base, prec, div); }
 int set_vec_min(pgh_ctx* c, int64_t n) {
     if (n < 0) return fail(c, PGH_E_ARG, "negative vector length");
     c->vec_min = n;

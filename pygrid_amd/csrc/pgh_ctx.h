@@ -7,8 +7,12 @@
 //   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks
 //   pgh_order.cpp   which stream waits for what, and the timing events
 //   pgh_ingest.cpp  host bytes -> HBM slab rows (raw, State messages, int64 shares, synthetic)
-//   pgh_reduce.cpp  fold_run, RESIDENT and STREAM folds, the resident checkpoint, secagg, clipping, trimming, the median
-//   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order)
+//   pgh_reduce.cpp  what a mode may do (check_mode_use), the one fp32 fold launch (fold_prepare, fold_launch) and
+//                   what the rules add to it (clipping, trimming, the median); fold_run's ring walk and the
+//                   share sum; RESIDENT and STREAM entry points, the resident checkpoint
+//   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order): slot_fold
+// A new averaging rule touches check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run,
+// slot_fold) reach the kernels through them alone.
 // The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -299,9 +303,12 @@ static_assert(PGH_TRIMMED_MEAN == pgh::MODE_TRIMMED && PGH_TRIM_MAX == pgh::TRIM
 static_assert(PGH_MEDIAN == pgh::MODE_MEDIAN && PGH_MEDIAN_NCHIP == pgh::MEDIAN_NCHIP, "the kernels' numbering");
 // The kernels' mode: a clipped mean is the weighted fold with the scales as weights.
 inline int kernel_mode(int m) { return m == PGH_CLIPPED_MEAN ? PGH_WEIGHTED_MEAN : m; }
-// valid_mode, and PGH_CLIPPED_MEAN only with a bound set, PGH_TRIMMED_MEAN only with a trim count
-// (PGH_E_STATE otherwise)
-int check_mode(pgh_ctx* c, int mode);
+// May `mode` be folded this way on this context?  The one place that says so, in this order: an unknown
+// mode (PGH_E_ARG); a rule that the use or a group cannot serve -- a stream neither clips, trims nor
+// takes a median, a median folds nothing early, a group does not clip (PGH_E_UNSUPPORTED); a rule whose
+// bound or trim count is not set (PGH_E_STATE; a group leaves that to its children).
+enum ModeUse { USE_RESIDENT, USE_STREAM, USE_SLOT_EARLY, USE_SLOT_FINAL };
+int check_mode_use(pgh_ctx* c, int mode, ModeUse use);
 int check_ready(pgh_ctx* c);
 int check_dtype(pgh_ctx* c, int dtype);
 int check_ckpt(pgh_ctx* c, const char* what);
@@ -404,8 +411,6 @@ int final_ranges(const pgh_ctx* c);
 int64_t range_edge(const pgh_ctx* c, int k, int K);
 
 // ---- folds ---------------------------------------------------------------------------------------
-int sync_weights(pgh_ctx* c, hipStream_t s);
-int ensure_recips(pgh_ctx* c, int64_t n, hipStream_t s);
 int fixed_point_divisor(pgh_ctx* c, int base, int prec, float* div);
 int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div);
 
@@ -454,6 +459,21 @@ struct FinalArgs {
     int64_t off = 0;   // param range within the shard
     int64_t len = -1;  // -1 = to the end of the shard
 };
+// The two steps every fp32 fold driver takes (fold_run, slot_fold; nothing else calls them).
+// Before the launches of a fold that brings the cycle to `total` clients, on the fold's stream: the
+// weights of all of them on the device (weighted, clipped), the reciprocal table covering them (iterative).
+int fold_prepare(pgh_ctx* c, int mode, int64_t total, hipStream_t s);
+// The rows of one launch: n contiguous slab rows from `diffs`, or, with diffs = the slab at row 0,
+// the rows of tab or (a median of more rows than a RowTab carries) of the device table d_rows.
+struct FoldRows {
+    const float* diffs;
+    int n;
+    const pgh::RowTab* tab = nullptr;
+    const int32_t* d_rows = nullptr;
+};
+// One launch (the median: all of its launches) of `mode` over the shard params [fa.off, fa.off + fa.len)
+// on stream s, timed and accounted; client0 = the fold index of row 0.
+int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int flags, const FinalArgs& fa, hipStream_t s);
 int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const FinalArgs& fa, hipStream_t s);
 int64_t ready_run(pgh_ctx* c, int64_t from);
 int check_no_gaps(pgh_ctx* c, int64_t from, int64_t run);

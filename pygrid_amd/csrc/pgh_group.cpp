@@ -246,12 +246,6 @@ int apply_shards(pgh_ctx* c, bool client_shard) {
     });
 }
 
-float fixed_point_divisor(int base, int prec) {
-    long double scale = 1;
-    for (int k = 0; k < prec; ++k) scale *= base;
-    return (float)(int64_t)scale;
-}
-
 struct DevSel {  // select a device for this thread, restore the previous one after
     int prev = -1;
     explicit DevSel(int d) {
@@ -348,7 +342,8 @@ int secagg_client_sharded(pgh_ctx* c, int base, int prec, int64_t* sum_out, floa
     int total = 0;
     for (int v : g->kid_clients) total += v;
     if (total == 0) return fail(c, PGH_E_STATE, "no diffs ingested");
-    if (base < 2 || prec < 0 || prec > 18) return fail(c, PGH_E_ARG, "bad fixed-point base %d / precision %d", base, prec);
+    float div = 1.f;
+    RC(pgh_int::fixed_point_divisor(c, base, prec, &div));
     // 1. every GPU sums its own clients over the whole range (zeros if it holds none); the tail
     //    [len, L) of the send buffer stays zero so the padded slices reduce to zero
     RC(fan(c, [&](int i, pgh_ctx* k) -> int {
@@ -366,7 +361,6 @@ int secagg_client_sharded(pgh_ctx* c, int base, int prec, int64_t* sum_out, floa
     }, n));
     RC(ensure_backend(c, n));
     RC(grow(c, &g->d_rs, &g->rs_cap, S * 8));
-    const float div = fixed_point_divisor(base, prec);
     if (g->backend == 1) {
         // 2. reduce-scatter over RCCL: GPU i receives the Z_2^64 total of slice i
         g->rccl->group_start();

@@ -24,6 +24,8 @@ void free_group_ctx(pgh_ctx* c);                    // the shell only (the group
 // per-context internals the group driver uses
 int device_of(const pgh_ctx* c);
 hipStream_t stream_of(const pgh_ctx* c);
+// *div = float(base ** prec), the share decode's divisor; PGH_E_ARG for a base, precision or power out of range.
+int fixed_point_divisor(pgh_ctx* c, int base, int prec, float* div);
 // [P_shard] device vectors at least n elements long from the next pgh_reserve on (collectives send
 // equal padded shards).
 int set_vec_min(pgh_ctx* c, int64_t n);

@@ -42,9 +42,7 @@ struct FedavgArgs {
     int64_t p;              // params in this shard
     const float* weights;   // [n_rows] device, MODE_WEIGHTED only
     const double* recips;   // [n_rows] device, MODE_ITERATIVE: 1 / (double)(float)(client0 + r + 1)
-    float* acc;             // [p] running state; written unless FL_FINAL
-    const float* acc_in;    // [p] running state read unless FL_FIRST (nullptr: acc; a saved fold
-                            // state, pgh_fold_rewind, is read from where it was saved)
+    float* acc;             // [p] running state; read unless FL_FIRST, written unless FL_FINAL
     const float* ckpt;      // [p], FL_FINAL only
     float* out;             // [p], FL_FINAL only
     float divisor;          // float(N) or sum of weights, FL_FINAL of MEAN / WEIGHTED
@@ -118,6 +116,7 @@ struct SecaggArgs {
     int flags;
     int variant;
 };
+constexpr int SECAGG_AUTO_VARIANT = 14;  // what variant < 0 runs (measured in launch_secagg)
 hipError_t launch_secagg(const SecaggArgs& a, hipStream_t s);
 // The fp32 fold variant the auto choice (variant < 0) picks for a shard of p params.
 int auto_variant(int64_t p, int mode);

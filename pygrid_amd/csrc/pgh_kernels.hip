@@ -213,7 +213,7 @@ __device__ __forceinline__ void fedavg_columns(const FedavgArgs& a, const RowTab
         r = 1;
     } else {
 #pragma unroll
-        for (int w = 0; w < W; ++w) acc[w] = L::load_tail(a.acc_in, q0 + w * qstep, a.p);
+        for (int w = 0; w < W; ++w) acc[w] = L::load_tail(a.acc, q0 + w * qstep, a.p);
         r = 0;
     }
     for (; r + U <= n; r += U) {
@@ -266,7 +266,7 @@ __device__ __forceinline__ void fedavg_columns_pipe(const FedavgArgs& a, int64_t
         if constexpr (MODE == MODE_WEIGHTED) acc[0] = acc[0] * a.weights[0];
         r = 1;
     } else {
-        acc[0] = L::load_tail(a.acc_in, q, a.p);
+        acc[0] = L::load_tail(a.acc, q, a.p);
         r = 0;
     }
     T A[U][1], B[U][1];
@@ -444,7 +444,7 @@ __device__ __forceinline__ void trim_column(const FedavgArgs& a, const RowTab* t
             trim_plane_load<VEC>(a.tstate + (int64_t)j * a.tplane, q, a.p, s.lo[j]);
             trim_plane_load<VEC>(a.tstate + (int64_t)(B + j) * a.tplane, q, a.p, s.hi[j]);
         }
-        const T v = L::load_tail(a.acc_in, q, a.p);
+        const T v = L::load_tail(a.acc, q, a.p);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) s.acc[e] = lane_get(v, e);
     }
@@ -1148,7 +1148,6 @@ int cu_count() {
 // balance, not by the loads: the auto choice (variant -1) picks by shard size and mode
 // (auto_variant below, r01l measurements on the column-blocked slab).
 constexpr int N_VARIANTS = 24;
-constexpr int SECAGG_AUTO_VARIANT = 14;
 
 inline unsigned grid_for(int64_t ncol, int64_t tile, bool persistent) {
     const int64_t full = (ncol + tile - 1) / tile;
@@ -1328,20 +1327,20 @@ static hipError_t launch_trim(const FedavgArgs& a, const RowTab* t, hipStream_t 
     return vec == 4 ? dispatch_trim<4>(a, t, s) : dispatch_trim<1>(a, t, s);
 }
 
-hipError_t launch_fedavg(const FedavgArgs& a_, hipStream_t s) {
-    FedavgArgs a = a_;
-    if (!a.acc_in) a.acc_in = a.acc;
-    if (!(a.flags & FL_FIRST) && (!a.acc_in || !aligned16(a.acc_in))) return hipErrorInvalidValue;
-    if (a.p <= 0 || a.n_rows < 0 || !valid_map(a.map, a.p)) return hipErrorInvalidValue;
-    if ((a.flags & FL_FIRST) && a.n_rows < 1) return hipErrorInvalidValue;
-    if (a.n_rows > 0 && (!a.diffs || (reinterpret_cast<uintptr_t>(a.diffs) & 15))) return hipErrorInvalidValue;
-    if (!(a.flags & FL_FIRST) && (!a.acc || (reinterpret_cast<uintptr_t>(a.acc) & 15))) return hipErrorInvalidValue;
-    if (!(a.flags & FL_FINAL) && (!a.acc || (reinterpret_cast<uintptr_t>(a.acc) & 15))) return hipErrorInvalidValue;
-    if ((a.flags & FL_FINAL) && (!a.ckpt || !a.out || (reinterpret_cast<uintptr_t>(a.ckpt) & 15) ||
-                                 (reinterpret_cast<uintptr_t>(a.out) & 15)))
-        return hipErrorInvalidValue;
-    if (a.mode == MODE_WEIGHTED && a.n_rows > 0 && !a.weights) return hipErrorInvalidValue;
-    if (a.mode == MODE_ITERATIVE && a.n_rows > 0 && !a.recips) return hipErrorInvalidValue;
+// What launch_fedavg and launch_fedavg_rows both ask of their arguments.
+static bool valid_fedavg(const FedavgArgs& a) {
+    if (a.p <= 0 || a.n_rows < 0 || !valid_map(a.map, a.p)) return false;
+    if ((a.flags & FL_FIRST) && a.n_rows < 1) return false;
+    if (a.n_rows > 0 && (!a.diffs || !aligned16(a.diffs))) return false;
+    if ((a.flags & (FL_FIRST | FL_FINAL)) != (FL_FIRST | FL_FINAL) && (!a.acc || !aligned16(a.acc))) return false;
+    if ((a.flags & FL_FINAL) && (!a.ckpt || !a.out || !aligned16(a.ckpt) || !aligned16(a.out))) return false;
+    if (a.mode == MODE_WEIGHTED && a.n_rows > 0 && !a.weights) return false;
+    if (a.mode == MODE_ITERATIVE && a.n_rows > 0 && !a.recips) return false;
+    return true;
+}
+
+hipError_t launch_fedavg(const FedavgArgs& a, hipStream_t s) {
+    if (!valid_fedavg(a)) return hipErrorInvalidValue;
     if (a.mode == MODE_TRIMMED) return launch_trim(a, nullptr, s);
     const int v = a.variant < 0 ? auto_variant(a.p, a.mode) : a.variant;
     switch (a.mode) {
@@ -1353,20 +1352,8 @@ hipError_t launch_fedavg(const FedavgArgs& a_, hipStream_t s) {
 }
 
 hipError_t launch_fedavg_rows(const FedavgArgs& a_, const RowTab& t, hipStream_t s) {
-    FedavgArgs a = a_;
-    if (!a.acc_in) a.acc_in = a.acc;
-    if (!(a.flags & FL_FIRST) && (!a.acc_in || !aligned16(a.acc_in))) return hipErrorInvalidValue;
-    if (a.n_rows > ROWTAB_MAX) return hipErrorInvalidValue;
-    if (a.p <= 0 || a.n_rows < 0 || !valid_map(a.map, a.p)) return hipErrorInvalidValue;
-    if ((a.flags & FL_FIRST) && a.n_rows < 1) return hipErrorInvalidValue;
-    if (a.n_rows > 0 && (!a.diffs || (reinterpret_cast<uintptr_t>(a.diffs) & 15))) return hipErrorInvalidValue;
-    if (!(a.flags & FL_FIRST) && (!a.acc || (reinterpret_cast<uintptr_t>(a.acc) & 15))) return hipErrorInvalidValue;
-    if (!(a.flags & FL_FINAL) && (!a.acc || (reinterpret_cast<uintptr_t>(a.acc) & 15))) return hipErrorInvalidValue;
-    if ((a.flags & FL_FINAL) && (!a.ckpt || !a.out || (reinterpret_cast<uintptr_t>(a.ckpt) & 15) ||
-                                 (reinterpret_cast<uintptr_t>(a.out) & 15)))
-        return hipErrorInvalidValue;
-    if (a.mode == MODE_WEIGHTED && a.n_rows > 0 && !a.weights) return hipErrorInvalidValue;
-    if (a.mode == MODE_ITERATIVE && a.n_rows > 0 && !a.recips) return hipErrorInvalidValue;
+    const FedavgArgs& a = a_;
+    if (a.n_rows > ROWTAB_MAX || !valid_fedavg(a)) return hipErrorInvalidValue;
     if (a.mode == MODE_TRIMMED) return launch_trim(a, &t, s);
     int v = auto_variant(a.p, a.mode);
     if (a.variant == 0 || a.variant == 11 || a.variant == 14 || a.variant == 17) v = a.variant;

@@ -1,4 +1,5 @@
-// libpygrid_hip: fold_run and its bookkeeping, RESIDENT folds (every ingested client in one launch, repeatable), the resident
+// libpygrid_hip: what a mode may do (check_mode_use), the one fp32 fold launch (fold_prepare, fold_launch),
+// fold_run and its bookkeeping, RESIDENT folds (every ingested client in one launch, repeatable), the resident
 // checkpoint kept in HBM across cycles, secure aggregation (Z_2^64 share sum + fixed-point decode) and
 // STREAM folds (a ring of slots folded in client order while ingest continues).  Reference:
 // cycle_manager.py:252-296 (fedavg), test_basic_syft_operations.py:417-424 (secagg).
@@ -15,7 +16,7 @@ using namespace pgh_detail;
 
 namespace pgh_detail {
 
-int sync_weights(pgh_ctx* c, hipStream_t s) {
+static int sync_weights(pgh_ctx* c, hipStream_t s) {
     if (c->weights_on_device || c->weights.empty()) return PGH_OK;
     if (!c->d_w.reserve(sizeof(float) * c->weights.size())) return fail(c, PGH_E_OOM, "weight vector allocation failed");
     CK(c, hipMemcpyAsync(c->d_w.as<float>(), c->weights.data(), sizeof(float) * c->weights.size(), hipMemcpyHostToDevice, s));
@@ -26,7 +27,7 @@ int sync_weights(pgh_ctx* c, hipStream_t s) {
 
 // Reciprocal table covering clients [0, n) for the iterative fold's division (div_by_count in
 // pgh_kernels.hip).  Grows geometrically; the upload is ordered before stream `s`'s next fold.
-int ensure_recips(pgh_ctx* c, int64_t n, hipStream_t s) {
+static int ensure_recips(pgh_ctx* c, int64_t n, hipStream_t s) {
     const int64_t have = (int64_t)(c->d_rec.cap() / sizeof(double));
     if (n <= have) return PGH_OK;
     const int64_t cap = std::max<int64_t>({n, 2 * have, 4096});
@@ -56,27 +57,58 @@ float weight_total(const std::vector<float>& w, int64_t n) {  // left fold, floa
     return t;
 }
 
+int fold_prepare(pgh_ctx* c, int mode, int64_t total, hipStream_t s) {
+    if (kernel_mode(mode) == PGH_WEIGHTED_MEAN) {
+        if ((int64_t)c->weights.size() < total)
+            return fail(c, PGH_E_STATE, "weighted mean: %zu weights for %lld clients", c->weights.size(), (long long)total);
+        RC(sync_weights(c, s));
+    }
+    if (mode == PGH_ITERATIVE_MEAN) RC(ensure_recips(c, total, s));
+    return PGH_OK;
+}
+
+int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int flags, const FinalArgs& fa, hipStream_t s) {
+    const int64_t off = fa.off;
+    pgh::FedavgArgs a{};
+    a.diffs = rows.diffs;
+    a.map = slab_map(c);
+    a.map.off = off;
+    a.n_rows = rows.n;
+    a.client0 = client0;
+    a.p = fa.len;
+    a.weights = c->d_w ? c->d_w.as<float>() + client0 : nullptr;
+    a.recips = c->d_rec ? c->d_rec.as<double>() + client0 : nullptr;
+    a.acc = c->d_acc.as<float>() + off;
+    a.ckpt = fa.ckpt ? fa.ckpt + off : nullptr;
+    a.out = fa.out ? fa.out + off : nullptr;
+    a.divisor = fa.divisor;
+    a.flags = flags;
+    a.mode = kernel_mode(mode);
+    a.variant = c->variant;
+    if (mode == PGH_MEDIAN) return median_fold(c, a, rows.tab, rows.d_rows, s);  // (its own launches and bytes)
+    // HBM bytes: the rows; the running state in unless FIRST; the state out, or ckpt in and out when FINAL
+    const uint64_t pg = (uint64_t)fa.len;
+    uint64_t bytes = 4ull * (uint64_t)rows.n * pg + ((flags & pgh::FL_FIRST) ? 0 : 4 * pg) +
+                     ((flags & pgh::FL_FINAL) ? 8 * pg : 4 * pg);
+    if (mode == PGH_TRIMMED_MEAN) {
+        RC(trim_args(c, &a));
+        bytes += trim_state_bytes(c, flags, pg);
+    }
+    if (rows.tab) return timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg_rows(a, *rows.tab, s); });
+    return timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); });
+}
+
 // Fold slots holding clients [c0, c0 + n) (slot order may wrap) into the running state.
 // FIRST when c0 == 0; FINAL writes out (fedavg: ckpt - avg; secagg: sum/dec) instead of the state.
 int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const FinalArgs& fa, hipStream_t s) {
-    if (kind == PGH_CLIPPED_MEAN) {  // resident only: the weighted fold over the scales of clients [0, n)
-        if (c0 != 0 || !final) return fail(c, PGH_E_UNSUPPORTED, "a clipped mean folds a resident slab in one pass");
-        RC(resident_clip_scales(c, n));
-        kind = PGH_WEIGHTED_MEAN;
-    }
-    if (kind == PGH_MEDIAN && (c0 != 0 || !final || n > c->slots))
-        return fail(c, PGH_E_UNSUPPORTED, "a median folds every row of a resident slab in one call");
+    // (resident only, check_mode_use: the scales of clients [0, n) become the fold's weights)
+    if (kind == PGH_CLIPPED_MEAN) RC(resident_clip_scales(c, n));
     RC(order_after_ingest(c, s));
-    if (kind == PGH_WEIGHTED_MEAN && n > 0) {
-        if ((int64_t)c->weights.size() < c0 + n)
-            return fail(c, PGH_E_STATE, "weighted mean: %zu weights for %lld clients", c->weights.size(),
-                        (long long)(c0 + n));
-        RC(sync_weights(c, s));
-    }
-    if (kind == PGH_ITERATIVE_MEAN && n > 0) RC(ensure_recips(c, c0 + n, s));
+    if (kind != KIND_SECAGG && n > 0) RC(fold_prepare(c, kind, c0 + n, s));
     const int R = c->slots;
-    const int64_t off = fa.off;
-    const int64_t len = fa.len < 0 ? c->pg - off : fa.len;
+    FinalArgs r = fa;  // the launches' param range, its length resolved
+    if (r.len < 0) r.len = c->pg - r.off;
+    const int64_t off = r.off, len = r.len;
     if (off < 0 || (off & 3) || len <= 0 || off + len > c->pg)
         return fail(c, PGH_E_ARG, "param range [%lld,+%lld) outside the shard or not 4-aligned", (long long)off,
                     (long long)len);
@@ -87,8 +119,8 @@ int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const Fina
         const bool first = (c0 + done == 0);
         const bool last = (done + seg == n);
         const int flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
-        const uint64_t pg = (uint64_t)len;
         if (kind == KIND_SECAGG) {
+            const uint64_t pg = (uint64_t)len;
             pgh::SecaggArgs a{};
             a.shares = (const int64_t*)slot_row(c, slot, 0);
             a.map = slab_map(c);
@@ -105,30 +137,7 @@ int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const Fina
                                    ((flags & pgh::FL_FINAL) ? (fa.sum ? 8 * pg : 0) + (fa.dec ? 4 * pg : 0) : 8 * pg);
             RC(timed_launch(c, s, bytes, [&] { return pgh::launch_secagg(a, s); }));
         } else {
-            pgh::FedavgArgs a{};
-            a.diffs = (const float*)slot_row(c, slot, 0);
-            a.map = slab_map(c);
-            a.map.off = off;
-            a.n_rows = (int)seg;
-            a.client0 = c0 + done;
-            a.p = len;
-            a.weights = c->d_w ? c->d_w.as<float>() + (c0 + done) : nullptr;
-            a.recips = c->d_rec ? c->d_rec.as<double>() + (c0 + done) : nullptr;
-            a.acc = c->d_acc.as<float>() + off;
-            a.ckpt = fa.ckpt ? fa.ckpt + off : nullptr;
-            a.out = fa.out ? fa.out + off : nullptr;
-            a.divisor = fa.divisor;
-            a.flags = flags;
-            a.mode = kind;
-            a.variant = c->variant;
-            uint64_t bytes = 4ull * (uint64_t)seg * pg + (first ? 0 : 4 * pg) +
-                             ((flags & pgh::FL_FINAL) ? 8 * pg : 4 * pg);
-            if (kind == PGH_TRIMMED_MEAN) {
-                RC(trim_args(c, &a));
-                bytes += trim_state_bytes(c, flags, pg);
-            }
-            if (kind == PGH_MEDIAN) RC(median_fold(c, a, nullptr, nullptr, s));  // (its own launches and bytes)
-            else RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
+            RC(fold_launch(c, kind, FoldRows{(const float*)slot_row(c, slot, 0), (int)seg}, c0 + done, flags, r, s));
         }
         done += seg;
     } while (done < n);
@@ -228,13 +237,26 @@ int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
 
 namespace pgh_detail {
 
-int check_mode(pgh_ctx* c, int mode) {
-    if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
-    if (mode == PGH_CLIPPED_MEAN && !(c->clip_c > 0.f))
-        return fail(c, PGH_E_STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first");
-    if (mode == PGH_TRIMMED_MEAN && c->trim_b == 0)
-        return fail(c, PGH_E_STATE, "PGH_TRIMMED_MEAN needs a trim count: call pgh_set_trim first");
-    return PGH_OK;
+int check_mode_use(pgh_ctx* c, int mode, ModeUse use) {
+    switch (mode) {
+    case PGH_MEAN: case PGH_ITERATIVE_MEAN: case PGH_WEIGHTED_MEAN:
+        return PGH_OK;
+    case PGH_CLIPPED_MEAN:
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not clip: a scale needs the whole row of every client");
+        if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts do not clip: the shards each hold part of a row");
+        if (!(c->clip_c > 0.f)) return fail(c, PGH_E_STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first");
+        return PGH_OK;
+    case PGH_TRIMMED_MEAN:
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not trim: fold a RESIDENT slab or slots");
+        if (!c->grp && c->trim_b == 0) return fail(c, PGH_E_STATE, "PGH_TRIMMED_MEAN needs a trim count: call pgh_set_trim first");
+        return PGH_OK;
+    case PGH_MEDIAN:  // it needs every row of the cycle at once
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no median: it needs every row at once");
+        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a median needs every row at once: nothing can be folded early");
+        return PGH_OK;
+    default:
+        return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
+    }
 }
 
 int trim_args(pgh_ctx* c, pgh::FedavgArgs* a) {
@@ -506,29 +528,16 @@ int pgh_clip_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_clipped, double* max_
 // ---- RESIDENT reductions -------------------------------------------------------------------------
 
 int pgh_fedavg_device(pgh_ctx* c, int mode, const float* d_ckpt, float* d_out, void* stream) {
-    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s takes device pointers, which name one GPU: call it on pgh_group_child", __func__);
-    RC(check_dtype(c, PGH_F32));
-    RC(check_mode(c, mode));
-    if (!d_ckpt || !d_out) return fail(c, PGH_E_ARG, "d_ckpt / d_out is NULL");
-    if (((uintptr_t)d_ckpt | (uintptr_t)d_out) & 15) return fail(c, PGH_E_ARG, "device buffers must be 16-byte aligned");
-    DeviceGuard g(c->device);
-    int64_t n = 0;
-    RC(resident_count(c, &n));
-    FinalArgs fa;
-    fa.ckpt = d_ckpt;
-    fa.out = d_out;
-    RC(fedavg_divisor(c, mode, n, &fa.divisor));
-    hipStream_t s = (hipStream_t)stream;
-    return fold_run(c, mode, 0, n, true, fa, s);
+    return pgh_fedavg_device_range(c, mode, 0, -1, d_ckpt, d_out, stream);  // the whole shard
 }
 
 int pgh_fedavg_device_range(pgh_ctx* c, int mode, int64_t off, int64_t len, const float* d_ckpt, float* d_out,
                             void* stream) {
-    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s takes device pointers, which name one GPU: call it on pgh_group_child", __func__);
+    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_fedavg_device* takes device pointers, which name one GPU: call it on pgh_group_child");
     RC(check_dtype(c, PGH_F32));
-    RC(check_mode(c, mode));
-    if (!d_ckpt || !d_out || (((uintptr_t)d_ckpt | (uintptr_t)d_out) & 15))
-        return fail(c, PGH_E_ARG, "d_ckpt / d_out must be 16-byte aligned device pointers");
+    RC(check_mode_use(c, mode, USE_RESIDENT));
+    if (!d_ckpt || !d_out) return fail(c, PGH_E_ARG, "d_ckpt / d_out is NULL");
+    if (((uintptr_t)d_ckpt | (uintptr_t)d_out) & 15) return fail(c, PGH_E_ARG, "device buffers must be 16-byte aligned");
     DeviceGuard g(c->device);
     int64_t n = 0;
     RC(resident_count(c, &n));
@@ -541,20 +550,27 @@ int pgh_fedavg_device_range(pgh_ctx* c, int mode, int64_t off, int64_t len, cons
     return fold_run(c, mode, 0, n, true, fa, (hipStream_t)stream);
 }
 
+// New checkpoint bytes into d_ckpt (one host range, or the pieces of a State message): on the copy
+// stream behind every fold that may still read it; the range marks of the last FINAL pass go with it.
+static int upload_ckpt(pgh_ctx* c, const uint8_t* src, size_t n, bool pinned_src, const std::vector<Piece>* pieces = nullptr) {
+    const Dest dst = vec_dest(c->d_ckpt.as<float>(), c->pvec, 4);
+    RC(order_before_overwrite(c));
+    c->ckpt_valid = false;
+    clear_final_marks(c);
+    RC(pieces ? stage_pieces_h2d(c, dst, *pieces) : stage_h2d(c, dst, src, n, pinned_src));
+    c->ckpt_valid = true;
+    return PGH_OK;
+}
+
 int pgh_fedavg(pgh_ctx* c, int mode, const float* ckpt, float* out) {
-    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
+    if (c) RC(check_mode_use(c, mode, USE_RESIDENT));
     if (c && c->grp) return pgh_group_api::fedavg(c, mode, ckpt, out);
     RC(check_dtype(c, PGH_F32));
-    RC(check_mode(c, mode));
     if (!ckpt || !out) return fail(c, PGH_E_ARG, "ckpt / out is NULL");
     DeviceGuard g(c->device);
     const double t0 = now_ms();
     const size_t bytes = sizeof(float) * (size_t)c->pg;
-    RC(order_before_overwrite(c));
-    c->ckpt_valid = false;
-    clear_final_marks(c);
-    RC(stage_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
-    c->ckpt_valid = true;
+    RC(upload_ckpt(c, (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
     RC(pgh_fedavg_device(c, mode, c->d_ckpt.as<float>(), c->d_out.as<float>(), c->stream));
     if (is_pinned(out)) {
         CK(c, hipMemcpyAsync(out, c->d_out.as<float>(), bytes, hipMemcpyDeviceToHost, c->stream));
@@ -577,13 +593,8 @@ int pgh_ckpt_upload(pgh_ctx* c, const float* ckpt, size_t nbytes) {
         return fail(c, PGH_E_ARG, "checkpoint: got %zu bytes, layout needs %zu (model) or %zu (shard)", nbytes, whole,
                     shard);
     DeviceGuard g(c->device);
-    RC(order_before_overwrite(c));
     const uint8_t* src = (const uint8_t*)ckpt + (nbytes == whole ? 4 * (size_t)c->lo : 0);
-    c->ckpt_valid = false;
-    clear_final_marks(c);
-    RC(stage_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), src, shard, is_pinned(ckpt)));
-    c->ckpt_valid = true;
-    return PGH_OK;
+    return upload_ckpt(c, src, shard, is_pinned(ckpt));
 }
 
 int pgh_ckpt_upload_state(pgh_ctx* c, const uint8_t* pb, size_t n) {
@@ -595,20 +606,14 @@ int pgh_ckpt_upload_state(pgh_ctx* c, const uint8_t* pb, size_t n) {
     std::vector<Piece> pieces;
     for (auto& sp : spans) pieces.push_back(Piece{pb + sp.first, sp.second});
     DeviceGuard g(c->device);
-    RC(order_before_overwrite(c));
-    c->ckpt_valid = false;
-    clear_final_marks(c);
-    RC(stage_pieces_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), pieces));
-    c->ckpt_valid = true;
-    return PGH_OK;
+    return upload_ckpt(c, nullptr, 0, false, &pieces);
 }
 
 int pgh_fedavg_resident(pgh_ctx* c, int mode) {
-    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
+    if (c) RC(check_mode_use(c, mode, USE_RESIDENT));
     if (c && c->grp) return pgh_group_api::fedavg_resident(c, mode);
     RC(check_dtype(c, PGH_F32));
     RC(check_ckpt(c, "pgh_fedavg_resident"));
-    RC(check_mode(c, mode));
     DeviceGuard g(c->device);
     const double t0 = now_ms();
     clear_final_marks(c);
@@ -690,21 +695,12 @@ int pgh_ckpt_patch_state(pgh_ctx* c, const uint8_t* tmpl, size_t n, uint8_t* out
 }
 
 int pgh_secagg_device(pgh_ctx* c, int base, int prec, int64_t* d_sum, float* d_dec, void* stream) {
-    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s takes device pointers, which name one GPU: call it on pgh_group_child", __func__);
-    RC(check_dtype(c, PGH_I64));
-    DeviceGuard g(c->device);
-    int64_t n = 0;
-    RC(resident_count(c, &n));
-    FinalArgs fa;
-    fa.sum = d_sum;
-    fa.dec = d_dec;
-    RC(fixed_point_divisor(c, base, prec, &fa.divisor));
-    return fold_run(c, KIND_SECAGG, 0, n, true, fa, (hipStream_t)stream);
+    return pgh_secagg_device_range(c, base, prec, 0, -1, d_sum, d_dec, stream);  // the whole shard
 }
 
 int pgh_secagg_device_range(pgh_ctx* c, int base, int prec, int64_t off, int64_t len, int64_t* d_sum, float* d_dec,
                             void* stream) {
-    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s takes device pointers, which name one GPU: call it on pgh_group_child", __func__);
+    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_secagg_device* takes device pointers, which name one GPU: call it on pgh_group_child");
     RC(check_dtype(c, PGH_I64));
     DeviceGuard g(c->device);
     int64_t n = 0;
@@ -716,6 +712,16 @@ int pgh_secagg_device_range(pgh_ctx* c, int base, int prec, int64_t off, int64_t
     fa.len = len;
     RC(fixed_point_divisor(c, base, prec, &fa.divisor));
     return fold_run(c, KIND_SECAGG, 0, n, true, fa, (hipStream_t)stream);
+}
+
+// The share sum and / or its decode from d_sum / d_dec to the host behind the fold on c->stream; ends
+// the close that began at t0.
+static int secagg_download(pgh_ctx* c, int64_t* sum_out, float* dec_out, double t0) {
+    if (sum_out) CK(c, hipMemcpyAsync(sum_out, c->d_sum.as<int64_t>(), 8ull * c->pg, hipMemcpyDeviceToHost, c->stream));
+    if (dec_out) CK(c, hipMemcpyAsync(dec_out, c->d_dec.as<float>(), 4ull * c->pg, hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    c->st.close_ms_last = now_ms() - t0;
+    return collect_timings(c);
 }
 
 int pgh_secagg_decode_device(pgh_ctx* c, int base, int prec, const int64_t* d_sum, int64_t n, float* d_dec,
@@ -739,24 +745,18 @@ int pgh_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, float* dec_out)
     DeviceGuard g(c->device);
     const double t0 = now_ms();
     RC(pgh_secagg_device(c, base, prec, sum_out ? c->d_sum.as<int64_t>() : nullptr, dec_out ? c->d_dec.as<float>() : nullptr, c->stream));
-    if (sum_out) CK(c, hipMemcpyAsync(sum_out, c->d_sum.as<int64_t>(), 8ull * c->pg, hipMemcpyDeviceToHost, c->stream));
-    if (dec_out) CK(c, hipMemcpyAsync(dec_out, c->d_dec.as<float>(), 4ull * c->pg, hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    c->st.close_ms_last = now_ms() - t0;
-    return collect_timings(c);
+    return secagg_download(c, sum_out, dec_out, t0);
 }
 
 // ---- STREAM reductions ---------------------------------------------------------------------------
 
 int pgh_stream_begin(pgh_ctx* c, int kind, int fold_batch) {
-    if (c && kind == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not clip: a scale needs the whole row of every client");
-    if (c && kind == PGH_TRIMMED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not trim: fold a RESIDENT slab or slots");
-    if (c && kind == PGH_MEDIAN) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no median: it needs every row at once");
+    if (c && kind != PGH_STREAM_SECAGG) RC(check_mode_use(c, kind, USE_STREAM));
     if (c && c->grp) return pgh_group_api::stream_begin(c, kind, fold_batch);
     RC(check_ready(c));
     if (kind == PGH_STREAM_SECAGG) {
         if (c->dtype != PGH_I64) return fail(c, PGH_E_STATE, "secagg stream needs an int64 slab");
-    } else if (!valid_mode(kind) || c->dtype != PGH_F32) {
+    } else if (c->dtype != PGH_F32) {
         return fail(c, PGH_E_ARG, "stream kind %d does not match the slab", kind);
     }
     DeviceGuard g(c->device);
@@ -829,11 +829,7 @@ int pgh_stream_finish(pgh_ctx* c, const float* ckpt, float* out) {
     // staged like pgh_fedavg's checkpoint: on the copy stream after every fold that may still read
     // d_ckpt, so fold_run's order_after_ingest orders the final fold after it (a pageable
     // pgh_ckpt_upload's last ring DMA can no longer land after this copy)
-    RC(order_before_overwrite(c));
-    c->ckpt_valid = false;
-    clear_final_marks(c);
-    RC(stage_h2d(c, vec_dest(c->d_ckpt.as<float>(), c->pvec, 4), (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
-    c->ckpt_valid = true;
+    RC(upload_ckpt(c, (const uint8_t*)ckpt, bytes, is_pinned(ckpt)));
     RC(pgh_stream_finish_device(c, c->d_ckpt.as<float>(), c->d_out.as<float>(), c->stream));
     CK(c, hipMemcpyAsync(out, c->d_out.as<float>(), bytes, hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
@@ -859,10 +855,6 @@ int pgh_stream_finish_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, f
     const double t0 = now_ms();
     RC(pgh_stream_finish_secagg_device(c, base, prec, sum_out ? c->d_sum.as<int64_t>() : nullptr, dec_out ? c->d_dec.as<float>() : nullptr,
                                        c->stream));
-    if (sum_out) CK(c, hipMemcpyAsync(sum_out, c->d_sum.as<int64_t>(), 8ull * c->pg, hipMemcpyDeviceToHost, c->stream));
-    if (dec_out) CK(c, hipMemcpyAsync(dec_out, c->d_dec.as<float>(), 4ull * c->pg, hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    c->st.close_ms_last = now_ms() - t0;
-    return collect_timings(c);
+    return secagg_download(c, sum_out, dec_out, t0);
 }
 

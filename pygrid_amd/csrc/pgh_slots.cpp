@@ -12,7 +12,6 @@ using namespace pgh_detail;
 namespace {
 int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     RC(check_dtype(c, PGH_F32));
-    RC(check_mode(c, mode));
     if (c->streaming) return fail(c, PGH_E_STATE, "context is streaming: slot folds need a RESIDENT slab");
     if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
     if (c->slot_mode >= 0 && c->slot_mode != mode)
@@ -25,12 +24,13 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         if (seen[(size_t)sl]) return fail(c, PGH_E_ARG, "slot %d listed twice", sl);
         seen[(size_t)sl] = 1;
     }
-    const bool median = mode == PGH_MEDIAN;  // every row of the cycle in this one call
-    if (median && !final) return fail(c, PGH_E_UNSUPPORTED, "a median needs every row at once: nothing can be folded early");
+    const bool median = mode == PGH_MEDIAN;  // every row of the cycle in this one call (check_mode_use: final)
     if (median && c->folded > 0)
         return fail(c, PGH_E_STATE, "a median closes a cycle without earlier slot folds (%lld diffs folded)", (long long)c->folded);
     const int64_t c0 = c->folded, total = c0 + n;
     FinalArgs fa;
+    fa.ckpt = c->d_ckpt.as<float>();
+    fa.out = c->d_out.as<float>();
     if (final) {
         RC(check_ckpt(c, "pgh_fold_slots_finish_resident"));
         if (total == 0) return fail(c, PGH_E_STATE, "no diffs folded");
@@ -52,13 +52,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     }
     if (!ranged) RC(order_after_ingest(c, s));
     else if (c->dec_last) CK(c, hipStreamWaitEvent(s, c->dec_last, 0));  // the copy stream: per range below
-    if (kernel_mode(mode) == PGH_WEIGHTED_MEAN && n > 0) {
-        if ((int64_t)c->weights.size() < total)
-            return fail(c, PGH_E_STATE, "weighted mean: %zu weights for %lld clients", c->weights.size(),
-                        (long long)total);
-        RC(sync_weights(c, s));
-    }
-    if (mode == PGH_ITERATIVE_MEAN && n > 0) RC(ensure_recips(c, total, s));
+    if (n > 0) RC(fold_prepare(c, mode, total, s));
     if (median && n > pgh::ROWTAB_MAX) RC(median_row_table(c, slots, n, s));  // more rows than a RowTab carries
     int done = 0;
     bool prequeued = false;
@@ -67,21 +61,11 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         pgh::RowTab tab;
         for (int k = 0; k < std::min(m, pgh::ROWTAB_MAX); ++k) tab.rows[k] = slots[done + k] * c->parties;
         const bool first = (c0 + done == 0), last = (done + m == n);
-        pgh::FedavgArgs a{};
-        a.diffs = c->d_slab.as<float>();
-        a.map = slab_map(c);
-        a.n_rows = m;
-        a.client0 = c0 + done;
-        a.p = c->pg;
-        a.weights = c->d_w ? c->d_w.as<float>() + (c0 + done) : nullptr;
-        a.recips = c->d_rec ? c->d_rec.as<double>() + (c0 + done) : nullptr;
-        a.acc = c->d_acc.as<float>();
-        a.ckpt = c->d_ckpt.as<float>();
-        a.out = c->d_out.as<float>();
-        a.divisor = fa.divisor;
-        a.flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
-        a.mode = kernel_mode(mode);
-        a.variant = c->variant;
+        const int flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
+        // (only a median comes with more rows than the table carries: they are in d_rowidx then)
+        FoldRows rows{c->d_slab.as<float>(), m};
+        if (m <= pgh::ROWTAB_MAX) rows.tab = &tab;
+        else rows.d_rows = c->d_rowidx.as<int32_t>();
         // The FINAL pass of a report-time close (a short fold of the rows left) as ranges of 4 MiB of
         // output, one after another on one stream, a mark behind every second one: each 8 MiB D2H
         // piece starts behind the two ranges that wrote it instead of behind the whole fold.  Ranges
@@ -89,14 +73,14 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         // alternating over two streams (profiles/r04m/: 2.04 vs 2.19 ms, close start -> new
         // checkpoint bytes); a mark (a system-scope release) only where a piece ends (r05).
         const int64_t RF = (int64_t)(D2H_PIECE / 8);
-        const int K = (a.flags & pgh::FL_FINAL) && c->pg >= (1 << 20) ? (int)((c->pg + RF - 1) / RF) : 1;
-        if (a.flags & pgh::FL_FINAL) clear_final_marks(c);
+        const int K = (flags & pgh::FL_FINAL) && c->pg >= (1 << 20) ? (int)((c->pg + RF - 1) / RF) : 1;
+        if (flags & pgh::FL_FINAL) clear_final_marks(c);
         // the new checkpoint's D2H starts here: after each mark, the pieces whose ranges have
         // finished go out while the later ranges are still being issued (stage_d2h_pieces adopts the
         // ring).  The result is d_out until the swap below.
         pgh_ctx::D2HRing& pre = c->pre_d2h;
         bool prequeue = false;
-        if (K > 1 && (a.flags & pgh::FL_FINAL)) {
+        if (K > 1 && (flags & pgh::FL_FINAL)) {
             RC(d2h_ring_begin(c, &pre, c->d_out.as<uint8_t>(), 4 * (size_t)c->pg, s, true, false));
             prequeue = pre.base || pre.n_free > 0;  // own cells, or a free staging slot
         }
@@ -109,20 +93,9 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
             } else if (ranged && r == 0) {
                 CK(c, hipStreamWaitEvent(rs, c->rng_ev[(size_t)(c->rng_n - 1)], 0));  // ... or all of it
             }
-            pgh::FedavgArgs ar = a;
-            ar.map.off = lo;
-            ar.p = hi - lo;
-            ar.acc = c->d_acc.as<float>() + lo;
-            ar.ckpt = c->d_ckpt.as<float>() + lo;
-            ar.out = c->d_out.as<float>() + lo;
-            const uint64_t rp = (uint64_t)(hi - lo);
-            uint64_t bytes = 4ull * (uint64_t)m * rp + (first ? 0 : 4 * rp) + ((a.flags & pgh::FL_FINAL) ? 8 * rp : 4 * rp);
-            if (mode == PGH_TRIMMED_MEAN) {
-                RC(trim_args(c, &ar));
-                bytes += trim_state_bytes(c, a.flags, rp);
-            }
-            if (median) RC(median_fold(c, ar, m <= pgh::ROWTAB_MAX ? &tab : nullptr, c->d_rowidx.as<int32_t>(), rs));
-            else RC(timed_launch(c, rs, bytes, [&] { return pgh::launch_fedavg_rows(ar, tab, rs); }));
+            fa.off = lo;
+            fa.len = hi - lo;
+            RC(fold_launch(c, mode, rows, c0 + done, flags, fa, rs));
             if (K > 1 && (hi % (2 * RF) == 0 || hi == c->pg)) {
                 RC(add_final_mark(c, rs, hi));
                 const size_t before = prequeue ? pre.queued : 0;
@@ -159,15 +132,14 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
 }  // namespace
 
 int pgh_fold_slots(pgh_ctx* c, int mode, const int32_t* slots, int n) {
-    if (c && mode == PGH_MEDIAN) return fail(c, PGH_E_UNSUPPORTED, "%s: a median needs every row at once, nothing can be folded early", __func__);
-    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
+    if (c) RC(check_mode_use(c, mode, USE_SLOT_EARLY));
     if (c && c->grp) return pgh_group_api::fold_slots(c, mode, slots, n, false);
     if (!c) return PGH_E_ARG;
     return slot_fold(c, mode, slots, n, false);
 }
 
 int pgh_fold_slots_finish_resident(pgh_ctx* c, int mode, const int32_t* slots, int n) {
-    if (c && c->grp && mode == PGH_CLIPPED_MEAN) return fail(c, PGH_E_UNSUPPORTED, "%s: group contexts do not clip", __func__);
+    if (c) RC(check_mode_use(c, mode, USE_SLOT_FINAL));
     if (c && c->grp) return pgh_group_api::fold_slots(c, mode, slots, n, true);
     if (!c) return PGH_E_ARG;
     const double t0 = now_ms();
