@@ -268,6 +268,55 @@ int pgh_set_trim(pgh_ctx* ctx, int b);
  * median folds. */
 #define PGH_MEDIAN_NCHIP 1024
 
+/* ---- server optimizers: how the average is applied (FedAvgM, FedAdagrad, FedAdam, FedYogi) ------
+ * Without one, a close writes out = ckpt - g, g being the cycle's average as its mode defines it
+ * (acc / divisor; the iterative mean's acc; the trimmed mean; the median).  With one set, every
+ * fp32 FINAL fold (pgh_fedavg, pgh_fedavg_device[_range], pgh_fedavg_resident,
+ * pgh_fold_slots_finish_resident, pgh_stream_finish*; every mode; shards and groups) applies, per
+ * parameter and in f32, each operation rounded on its own (no FMA; sqrt and / correctly rounded):
+ *   c1 = 1.0f - beta1, c2 = 1.0f - beta2, v0 = tau * tau (computed once, in f32);
+ *   state: m starts at +0.0f, v at v0;
+ *   PGH_OPT_MOMENTUM (Hsu et al. 2019):  m' = beta1 * m + g;  out = ckpt - lr * m'            (no v)
+ *   PGH_OPT_ADAGRAD (Reddi et al. 2021): m' = beta1 * m + c1 * g;  q = g * g;  v' = v + q;
+ *                                        out = ckpt - (lr * m') / (sqrt(v') + tau)
+ *   PGH_OPT_ADAM:   as Adagrad with v' = beta2 * v + c2 * q
+ *   PGH_OPT_YOGI:   as Adagrad with s = v > q ? 1.0f : v < q ? -1.0f : 0.0f (a NaN gives 0) and
+ *                   v' = v - (c2 * q) * s
+ * There is no bias correction.  Non-finite values follow IEEE and are not sanitised: a NaN in g stays
+ * in that parameter's m / v until the state is uploaded again (PGH_TRIMMED_MEAN and PGH_MEDIAN keep
+ * a minority's NaN out of g).  The fold kernels run unchanged, against a plane of -0.0f into a delta
+ * plane d = (-0.0f) - g = -g (exact for every non-NaN g, signed zeros included), and kernel K10
+ * follows on the same stream over the same parameter range.  Secure aggregation is not affected.
+ *
+ * pgh_set_server_opt: PGH_E_ARG unless lr is finite and > 0, beta1 in [0, 1), and -- for the kinds that
+ * use them, ignored otherwise -- beta2 in [0, 1) and tau finite and > 0.  The same kind and values again
+ * keep the state; any change initialises it again; PGH_OPT_NONE frees the planes and restores the plain
+ * path.  It needs a layout (PGH_E_STATE).  The planes are six [P_shard] float vectors in HBM (four for
+ * PGH_OPT_MOMENTUM): -0, d, and m and v twice.  The state belongs to the model: it survives pgh_reset
+ * and pgh_reserve; pgh_set_layout and pgh_set_shard drop it and the setting, and so does a group's
+ * pgh_reserve of a client-sharded int64 slab (pgh_set_client_sharding), which shards its children anew.
+ * A FINAL never updates the state in place: it reads the committed m / v and writes pending ones, so a
+ * repeated FINAL gives identical bits.  pgh_server_opt_commit makes the pending state the committed one
+ * (a pointer swap) and counts a step; PGH_E_STATE when no FINAL has run since the last commit or
+ * upload.  Where the FINAL launches since the last commit covered only part of the shard
+ * (pgh_fedavg_device_range), the commit leaves the moments of every other parameter as they were.
+ * The library never commits by itself.  pgh_server_opt_download copies the committed state
+ * out (P_shard floats each; v may be NULL for PGH_OPT_MOMENTUM); pgh_server_opt_upload replaces it
+ * (each array the whole model or this shard, like pgh_ckpt_upload) and clears anything pending.  A
+ * group hands the setting and the commit to its children and scatters / gathers the state by slice. */
+typedef enum {
+    PGH_OPT_NONE = 0,
+    PGH_OPT_MOMENTUM = 1,
+    PGH_OPT_ADAGRAD = 2,
+    PGH_OPT_ADAM = 3,
+    PGH_OPT_YOGI = 4
+} pgh_server_opt;
+int pgh_set_server_opt(pgh_ctx* ctx, int kind, float lr, float beta1, float beta2, float tau);
+int pgh_server_opt_commit(pgh_ctx* ctx);
+int pgh_server_opt_steps(pgh_ctx* ctx, int64_t* committed);
+int pgh_server_opt_download(pgh_ctx* ctx, float* m, float* v);
+int pgh_server_opt_upload(pgh_ctx* ctx, const float* m, const float* v, size_t nbytes);
+
 /* ---- reduction ----------------------------------------------------------------------------
  * out = ckpt - avg(diffs), over this context's shard.  Host pointers, P_shard floats each. */
 int pgh_fedavg(pgh_ctx* ctx, int mode, const float* ckpt, float* out);

@@ -17,7 +17,8 @@ thresholds for 47 MB buffers).
 """
 from .exceptions import (AggregationError, ClipUnavailableError, EngineUnavailableError, MedianUnavailableError,
                          ModelNotAcceleratedError,
-                         PlanNotAcceleratedError, PyGridError, StateParseError, TrimUnavailableError)
+                         PlanNotAcceleratedError, PyGridError, ServerOptUnavailableError, StateParseError,
+                         TrimUnavailableError)
 from .engine import (CLIPPED_MEAN, F32, I64, ITERATIVE_MEAN, MEAN, MEDIAN, MEDIAN_NCHIP, MODE_NAMES, STREAM_SECAGG,
                      TRIMMED_MEAN, TRIM_MAX,
                      WEIGHTED_MEAN, Engine, PinnedBuffer, device_count)
@@ -40,7 +41,7 @@ def tune_process(hw_queues: bool = True, malloc: bool = True) -> dict:
 
 __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
-    "StateParseError", "TrimUnavailableError", "MedianUnavailableError",
+    "StateParseError", "TrimUnavailableError", "MedianUnavailableError", "ServerOptUnavailableError",
     "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
     "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "MODE_NAMES", "F32", "I64",
     "tune_process",

@@ -105,6 +105,11 @@ SIGNATURES = {
     "pgh_clip_scale": (_i, [C.c_double, C.c_float, C.POINTER(C.c_float)]),
     "pgh_clip_stats": (_i, [_vp, _P64, _P64, C.POINTER(C.c_double)]),
     "pgh_set_trim": (_i, [_vp, _i]),
+    "pgh_set_server_opt": (_i, [_vp, _i, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "pgh_server_opt_commit": (_i, [_vp]),
+    "pgh_server_opt_steps": (_i, [_vp, _P64]),
+    "pgh_server_opt_download": (_i, [_vp, _vp, _vp]),
+    "pgh_server_opt_upload": (_i, [_vp, _vp, _vp, _sz]),
     "pgh_fedavg": (_i, [_vp, _i, _vp, _vp]),
     "pgh_fedavg_device": (_i, [_vp, _i, _vp, _vp, _vp]),
     "pgh_fedavg_device_range": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp]),

@@ -281,19 +281,29 @@ int pgh_set_layout(pgh_ctx* c, int n_tensors, const int64_t* numel) {
 int pgh_set_shard(pgh_ctx* c, int64_t lo, int64_t hi) {
     if (c && c->grp) return pgh_group_api::set_shard(c, lo, hi);
     if (!c) return PGH_E_ARG;
+    return pgh_detail::set_shard(c, lo, hi, false);
+}
+
+}  // extern "C"
+
+int pgh_detail::set_shard(pgh_ctx* c, int64_t lo, int64_t hi, bool keep_opt) {
     if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
     if (lo < 0 || hi > c->P || lo >= hi)
         return fail(c, PGH_E_ARG, "shard [%lld,%lld) outside [0,%lld)", (long long)lo, (long long)hi, (long long)c->P);
     DeviceGuard g(c->device);
     free_slab(c);
+    const int64_t pvec = std::max((hi - lo + 63) & ~(int64_t)63, (c->vec_min + 63) & ~(int64_t)63);
+    if (!(keep_opt && lo == c->lo && hi == c->hi && pvec == c->opt_pvec)) free_server_opt(c);
     c->lo = lo;
     c->hi = hi;
     c->pg = hi - lo;
-    c->pvec = std::max((c->pg + 63) & ~(int64_t)63, (c->vec_min + 63) & ~(int64_t)63);
+    c->pvec = pvec;
     if (c->pg != c->P) c->clip_c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
     c->st.p_shard = c->pg;
     return PGH_OK;
 }
+
+extern "C" {
 
 int pgh_reserve(pgh_ctx* c, int max_clients, int dtype, int n_parties) {
     if (c && c->grp) return pgh_group_api::reserve(c, max_clients, dtype, n_parties);
@@ -465,6 +475,7 @@ int set_copy_threads(pgh_ctx* c, int n) {
     c->pool_copy.reset(new CopyPool(n, c->local_cpus));
     return PGH_OK;
 }
+int set_shard_keep_opt(pgh_ctx* c, int64_t lo, int64_t hi) { return pgh_detail::set_shard(c, lo, hi, true); }
 int set_client_base(pgh_ctx* c, int64_t base) {
     c->client_base = base;
     return PGH_OK;

@@ -12,7 +12,8 @@
 //                   share sum; RESIDENT and STREAM entry points, the resident checkpoint
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order): slot_fold
 // A new averaging rule touches check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run,
-// slot_fold) reach the kernels through them alone.
+// slot_fold) reach the kernels through them alone.  The server optimizer (pgh_set_server_opt) hangs on
+// fold_launch too: a FINAL launch with one set is followed by K10 (server_opt_launch).
 // The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -245,6 +246,23 @@ struct pgh_ctx {
     DeviceBuf d_med;             // uint32 [pvec]
     DeviceBuf d_rowidx;          // int32 [slots]
 
+    // Server optimizer (pgh_set_server_opt).  With one set, fold_launch runs every
+    // fp32 FINAL against the -0 plane into the delta plane and K10 behind it, which reads the committed
+    // moments and writes the pending ones; pgh_server_opt_commit swaps the two.  All planes are
+    // float [pvec] and belong to the model: pgh_reset / pgh_reserve keep them (free_slab does not touch
+    // them), a new layout or shard drops them and the setting (free_server_opt).
+    int opt_kind = 0;  // pgh_server_opt; 0 = off
+    float opt_lr = 0.f, opt_beta1 = 0.f, opt_beta2 = 0.f, opt_tau = 0.f, opt_c1 = 0.f, opt_c2 = 0.f;
+    DeviceBuf d_opt_nz, d_opt_d;          // -0.0f everywhere; d = -g of the last FINAL
+    DeviceBuf d_opt_m, d_opt_v;           // committed
+    DeviceBuf d_opt_m2, d_opt_v2;         // pending: written by K10, committed by the swap
+    bool opt_pending = false;             // a FINAL has run since the last commit / upload / (re)initialisation
+    // the param ranges K10 has written into the pending planes since then: at the commit every param
+    // outside them keeps its committed moments (a FINAL over part of the shard)
+    std::vector<std::pair<int64_t, int64_t>> opt_cov;
+    int64_t opt_steps = 0;                // commits since the state was initialised
+    int64_t opt_pvec = 0;                 // the planes' length (pvec when they were allocated)
+
     bool streaming = false;
     int slot_mode = -1;  // pgh_fold_slots: averaging mode of the cycle being folded slot by slot
     int kind = 0;
@@ -448,6 +466,14 @@ inline int median_variant(const pgh_ctx* c, int64_t n) { return c->median_passes
 int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s);
 // slots[k] * parties for k < n, uploaded to d_rowidx on stream s (waits for the copy)
 int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s);
+
+// ---- server optimizer (pgh_reduce.cpp) -----------------------------------------------------------------
+void free_server_opt(pgh_ctx* c);  // planes and setting; the caller has waited for the context's work
+struct FinalArgs;
+int server_opt_launch(pgh_ctx* c, const FinalArgs& fa, hipStream_t s);  // K10 behind a FINAL launch (fold_launch)
+// pgh_set_shard, keep_opt: the optimizer's setting and state stay when neither the shard nor the length
+// of the [P_shard] vectors changes (a group's pgh_reserve lays its children's shards out again)
+int set_shard(pgh_ctx* c, int64_t lo, int64_t hi, bool keep_opt);
 
 // What a FINAL fold pass writes (fedavg: ckpt - avg; secagg: sum/dec) and over which param range.
 struct FinalArgs {

@@ -228,7 +228,7 @@ int64_t kid_lo(const pgh_group* g, int i) { return g->lo + (int64_t)i * g->S; }
 int64_t kid_hi(const pgh_group* g, int i) { return std::min(g->hi, g->lo + (int64_t)(i + 1) * g->S); }
 
 // Lay the children out: param shards (default) or, client-sharded, the whole range on every GPU.
-int apply_shards(pgh_ctx* c, bool client_shard) {
+int apply_shards(pgh_ctx* c, bool client_shard, bool keep_opt = false) {
     pgh_group* g = G(c);
     RC(plan_shards(c));
     if (client_shard) {
@@ -242,7 +242,8 @@ int apply_shards(pgh_ctx* c, bool client_shard) {
     return fan(c, [&](int i, pgh_ctx* k) -> int {
         RC(pgh_int::set_client_base(k, 0));
         RC(pgh_int::set_vec_min(k, g->S));  // all-gather: equal padded shards
-        return pgh_set_shard(k, kid_lo(g, i), kid_hi(g, i));
+        // (pgh_reserve: a child whose shard stays what it was keeps its server optimizer's state)
+        return keep_opt ? pgh_int::set_shard_keep_opt(k, kid_lo(g, i), kid_hi(g, i)) : pgh_set_shard(k, kid_lo(g, i), kid_hi(g, i));
     });
 }
 
@@ -610,7 +611,7 @@ int reserve(pgh_ctx* c, int max_clients, int dtype, int n_parties) {
     if (dtype != PGH_F32 && dtype != PGH_I64) return fail(c, PGH_E_ARG, "unknown dtype %d", dtype);
     const bool cs = g->want_client_shard && dtype == PGH_I64;
     g->max_clients = 0;
-    RC(apply_shards(c, cs));
+    RC(apply_shards(c, cs, true));
     const int n = (int)g->kids.size();
     g->client_shard = cs;
     g->per = cs ? (max_clients + n - 1) / n : max_clients;
@@ -723,6 +724,50 @@ int set_weights(pgh_ctx* c, const float* w, int n) {
 
 int set_trim(pgh_ctx* c, int b) {
     return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_trim(k, b); }, (int)G(c)->kids.size());
+}
+
+// The server optimizer looks at one parameter at a time: every child runs it on its own shard.
+int set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2, float tau) {
+    pgh_group* g = G(c);
+    if (kind == PGH_OPT_NONE)
+        return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_server_opt(k, kind, lr, beta1, beta2, tau); }, (int)g->kids.size());
+    RC(need_layout(c));
+    return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_server_opt(k, kind, lr, beta1, beta2, tau); });
+}
+
+int server_opt_commit(pgh_ctx* c) {
+    RC(need_layout(c));
+    return fan(c, [](int, pgh_ctx* k) -> int { return pgh_server_opt_commit(k); });
+}
+
+int server_opt_steps(pgh_ctx* c, int64_t* committed) {
+    RC(need_layout(c));
+    return pgh_server_opt_steps(G(c)->kids[0], committed);  // the children commit together
+}
+
+int server_opt_download(pgh_ctx* c, float* m, float* v) {
+    pgh_group* g = G(c);
+    RC(need_layout(c));
+    if (!m) return fail(c, PGH_E_ARG, "m is NULL");
+    return fan(c, [&](int i, pgh_ctx* k) -> int {
+        const int64_t off = kid_lo(g, i) - g->lo;
+        return pgh_server_opt_download(k, m + off, v ? v + off : nullptr);
+    });
+}
+
+int server_opt_upload(pgh_ctx* c, const float* m, const float* v, size_t nbytes) {
+    pgh_group* g = G(c);
+    RC(need_layout(c));
+    if (!m) return fail(c, PGH_E_ARG, "m is NULL");
+    const size_t whole = 4 * (size_t)g->P, range = 4 * (size_t)(g->hi - g->lo);
+    if (nbytes != whole && nbytes != range)
+        return fail(c, PGH_E_ARG, "optimizer state: got %zu bytes, layout needs %zu (model) or %zu (group range)", nbytes,
+                    whole, range);
+    if (nbytes == whole) return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_server_opt_upload(k, m, v, nbytes); });
+    return fan(c, [&](int i, pgh_ctx* k) -> int {
+        const int64_t off = kid_lo(g, i) - g->lo;
+        return pgh_server_opt_upload(k, m + off, v ? v + off : nullptr, 4 * (size_t)(kid_hi(g, i) - kid_lo(g, i)));
+    });
 }
 
 int fedavg(pgh_ctx* c, int mode, const float* ckpt, float* out) {

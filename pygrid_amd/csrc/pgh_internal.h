@@ -29,6 +29,9 @@ int fixed_point_divisor(pgh_ctx* c, int base, int prec, float* div);
 // [P_shard] device vectors at least n elements long from the next pgh_reserve on (collectives send
 // equal padded shards).
 int set_vec_min(pgh_ctx* c, int64_t n);
+// pgh_set_shard that keeps the server optimizer's setting and state when the shard and the vector length
+// stay what they were (a group's pgh_reserve lays the shards out again; the state outlives a reserve).
+int set_shard_keep_opt(pgh_ctx* c, int64_t lo, int64_t hi);
 // Host copy threads of the context's staging pool (a group splits the host between its GPUs).
 int set_copy_threads(pgh_ctx* c, int n);
 // Synthetic inputs of local client k are generated as global client base + k (client-sharded groups).
@@ -60,6 +63,11 @@ int set_synth_kind(pgh_ctx* c, int kind);
 int set_ingest_ranges(pgh_ctx* c, int on);
 int set_weights(pgh_ctx* c, const float* w, int n);
 int set_trim(pgh_ctx* c, int b);
+int set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2, float tau);
+int server_opt_commit(pgh_ctx* c);
+int server_opt_steps(pgh_ctx* c, int64_t* committed);
+int server_opt_download(pgh_ctx* c, float* m, float* v);
+int server_opt_upload(pgh_ctx* c, const float* m, const float* v, size_t nbytes);
 int fedavg(pgh_ctx* c, int mode, const float* ckpt, float* out);
 int ckpt_upload(pgh_ctx* c, const float* ckpt, size_t nbytes);
 int ckpt_upload_state(pgh_ctx* c, const uint8_t* pb, size_t n);

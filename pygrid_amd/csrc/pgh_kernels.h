@@ -185,6 +185,32 @@ struct SumsqArgs {
 };
 hipError_t launch_row_sumsq(const SumsqArgs& a, const RowTab* tab, hipStream_t s);
 
+// K10: the server optimizer's step behind a FINAL fold (the definition is in include/pgh_api.h).  The
+// fold ran with ckpt = a plane of -0.0f and out = d, so d = (-0.0f) - g, which is -g bit for bit for
+// every non-NaN g: x - y = x + (-y) in IEEE 754, so d = (-0) + (-g); a finite non-zero or infinite
+// -g added to a zero is itself, (-0) + (-0) = -0 = -(+0), and (-0) + (+0) = +0 = -(-0) when rounding
+// to nearest.  K10 takes g back by flipping d's sign bit (a NaN stays a NaN).  Elementwise over the
+// launch's p params: a lane owns one 16-byte column per grid step and issues the loads of d
+// (non-temporal: nobody reads it again), ckpt, m and v before any arithmetic; the last column of a
+// ragged p goes scalar.  It reads the committed m / v and writes out and the pending m2 / v2, never
+// in place.  KIND 1 (FedAvgM) touches neither v nor v2.  Workgroups of SERVER_OPT_WG_PARAMS params,
+// at most SERVER_OPT_MAX_WGS of them (grid-stride beyond).
+constexpr int SERVER_OPT_WG_PARAMS = 1024;
+constexpr int SERVER_OPT_MAX_WGS = 2048;
+struct ServerOptArgs {
+    const float* d;      // every pointer at the launch's column 0, 16-byte aligned
+    const float* ckpt;
+    float* out;
+    const float* m;
+    const float* v;      // kinds 2 .. 4
+    float* m2;
+    float* v2;           // kinds 2 .. 4
+    int64_t p;           // params of the launch
+    int kind;            // 1 momentum, 2 adagrad, 3 adam, 4 yogi (pgh_server_opt)
+    float lr, beta1, beta2, c1, c2, tau;
+};
+hipError_t launch_server_opt(const ServerOptArgs& a, hipStream_t s);
+
 constexpr uint64_t STREAM_DIFF = 0, STREAM_CKPT = 1, STREAM_SECRET = 2, STREAM_SHARE = 3;
 constexpr float DIFF_SCALE = 2.6429e-7f;
 constexpr float CKPT_SCALE = 1.32145e-6f;

@@ -14,6 +14,8 @@
 //       (build-owned: PGH_MEDIAN)
 // K7  k_row_sumsq              sumsq_c = sum_i (double)d_c[i]^2 along a client's row, in one fixed
 //       order (build-owned: the norms of PGH_CLIPPED_MEAN)
+// K10 k_server_opt             the server optimizer's step behind a FINAL fold: FedAvgM, FedAdagrad,
+//       FedAdam, FedYogi on g = the cycle's average (build-owned: pgh_set_server_opt)
 //
 // Design (DESIGN.md "Kernels"): every kernel is a single streaming pass over the slab held in
 // HBM, column-blocked (SlabMap in pgh_kernels.h: blocks of ld columns, each block all rows,
@@ -772,6 +774,66 @@ __global__ __launch_bounds__(BLOCK) void k_secagg_decode(const int64_t* sum, flo
         dec[i] = (float)sum[i] / divisor;
 }
 
+// K10 (pgh_kernels.h).  Every operation is one rounded f32 operation (-ffp-contract=off: no FMA); `/`
+// and __builtin_sqrtf are the correctly rounded ones under hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt (__fsqrt_rn is the native, approximate square root in
+// this toolchain unless OCML's rounded operations are switched on, so it is not used).
+template <int KIND>
+__device__ __forceinline__ void server_opt_step(const ServerOptArgs& a, float d, float ck, float m, float v, float& out,
+                                                float& m2, float& v2) {
+    const float g = __uint_as_float(__float_as_uint(d) ^ 0x80000000u);
+    if constexpr (KIND == 1) {
+        m2 = a.beta1 * m + g;
+        v2 = v;
+        out = ck - a.lr * m2;
+    } else {
+        m2 = a.beta1 * m + a.c1 * g;
+        const float q = g * g;
+        if constexpr (KIND == 2) {
+            v2 = v + q;
+        } else if constexpr (KIND == 3) {
+            v2 = a.beta2 * v + a.c2 * q;
+        } else {
+            const float sgn = v > q ? 1.0f : v < q ? -1.0f : 0.0f;
+            v2 = v - (a.c2 * q) * sgn;
+        }
+        out = ck - (a.lr * m2) / (__builtin_sqrtf(v2) + a.tau);
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(BLOCK) void k_server_opt(ServerOptArgs a) {
+    constexpr bool ADAPTIVE = KIND != 1;
+    const int64_t ncol = (a.p + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x; q < ncol; q += (int64_t)gridDim.x * BLOCK) {
+        const int64_t i = 4 * q;
+        f32x4 d, ck, m, v = {0.f, 0.f, 0.f, 0.f};
+        if (i + 4 <= a.p) {
+            d = ld4<true>(a.d + i);
+            ck = ld4<false>(a.ckpt + i);
+            m = ld4<false>(a.m + i);
+            if constexpr (ADAPTIVE) v = ld4<false>(a.v + i);
+        } else {
+            d = ld4_tail(a.d, q, a.p);
+            ck = ld4_tail(a.ckpt, q, a.p);
+            m = ld4_tail(a.m, q, a.p);
+            if constexpr (ADAPTIVE) v = ld4_tail(a.v, q, a.p);
+        }
+        f32x4 o, m2, v2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float oe, me, ve;
+            server_opt_step<KIND>(a, d[e], ck[e], m[e], v[e], oe, me, ve);
+            o[e] = oe;
+            m2[e] = me;
+            v2[e] = ve;
+        }
+        st4_tail(a.out, q, a.p, o);
+        st4_tail(a.m2, q, a.p, m2);
+        if constexpr (ADAPTIVE) st4_tail(a.v2, q, a.p, v2);
+    }
+}
+
 // KIND 0: one splitmix64 word per param -> Irwin-Hall(4 x u16).  KIND 1 ("fast", config 4's
 // on-device data source): one word per 4 consecutive params (global index g >> 2), param g takes
 // u16 number g & 3 of it, centred, times 2 * scale (same sigma ~ 1e-2): a quarter of the integer
@@ -1493,6 +1555,25 @@ hipError_t launch_secagg_decode(const int64_t* sum, float* dec, int64_t n, float
     int64_t g = (n + BLOCK - 1) / BLOCK;
     if (g > 8192) g = 8192;
     k_secagg_decode<<<(unsigned)g, BLOCK, 0, s>>>(sum, dec, n, divisor);
+    return hipGetLastError();
+}
+
+hipError_t launch_server_opt(const ServerOptArgs& a, hipStream_t s) {
+    static_assert(SERVER_OPT_WG_PARAMS == 4 * BLOCK, "one 16-byte column per lane");
+    const bool adaptive = a.kind != 1;
+    if (a.kind < 1 || a.kind > 4 || a.p <= 0 || !a.d || !a.ckpt || !a.out || !a.m || !a.m2 || (adaptive && (!a.v || !a.v2)))
+        return hipErrorInvalidValue;
+    for (const void* p : {(const void*)a.d, (const void*)a.ckpt, (const void*)a.out, (const void*)a.m, (const void*)a.v,
+                          (const void*)a.m2, (const void*)a.v2})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return hipErrorInvalidValue;
+    const int64_t ncol = (a.p + 3) >> 2;
+    const unsigned g = (unsigned)std::min<int64_t>((ncol + BLOCK - 1) / BLOCK, SERVER_OPT_MAX_WGS);
+    switch (a.kind) {
+    case 1: k_server_opt<1><<<g, BLOCK, 0, s>>>(a); break;
+    case 2: k_server_opt<2><<<g, BLOCK, 0, s>>>(a); break;
+    case 3: k_server_opt<3><<<g, BLOCK, 0, s>>>(a); break;
+    default: k_server_opt<4><<<g, BLOCK, 0, s>>>(a); break;
+    }
     return hipGetLastError();
 }
 

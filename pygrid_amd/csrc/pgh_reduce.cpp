@@ -81,11 +81,21 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     a.acc = c->d_acc.as<float>() + off;
     a.ckpt = fa.ckpt ? fa.ckpt + off : nullptr;
     a.out = fa.out ? fa.out + off : nullptr;
+    // A server optimizer: the FINAL launch, unchanged, subtracts the average from -0 into the delta
+    // plane, and K10 behind it on the same stream applies the step to the real ckpt / out.
+    const bool opt = c->opt_kind != PGH_OPT_NONE && (flags & pgh::FL_FINAL);
+    if (opt) {
+        a.ckpt = c->d_opt_nz.as<float>() + off;
+        a.out = c->d_opt_d.as<float>() + off;
+    }
     a.divisor = fa.divisor;
     a.flags = flags;
     a.mode = kernel_mode(mode);
     a.variant = c->variant;
-    if (mode == PGH_MEDIAN) return median_fold(c, a, rows.tab, rows.d_rows, s);  // (its own launches and bytes)
+    if (mode == PGH_MEDIAN) {  // (its own launches and bytes)
+        RC(median_fold(c, a, rows.tab, rows.d_rows, s));
+        return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+    }
     // HBM bytes: the rows; the running state in unless FIRST; the state out, or ckpt in and out when FINAL
     const uint64_t pg = (uint64_t)fa.len;
     uint64_t bytes = 4ull * (uint64_t)rows.n * pg + ((flags & pgh::FL_FIRST) ? 0 : 4 * pg) +
@@ -94,8 +104,33 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
         RC(trim_args(c, &a));
         bytes += trim_state_bytes(c, flags, pg);
     }
-    if (rows.tab) return timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg_rows(a, *rows.tab, s); });
-    return timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); });
+    if (rows.tab) RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg_rows(a, *rows.tab, s); }));
+    else RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
+    return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+}
+
+// K10 behind a FINAL fold of [fa.off, fa.off + fa.len) on stream s: d, the real ckpt and the committed
+// moments in; the real out and the pending moments out.  28 bytes per param (20 for FedAvgM, which has no v).
+int server_opt_launch(pgh_ctx* c, const FinalArgs& fa, hipStream_t s) {
+    if (!fa.ckpt || !fa.out) return fail(c, PGH_E_ARG, "a FINAL fold with a server optimizer needs ckpt and out");
+    const bool adaptive = c->opt_kind != PGH_OPT_MOMENTUM;
+    pgh::ServerOptArgs o{};
+    o.d = c->d_opt_d.as<float>() + fa.off;
+    o.ckpt = fa.ckpt + fa.off;
+    o.out = fa.out + fa.off;
+    o.m = c->d_opt_m.as<float>() + fa.off;
+    o.m2 = c->d_opt_m2.as<float>() + fa.off;
+    o.v = adaptive ? c->d_opt_v.as<float>() + fa.off : nullptr;
+    o.v2 = adaptive ? c->d_opt_v2.as<float>() + fa.off : nullptr;
+    o.p = fa.len;
+    o.kind = c->opt_kind;
+    o.lr = c->opt_lr; o.beta1 = c->opt_beta1; o.beta2 = c->opt_beta2;
+    o.c1 = c->opt_c1; o.c2 = c->opt_c2; o.tau = c->opt_tau;
+    RC(timed_launch(c, s, (adaptive ? 28ull : 20ull) * (uint64_t)fa.len, [&] { return pgh::launch_server_opt(o, s); }));
+    c->opt_pending = true;
+    const std::pair<int64_t, int64_t> r{fa.off, fa.off + fa.len};  // (a repeated FINAL lists its range once)
+    if (std::find(c->opt_cov.begin(), c->opt_cov.end(), r) == c->opt_cov.end()) c->opt_cov.push_back(r);
+    return PGH_OK;
 }
 
 // Fold slots holding clients [c0, c0 + n) (slot order may wrap) into the running state.
@@ -481,6 +516,180 @@ int pgh_set_trim(pgh_ctx* c, int b) {
         return fail(c, PGH_E_STATE, "trim count changed from %d to %d with %lld diffs of the cycle folded", c->trim_b, b,
                     (long long)c->folded);
     c->trim_b = b;
+    return PGH_OK;
+}
+
+// ---- server optimizers (K10): the setting, the moment planes, commit, download / upload ------------
+
+namespace pgh_detail {
+
+void free_server_opt(pgh_ctx* c) {
+    for (auto* v : {&c->d_opt_nz, &c->d_opt_d, &c->d_opt_m, &c->d_opt_v, &c->d_opt_m2, &c->d_opt_v2}) v->reset();
+    c->opt_kind = PGH_OPT_NONE;
+    c->opt_pending = false;
+    c->opt_cov.clear();
+    c->opt_steps = 0;
+    c->opt_pvec = 0;
+}
+
+namespace {
+// Every launch that reads or writes the planes has finished: the context's reduction stream and the
+// folds issued on callers' streams.
+int opt_quiesce(pgh_ctx* c) {
+    CK(c, hipStreamSynchronize(c->stream));
+    CK(c, hipStreamSynchronize(c->aux));
+    for (auto& fe : c->fold_evs) CK(c, hipEventSynchronize(fe.second));
+    return PGH_OK;
+}
+
+// m = +0, v = tau * tau in the committed planes; nothing pending, no step counted.
+int opt_init_state(pgh_ctx* c) {
+    const size_t n = (size_t)c->opt_pvec;
+    const float v0 = c->opt_tau * c->opt_tau;
+    uint32_t v0_bits;
+    std::memcpy(&v0_bits, &v0, 4);
+    // (the pending planes too: a first close that covers only part of the shard leaves the rest as it began)
+    for (auto* b : {&c->d_opt_m, &c->d_opt_m2}) CK(c, hipMemsetD32Async((hipDeviceptr_t)b->as<void>(), 0, n, c->stream));
+    for (auto* b : {&c->d_opt_v, &c->d_opt_v2})
+        if (*b) CK(c, hipMemsetD32Async((hipDeviceptr_t)b->as<void>(), (int)v0_bits, n, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    c->opt_pending = false;
+    c->opt_cov.clear();
+    c->opt_steps = 0;
+    return PGH_OK;
+}
+
+int check_opt_on(pgh_ctx* c, const char* what) {
+    if (c->opt_kind == PGH_OPT_NONE) return fail(c, PGH_E_STATE, "%s: no server optimizer is set", what);
+    return PGH_OK;
+}
+}  // namespace
+
+}  // namespace pgh_detail
+
+int pgh_set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2, float tau) {
+    if (!c) return PGH_E_ARG;
+    if (kind < PGH_OPT_NONE || kind > PGH_OPT_YOGI) return fail(c, PGH_E_ARG, "unknown server optimizer %d", kind);
+    if (kind != PGH_OPT_NONE) {
+        if (!std::isfinite(lr) || !(lr > 0.f)) return fail(c, PGH_E_ARG, "the server learning rate must be finite and > 0");
+        if (!(beta1 >= 0.f && beta1 < 1.f)) return fail(c, PGH_E_ARG, "beta1 must be in [0, 1)");
+        if (kind == PGH_OPT_MOMENTUM) {
+            beta2 = 0.f;  // (not used: ignored)
+            tau = 0.f;
+        } else {
+            if (kind == PGH_OPT_ADAGRAD) beta2 = 0.f;
+            else if (!(beta2 >= 0.f && beta2 < 1.f)) return fail(c, PGH_E_ARG, "beta2 must be in [0, 1)");
+            if (!std::isfinite(tau) || !(tau > 0.f)) return fail(c, PGH_E_ARG, "tau must be finite and > 0");
+        }
+    }
+    if (c->grp) return pgh_group_api::set_server_opt(c, kind, lr, beta1, beta2, tau);
+    if (kind == PGH_OPT_NONE) {
+        if (c->opt_kind == PGH_OPT_NONE) return PGH_OK;
+        DeviceGuard g(c->device);
+        RC(opt_quiesce(c));
+        free_server_opt(c);
+        return PGH_OK;
+    }
+    if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
+    if (kind == c->opt_kind && lr == c->opt_lr && beta1 == c->opt_beta1 && beta2 == c->opt_beta2 && tau == c->opt_tau)
+        return PGH_OK;  // the same again: the state stays
+    DeviceGuard g(c->device);
+    RC(opt_quiesce(c));
+    free_server_opt(c);
+    const size_t bytes = 4 * (size_t)c->pvec;
+    const bool adaptive = kind != PGH_OPT_MOMENTUM;
+    if (!c->d_opt_nz.reserve(bytes) || !c->d_opt_d.reserve(bytes) || !c->d_opt_m.reserve(bytes) || !c->d_opt_m2.reserve(bytes) ||
+        (adaptive && (!c->d_opt_v.reserve(bytes) || !c->d_opt_v2.reserve(bytes)))) {
+        free_server_opt(c);
+        return fail(c, PGH_E_OOM, "allocation of the server optimizer's planes (%zu bytes each) failed", bytes);
+    }
+    c->opt_pvec = c->pvec;
+    c->opt_lr = lr; c->opt_beta1 = beta1; c->opt_beta2 = beta2; c->opt_tau = tau;
+    c->opt_c1 = 1.0f - beta1;
+    c->opt_c2 = 1.0f - beta2;
+    const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)c->d_opt_nz.as<void>(), (int)0x80000000u, (size_t)c->pvec, c->stream);
+    const int rc = e == hipSuccess ? opt_init_state(c) : fail(c, PGH_E_HIP, "hipMemsetD32Async failed: %s", hipGetErrorString(e));
+    if (rc) {
+        free_server_opt(c);
+        return rc;
+    }
+    c->opt_kind = kind;
+    return PGH_OK;
+}
+
+int pgh_server_opt_commit(pgh_ctx* c) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return pgh_group_api::server_opt_commit(c);
+    RC(check_opt_on(c, "pgh_server_opt_commit"));
+    if (!c->opt_pending) return fail(c, PGH_E_STATE, "pgh_server_opt_commit: no FINAL fold has run since the last commit or upload");
+    // K10 wrote only the ranges its FINAL launches covered: a param outside them (a cycle closed with
+    // pgh_fedavg_device_range over part of the shard) keeps its committed moments, copied into the
+    // pending planes before the swap.  A close over the whole shard copies nothing.
+    std::sort(c->opt_cov.begin(), c->opt_cov.end());
+    DeviceGuard g(c->device);
+    bool copied = false;
+    const auto keep = [&](int64_t a, int64_t b) -> int {
+        if (a >= b) return PGH_OK;
+        const size_t n = 4 * (size_t)(b - a);
+        CK(c, hipMemcpyAsync(c->d_opt_m2.as<float>() + a, c->d_opt_m.as<float>() + a, n, hipMemcpyDeviceToDevice, c->stream));
+        if (c->d_opt_v) CK(c, hipMemcpyAsync(c->d_opt_v2.as<float>() + a, c->d_opt_v.as<float>() + a, n, hipMemcpyDeviceToDevice, c->stream));
+        copied = true;
+        return PGH_OK;
+    };
+    int64_t pos = 0;
+    for (const auto& r : c->opt_cov) {
+        RC(keep(pos, r.first));
+        pos = std::max(pos, r.second);
+    }
+    RC(keep(pos, c->pg));
+    if (copied) CK(c, hipStreamSynchronize(c->stream));  // (a later K10 may read them on a caller's stream)
+    // (a pointer swap: the next cycle's K10 writes the planes committed until now behind this cycle's
+    // on the same stream; folds on different caller streams are the caller's to order, as for d_acc)
+    std::swap(c->d_opt_m, c->d_opt_m2);
+    std::swap(c->d_opt_v, c->d_opt_v2);
+    c->opt_pending = false;
+    c->opt_cov.clear();
+    c->opt_steps += 1;
+    return PGH_OK;
+}
+
+int pgh_server_opt_steps(pgh_ctx* c, int64_t* committed) {
+    if (!c || !committed) return c ? fail(c, PGH_E_ARG, "committed is NULL") : PGH_E_ARG;
+    if (c->grp) return pgh_group_api::server_opt_steps(c, committed);
+    *committed = c->opt_steps;
+    return PGH_OK;
+}
+
+int pgh_server_opt_download(pgh_ctx* c, float* m, float* v) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return pgh_group_api::server_opt_download(c, m, v);
+    RC(check_opt_on(c, "pgh_server_opt_download"));
+    const bool adaptive = c->opt_kind != PGH_OPT_MOMENTUM;
+    if (!m || (adaptive && !v)) return fail(c, PGH_E_ARG, "m / v is NULL");
+    DeviceGuard g(c->device);
+    RC(opt_quiesce(c));
+    const size_t bytes = 4 * (size_t)c->pg;
+    CK(c, hipMemcpy(m, c->d_opt_m.as<float>(), bytes, hipMemcpyDeviceToHost));
+    if (adaptive) CK(c, hipMemcpy(v, c->d_opt_v.as<float>(), bytes, hipMemcpyDeviceToHost));
+    return PGH_OK;
+}
+
+int pgh_server_opt_upload(pgh_ctx* c, const float* m, const float* v, size_t nbytes) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return pgh_group_api::server_opt_upload(c, m, v, nbytes);
+    RC(check_opt_on(c, "pgh_server_opt_upload"));
+    const bool adaptive = c->opt_kind != PGH_OPT_MOMENTUM;
+    if (!m || (adaptive && !v)) return fail(c, PGH_E_ARG, "m / v is NULL");
+    const size_t whole = 4 * (size_t)c->P, shard = 4 * (size_t)c->pg;
+    if (nbytes != whole && nbytes != shard)
+        return fail(c, PGH_E_ARG, "optimizer state: got %zu bytes, layout needs %zu (model) or %zu (shard)", nbytes, whole, shard);
+    const size_t skip = nbytes == whole ? (size_t)c->lo : 0;
+    DeviceGuard g(c->device);
+    RC(opt_quiesce(c));
+    CK(c, hipMemcpy(c->d_opt_m.as<float>(), m + skip, shard, hipMemcpyHostToDevice));
+    if (adaptive) CK(c, hipMemcpy(c->d_opt_v.as<float>(), v + skip, shard, hipMemcpyHostToDevice));
+    c->opt_pending = false;
+    c->opt_cov.clear();
     return PGH_OK;
 }
 

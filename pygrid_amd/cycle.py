@@ -31,6 +31,8 @@ from .engine import ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
 from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, check_trim_count, clip_norm_of, failing_closed, median_of, \
     rule_kwargs, rule_of, set_on_engine, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
+from . import serveropt
+from .serveropt import ServerOptStates, server_opt_of
 
 
 def ready_to_average(server_config: dict, received_diffs: int, cycle_end=None, now=None) -> bool:
@@ -282,10 +284,12 @@ class CycleAggregator:
     each GPU's slice of every diff over its own PCIe link, bit-identical results)."""
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
-                 mean_plans: Optional[str] = None):
+                 mean_plans: Optional[str] = None, opt_states: Optional[ServerOptStates] = None):
         if engine is None:
             engine = Engine(devices=devices) if devices is not None else Engine(device)
         self.engine = engine
+        # server-optimizer moments per FL process (serveropt.py); share one between the users of an engine
+        self.opt_states = opt_states if opt_states is not None else ServerOptStates()
         self.mean_plans = mean_plan_policy(mean_plans)  # non-iterative hosted plans: "decline" | "probe"
         self._numel: tuple = ()
         self._cap = 0
@@ -298,6 +302,7 @@ class CycleAggregator:
         eng = self.engine
         numel = tuple(int(x) for x in numel)
         if numel != tuple(eng.numel) or numel != self._numel:  # (a new aggregator always lays out)
+            serveropt.evict(eng)  # a new layout drops the resident moments: their owner keeps a host copy
             eng.set_layout(numel)
             self._resident = None
         if n > eng.max_clients or dtype != eng.dtype or (dtype != F32 and parties != eng.parties):
@@ -312,22 +317,26 @@ class CycleAggregator:
     # ---- bytes in / bytes out: the replaceable slice cycle_manager.py:240-303 -------------------
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
-                           plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET) -> bytes:
+                           plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
         byte and only replaces the payloads (ids and tags survive).  ``plan_key``: the hosted
-        plan's serialized bytes, to probe it once per plan instead of once per cycle."""
+        plan's serialized bytes, to probe it once per plan instead of once per cycle.  ``opt_key``: the
+        FL process id under which ``server_config["server_optimizer"]``'s moments are kept (required
+        when the key is set); the step is committed once the new checkpoint bytes exist."""
         if framing not in ("fresh", "template"):
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         rule = rule_of(server_config, clip_norm, trim_count, median)
-        with failing_closed(rule, "the engine cannot average this cycle"):
+        opt = server_opt_of(server_config)
+        with serveropt.failing_closed_opt(opt), failing_closed(rule, "the engine cannot average this cycle"):
             return self._average_plan_diffs(server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key,
-                                            rule)
+                                            rule, opt, opt_key)
 
-    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, rule):
+    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, rule,
+                            opt=None, opt_key=None):
         mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                            shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), **rule_kwargs(rule))
         _check_diff_count(rule, len(diffs))
@@ -338,6 +347,7 @@ class CycleAggregator:
             raise
         self._prepare(numel, len(diffs))
         set_on_engine(self.engine, rule)  # before the first ingest: each diff's norm pass rides behind its copy
+        self.opt_states.bind(self.engine, opt_key, opt, sum(numel))  # before the fold: this process's moments
         if checkpoint is not self._resident or self.engine.ckpt_owner is not self:
             self.engine.ckpt_upload_state(checkpoint)  # else: the last cycle's output is still in HBM
         for i, d in enumerate(diffs):  # :247-250
@@ -355,6 +365,8 @@ class CycleAggregator:
         self.engine.fedavg_resident(mode)  # :252-296
         new = (state_codec.fresh_checkpoint(self.engine, checkpoint) if framing == "fresh"  # :303
                else self.engine.ckpt_patch_state(checkpoint))
+        if opt is not None:
+            self.opt_states.commit(self.engine)  # the new checkpoint's bytes exist: the step counts
         self.engine.ckpt_owner = self
         self.engine.ckpt_bytes = new  # the bytes whose params are resident (IncrementalCycle reuses them)
         self._resident = new
@@ -363,11 +375,12 @@ class CycleAggregator:
     # ---- tensor lists in / out (what the reference holds after unserialize) ---------------------
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
-                       weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET) -> List[np.ndarray]:
+                       weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         rule = rule_of(server_config, clip_norm, trim_count, median)
-        with failing_closed(rule, "the engine cannot average this cycle"):
+        opt = server_opt_of(server_config)
+        with serveropt.failing_closed_opt(opt), failing_closed(rule, "the engine cannot average this cycle"):
             shapes = [np.shape(p) for p in model_params]
             mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
                                n_clients=len(diffs), **rule_kwargs(rule))
@@ -375,6 +388,7 @@ class CycleAggregator:
             numel = [int(np.prod(s)) for s in shapes]
             self._prepare(numel, len(diffs))
             set_on_engine(self.engine, rule)
+            self.opt_states.bind(self.engine, opt_key, opt, sum(numel))
             for i, d in enumerate(diffs):
                 if len(d) != len(numel):
                     raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
@@ -384,6 +398,8 @@ class CycleAggregator:
             flat = np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in model_params])
             self._resident = None  # the host-buffer fold overwrites the resident checkpoint
             out = self.engine.fedavg(mode, flat)
+            if opt is not None:
+                self.opt_states.commit(self.engine)  # the new parameters are on the host: the step counts
             res, off = [], 0
             for s, n in zip(shapes, numel):
                 res.append(out[off:off + n].reshape(s))
@@ -446,12 +462,17 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
             reports = self._worker_cycles.query(cycle_id=cycle.id, is_completed=True)
             diffs = [r.diff for r in reports]  # what :247-250 reads, at the query
         rule = rule_of(server_config)  # a malformed setting fails the close
+        opt = server_opt_of(server_config)  # likewise
+        # (the key only beside an optimizer: aggregators with the earlier signature keep working without one)
+        opt_kw = {"opt_key": cycle.fl_process_id} if opt is not None else {}
         try:
-            with failing_closed(rule):
+            # a plan whose cached verdict is a decline raises from hosted_plan already: under an optimizer
+            # or a rule that must fail the close too, not reach the fall-back below
+            with serveropt.failing_closed_opt(opt), failing_closed(rule):
                 avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
                                                  getattr(aggregator, "mean_plans", None))
                 new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,
-                                                         plan_key=plan_key, framing=framing)
+                                                         plan_key=plan_key, framing=framing, **opt_kw)
         except PlanNotAcceleratedError as e:
             logging.info("engine declined (%s): running the reference averaging", e)
             return original(self, server_config, cycle)

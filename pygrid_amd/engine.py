@@ -21,6 +21,7 @@ MEDIAN_NCHIP = 1024  # PGH_MEDIAN_NCHIP: rows the on-chip median kernel takes
 STREAM_SECAGG = 16
 DEFAULT_VARIANT = -1  # PGH_DEFAULT_VARIANT: auto by shard size
 F32, I64 = 0, 1
+OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4  # pgh_server_opt
 MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
               CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean", MEDIAN: "median"}
 
@@ -117,6 +118,7 @@ class Engine:
                 raise EngineUnavailableError(f"pgh_create(device={device}) failed: {msg}")
         self._h = h
         self.devices = devs
+        self.is_group = _borrowed is None and devices is not None
         self.device = devs[0]
         self.numel: Tuple[int, ...] = ()
         self.P = 0
@@ -131,6 +133,10 @@ class Engine:
         # The bytes object the resident checkpoint was produced as (valid while ckpt_owner is set):
         # the next cycle, handed those very bytes, skips the upload.
         self.ckpt_bytes = None
+        # Whose server-optimizer moments are resident (serveropt.ServerOptStates: (states, key)); a new
+        # layout or shard drops them in the library, so it resets this too.
+        self.opt_owner = None
+        self.opt_kind = OPT_NONE
 
     # ---- plumbing ----------------------------------------------------------------------------
     def _check(self, rc: int, what: str):
@@ -203,14 +209,23 @@ class Engine:
         self.lo, self.hi = 0, self.P
         self.max_clients = 0  # the slab was freed
         self.ckpt_owner = None
+        self.opt_owner, self.opt_kind = None, OPT_NONE  # the library dropped the optimizer with the layout
 
     def set_shard(self, lo: int, hi: int):
         self._check(self._lib.pgh_set_shard(self._h, int(lo), int(hi)), "set_shard")
         self.lo, self.hi = int(lo), int(hi)
         self.max_clients = 0
         self.ckpt_owner = None
+        self.opt_owner, self.opt_kind = None, OPT_NONE
 
     def reserve(self, max_clients: int, dtype: int = F32, n_parties: int = 1):
+        if self.is_group and dtype != F32 and self.opt_kind != OPT_NONE:
+            # a group may lay an int64 slab out client-sharded, which re-shards its children and drops
+            # their server-optimizer moments: their owner gets a host copy first, and the optimizer is off
+            from . import serveropt
+
+            serveropt.evict(self)
+            self.set_server_opt(OPT_NONE)
         self._check(self._lib.pgh_reserve(self._h, int(max_clients), int(dtype), int(n_parties)), "reserve")
         self.dtype = dtype
         self.parties = 1 if dtype == F32 else int(n_parties)
@@ -300,6 +315,44 @@ class Engine:
         """Values dropped per side and parameter by later TRIMMED_MEAN folds (1 .. TRIM_MAX); 0 turns
         trimming off.  Refused (PGH_E_STATE) while slot folds of a cycle are under way."""
         self._check(self._lib.pgh_set_trim(self._h, int(b)), "set_trim")
+
+    # ---- server optimizers (FedAvgM, FedAdagrad, FedAdam, FedYogi) ---------------------------------
+    def set_server_opt(self, kind: int, lr: float = 0.0, beta1: float = 0.0, beta2: float = 0.0, tau: float = 0.0):
+        """How later fp32 closes apply the average (``pgh_set_server_opt``): OPT_MOMENTUM .. OPT_YOGI,
+        or OPT_NONE for the plain ``ckpt - avg``.  The same kind and values again keep the moment state
+        in HBM; any change initialises it (m = 0, v = tau^2)."""
+        self._check(self._lib.pgh_set_server_opt(self._h, int(kind), C.c_float(float(lr)), C.c_float(float(beta1)),
+                                                 C.c_float(float(beta2)), C.c_float(float(tau))), "set_server_opt")
+        self.opt_kind = int(kind)
+        if self.opt_kind == OPT_NONE:
+            self.opt_owner = None
+
+    def server_opt_commit(self):
+        """Make the moments the last close wrote the committed ones: once per close, when its result
+        is safe.  Until then a repeated close gives the same bits."""
+        self._check(self._lib.pgh_server_opt_commit(self._h), "server_opt_commit")
+
+    def server_opt_steps(self) -> int:
+        n = C.c_int64(0)
+        self._check(self._lib.pgh_server_opt_steps(self._h, C.byref(n)), "server_opt_steps")
+        return n.value
+
+    def server_opt_state(self) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """The committed moments of this shard, ``(m, v)``; ``v`` is None for OPT_MOMENTUM."""
+        m = np.empty(self.p_shard, dtype=np.float32)
+        v = np.empty(self.p_shard, dtype=np.float32) if self.opt_kind != OPT_MOMENTUM else None
+        self._check(self._lib.pgh_server_opt_download(self._h, _ptr(m), _ptr(v) if v is not None else None),
+                    "server_opt_download")
+        return m, v
+
+    def load_server_opt_state(self, m: np.ndarray, v: Optional[np.ndarray] = None):
+        """Replace the committed moments (each the whole model or this shard); drops a pending step."""
+        a = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+        b = np.ascontiguousarray(v, dtype=np.float32).reshape(-1) if v is not None else None
+        if b is not None and b.size != a.size:
+            raise AggregationError(f"optimizer state: m has {a.size} params, v has {b.size}")
+        self._check(self._lib.pgh_server_opt_upload(self._h, _ptr(a), _ptr(b) if b is not None else None, a.nbytes),
+                    "server_opt_upload")
 
     # ---- reduction -----------------------------------------------------------------------------
     def fedavg(self, mode: int, ckpt: np.ndarray) -> np.ndarray:

@@ -60,6 +60,14 @@ class MedianUnavailableError(AggregationError):
     no median, so the close fails closed."""
 
 
+class ServerOptUnavailableError(AggregationError):
+    """The FL process asks for a server optimizer (``server_config["server_optimizer"]``) and the
+    engine cannot apply it this cycle: it declines the cycle (an unaccelerated plan, a non-float32
+    model), it lacks ``set_server_opt``, or it answers PGH_E_UNSUPPORTED.  Like the robust rules'
+    errors it is NOT a ``PlanNotAcceleratedError``: the node's own averaging applies no optimizer, so
+    the close fails closed."""
+
+
 class ModelNotAcceleratedError(PlanNotAcceleratedError):
     """The checkpoint or a diff holds well-formed tensors that are not float32 (another dtype, or a
     serializer other than syft's "all").  The reference averages them with torch's type promotion;

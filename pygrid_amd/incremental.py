@@ -68,6 +68,7 @@ from . import state as state_codec
 from .cycle import _decline_non_float32
 from .engine import F32, MEAN, WEIGHTED_MEAN, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
+from . import serveropt
 from .robust import check_trim_count, failing_closed, rule_of, set_on_engine
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
@@ -84,8 +85,13 @@ class IncrementalCycle:
     def __init__(self, engine: Engine, numel, mode: int = MEAN, slots: Optional[int] = None, fold_batch: int = 8,
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
-                 median: bool = False):
-        """``median``: the FL process asks for the coordinate-wise median (``cycle.median_of``).  ``mode``
+                 median: bool = False, server_opt=None, opt_key=None, opt_states=None):
+        """``server_opt``: the FL process's server optimizer (``serveropt.server_opt_of``), its moments
+        kept under ``opt_key`` (the FL process id) in ``opt_states`` (share the close-time aggregator's).
+        Early folds do not involve it; the close binds the process's moments before its FINAL pass and
+        commits the step once the new checkpoint bytes exist.
+
+        ``median``: the FL process asks for the coordinate-wise median (``cycle.median_of``).  ``mode``
         must then be MEAN, without weights, ``clip_norm`` or ``trim_count``.  A median needs every row
         at once, so nothing is folded early whatever ``early_fold`` says: reports still go to HBM
         slots as they arrive (every slot may be taken: there is no fold front to keep one for), and
@@ -113,6 +119,10 @@ class IncrementalCycle:
         if rule is not None:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
         self._fold_mode = rule.mode if rule else mode
+        self._opt, self._opt_key = server_opt, opt_key
+        self._opt_states = opt_states if opt_states is not None else serveropt.ServerOptStates()
+        if server_opt is not None and opt_key is None:
+            raise AggregationError(f"{serveropt.OPT_KEY} is set but the cycle has no opt_key to keep its state under")
         self._numel = tuple(int(n) for n in numel)
         P = sum(self._numel)
         self.slots = int(slots) if slots else default_slots(P)
@@ -150,6 +160,7 @@ class IncrementalCycle:
         # keep the engine's slab when a cycle of the same model follows (no re-allocation)
         if tuple(getattr(engine, "numel", ())) != self._numel or getattr(engine, "max_clients", 0) != self.slots \
                 or getattr(engine, "dtype", None) != F32:
+            serveropt.evict(engine)  # a new layout drops the resident moments: their owner keeps a host copy
             engine.set_layout(list(self._numel))
             engine.reserve(self.slots)
         else:
@@ -465,6 +476,8 @@ class IncrementalCycle:
                 self._prep_thread = None
             prep = self._prepared[1] if self._prepared and self._prepared[0] is checkpoint else None
             self._prepared = None
+            # before the FINAL pass: this process's moments (another process may have closed on the engine since)
+            self._opt_states.bind(self.engine, self._opt_key, self._opt, sum(self._numel))
             stats = self._fold_in_order(rest, fetch)
             del stats["db_rows"]
             stats.update(refold=bool(refold), reason=refold or None, early=k, n=len(order),
@@ -478,6 +491,8 @@ class IncrementalCycle:
             self.last_close = stats
             new = (state_codec.fresh_checkpoint(self.engine, checkpoint, prepared=prep) if framing == "fresh"
                    else self.engine.ckpt_patch_state(checkpoint))
+            if self._opt is not None:
+                self._opt_states.commit(self.engine)  # the new checkpoint's bytes exist: the step counts
             self.engine.ckpt_owner = self
             self.engine.ckpt_bytes = new
             return new

@@ -75,8 +75,10 @@ from .checkpoints import Checkpoint, CheckpointStore
 from .cycle import CycleAggregator, _decline_non_float32, finish_cycle, hosted_plan, make_average_plan_diffs, \
     select_mode
 from .engine import MEAN
-from .exceptions import AggregationError, PlanNotAcceleratedError, PyGridError, StateParseError
+from .exceptions import AggregationError, PlanNotAcceleratedError, PyGridError, ServerOptUnavailableError, \
+    StateParseError
 from .incremental import IncrementalCycle
+from .serveropt import OPT_KEY, server_opt_of
 from .robust import failing_closed, rule_kwargs, rule_of
 from .trigger import CycleCloseTrigger
 
@@ -322,6 +324,14 @@ class NodeEngine:
         with failing_closed(rule):
             return self._new_cycle_for(cm, cycle, server_config, rule, fresh)
 
+    def _opt_kwargs(self, server_config, cycle) -> dict:
+        """The FL process's server optimizer for its report-time cycle: the setting, the key its moments
+        are kept under and the states shared with the close-time path (nothing when none is set)."""
+        opt = server_opt_of(server_config)
+        if opt is None:
+            return {}
+        return {"server_opt": opt, "opt_key": cycle.fl_process_id, "opt_states": self.aggregator.opt_states}
+
     def _new_cycle_for(self, cm, cycle, server_config, rule, fresh: bool) -> IncrementalCycle:
         avg_plan, plan_key = hosted_plan(server_config, cycle, self.process_manager, self.plan_manager,
                                          self.aggregator.mean_plans)
@@ -337,7 +347,8 @@ class NodeEngine:
                            shapes=lambda: _shapes(ckpt), **rule_kwargs(rule))
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
         inc = IncrementalCycle(self.engine, numel, mode=MEAN if rule else mode, slots=self.slots,
-                               fold_batch=self.fold_batch, checkpoint=ckpt, **rule_kwargs(rule))
+                               fold_batch=self.fold_batch, checkpoint=ckpt, **rule_kwargs(rule),
+                               **self._opt_kwargs(server_config, cycle))
         if not fresh:  # after a restart: the rows assigned before it (a cycle just created has none;
             # an assignment that lands while this state is built is recorded from _pending_assign)
             for row in _rows(cm, cycle_id=cycle.id):
@@ -416,6 +427,8 @@ class NodeEngine:
         """The close (executor thread).  Holds the engine lock throughout, the report gate only for
         the snapshot of the completed rows (see the module docstring)."""
         rule = rule_of(server_config)  # a malformed setting, or two rules at once, fails the close
+        if server_opt_of(server_config) is not None:  # (a malformed setting fails the close)
+            original = _refuse_opt(cycle.id)  # fail closed: the node's own averaging applies no optimizer
         if rule is not None:
             original = _refuse(rule, cycle.id)  # fail closed: the node's own averaging does not apply the rule
         with self._engine_for_close():
@@ -530,6 +543,14 @@ class NodeEngine:
         for k in self._assigned_keys.pop(cycle_id, ()):
             if self._assigned.get(k, (None, None))[1] == cycle_id:
                 del self._assigned[k]
+
+
+def _refuse_opt(cycle_id):
+    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for a server optimizer."""
+    def original(*_a, **_k):
+        raise ServerOptUnavailableError(f"{OPT_KEY} is set and the engine does not average cycle {cycle_id}; not "
+                                        "falling back to the node's own averaging, which applies no optimizer")
+    return original
 
 
 def _refuse(rule, cycle_id):
