@@ -92,10 +92,10 @@ static void sync_work(pgh_ctx* c) {
 
 void free_slab(pgh_ctx* c) {
     sync_work(c);
-    for (auto* v : {&c->d_slab, &c->d_ckpt, &c->d_out, &c->d_acc, &c->d_uacc, &c->d_sum, &c->d_dec, &c->d_w, &c->d_trim, &c->d_med, &c->d_rowidx}) v->reset();
+    for (auto* v : {&c->d_slab, &c->d_ckpt, &c->d_out, &c->d_acc, &c->d_uacc, &c->d_sum, &c->d_dec, &c->d_w}) v->reset();
     c->ckpt_valid = false;
     clear_final_marks(c);
-    free_clip(c);
+    rules_slab_freed(c);
     c->slots = 0;
     c->slot_mode = -1;
     c->slot_client.clear();
@@ -126,6 +126,14 @@ int check_ckpt(pgh_ctx* c, const char* what) {
     if (!c->ckpt_valid)
         return fail(c, PGH_E_STATE, "%s: no checkpoint in HBM (pgh_ckpt_upload* since the last pgh_reserve / layout "
                     "change)", what);
+    return PGH_OK;
+}
+
+int shard_start(pgh_ctx* c, const char* what, size_t nbytes, size_t unit, size_t* first) {
+    const size_t whole = (size_t)c->P * unit, shard = (size_t)c->pg * unit;
+    if (nbytes != whole && nbytes != shard)
+        return fail(c, PGH_E_ARG, "%s: got %zu bytes, layout needs %zu (model) or %zu (shard)", what, nbytes, whole, shard);
+    *first = nbytes == whole ? (size_t)c->lo : 0;  // the whole model: take the slice
     return PGH_OK;
 }
 
@@ -187,16 +195,15 @@ int pgh_create(int device, size_t pinned_bytes, pgh_ctx** out) {
     c->pool_copy.reset(new CopyPool(c->copy_threads, c->local_cpus));
     if (const char* e = std::getenv("PGH_PINNED_GATHER")) c->pinned_gather = std::atoi(e) != 0;
     if (const char* e = std::getenv("PGH_BLOCK_BYTES")) c->block_bytes = (size_t)std::max(0LL, std::atoll(e));
-    if (const char* e = std::getenv("PGH_TRIM_VEC")) c->trim_vec = std::atoi(e) == 4 ? 4 : std::atoi(e) == 1 ? 1 : 0;
-    if (const char* e = std::getenv("PGH_MEDIAN_PATH")) c->median_passes = std::strcmp(e, "passes") == 0;
     if (const char* e = std::getenv("PGH_FINAL_RANGES")) c->final_split = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("PGH_D2H_STREAM")) c->d2h_mode = std::max(0, std::min(1, std::atoi(e)));
     c->own_d2h = c->d2h_mode > 0;
     bool ok = c->stream.make() == hipSuccess && c->copy.make() == hipSuccess && c->aux.make() == hipSuccess &&
               (!c->own_d2h || c->d2h.make() == hipSuccess);  // (dec, a fifth stream, only on first use)
-    for (pgh_ctx::Event* ev : {&c->copy_done, &c->xsync, &c->aux_ev, &c->pin_ev[0], &c->pin_ev[1], &c->sq_ev, &c->gtab_ev,
+    for (pgh_ctx::Event* ev : {&c->copy_done, &c->xsync, &c->aux_ev, &c->pin_ev[0], &c->pin_ev[1], &c->gtab_ev,
                                &c->gdma_ev, &c->vtab_ev, &c->dec_in, &c->vbuf[0].done, &c->vbuf[1].done})
         ok = ok && ev->make() == hipSuccess;
+    ok = ok && rules_made(c);
     if (!ok) { pgh_destroy(c); return fail(nullptr, PGH_E_HIP, "stream/event creation failed"); }
     {
         // the pinned ring on the GPU's socket: allocated by a thread bound there, pages placed by
@@ -293,12 +300,11 @@ int pgh_detail::set_shard(pgh_ctx* c, int64_t lo, int64_t hi, bool keep_opt) {
     DeviceGuard g(c->device);
     free_slab(c);
     const int64_t pvec = std::max((hi - lo + 63) & ~(int64_t)63, (c->vec_min + 63) & ~(int64_t)63);
-    if (!(keep_opt && lo == c->lo && hi == c->hi && pvec == c->opt_pvec)) free_server_opt(c);
+    rules_shard_set(c, lo, hi, pvec, keep_opt);
     c->lo = lo;
     c->hi = hi;
     c->pg = hi - lo;
     c->pvec = pvec;
-    if (c->pg != c->P) c->clip_c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
     c->st.p_shard = c->pg;
     return PGH_OK;
 }
@@ -337,8 +343,7 @@ int pgh_reserve(pgh_ctx* c, int max_clients, int dtype, int n_parties) {
     c->parties = n_parties;
     c->slot_client.assign((size_t)max_clients, -1);
     c->slot_read_seq.assign((size_t)max_clients, 0);
-    c->sq_state.assign((size_t)max_clients, (uint8_t)pgh_ctx::SQ_NONE);
-    c->sq_host.assign((size_t)max_clients, 0.0);
+    rules_reserved(c, max_clients);
     c->weights.clear();
     c->weights_on_device = false;
     c->st.max_clients = max_clients;
@@ -358,7 +363,7 @@ int pgh_reset(pgh_ctx* c) {
     clear_marks(c);
     release_slot_fold_events(c);  // c->stream is idle (synchronised above)
     std::fill(c->slot_client.begin(), c->slot_client.end(), -1);
-    sumsq_forget(c);
+    rules_reset(c);
     c->weights.clear();
     c->weights_on_device = false;
     c->streaming = false;
@@ -383,8 +388,7 @@ int pgh_effective_variant(pgh_ctx* c, int mode) {
     if (c && c->grp) return pgh_group_api::effective_variant(c, mode);
     if (!c) return PGH_E_ARG;
     if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
-    if (mode == PGH_TRIMMED_MEAN)  // K8's two column widths, whatever pgh_set_variant says
-        return (c->trim_vec ? c->trim_vec : pgh::auto_trim_vec(c->pg, c->trim_b)) == 4 ? 40 : 41;
+    if (mode == PGH_TRIMMED_MEAN) return trim_variant(c);  // K8's two column widths, whatever pgh_set_variant says
     if (mode == PGH_MEDIAN) {  // K9 or K9p by the diffs held now, whatever pgh_set_variant says
         int64_t n = 0;
         for (int64_t k : c->slot_client) n += k >= 0 ? 1 : 0;

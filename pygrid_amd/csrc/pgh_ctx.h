@@ -7,13 +7,19 @@
 //   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks
 //   pgh_order.cpp   which stream waits for what, and the timing events
 //   pgh_ingest.cpp  host bytes -> HBM slab rows (raw, State messages, int64 shares, synthetic)
-//   pgh_reduce.cpp  what a mode may do (check_mode_use), the one fp32 fold launch (fold_prepare, fold_launch) and
-//                   what the rules add to it (clipping, trimming, the median); fold_run's ring walk and the
-//                   share sum; RESIDENT and STREAM entry points, the resident checkpoint
+//   pgh_reduce.cpp  the one fp32 fold launch (fold_prepare, fold_launch); fold_run's ring walk and the share
+//                   sum; the divisors; RESIDENT and STREAM entry points, the resident checkpoint
+//   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: clipping (K7's sums,
+//                   the scales, the tallies), trimming (K8's planes), the median (K9, K9p); the rules' lifecycle
+//                   calls (rules_*) and entry points.  Their state: pgh_rules.h
+//   pgh_serveropt.cpp  the server optimizer: K10 behind a FINAL launch, its planes, commit, download, upload
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order): slot_fold
-// A new averaging rule touches check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run,
-// slot_fold) reach the kernels through them alone.  The server optimizer (pgh_set_server_opt) hangs on
-// fold_launch too: a FINAL launch with one set is followed by K10 (server_opt_launch).
+// A new averaging rule adds its state struct to pgh_rules.h (a member of pgh_ctx), its lines to the lifecycle
+// functions rules_* in pgh_rules.cpp -- the one call each event of the context makes: made, slab freed, shard
+// set, reserved, reset, slot written, weights replaced, folds restarted, cycle finished -- and touches
+// check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run, slot_fold) reach the kernels
+// through the last two alone.  The server optimizer (pgh_set_server_opt) hangs on fold_launch too: a FINAL
+// launch with one set is followed by K10 (server_opt_launch).
 // The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,6 +45,7 @@
 #include "pgh_internal.h"
 #include "pgh_kernels.h"
 #include "pgh_res.h"
+#include "pgh_rules.h"
 #include "pgh_state.h"
 
 namespace pgh_detail {
@@ -210,58 +217,12 @@ struct pgh_ctx {
     std::vector<float> weights;
     bool weights_on_device = false;
 
-    // Clipped FedAvg (pgh_set_clip_norm, PGH_CLIPPED_MEAN).  K7 (k_row_sumsq)
-    // runs on the copy stream -- behind the row's ingest, ahead of any later overwrite of the slot --
-    // and its sum comes back through h_sq in a small D2H on the same stream, followed by sq_ev.
-    // sq_state: NONE (no sum of the slot's present diff), QUEUED (K7 + D2H issued, value lands in
-    // h_sq before the latest sq_ev), VALID (sq_host holds it).  Any ingest into a slot resets it.
-    enum : uint8_t { SQ_NONE = 0, SQ_QUEUED = 1, SQ_VALID = 2 };
-    float clip_c = 0.f;               // the L2 bound; 0 = clipping off
-    std::vector<uint8_t> sq_state;    // per slot
-    std::vector<double> sq_host;      // per slot: the cached sum of squares
-    std::vector<int32_t> sq_queued;   // slots that went QUEUED since the last harvest
-    DeviceBuf d_sq_part;              // double [slots][ceil(pg / SUMSQ_TILE)] tile partials
-    DeviceBuf d_sq;                   // double [slots]
-    PinnedBuf h_sq;                   // double [slots]
-    Event sq_ev;
-    // the scales live in `weights` (fold order) and go to the device like weights.  Resident folds:
-    // clip_scales_valid says weights[0, n) are the scales of the slab as it is (range folds reuse them).
-    bool clip_scales_valid = false;
-    std::vector<double> clip_norms;   // slot folds of the running cycle, in fold order (beside weights)
-    int64_t clip_rows = 0, clip_clipped = 0;  // folds finished since pgh_reset / pgh_reserve
-    double clip_max_norm = 0.0;
-
-    // Trimmed-mean FedAvg (pgh_set_trim, PGH_TRIMMED_MEAN).  A fold that is a
-    // whole cycle in one launch keeps K8's selection state in registers; any other keeps it in HBM
-    // between launches: 2 trim_b planes of pvec int32 keys here (lo, then hi) and the running sum in
-    // d_acc -- (2b + 1) x 4 x pvec bytes, allocated by the first launch that needs them.
-    int trim_b = 0;    // values dropped per side; 0 = trimming off
-    int trim_vec = 0;  // PGH_TRIM_VEC: 4 or 1 forces K8's column width, 0 = by shard size
-    DeviceBuf d_trim;
-
-    // Median FedAvg (PGH_MEDIAN).  K9 keeps everything on chip; K9p keeps the
-    // bisection's prefix in a plane of pvec words between its launches, and a slot list longer than
-    // a RowTab goes to the kernels as a device table: both allocated by the first fold that needs them.
-    bool median_passes = false;  // PGH_MEDIAN_PATH=passes: K9p whatever the row count
-    DeviceBuf d_med;             // uint32 [pvec]
-    DeviceBuf d_rowidx;          // int32 [slots]
-
-    // Server optimizer (pgh_set_server_opt).  With one set, fold_launch runs every
-    // fp32 FINAL against the -0 plane into the delta plane and K10 behind it, which reads the committed
-    // moments and writes the pending ones; pgh_server_opt_commit swaps the two.  All planes are
-    // float [pvec] and belong to the model: pgh_reset / pgh_reserve keep them (free_slab does not touch
-    // them), a new layout or shard drops them and the setting (free_server_opt).
-    int opt_kind = 0;  // pgh_server_opt; 0 = off
-    float opt_lr = 0.f, opt_beta1 = 0.f, opt_beta2 = 0.f, opt_tau = 0.f, opt_c1 = 0.f, opt_c2 = 0.f;
-    DeviceBuf d_opt_nz, d_opt_d;          // -0.0f everywhere; d = -g of the last FINAL
-    DeviceBuf d_opt_m, d_opt_v;           // committed
-    DeviceBuf d_opt_m2, d_opt_v2;         // pending: written by K10, committed by the swap
-    bool opt_pending = false;             // a FINAL has run since the last commit / upload / (re)initialisation
-    // the param ranges K10 has written into the pending planes since then: at the commit every param
-    // outside them keeps its committed moments (a FINAL over part of the shard)
-    std::vector<std::pair<int64_t, int64_t>> opt_cov;
-    int64_t opt_steps = 0;                // commits since the state was initialised
-    int64_t opt_pvec = 0;                 // the planes' length (pvec when they were allocated)
+    // What the averaging rules and the server optimizer keep (pgh_rules.h): touched only by their own code
+    // (pgh_rules.cpp, pgh_serveropt.cpp), by fold_launch and fedavg_divisor, and through rules_* below.
+    pgh_detail::ClipState clip;
+    pgh_detail::TrimState trim;
+    pgh_detail::MedianState med;
+    pgh_detail::ServerOptState opt;
 
     bool streaming = false;
     int slot_mode = -1;  // pgh_fold_slots: averaging mode of the cycle being folded slot by slot
@@ -313,7 +274,7 @@ double now_ms();
 
 // ---- state checks and slab geometry -------------------------------------------------------------
 inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
-inline bool valid_mode(int m) {
+inline bool valid_mode(int m) {  // (pgh_effective_variant's alone: check_mode_use has its own switch)
     return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN ||
            m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN;
 }
@@ -330,6 +291,9 @@ int check_mode_use(pgh_ctx* c, int mode, ModeUse use);
 int check_ready(pgh_ctx* c);
 int check_dtype(pgh_ctx* c, int dtype);
 int check_ckpt(pgh_ctx* c, const char* what);
+// A host vector of nbytes given as the whole model or as this shard alone, `unit` bytes per param: *first =
+// the param of it at which this shard's part starts.  Any other length: PGH_E_ARG, `what` leading the message.
+int shard_start(pgh_ctx* c, const char* what, size_t nbytes, size_t unit, size_t* first);
 void free_slab(pgh_ctx* c);
 
 // Slab geometry for kernels (off = 0) and the start of a slot's first row inside block 0.
@@ -432,12 +396,27 @@ int64_t range_edge(const pgh_ctx* c, int k, int K);
 int fixed_point_divisor(pgh_ctx* c, int base, int prec, float* div);
 int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div);
 
-// ---- clipped FedAvg (pgh_reduce.cpp) ---------------------------------------------------------------
-inline bool clip_on(const pgh_ctx* c) { return c->clip_c > 0.f && c->dtype == PGH_F32 && !c->streaming; }
+// ---- the rules at the context's lifecycle events (pgh_rules.cpp): the one call each event's site makes ----
+bool rules_made(pgh_ctx* c);         // pgh_create: PGH_TRIM_VEC, PGH_MEDIAN_PATH, the rules' events; false fails it
+void rules_slab_freed(pgh_ctx* c);   // free_slab: every buffer and cache sized by the slab or the shard goes
+// set_shard, before the context takes [lo, hi) and pvec.  keep_opt: the optimizer's setting and state stay when
+// neither the shard nor the length of the [P_shard] vectors changes; a sub-range shard clears the clipping bound
+void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep_opt);
+void rules_reserved(pgh_ctx* c, int slots);  // pgh_reserve: the per-slot caches at their new length
+void rules_reset(pgh_ctx* c);                // pgh_reset: the cycle's sums, scales, tallies
+// The diffs of slots [slot, slot + n) are about to be replaced (claim_slot, the synthetic fill).  The fill's
+// runs begin with a claim_slot on a RESIDENT slab, and a STREAM slab never has valid resident scales
+// (pgh_stream_begin resets; only a resident clipped fold sets them), so clearing them here for every slot of
+// a run changes nothing a caller can see.
+void rules_slot_written(pgh_ctx* c, int slot, int n = 1);
+void rules_weights_replaced(pgh_ctx* c);        // pgh_set_weights: they are no longer the slab's scales
+void rules_folds_restarted(pgh_ctx* c);         // pgh_fold_slots_restart (the caller clears the weights)
+void rules_clipped_cycle_finished(pgh_ctx* c);  // a clipped slot close: the cycle's rows join the finished totals
+
+// ---- clipped FedAvg (pgh_rules.cpp) ----------------------------------------------------------------
+inline bool clip_on(const pgh_ctx* c) { return c->clip.c > 0.f && c->dtype == PGH_F32 && !c->streaming; }
 // scale = norm <= C ? 1 : (float)(C / norm), norm = sqrt(sumsq) in f64 (IEEE: NaN -> NaN, inf -> 0)
 float clip_scale_of(double sumsq, float c);
-void sumsq_forget(pgh_ctx* c);             // every slot back to SQ_NONE (pgh_reset / pgh_reserve)
-void free_clip(pgh_ctx* c);                // the device / pinned buffers (free_slab)
 // K7 on the copy stream for those of `slots` that have no sum yet, and the D2H of the sums
 int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n);
 int sumsq_wait(pgh_ctx* c);                // the queued sums are in sq_host afterwards
@@ -445,34 +424,38 @@ int sumsq_after_ingest(pgh_ctx* c, int slot);  // clipping on: queue the row's K
 // weights[c0 + k] = the scale of slots[k] (waits for the sums); norms (nullable) receives sqrt(sumsq)
 int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms);
 int resident_clip_scales(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n)
-void clip_count(pgh_ctx* c, const float* scales, const double* norms, int64_t n);  // into the finished totals
+// a slot fold of a clipped cycle: the scales and norms of slots[0, n) at fold index c0 (0 begins the cycle)
+int clip_slot_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0);
 
-// ---- trimmed-mean FedAvg (pgh_reduce.cpp) -----------------------------------------------------------
+// ---- trimmed-mean FedAvg (pgh_rules.cpp) ------------------------------------------------------------
 // K8's arguments on top of a filled FedavgArgs (map.off = the launch's first shard param): the mode,
 // b, the column width and -- unless the launch is FIRST and FINAL -- the state planes, allocated here.
 int trim_args(pgh_ctx* c, pgh::FedavgArgs* a);
 // HBM bytes of K8's state a launch with these flags moves over rp params
 inline uint64_t trim_state_bytes(const pgh_ctx* c, int flags, uint64_t rp) {
-    const uint64_t planes = 2ull * (uint64_t)c->trim_b;  // (the acc plane is counted like the other modes')
+    const uint64_t planes = 2ull * (uint64_t)c->trim.b;  // (the acc plane is counted like the other modes')
     return ((flags & pgh::FL_FIRST) ? 0 : 4 * planes * rp) + ((flags & pgh::FL_FINAL) ? 0 : 4 * planes * rp);
 }
+// The form a trimmed fold takes: 40 (K8, 4 columns per lane) or 41 (1 column), whatever pgh_set_variant says.
+inline int trim_variant(const pgh_ctx* c) {
+    return (c->trim.vec ? c->trim.vec : pgh::auto_trim_vec(c->pg, c->trim.b)) == 4 ? 40 : 41;
+}
 
-// ---- median FedAvg (pgh_reduce.cpp) ------------------------------------------------------------------
+// ---- median FedAvg (pgh_rules.cpp) -------------------------------------------------------------------
 // The path a median fold of n rows takes: 50 (K9, on chip) or 51 (K9p, one pass per bit).
-inline int median_variant(const pgh_ctx* c, int64_t n) { return c->median_passes || n > pgh::MEDIAN_NCHIP ? 51 : 50; }
+inline int median_variant(const pgh_ctx* c, int64_t n) { return c->med.passes || n > pgh::MEDIAN_NCHIP ? 51 : 50; }
 // The whole median fold of a filled FedavgArgs (diffs, map, n_rows, p, ckpt, out; every row of the
 // cycle) on stream s: K9's one launch or K9p's 32 or 33.  The rows: tab, else d_rows (a device table
 // of n_rows entries), else contiguous from a.diffs.
 int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s);
 // slots[k] * parties for k < n, uploaded to d_rowidx on stream s (waits for the copy)
 int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s);
+inline const int32_t* median_rows(const pgh_ctx* c) { return c->med.d_rowidx.as<int32_t>(); }  // that table
 
-// ---- server optimizer (pgh_reduce.cpp) -----------------------------------------------------------------
-void free_server_opt(pgh_ctx* c);  // planes and setting; the caller has waited for the context's work
+// ---- server optimizer (pgh_serveropt.cpp) --------------------------------------------------------------
 struct FinalArgs;
 int server_opt_launch(pgh_ctx* c, const FinalArgs& fa, hipStream_t s);  // K10 behind a FINAL launch (fold_launch)
-// pgh_set_shard, keep_opt: the optimizer's setting and state stay when neither the shard nor the length
-// of the [P_shard] vectors changes (a group's pgh_reserve lays its children's shards out again)
+// pgh_set_shard; keep_opt (rules_shard_set): a group's pgh_reserve lays its children's shards out again
 int set_shard(pgh_ctx* c, int64_t lo, int64_t hi, bool keep_opt);
 
 // What a FINAL fold pass writes (fedavg: ckpt - avg; secagg: sum/dec) and over which param range.

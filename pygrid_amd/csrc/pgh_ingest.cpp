@@ -14,18 +14,16 @@ int pgh_ingest_raw(pgh_ctx* c, int client, const void* flat, size_t nbytes, int 
     RC(check_dtype(c, dtype));
     if (!flat) return fail(c, PGH_E_ARG, "flat is NULL");
     const size_t es = esize(dtype);
-    const size_t whole = (size_t)c->P * es * (size_t)c->parties;  // the whole model: take the slice
-    const size_t shard = (size_t)c->pg * es * (size_t)c->parties; // this shard only
-    if (nbytes != whole && nbytes != shard)
-        return fail(c, PGH_E_ARG, "client %d: got %zu bytes, layout needs %zu (model) or %zu (shard)", client, nbytes,
-                    whole, shard);
+    char what[32];
+    snprintf(what, sizeof what, "client %d", client);
+    size_t first = 0;
+    RC(shard_start(c, what, nbytes, es * (size_t)c->parties, &first));
     DeviceGuard g(c->device);
     int slot = 0;
     RC(claim_slot(c, client, &slot));
     const bool pinned = is_pinned(flat);
     const uint8_t* src = (const uint8_t*)flat;
-    const size_t row_elems = nbytes == whole ? (size_t)c->P : (size_t)c->pg;
-    const size_t first = nbytes == whole ? (size_t)c->lo : 0;
+    const size_t row_elems = nbytes / (es * (size_t)c->parties);  // each party's row: the model's or the shard's
     for (int s = 0; s < c->parties; ++s)
         RC(stage_h2d(c, row_dest(c, slot, s), src + ((size_t)s * row_elems + first) * es, (size_t)c->pg * es, pinned));
     RC(sumsq_after_ingest(c, slot));
@@ -408,8 +406,8 @@ int pgh_synth_ingest(pgh_ctx* c, uint64_t seed, int client0, int n) {
         for (int j = 0; j < run; ++j) {
             if (c->slot_client[(size_t)(slot + j)] != client + j) c->st.n_clients += 1;
             c->slot_client[(size_t)(slot + j)] = client + j;
-            c->sq_state[(size_t)(slot + j)] = pgh_ctx::SQ_NONE;  // a clipped fold sums these rows in one batch
         }
+        rules_slot_written(c, slot, run);  // (a clipped fold sums these rows in one batch)
         if (c->streaming) RC(maybe_fold(c, false));
         k += run;
     }
@@ -476,7 +474,7 @@ int pgh_set_weights(pgh_ctx* c, const float* w, int n) {
     }
     c->weights.assign(w, w + n);
     c->weights_on_device = false;
-    c->clip_scales_valid = false;
+    rules_weights_replaced(c);
     return PGH_OK;
 }
 

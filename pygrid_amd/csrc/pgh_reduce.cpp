@@ -1,12 +1,11 @@
-// libpygrid_hip: what a mode may do (check_mode_use), the one fp32 fold launch (fold_prepare, fold_launch),
-// fold_run and its bookkeeping, RESIDENT folds (every ingested client in one launch, repeatable), the resident
-// checkpoint kept in HBM across cycles, secure aggregation (Z_2^64 share sum + fixed-point decode) and
-// STREAM folds (a ring of slots folded in client order while ingest continues).  Reference:
+// libpygrid_hip: the one fp32 fold launch (fold_prepare, fold_launch), fold_run and its bookkeeping, the
+// divisors, RESIDENT folds (every ingested client in one launch, repeatable), the resident checkpoint kept in
+// HBM across cycles, secure aggregation (Z_2^64 share sum + fixed-point decode) and STREAM folds (a ring of
+// slots folded in client order while ingest continues).  What the rules add to the fold: pgh_rules.cpp; the
+// server optimizer behind a FINAL launch: pgh_serveropt.cpp.  Reference:
 // cycle_manager.py:252-296 (fedavg), test_basic_syft_operations.py:417-424 (secagg).
 // (struct pgh_ctx and the shared helpers: pgh_ctx.h)
 #include "pgh_ctx.h"
-
-#include <cmath>
 
 using namespace pgh_detail;
 
@@ -83,10 +82,10 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     a.out = fa.out ? fa.out + off : nullptr;
     // A server optimizer: the FINAL launch, unchanged, subtracts the average from -0 into the delta
     // plane, and K10 behind it on the same stream applies the step to the real ckpt / out.
-    const bool opt = c->opt_kind != PGH_OPT_NONE && (flags & pgh::FL_FINAL);
+    const bool opt = c->opt.kind != PGH_OPT_NONE && (flags & pgh::FL_FINAL);
     if (opt) {
-        a.ckpt = c->d_opt_nz.as<float>() + off;
-        a.out = c->d_opt_d.as<float>() + off;
+        a.ckpt = c->opt.d_nz.as<float>() + off;
+        a.out = c->opt.d_d.as<float>() + off;
     }
     a.divisor = fa.divisor;
     a.flags = flags;
@@ -107,30 +106,6 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     if (rows.tab) RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg_rows(a, *rows.tab, s); }));
     else RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
     return opt ? server_opt_launch(c, fa, s) : PGH_OK;
-}
-
-// K10 behind a FINAL fold of [fa.off, fa.off + fa.len) on stream s: d, the real ckpt and the committed
-// moments in; the real out and the pending moments out.  28 bytes per param (20 for FedAvgM, which has no v).
-int server_opt_launch(pgh_ctx* c, const FinalArgs& fa, hipStream_t s) {
-    if (!fa.ckpt || !fa.out) return fail(c, PGH_E_ARG, "a FINAL fold with a server optimizer needs ckpt and out");
-    const bool adaptive = c->opt_kind != PGH_OPT_MOMENTUM;
-    pgh::ServerOptArgs o{};
-    o.d = c->d_opt_d.as<float>() + fa.off;
-    o.ckpt = fa.ckpt + fa.off;
-    o.out = fa.out + fa.off;
-    o.m = c->d_opt_m.as<float>() + fa.off;
-    o.m2 = c->d_opt_m2.as<float>() + fa.off;
-    o.v = adaptive ? c->d_opt_v.as<float>() + fa.off : nullptr;
-    o.v2 = adaptive ? c->d_opt_v2.as<float>() + fa.off : nullptr;
-    o.p = fa.len;
-    o.kind = c->opt_kind;
-    o.lr = c->opt_lr; o.beta1 = c->opt_beta1; o.beta2 = c->opt_beta2;
-    o.c1 = c->opt_c1; o.c2 = c->opt_c2; o.tau = c->opt_tau;
-    RC(timed_launch(c, s, (adaptive ? 28ull : 20ull) * (uint64_t)fa.len, [&] { return pgh::launch_server_opt(o, s); }));
-    c->opt_pending = true;
-    const std::pair<int64_t, int64_t> r{fa.off, fa.off + fa.len};  // (a repeated FINAL lists its range once)
-    if (std::find(c->opt_cov.begin(), c->opt_cov.end(), r) == c->opt_cov.end()) c->opt_cov.push_back(r);
-    return PGH_OK;
 }
 
 // Fold slots holding clients [c0, c0 + n) (slot order may wrap) into the running state.
@@ -216,8 +191,7 @@ int claim_slot(pgh_ctx* c, int64_t client, int* slot_out) {
         if (client >= c->slots)
             return fail(c, PGH_E_ARG, "client %lld outside slab capacity %d", (long long)client, c->slots);
         RC(order_slot_overwrite(c, (int)client));  // a fold issued earlier may still read the slot
-        c->sq_state[(size_t)client] = pgh_ctx::SQ_NONE;  // the cached sum of squares was the old diff's
-        c->clip_scales_valid = false;
+        rules_slot_written(c, (int)client);
         *slot_out = (int)client;
         return PGH_OK;
     }
@@ -250,10 +224,10 @@ int resident_count(pgh_ctx* c, int64_t* n_out) {
 
 int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
     if (mode == PGH_TRIMMED_MEAN) {  // b dropped per side; at least one value must be left
-        if (n < 2 * (int64_t)c->trim_b + 1)
-            return fail(c, PGH_E_STATE, "trimmed mean with b = %d needs at least %d diffs, have %lld", c->trim_b,
-                        2 * c->trim_b + 1, (long long)n);
-        *div = (float)(n - 2 * (int64_t)c->trim_b);
+        if (n < 2 * (int64_t)c->trim.b + 1)
+            return fail(c, PGH_E_STATE, "trimmed mean with b = %d needs at least %d diffs, have %lld", c->trim.b,
+                        2 * c->trim.b + 1, (long long)n);
+        *div = (float)(n - 2 * (int64_t)c->trim.b);
     } else if (mode == PGH_WEIGHTED_MEAN) {
         if ((int64_t)c->weights.size() < n)
             return fail(c, PGH_E_STATE, "weighted mean needs %lld weights, have %zu", (long long)n, c->weights.size());
@@ -267,472 +241,6 @@ int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
 }
 
 }  // namespace pgh_detail
-
-// ---- clipped FedAvg: per-row sums of squares (K7), their host cache, the scales --------------------
-
-namespace pgh_detail {
-
-int check_mode_use(pgh_ctx* c, int mode, ModeUse use) {
-    switch (mode) {
-    case PGH_MEAN: case PGH_ITERATIVE_MEAN: case PGH_WEIGHTED_MEAN:
-        return PGH_OK;
-    case PGH_CLIPPED_MEAN:
-        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not clip: a scale needs the whole row of every client");
-        if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts do not clip: the shards each hold part of a row");
-        if (!(c->clip_c > 0.f)) return fail(c, PGH_E_STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first");
-        return PGH_OK;
-    case PGH_TRIMMED_MEAN:
-        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not trim: fold a RESIDENT slab or slots");
-        if (!c->grp && c->trim_b == 0) return fail(c, PGH_E_STATE, "PGH_TRIMMED_MEAN needs a trim count: call pgh_set_trim first");
-        return PGH_OK;
-    case PGH_MEDIAN:  // it needs every row of the cycle at once
-        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no median: it needs every row at once");
-        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a median needs every row at once: nothing can be folded early");
-        return PGH_OK;
-    default:
-        return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
-    }
-}
-
-int trim_args(pgh_ctx* c, pgh::FedavgArgs* a) {
-    a->mode = pgh::MODE_TRIMMED;
-    a->trim_b = c->trim_b;
-    a->trim_vec = c->trim_vec;
-    if ((a->flags & (pgh::FL_FIRST | pgh::FL_FINAL)) == (pgh::FL_FIRST | pgh::FL_FINAL)) return PGH_OK;
-    // (a buffer left from a larger b serves; one too small is only ever replaced before a cycle's
-    // first launch -- pgh_set_trim -- and hipFree waits for the launches that still use it)
-    if (!c->d_trim.reserve(2 * (size_t)c->trim_b * 4 * (size_t)c->pvec))
-        return fail(c, PGH_E_OOM, "allocation of the trimmed mean's %d state planes failed", 2 * c->trim_b);
-    a->tstate = c->d_trim.as<int32_t>() + a->map.off;
-    a->tplane = c->pvec;
-    return PGH_OK;
-}
-
-int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s) {
-    if (!c->d_rowidx.reserve(sizeof(int32_t) * (size_t)c->slots))
-        return fail(c, PGH_E_OOM, "allocation of the median's row table (%d rows) failed", c->slots);
-    std::vector<int32_t> rows((size_t)n);
-    for (int k = 0; k < n; ++k) rows[(size_t)k] = slots[k] * c->parties;
-    // (an earlier fold that still reads the table runs on c->stream too, or has been waited for)
-    CK(c, hipMemcpyAsync(c->d_rowidx.as<int32_t>(), rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-    CK(c, hipStreamSynchronize(s));  // rows is freed on return
-    return PGH_OK;
-}
-
-int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s) {
-    pgh::MedianArgs m{};
-    m.diffs = a.diffs;
-    m.map = a.map;
-    m.n_rows = a.n_rows;
-    m.p = a.p;
-    m.rowidx = tab ? nullptr : d_rows;
-    m.ckpt = a.ckpt;
-    m.out = a.out;
-    const uint64_t rows = 4ull * (uint64_t)a.n_rows * (uint64_t)a.p, rp = (uint64_t)a.p;
-    if (median_variant(c, a.n_rows) == 50)  // K9: the slab once, ckpt in, out
-        return timed_launch(c, s, rows + 8 * rp, [&] { return pgh::launch_median(m, tab, s); });
-    if (!c->d_med.reserve(sizeof(uint32_t) * (size_t)c->pvec))
-        return fail(c, PGH_E_OOM, "allocation of the median's prefix plane failed");
-    m.prefix = c->d_med.as<uint32_t>() + a.map.off;
-    // K9p: bits 31 .. 0, then the upper middle of an even count; each launch reads the rows, reads
-    // the prefix plane (not the first) and writes it, or ckpt in and out (the last)
-    const int last = (a.n_rows & 1) ? 0 : -1;
-    for (int bit = 31; bit >= last; --bit) {
-        const uint64_t bytes = rows + (bit == 31 ? 0 : 4 * rp) + (bit == last ? 8 * rp : 4 * rp);
-        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_median_pass(m, tab, bit, s); }));
-    }
-    return PGH_OK;
-}
-
-float clip_scale_of(double sumsq, float c) {
-    const double norm = std::sqrt(sumsq);
-    return norm <= (double)c ? 1.0f : (float)((double)c / norm);
-}
-
-void sumsq_forget(pgh_ctx* c) {
-    std::fill(c->sq_state.begin(), c->sq_state.end(), (uint8_t)pgh_ctx::SQ_NONE);
-    c->sq_queued.clear();
-    c->clip_scales_valid = false;
-    c->clip_norms.clear();
-    c->clip_rows = c->clip_clipped = 0;
-    c->clip_max_norm = 0.0;
-}
-
-void free_clip(pgh_ctx* c) {  // the copy stream is idle (free_slab synchronised it)
-    c->d_sq_part.reset();
-    c->d_sq.reset();
-    c->h_sq.reset();
-    c->sq_state.clear();
-    c->sq_host.clear();
-    sumsq_forget(c);
-}
-
-namespace {
-int ensure_sumsq_buffers(pgh_ctx* c) {
-    if (c->d_sq_part) return PGH_OK;
-    const size_t ntiles = (size_t)((c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE);
-    const size_t rows = (size_t)c->slots;
-    if (!c->d_sq_part.reserve(8 * rows * ntiles) || !c->d_sq.reserve(8 * rows) || !c->h_sq.reserve(8 * rows)) {
-        c->d_sq_part.reset();  // (the test above: all three or none)
-        return fail(c, PGH_E_OOM, "allocation of the clipping sums (%zu rows x %zu tiles) failed", rows, ntiles);
-    }
-    return PGH_OK;
-}
-}  // namespace
-
-int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n) {
-    std::vector<int32_t> todo;
-    for (int k = 0; k < n; ++k)
-        if (c->sq_state[(size_t)slots[k]] == pgh_ctx::SQ_NONE) todo.push_back(slots[k]);
-    if (todo.empty()) return PGH_OK;
-    RC(ensure_sumsq_buffers(c));
-    pgh::SumsqArgs a{};
-    a.slab = c->d_slab.as<float>();
-    a.map = slab_map(c);
-    a.p = c->pg;
-    a.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
-    a.part = c->d_sq_part.as<double>();
-    a.sumsq = c->d_sq.as<double>();
-    const hipStream_t s = c->copy;
-    bool run = true;  // consecutive slots: one launch over contiguous rows
-    int32_t lo = todo[0], hi = todo[0];
-    for (size_t k = 0; k < todo.size(); ++k) {
-        run = run && todo[k] == todo[0] + (int32_t)k;
-        lo = std::min(lo, todo[k]);
-        hi = std::max(hi, todo[k]);
-    }
-    const auto bytes = [&](size_t rows) { return rows * (4ull * (uint64_t)c->pg + 8ull * (uint64_t)a.ntiles); };
-    if (run) {
-        a.row0 = todo[0];
-        a.n_rows = (int)todo.size();
-        RC(timed_launch(c, s, bytes(todo.size()), [&] { return pgh::launch_row_sumsq(a, nullptr, s); }));
-    } else {
-        for (size_t done = 0; done < todo.size(); done += pgh::ROWTAB_MAX) {
-            const size_t m = std::min(todo.size() - done, (size_t)pgh::ROWTAB_MAX);
-            pgh::RowTab tab;
-            for (size_t k = 0; k < m; ++k) tab.rows[k] = todo[done + k];
-            a.n_rows = (int)m;
-            RC(timed_launch(c, s, bytes(m), [&] { return pgh::launch_row_sumsq(a, &tab, s); }));
-        }
-    }
-    // entries of other slots inside [lo, hi] are rewritten with what the device holds for them: the
-    // same value an earlier copy brought (same stream), or one nobody reads
-    CK(c, hipMemcpyAsync(c->h_sq.as<double>() + lo, c->d_sq.as<double>() + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
-    CK(c, hipEventRecord(c->sq_ev, s));
-    for (int32_t sl : todo) {
-        c->sq_state[(size_t)sl] = pgh_ctx::SQ_QUEUED;
-        c->sq_queued.push_back(sl);
-    }
-    return PGH_OK;
-}
-
-int sumsq_wait(pgh_ctx* c) {
-    if (c->sq_queued.empty()) return PGH_OK;
-    CK(c, hipEventSynchronize(c->sq_ev));
-    for (int32_t sl : c->sq_queued)
-        if (c->sq_state[(size_t)sl] == pgh_ctx::SQ_QUEUED) {
-            c->sq_host[(size_t)sl] = c->h_sq.as<double>()[sl];
-            c->sq_state[(size_t)sl] = pgh_ctx::SQ_VALID;
-        }
-    c->sq_queued.clear();
-    return PGH_OK;
-}
-
-int sumsq_after_ingest(pgh_ctx* c, int slot) {
-    if (!clip_on(c)) return PGH_OK;
-    const int32_t sl = slot;
-    return sumsq_queue(c, &sl, 1);
-}
-
-int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms) {
-    RC(sumsq_queue(c, slots, n));
-    RC(sumsq_wait(c));
-    c->weights.resize((size_t)(c0 + n));
-    if (norms) norms->resize((size_t)(c0 + n));
-    for (int k = 0; k < n; ++k) {
-        const double ss = c->sq_host[(size_t)slots[k]];
-        c->weights[(size_t)(c0 + k)] = clip_scale_of(ss, c->clip_c);
-        if (norms) (*norms)[(size_t)(c0 + k)] = std::sqrt(ss);
-    }
-    c->weights_on_device = false;
-    return PGH_OK;
-}
-
-void clip_count(pgh_ctx* c, const float* scales, const double* norms, int64_t n) {
-    for (int64_t k = 0; k < n; ++k) {
-        c->clip_rows += 1;
-        c->clip_clipped += scales[k] == 1.0f ? 0 : 1;
-        if (!std::isnan(c->clip_max_norm) && (std::isnan(norms[k]) || norms[k] > c->clip_max_norm))
-            c->clip_max_norm = norms[k];
-    }
-}
-
-}  // namespace pgh_detail
-
-// Resident folds in PGH_CLIPPED_MEAN: the scales of clients [0, n) (slot k holds client k), computed
-// once per state of the slab -- the range form and repeated folds reuse them.
-int pgh_detail::resident_clip_scales(pgh_ctx* c, int64_t n) {
-    if (c->clip_scales_valid && (int64_t)c->weights.size() == n) return PGH_OK;
-    std::vector<int32_t> slots((size_t)n);
-    for (int64_t k = 0; k < n; ++k) slots[(size_t)k] = (int32_t)k;
-    std::vector<double> norms;
-    RC(clip_set_scales(c, slots.data(), (int)n, 0, &norms));
-    clip_count(c, c->weights.data(), norms.data(), n);
-    c->clip_scales_valid = true;
-    return PGH_OK;
-}
-
-namespace {
-int check_clip_ctx(pgh_ctx* c, const char* what) {
-    if (!c) return fail(nullptr, PGH_E_ARG, "null context");
-    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s: a group's shards each hold part of a row (the sums would need an all-reduce)", what);
-    if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
-    if (c->pg != c->P) return fail(c, PGH_E_UNSUPPORTED, "%s: the shard [%lld,%lld) is narrower than the model", what, (long long)c->lo, (long long)c->hi);
-    if (c->d_slab && c->dtype != PGH_F32) return fail(c, PGH_E_UNSUPPORTED, "%s: the slab holds int64 shares", what);
-    if (c->streaming) return fail(c, PGH_E_UNSUPPORTED, "%s: the context is streaming", what);
-    return PGH_OK;
-}
-}  // namespace
-
-int pgh_set_clip_norm(pgh_ctx* c, float bound) {
-    if (!c) return PGH_E_ARG;
-    if (bound == 0.f) {  // off: always possible (a group never clips)
-        c->clip_c = 0.f;
-        c->clip_scales_valid = false;
-        return PGH_OK;
-    }
-    RC(check_clip_ctx(c, "pgh_set_clip_norm"));
-    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(c, PGH_E_ARG, "the clipping bound must be finite and > 0, or 0 for off");
-    if (bound != c->clip_c) c->clip_scales_valid = false;
-    c->clip_c = bound;
-    return PGH_OK;
-}
-
-int pgh_set_trim(pgh_ctx* c, int b) {
-    if (!c) return PGH_E_ARG;
-    if (b < 0 || b > PGH_TRIM_MAX) return fail(c, PGH_E_ARG, "trim count %d outside [0,%d]", b, PGH_TRIM_MAX);
-    if (c->grp) return pgh_group_api::set_trim(c, b);
-    if (b != c->trim_b && c->folded > 0 && !c->streaming)
-        return fail(c, PGH_E_STATE, "trim count changed from %d to %d with %lld diffs of the cycle folded", c->trim_b, b,
-                    (long long)c->folded);
-    c->trim_b = b;
-    return PGH_OK;
-}
-
-// ---- server optimizers (K10): the setting, the moment planes, commit, download / upload ------------
-
-namespace pgh_detail {
-
-void free_server_opt(pgh_ctx* c) {
-    for (auto* v : {&c->d_opt_nz, &c->d_opt_d, &c->d_opt_m, &c->d_opt_v, &c->d_opt_m2, &c->d_opt_v2}) v->reset();
-    c->opt_kind = PGH_OPT_NONE;
-    c->opt_pending = false;
-    c->opt_cov.clear();
-    c->opt_steps = 0;
-    c->opt_pvec = 0;
-}
-
-namespace {
-// Every launch that reads or writes the planes has finished: the context's reduction stream and the
-// folds issued on callers' streams.
-int opt_quiesce(pgh_ctx* c) {
-    CK(c, hipStreamSynchronize(c->stream));
-    CK(c, hipStreamSynchronize(c->aux));
-    for (auto& fe : c->fold_evs) CK(c, hipEventSynchronize(fe.second));
-    return PGH_OK;
-}
-
-// m = +0, v = tau * tau in the committed planes; nothing pending, no step counted.
-int opt_init_state(pgh_ctx* c) {
-    const size_t n = (size_t)c->opt_pvec;
-    const float v0 = c->opt_tau * c->opt_tau;
-    uint32_t v0_bits;
-    std::memcpy(&v0_bits, &v0, 4);
-    // (the pending planes too: a first close that covers only part of the shard leaves the rest as it began)
-    for (auto* b : {&c->d_opt_m, &c->d_opt_m2}) CK(c, hipMemsetD32Async((hipDeviceptr_t)b->as<void>(), 0, n, c->stream));
-    for (auto* b : {&c->d_opt_v, &c->d_opt_v2})
-        if (*b) CK(c, hipMemsetD32Async((hipDeviceptr_t)b->as<void>(), (int)v0_bits, n, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    c->opt_pending = false;
-    c->opt_cov.clear();
-    c->opt_steps = 0;
-    return PGH_OK;
-}
-
-int check_opt_on(pgh_ctx* c, const char* what) {
-    if (c->opt_kind == PGH_OPT_NONE) return fail(c, PGH_E_STATE, "%s: no server optimizer is set", what);
-    return PGH_OK;
-}
-}  // namespace
-
-}  // namespace pgh_detail
-
-int pgh_set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2, float tau) {
-    if (!c) return PGH_E_ARG;
-    if (kind < PGH_OPT_NONE || kind > PGH_OPT_YOGI) return fail(c, PGH_E_ARG, "unknown server optimizer %d", kind);
-    if (kind != PGH_OPT_NONE) {
-        if (!std::isfinite(lr) || !(lr > 0.f)) return fail(c, PGH_E_ARG, "the server learning rate must be finite and > 0");
-        if (!(beta1 >= 0.f && beta1 < 1.f)) return fail(c, PGH_E_ARG, "beta1 must be in [0, 1)");
-        if (kind == PGH_OPT_MOMENTUM) {
-            beta2 = 0.f;  // (not used: ignored)
-            tau = 0.f;
-        } else {
-            if (kind == PGH_OPT_ADAGRAD) beta2 = 0.f;
-            else if (!(beta2 >= 0.f && beta2 < 1.f)) return fail(c, PGH_E_ARG, "beta2 must be in [0, 1)");
-            if (!std::isfinite(tau) || !(tau > 0.f)) return fail(c, PGH_E_ARG, "tau must be finite and > 0");
-        }
-    }
-    if (c->grp) return pgh_group_api::set_server_opt(c, kind, lr, beta1, beta2, tau);
-    if (kind == PGH_OPT_NONE) {
-        if (c->opt_kind == PGH_OPT_NONE) return PGH_OK;
-        DeviceGuard g(c->device);
-        RC(opt_quiesce(c));
-        free_server_opt(c);
-        return PGH_OK;
-    }
-    if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
-    if (kind == c->opt_kind && lr == c->opt_lr && beta1 == c->opt_beta1 && beta2 == c->opt_beta2 && tau == c->opt_tau)
-        return PGH_OK;  // the same again: the state stays
-    DeviceGuard g(c->device);
-    RC(opt_quiesce(c));
-    free_server_opt(c);
-    const size_t bytes = 4 * (size_t)c->pvec;
-    const bool adaptive = kind != PGH_OPT_MOMENTUM;
-    if (!c->d_opt_nz.reserve(bytes) || !c->d_opt_d.reserve(bytes) || !c->d_opt_m.reserve(bytes) || !c->d_opt_m2.reserve(bytes) ||
-        (adaptive && (!c->d_opt_v.reserve(bytes) || !c->d_opt_v2.reserve(bytes)))) {
-        free_server_opt(c);
-        return fail(c, PGH_E_OOM, "allocation of the server optimizer's planes (%zu bytes each) failed", bytes);
-    }
-    c->opt_pvec = c->pvec;
-    c->opt_lr = lr; c->opt_beta1 = beta1; c->opt_beta2 = beta2; c->opt_tau = tau;
-    c->opt_c1 = 1.0f - beta1;
-    c->opt_c2 = 1.0f - beta2;
-    const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)c->d_opt_nz.as<void>(), (int)0x80000000u, (size_t)c->pvec, c->stream);
-    const int rc = e == hipSuccess ? opt_init_state(c) : fail(c, PGH_E_HIP, "hipMemsetD32Async failed: %s", hipGetErrorString(e));
-    if (rc) {
-        free_server_opt(c);
-        return rc;
-    }
-    c->opt_kind = kind;
-    return PGH_OK;
-}
-
-int pgh_server_opt_commit(pgh_ctx* c) {
-    if (!c) return PGH_E_ARG;
-    if (c->grp) return pgh_group_api::server_opt_commit(c);
-    RC(check_opt_on(c, "pgh_server_opt_commit"));
-    if (!c->opt_pending) return fail(c, PGH_E_STATE, "pgh_server_opt_commit: no FINAL fold has run since the last commit or upload");
-    // K10 wrote only the ranges its FINAL launches covered: a param outside them (a cycle closed with
-    // pgh_fedavg_device_range over part of the shard) keeps its committed moments, copied into the
-    // pending planes before the swap.  A close over the whole shard copies nothing.
-    std::sort(c->opt_cov.begin(), c->opt_cov.end());
-    DeviceGuard g(c->device);
-    bool copied = false;
-    const auto keep = [&](int64_t a, int64_t b) -> int {
-        if (a >= b) return PGH_OK;
-        const size_t n = 4 * (size_t)(b - a);
-        CK(c, hipMemcpyAsync(c->d_opt_m2.as<float>() + a, c->d_opt_m.as<float>() + a, n, hipMemcpyDeviceToDevice, c->stream));
-        if (c->d_opt_v) CK(c, hipMemcpyAsync(c->d_opt_v2.as<float>() + a, c->d_opt_v.as<float>() + a, n, hipMemcpyDeviceToDevice, c->stream));
-        copied = true;
-        return PGH_OK;
-    };
-    int64_t pos = 0;
-    for (const auto& r : c->opt_cov) {
-        RC(keep(pos, r.first));
-        pos = std::max(pos, r.second);
-    }
-    RC(keep(pos, c->pg));
-    if (copied) CK(c, hipStreamSynchronize(c->stream));  // (a later K10 may read them on a caller's stream)
-    // (a pointer swap: the next cycle's K10 writes the planes committed until now behind this cycle's
-    // on the same stream; folds on different caller streams are the caller's to order, as for d_acc)
-    std::swap(c->d_opt_m, c->d_opt_m2);
-    std::swap(c->d_opt_v, c->d_opt_v2);
-    c->opt_pending = false;
-    c->opt_cov.clear();
-    c->opt_steps += 1;
-    return PGH_OK;
-}
-
-int pgh_server_opt_steps(pgh_ctx* c, int64_t* committed) {
-    if (!c || !committed) return c ? fail(c, PGH_E_ARG, "committed is NULL") : PGH_E_ARG;
-    if (c->grp) return pgh_group_api::server_opt_steps(c, committed);
-    *committed = c->opt_steps;
-    return PGH_OK;
-}
-
-int pgh_server_opt_download(pgh_ctx* c, float* m, float* v) {
-    if (!c) return PGH_E_ARG;
-    if (c->grp) return pgh_group_api::server_opt_download(c, m, v);
-    RC(check_opt_on(c, "pgh_server_opt_download"));
-    const bool adaptive = c->opt_kind != PGH_OPT_MOMENTUM;
-    if (!m || (adaptive && !v)) return fail(c, PGH_E_ARG, "m / v is NULL");
-    DeviceGuard g(c->device);
-    RC(opt_quiesce(c));
-    const size_t bytes = 4 * (size_t)c->pg;
-    CK(c, hipMemcpy(m, c->d_opt_m.as<float>(), bytes, hipMemcpyDeviceToHost));
-    if (adaptive) CK(c, hipMemcpy(v, c->d_opt_v.as<float>(), bytes, hipMemcpyDeviceToHost));
-    return PGH_OK;
-}
-
-int pgh_server_opt_upload(pgh_ctx* c, const float* m, const float* v, size_t nbytes) {
-    if (!c) return PGH_E_ARG;
-    if (c->grp) return pgh_group_api::server_opt_upload(c, m, v, nbytes);
-    RC(check_opt_on(c, "pgh_server_opt_upload"));
-    const bool adaptive = c->opt_kind != PGH_OPT_MOMENTUM;
-    if (!m || (adaptive && !v)) return fail(c, PGH_E_ARG, "m / v is NULL");
-    const size_t whole = 4 * (size_t)c->P, shard = 4 * (size_t)c->pg;
-    if (nbytes != whole && nbytes != shard)
-        return fail(c, PGH_E_ARG, "optimizer state: got %zu bytes, layout needs %zu (model) or %zu (shard)", nbytes, whole, shard);
-    const size_t skip = nbytes == whole ? (size_t)c->lo : 0;
-    DeviceGuard g(c->device);
-    RC(opt_quiesce(c));
-    CK(c, hipMemcpy(c->d_opt_m.as<float>(), m + skip, shard, hipMemcpyHostToDevice));
-    if (adaptive) CK(c, hipMemcpy(c->d_opt_v.as<float>(), v + skip, shard, hipMemcpyHostToDevice));
-    c->opt_pending = false;
-    c->opt_cov.clear();
-    return PGH_OK;
-}
-
-int pgh_row_sumsq(pgh_ctx* c, const int32_t* slots, int n, double* out) {
-    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_row_sumsq: a group's shards each hold part of a row");
-    RC(check_dtype(c, PGH_F32));
-    if (c->streaming) return fail(c, PGH_E_UNSUPPORTED, "pgh_row_sumsq: the context is streaming");
-    if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
-    for (int k = 0; k < n; ++k) {
-        if (slots[k] < 0 || slots[k] >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", slots[k], c->slots);
-        if (c->slot_client[(size_t)slots[k]] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", slots[k]);
-    }
-    DeviceGuard g(c->device);
-    RC(sumsq_queue(c, slots, n));
-    if (!out) return PGH_OK;
-    RC(sumsq_wait(c));
-    for (int k = 0; k < n; ++k) out[k] = c->sq_host[(size_t)slots[k]];
-    return PGH_OK;
-}
-
-int pgh_clip_scale(double sumsq, float bound, float* scale) {
-    if (!scale) return fail(nullptr, PGH_E_ARG, "scale is NULL");
-    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(nullptr, PGH_E_ARG, "the clipping bound must be finite and > 0");
-    *scale = clip_scale_of(sumsq, bound);
-    return PGH_OK;
-}
-
-int pgh_clip_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_clipped, double* max_norm) {
-    if (!c) return PGH_E_ARG;
-    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_clip_stats: group contexts do not clip");
-    // the finished folds, and the slot folds of the running cycle on top
-    const int64_t rows0 = c->clip_rows, cl0 = c->clip_clipped;
-    const double mx0 = c->clip_max_norm;
-    const int64_t m = std::min<int64_t>((int64_t)c->clip_norms.size(), (int64_t)c->weights.size());
-    clip_count(c, c->weights.data(), c->clip_norms.data(), m);
-    if (n_rows) *n_rows = c->clip_rows;
-    if (n_clipped) *n_clipped = c->clip_clipped;
-    if (max_norm) *max_norm = c->clip_max_norm;
-    c->clip_rows = rows0;
-    c->clip_clipped = cl0;
-    c->clip_max_norm = mx0;
-    return PGH_OK;
-}
 
 // ---- RESIDENT reductions -------------------------------------------------------------------------
 
@@ -797,13 +305,10 @@ int pgh_ckpt_upload(pgh_ctx* c, const float* ckpt, size_t nbytes) {
     if (c && c->grp) return pgh_group_api::ckpt_upload(c, ckpt, nbytes);
     RC(check_dtype(c, PGH_F32));
     if (!ckpt) return fail(c, PGH_E_ARG, "ckpt is NULL");
-    const size_t whole = 4 * (size_t)c->P, shard = 4 * (size_t)c->pg;
-    if (nbytes != whole && nbytes != shard)
-        return fail(c, PGH_E_ARG, "checkpoint: got %zu bytes, layout needs %zu (model) or %zu (shard)", nbytes, whole,
-                    shard);
+    size_t first = 0;
+    RC(shard_start(c, "checkpoint", nbytes, 4, &first));
     DeviceGuard g(c->device);
-    const uint8_t* src = (const uint8_t*)ckpt + (nbytes == whole ? 4 * (size_t)c->lo : 0);
-    return upload_ckpt(c, src, shard, is_pinned(ckpt));
+    return upload_ckpt(c, (const uint8_t*)(ckpt + first), 4 * (size_t)c->pg, is_pinned(ckpt));
 }
 
 int pgh_ckpt_upload_state(pgh_ctx* c, const uint8_t* pb, size_t n) {

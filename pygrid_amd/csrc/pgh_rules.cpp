@@ -1,0 +1,342 @@
+// libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); clipping's
+// per-row sums of squares (K7), their host cache, the scales and the tallies; the trimmed mean's state planes
+// (K8); the median's driver and row table (K9, K9p); and what the rules' state does at each lifecycle event of
+// the context (rules_*: the one call each event's site makes).  The state itself: pgh_rules.h.
+// (struct pgh_ctx and the shared helpers: pgh_ctx.h)
+#include "pgh_ctx.h"
+
+#include <cmath>
+
+using namespace pgh_detail;
+
+// (the public entry points take their C linkage from include/pgh_api.h)
+
+namespace pgh_detail {
+
+int check_mode_use(pgh_ctx* c, int mode, ModeUse use) {
+    switch (mode) {
+    case PGH_MEAN: case PGH_ITERATIVE_MEAN: case PGH_WEIGHTED_MEAN:
+        return PGH_OK;
+    case PGH_CLIPPED_MEAN:
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not clip: a scale needs the whole row of every client");
+        if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts do not clip: the shards each hold part of a row");
+        if (!(c->clip.c > 0.f)) return fail(c, PGH_E_STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first");
+        return PGH_OK;
+    case PGH_TRIMMED_MEAN:
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not trim: fold a RESIDENT slab or slots");
+        if (!c->grp && c->trim.b == 0) return fail(c, PGH_E_STATE, "PGH_TRIMMED_MEAN needs a trim count: call pgh_set_trim first");
+        return PGH_OK;
+    case PGH_MEDIAN:  // it needs every row of the cycle at once
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no median: it needs every row at once");
+        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a median needs every row at once: nothing can be folded early");
+        return PGH_OK;
+    default:
+        return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
+    }
+}
+
+// ---- the lifecycle events of the context, as the rules see them -------------------------------------------
+
+bool rules_made(pgh_ctx* c) {
+    if (const char* e = std::getenv("PGH_TRIM_VEC")) c->trim.vec = std::atoi(e) == 4 ? 4 : std::atoi(e) == 1 ? 1 : 0;
+    if (const char* e = std::getenv("PGH_MEDIAN_PATH")) c->med.passes = std::strcmp(e, "passes") == 0;
+    return c->clip.sq_ev.make() == hipSuccess;
+}
+
+void rules_slab_freed(pgh_ctx* c) {  // the streams are idle (free_slab synchronised them)
+    for (auto* v : {&c->trim.d_planes, &c->med.d_prefix, &c->med.d_rowidx, &c->clip.d_sq_part, &c->clip.d_sq}) v->reset();
+    c->clip.h_sq.reset();
+    c->clip.sq_state.clear();
+    c->clip.sq_host.clear();
+    c->clip.forget();
+}
+
+void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep_opt) {
+    if (!(keep_opt && lo == c->lo && hi == c->hi && pvec == c->opt.pvec)) c->opt.release();
+    if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
+}
+
+void rules_reserved(pgh_ctx* c, int slots) {
+    c->clip.sq_state.assign((size_t)slots, (uint8_t)ClipState::SQ_NONE);
+    c->clip.sq_host.assign((size_t)slots, 0.0);
+}
+
+void rules_reset(pgh_ctx* c) { c->clip.forget(); }
+
+void rules_slot_written(pgh_ctx* c, int slot, int n) { c->clip.slot_written(slot, n); }
+
+void rules_weights_replaced(pgh_ctx* c) { c->clip.scales_valid = false; }
+
+void rules_folds_restarted(pgh_ctx* c) { c->clip.norms.clear(); }
+
+void rules_clipped_cycle_finished(pgh_ctx* c) {
+    c->clip.count_cycle(c->weights);
+    c->clip.norms.clear();
+}
+
+// ---- trimmed mean: K8's arguments and state planes ---------------------------------------------------------
+
+int trim_args(pgh_ctx* c, pgh::FedavgArgs* a) {
+    a->mode = pgh::MODE_TRIMMED;
+    a->trim_b = c->trim.b;
+    a->trim_vec = c->trim.vec;
+    if ((a->flags & (pgh::FL_FIRST | pgh::FL_FINAL)) == (pgh::FL_FIRST | pgh::FL_FINAL)) return PGH_OK;
+    // (a buffer left from a larger b serves; one too small is only ever replaced before a cycle's
+    // first launch -- pgh_set_trim -- and hipFree waits for the launches that still use it)
+    if (!c->trim.d_planes.reserve(2 * (size_t)c->trim.b * 4 * (size_t)c->pvec))
+        return fail(c, PGH_E_OOM, "allocation of the trimmed mean's %d state planes failed", 2 * c->trim.b);
+    a->tstate = c->trim.d_planes.as<int32_t>() + a->map.off;
+    a->tplane = c->pvec;
+    return PGH_OK;
+}
+
+// ---- median: the row table and the fold's launches (K9, K9p) ------------------------------------------------
+
+int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s) {
+    if (!c->med.d_rowidx.reserve(sizeof(int32_t) * (size_t)c->slots))
+        return fail(c, PGH_E_OOM, "allocation of the median's row table (%d rows) failed", c->slots);
+    std::vector<int32_t> rows((size_t)n);
+    for (int k = 0; k < n; ++k) rows[(size_t)k] = slots[k] * c->parties;
+    // (an earlier fold that still reads the table runs on c->stream too, or has been waited for)
+    CK(c, hipMemcpyAsync(c->med.d_rowidx.as<int32_t>(), rows.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // rows is freed on return
+    return PGH_OK;
+}
+
+int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s) {
+    pgh::MedianArgs m{};
+    m.diffs = a.diffs;
+    m.map = a.map;
+    m.n_rows = a.n_rows;
+    m.p = a.p;
+    m.rowidx = tab ? nullptr : d_rows;
+    m.ckpt = a.ckpt;
+    m.out = a.out;
+    const uint64_t rows = 4ull * (uint64_t)a.n_rows * (uint64_t)a.p, rp = (uint64_t)a.p;
+    if (median_variant(c, a.n_rows) == 50)  // K9: the slab once, ckpt in, out
+        return timed_launch(c, s, rows + 8 * rp, [&] { return pgh::launch_median(m, tab, s); });
+    if (!c->med.d_prefix.reserve(sizeof(uint32_t) * (size_t)c->pvec))
+        return fail(c, PGH_E_OOM, "allocation of the median's prefix plane failed");
+    m.prefix = c->med.d_prefix.as<uint32_t>() + a.map.off;
+    // K9p: bits 31 .. 0, then the upper middle of an even count; each launch reads the rows, reads
+    // the prefix plane (not the first) and writes it, or ckpt in and out (the last)
+    const int last = (a.n_rows & 1) ? 0 : -1;
+    for (int bit = 31; bit >= last; --bit) {
+        const uint64_t bytes = rows + (bit == 31 ? 0 : 4 * rp) + (bit == last ? 8 * rp : 4 * rp);
+        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_median_pass(m, tab, bit, s); }));
+    }
+    return PGH_OK;
+}
+
+// ---- clipped FedAvg: per-row sums of squares (K7), their host cache, the scales, the tallies ---------------
+
+float clip_scale_of(double sumsq, float c) {
+    const double norm = std::sqrt(sumsq);
+    return norm <= (double)c ? 1.0f : (float)((double)c / norm);
+}
+
+void ClipState::forget() {
+    slot_written(0, (int)sq_state.size());
+    sq_queued.clear();
+    norms.clear();
+    rows = clipped = 0;
+    max_norm = 0.0;
+}
+
+void ClipState::count(const float* scales, const double* row_norms, int64_t n) {
+    for (int64_t k = 0; k < n; ++k) {
+        rows += 1;
+        clipped += scales[k] == 1.0f ? 0 : 1;
+        if (!std::isnan(max_norm) && (std::isnan(row_norms[k]) || row_norms[k] > max_norm)) max_norm = row_norms[k];
+    }
+}
+
+namespace {
+int ensure_sumsq_buffers(pgh_ctx* c) {
+    if (c->clip.d_sq_part) return PGH_OK;
+    const size_t ntiles = (size_t)((c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE);
+    const size_t rows = (size_t)c->slots;
+    if (!c->clip.d_sq_part.reserve(8 * rows * ntiles) || !c->clip.d_sq.reserve(8 * rows) || !c->clip.h_sq.reserve(8 * rows)) {
+        c->clip.d_sq_part.reset();  // (the test above: all three or none)
+        return fail(c, PGH_E_OOM, "allocation of the clipping sums (%zu rows x %zu tiles) failed", rows, ntiles);
+    }
+    return PGH_OK;
+}
+}  // namespace
+
+int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n) {
+    std::vector<int32_t> todo;
+    for (int k = 0; k < n; ++k)
+        if (c->clip.sq_state[(size_t)slots[k]] == ClipState::SQ_NONE) todo.push_back(slots[k]);
+    if (todo.empty()) return PGH_OK;
+    RC(ensure_sumsq_buffers(c));
+    pgh::SumsqArgs a{};
+    a.slab = c->d_slab.as<float>();
+    a.map = slab_map(c);
+    a.p = c->pg;
+    a.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
+    a.part = c->clip.d_sq_part.as<double>();
+    a.sumsq = c->clip.d_sq.as<double>();
+    const hipStream_t s = c->copy;
+    bool run = true;  // consecutive slots: one launch over contiguous rows
+    int32_t lo = todo[0], hi = todo[0];
+    for (size_t k = 0; k < todo.size(); ++k) {
+        run = run && todo[k] == todo[0] + (int32_t)k;
+        lo = std::min(lo, todo[k]);
+        hi = std::max(hi, todo[k]);
+    }
+    const auto bytes = [&](size_t rows) { return rows * (4ull * (uint64_t)c->pg + 8ull * (uint64_t)a.ntiles); };
+    if (run) {
+        a.row0 = todo[0];
+        a.n_rows = (int)todo.size();
+        RC(timed_launch(c, s, bytes(todo.size()), [&] { return pgh::launch_row_sumsq(a, nullptr, s); }));
+    } else {
+        for (size_t done = 0; done < todo.size(); done += pgh::ROWTAB_MAX) {
+            const size_t m = std::min(todo.size() - done, (size_t)pgh::ROWTAB_MAX);
+            pgh::RowTab tab;
+            for (size_t k = 0; k < m; ++k) tab.rows[k] = todo[done + k];
+            a.n_rows = (int)m;
+            RC(timed_launch(c, s, bytes(m), [&] { return pgh::launch_row_sumsq(a, &tab, s); }));
+        }
+    }
+    // entries of other slots inside [lo, hi] are rewritten with what the device holds for them: the
+    // same value an earlier copy brought (same stream), or one nobody reads
+    CK(c, hipMemcpyAsync(c->clip.h_sq.as<double>() + lo, c->clip.d_sq.as<double>() + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
+    CK(c, hipEventRecord(c->clip.sq_ev, s));
+    for (int32_t sl : todo) {
+        c->clip.sq_state[(size_t)sl] = ClipState::SQ_QUEUED;
+        c->clip.sq_queued.push_back(sl);
+    }
+    return PGH_OK;
+}
+
+int sumsq_wait(pgh_ctx* c) {
+    if (c->clip.sq_queued.empty()) return PGH_OK;
+    CK(c, hipEventSynchronize(c->clip.sq_ev));
+    for (int32_t sl : c->clip.sq_queued)
+        if (c->clip.sq_state[(size_t)sl] == ClipState::SQ_QUEUED) {
+            c->clip.sq_host[(size_t)sl] = c->clip.h_sq.as<double>()[sl];
+            c->clip.sq_state[(size_t)sl] = ClipState::SQ_VALID;
+        }
+    c->clip.sq_queued.clear();
+    return PGH_OK;
+}
+
+int sumsq_after_ingest(pgh_ctx* c, int slot) {
+    if (!clip_on(c)) return PGH_OK;
+    const int32_t sl = slot;
+    return sumsq_queue(c, &sl, 1);
+}
+
+int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms) {
+    RC(sumsq_queue(c, slots, n));
+    RC(sumsq_wait(c));
+    c->weights.resize((size_t)(c0 + n));
+    if (norms) norms->resize((size_t)(c0 + n));
+    for (int k = 0; k < n; ++k) {
+        const double ss = c->clip.sq_host[(size_t)slots[k]];
+        c->weights[(size_t)(c0 + k)] = clip_scale_of(ss, c->clip.c);
+        if (norms) (*norms)[(size_t)(c0 + k)] = std::sqrt(ss);
+    }
+    c->weights_on_device = false;
+    return PGH_OK;
+}
+
+int clip_slot_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0) {
+    if (c0 == 0) c->clip.norms.clear();
+    c->clip.scales_valid = false;
+    return clip_set_scales(c, slots, n, c0, &c->clip.norms);
+}
+
+// Resident folds in PGH_CLIPPED_MEAN: the scales of clients [0, n) (slot k holds client k), computed
+// once per state of the slab -- the range form and repeated folds reuse them.
+int resident_clip_scales(pgh_ctx* c, int64_t n) {
+    if (c->clip.scales_valid && (int64_t)c->weights.size() == n) return PGH_OK;
+    std::vector<int32_t> slots((size_t)n);
+    for (int64_t k = 0; k < n; ++k) slots[(size_t)k] = (int32_t)k;
+    std::vector<double> norms;
+    RC(clip_set_scales(c, slots.data(), (int)n, 0, &norms));
+    c->clip.count(c->weights.data(), norms.data(), n);
+    c->clip.scales_valid = true;
+    return PGH_OK;
+}
+
+}  // namespace pgh_detail
+
+namespace {
+int check_clip_ctx(pgh_ctx* c, const char* what) {
+    if (!c) return fail(nullptr, PGH_E_ARG, "null context");
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "%s: a group's shards each hold part of a row (the sums would need an all-reduce)", what);
+    if (!c->layout) return fail(c, PGH_E_STATE, "pgh_set_layout has not been called");
+    if (c->pg != c->P) return fail(c, PGH_E_UNSUPPORTED, "%s: the shard [%lld,%lld) is narrower than the model", what, (long long)c->lo, (long long)c->hi);
+    if (c->d_slab && c->dtype != PGH_F32) return fail(c, PGH_E_UNSUPPORTED, "%s: the slab holds int64 shares", what);
+    if (c->streaming) return fail(c, PGH_E_UNSUPPORTED, "%s: the context is streaming", what);
+    return PGH_OK;
+}
+}  // namespace
+
+int pgh_set_clip_norm(pgh_ctx* c, float bound) {
+    if (!c) return PGH_E_ARG;
+    if (bound == 0.f) {  // off: always possible (a group never clips)
+        c->clip.c = 0.f;
+        c->clip.scales_valid = false;
+        return PGH_OK;
+    }
+    RC(check_clip_ctx(c, "pgh_set_clip_norm"));
+    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(c, PGH_E_ARG, "the clipping bound must be finite and > 0, or 0 for off");
+    if (bound != c->clip.c) c->clip.scales_valid = false;
+    c->clip.c = bound;
+    return PGH_OK;
+}
+
+int pgh_set_trim(pgh_ctx* c, int b) {
+    if (!c) return PGH_E_ARG;
+    if (b < 0 || b > PGH_TRIM_MAX) return fail(c, PGH_E_ARG, "trim count %d outside [0,%d]", b, PGH_TRIM_MAX);
+    if (c->grp) return pgh_group_api::set_trim(c, b);
+    if (b != c->trim.b && c->folded > 0 && !c->streaming)
+        return fail(c, PGH_E_STATE, "trim count changed from %d to %d with %lld diffs of the cycle folded", c->trim.b, b,
+                    (long long)c->folded);
+    c->trim.b = b;
+    return PGH_OK;
+}
+
+int pgh_row_sumsq(pgh_ctx* c, const int32_t* slots, int n, double* out) {
+    if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_row_sumsq: a group's shards each hold part of a row");
+    RC(check_dtype(c, PGH_F32));
+    if (c->streaming) return fail(c, PGH_E_UNSUPPORTED, "pgh_row_sumsq: the context is streaming");
+    if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
+    for (int k = 0; k < n; ++k) {
+        if (slots[k] < 0 || slots[k] >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", slots[k], c->slots);
+        if (c->slot_client[(size_t)slots[k]] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", slots[k]);
+    }
+    DeviceGuard g(c->device);
+    RC(sumsq_queue(c, slots, n));
+    if (!out) return PGH_OK;
+    RC(sumsq_wait(c));
+    for (int k = 0; k < n; ++k) out[k] = c->clip.sq_host[(size_t)slots[k]];
+    return PGH_OK;
+}
+
+int pgh_clip_scale(double sumsq, float bound, float* scale) {
+    if (!scale) return fail(nullptr, PGH_E_ARG, "scale is NULL");
+    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(nullptr, PGH_E_ARG, "the clipping bound must be finite and > 0");
+    *scale = clip_scale_of(sumsq, bound);
+    return PGH_OK;
+}
+
+int pgh_clip_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_clipped, double* max_norm) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_clip_stats: group contexts do not clip");
+    // the finished folds, and the slot folds of the running cycle on top
+    ClipState& cl = c->clip;
+    const int64_t rows0 = cl.rows, cl0 = cl.clipped;
+    const double mx0 = cl.max_norm;
+    cl.count_cycle(c->weights);
+    if (n_rows) *n_rows = cl.rows;
+    if (n_clipped) *n_clipped = cl.clipped;
+    if (max_norm) *max_norm = cl.max_norm;
+    cl.rows = rows0;
+    cl.clipped = cl0;
+    cl.max_norm = mx0;
+    return PGH_OK;
+}

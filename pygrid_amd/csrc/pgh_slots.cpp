@@ -45,11 +45,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     // (never a clipped pass: a scale needs the last report's whole row, so it takes the whole-stream wait)
     const bool clipped = mode == PGH_CLIPPED_MEAN;
     const bool ranged = final && !clipped && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && ranged_ingest_valid(c);
-    if (clipped && n > 0) {  // the sums still missing in one batch, then the scales in fold order
-        if (c0 == 0) c->clip_norms.clear();
-        c->clip_scales_valid = false;
-        RC(clip_set_scales(c, slots, n, c0, &c->clip_norms));
-    }
+    if (clipped && n > 0) RC(clip_slot_scales(c, slots, n, c0));  // the sums still missing in one batch, then the scales in fold order
     if (!ranged) RC(order_after_ingest(c, s));
     else if (c->dec_last) CK(c, hipStreamWaitEvent(s, c->dec_last, 0));  // the copy stream: per range below
     if (n > 0) RC(fold_prepare(c, mode, total, s));
@@ -62,10 +58,10 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         for (int k = 0; k < std::min(m, pgh::ROWTAB_MAX); ++k) tab.rows[k] = slots[done + k] * c->parties;
         const bool first = (c0 + done == 0), last = (done + m == n);
         const int flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
-        // (only a median comes with more rows than the table carries: they are in d_rowidx then)
+        // (only a median comes with more rows than the table carries: they are in the device table then)
         FoldRows rows{c->d_slab.as<float>(), m};
         if (m <= pgh::ROWTAB_MAX) rows.tab = &tab;
-        else rows.d_rows = c->d_rowidx.as<int32_t>();
+        else rows.d_rows = median_rows(c);
         // The FINAL pass of a report-time close (a short fold of the rows left) as ranges of 4 MiB of
         // output, one after another on one stream, a mark behind every second one: each 8 MiB D2H
         // piece starts behind the two ranges that wrote it instead of behind the whole fold.  Ranges
@@ -121,11 +117,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         c->pre_d2h_valid = prequeued && c->pre_d2h.src == c->d_ckpt.as<uint8_t>();
         c->folded = 0;  // the next cycle folds from scratch
         c->slot_mode = -1;
-        if (clipped) {  // the cycle's rows join the finished totals (pgh_clip_stats)
-            const int64_t m = std::min<int64_t>((int64_t)c->clip_norms.size(), (int64_t)c->weights.size());
-            clip_count(c, c->weights.data(), c->clip_norms.data(), m);
-            c->clip_norms.clear();
-        }
+        if (clipped) rules_clipped_cycle_finished(c);  // the cycle's rows join the finished totals (pgh_clip_stats)
     }
     return PGH_OK;
 }
@@ -166,7 +158,7 @@ int pgh_fold_slots_restart(pgh_ctx* c) {
     c->st.n_folded = 0;
     c->slot_mode = -1;
     c->weights.clear();  // (a clipped cycle's scales among them)
-    c->clip_norms.clear();
+    rules_folds_restarted(c);
     c->weights_on_device = false;
     return PGH_OK;
 }

@@ -1,0 +1,264 @@
+"""GPU: what the averaging rules' state does at each lifecycle event of a context -- a slot written, the
+weights replaced, a reset, a reserve, slot folds restarted, a shard set, the context made -- for clipping,
+trimming and the median, bit-exact against tests/clip_oracle.py, tests/trim_oracle.py and
+tests/median_oracle.py.  (The server optimizer's events: test_gpu_serveropt.py::test_state_lifetime.)
+
+    python tests/test_gpu_rule_lifecycle.py median | trimmed     (the child processes)
+"""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+import clip_oracle as CO  # noqa: E402
+import median_oracle as MO  # noqa: E402
+import trim_oracle as TO  # noqa: E402
+from gen_trim_golden import special_rows  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+CLIPPED, TRIMMED, MEDIAN = 3, 4, 5
+STATE = -3
+P = 4101  # one full SUMSQ_TILE (4096) and a ragged tile of 5: not a multiple of 4
+BOUND = 1.0
+
+
+def device():
+    return int(os.environ.get("PGH_DEVICE", "0"))
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from pygrid_amd import Engine
+
+    with Engine(device()) as e:
+        yield e
+
+
+def u32(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def u64(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def clip_rows(n, seed):
+    """n rows of norm ~0.64; rows 1, 4 and 7 of norm ~3.2 (clipped at BOUND); a checkpoint."""
+    rng = np.random.default_rng(seed)
+    d = (rng.standard_normal((n, P)) * 0.01).astype(F)
+    d[1::3] *= F(5)
+    return d, rng.standard_normal(P).astype(F)
+
+
+def sums(rows):
+    return [CO.row_sumsq(r) for r in rows]
+
+
+def refused(status, text, fn, *a):
+    from pygrid_amd.exceptions import AggregationError
+
+    with pytest.raises(AggregationError) as e:
+        fn(*a)
+    assert e.value.status == status and text in str(e.value), e.value
+
+
+# ---- clip: a slot written, the weights replaced ------------------------------------------------------------
+
+@pytest.mark.parametrize("how", ["raw", "state"])
+def test_clip_slot_written(eng, how):
+    from pygrid_amd.state_schema import build_state_fast
+
+    def ingest(slot, row):
+        eng.ingest(slot, row) if how == "raw" else eng.ingest_state(slot, build_state_fast([row]))
+
+    diffs, ckpt = clip_rows(6, 41)
+    other = (diffs[0][::-1] * F(3)).astype(F)  # norm ~1.9: clipped, by another scale than rows 1 and 4
+    s_other = CO.scale(CO.row_sumsq(other), BOUND)
+    assert CO.scale(CO.row_sumsq(diffs[2]), BOUND) == 1 and s_other < 1 and s_other != CO.scales(diffs, BOUND)[1]
+    diffs2 = diffs.copy()
+    diffs2[2] = other
+    eng.set_clip_norm(0)
+    eng.set_layout([P])
+    eng.reserve(6)
+    try:
+        # the cached sum of a slot goes with the diff it was of (clipping off: the sums are computed on demand)
+        for k, d in enumerate(diffs):
+            ingest(k, d)
+        assert np.array_equal(u64(eng.row_sumsq(range(6))), u64(sums(diffs)))
+        ingest(2, other)
+        assert np.array_equal(u64(eng.row_sumsq(range(6))), u64(sums(diffs2)))
+        # the same with the bound set (the sums are queued behind each ingest) and a resident fold
+        # between the two writes: the slab's scales are computed again
+        eng.set_clip_norm(BOUND)
+        for k, d in enumerate(diffs):
+            ingest(k, d)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(CO.fedavg_clipped(ckpt, diffs, BOUND)))
+        ingest(2, other)
+        assert np.array_equal(u64(eng.row_sumsq([2])), u64(sums([other])))
+        want2 = CO.fedavg_clipped(ckpt, diffs2, BOUND)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(want2))
+        # weights replaced: they took the place of the scales, which the next clipped fold computes again
+        eng.set_weights([5.0] * 6)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(want2))
+    finally:
+        eng.set_clip_norm(0)
+
+
+# ---- clip: reset, reserve, slot folds restarted -------------------------------------------------------------
+
+def test_clip_reset_reserve_restart(eng):
+    diffs, ckpt = clip_rows(9, 42)
+    norms = np.sqrt(sums(diffs))
+    eng.set_layout([P])
+    eng.reserve(6)
+    eng.set_clip_norm(BOUND)
+    try:
+        for k in range(6):
+            eng.ingest(k, diffs[k])
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(CO.fedavg_clipped(ckpt, diffs[:6], BOUND)))
+        assert eng.clip_stats() == {"rows": 6, "clipped": 2, "max_norm": norms[:6].max()}
+        eng.reset()
+        assert eng.clip_stats() == {"rows": 0, "clipped": 0, "max_norm": 0.0}
+        # a larger slab: the sum cache has its length (slots 6 .. 8 did not exist before)
+        eng.reserve(9)
+        for k in range(9):
+            eng.ingest(k, diffs[k])
+        assert np.array_equal(u64(eng.row_sumsq(range(9))), u64(sums(diffs)))
+        assert eng.clip_stats()["rows"] == 0
+        # part of a cycle folded, then the restart: the running tally goes with the folds
+        eng.ckpt_upload(ckpt)
+        eng.fold_slots(CLIPPED, [0, 1, 2, 3])
+        assert eng.clip_stats() == {"rows": 4, "clipped": 1, "max_norm": norms[:4].max()}
+        eng.fold_restart()
+        assert eng.clip_stats() == {"rows": 0, "clipped": 0, "max_norm": 0.0}
+        for k in range(4):  # (a fold frees its slots)
+            eng.ingest(k, diffs[k])
+        eng.fold_slots(CLIPPED, [0, 1, 2, 3, 4])
+        eng.fold_slots_finish_resident(CLIPPED, [5, 6, 7, 8])
+        assert np.array_equal(u32(eng.ckpt_download()), u32(CO.fedavg_clipped(ckpt, diffs, BOUND)))
+        assert eng.clip_stats() == {"rows": 9, "clipped": 3, "max_norm": norms.max()}
+    finally:
+        eng.set_clip_norm(0)
+
+
+# ---- clip: a shard set ---------------------------------------------------------------------------------------
+
+def test_clip_shard_clears_the_bound_for_good(eng):
+    diffs, ckpt = clip_rows(3, 43)
+    eng.set_layout([P])
+    eng.set_clip_norm(BOUND)
+    try:
+        eng.set_shard(0, 2048)  # a sub-range: a norm needs the whole row
+        eng.reserve(3)
+        for k in range(3):
+            eng.ingest(k, diffs[k][:2048])
+        refused(STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first", eng.fedavg, CLIPPED, ckpt[:2048])
+        eng.set_shard(0, P)  # the whole model again: the bound does not come back by itself
+        eng.reserve(3)
+        for k in range(3):
+            eng.ingest(k, diffs[k])
+        refused(STATE, "PGH_CLIPPED_MEAN needs a bound: call pgh_set_clip_norm first", eng.fedavg, CLIPPED, ckpt)
+        eng.set_clip_norm(BOUND)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(CO.fedavg_clipped(ckpt, diffs, BOUND)))
+    finally:
+        eng.set_clip_norm(0)
+
+
+# ---- trim: the state planes over a reserve; b and the slot folds -----------------------------------------------
+
+def three_step_trimmed(eng, diffs, ckpt):
+    n = len(diffs)
+    for k, d in enumerate(diffs):
+        eng.ingest(k, d)
+    eng.ckpt_upload(ckpt)
+    eng.fold_slots(TRIMMED, [0, 1])
+    eng.fold_slots(TRIMMED, [2])
+    eng.fold_slots_finish_resident(TRIMMED, list(range(3, n)))
+    return eng.ckpt_download()
+
+
+@pytest.mark.parametrize("b", (1, 2))
+def test_trim_planes_over_a_reserve(eng, b):
+    n = 2 * b + 3  # 5 slots, 7 slots
+    rows = special_rows(2 * n + 3, P, 700 + b)
+    ckpt = np.random.default_rng(b).standard_normal(P).astype(F)
+    first, second = rows[:n], rows[n:]
+    eng.set_trim(0)
+    eng.set_layout([P])
+    eng.reserve(n)
+    eng.set_trim(b)
+    try:
+        assert TO.same_bits(three_step_trimmed(eng, first, ckpt), TO.fedavg_trimmed(ckpt, first, b))
+        eng.reserve(n + 3)  # the planes went with the slab and are made again
+        assert TO.same_bits(three_step_trimmed(eng, second, ckpt), TO.fedavg_trimmed(ckpt, second, b))
+        # b is the cycle's: fixed while its slot folds are under way
+        for k in range(3):
+            eng.ingest(k, first[k])
+        eng.fold_slots(TRIMMED, [0, 1])
+        refused(STATE, "trim count changed", eng.set_trim, b + 1)
+        eng.fold_restart()
+        eng.set_trim(b + 1)
+    finally:
+        eng.fold_restart()
+        eng.set_trim(0)
+
+
+# ---- median: the device row table over a reserve; the environment at creation ------------------------------------
+
+def test_median_row_table_over_a_reserve(eng):
+    p = 64
+    rows = special_rows(600, p, 900, every=5, rows=600)
+    ckpt = np.random.default_rng(9).standard_normal(p).astype(F)
+    eng.set_layout([p])
+    for n in (520, 600):  # both past a RowTab's 512 rows: the slots go to K9 as a device table of `slots` entries
+        eng.reserve(n)
+        order = np.random.default_rng(n).permutation(n)
+        for k in range(n):
+            eng.ingest(int(order[k]), rows[k])
+        eng.ckpt_upload(ckpt)
+        assert eng.effective_variant(MEDIAN) == 50
+        eng.fold_slots_finish_resident(MEDIAN, order)
+        assert MO.same_bits(eng.ckpt_download(), MO.fedavg_median(ckpt, rows[:n])), n
+
+
+def child(what, **env):
+    r = subprocess.run([sys.executable, str(Path(__file__).resolve()), what], env=dict(os.environ, **env),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    return r.stdout
+
+
+def test_median_path_is_read_at_creation():
+    assert "median variant 51" in child("median", PGH_MEDIAN_PATH="passes")
+
+
+def test_trim_vec_is_read_at_creation():
+    assert child("trimmed", PGH_TRIM_VEC="1").split() == ["trimmed", "variant", "41", "trimmed", "variant", "40"]
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] not in (["median"], ["trimmed"]):
+        sys.exit("usage: test_gpu_rule_lifecycle.py median | trimmed")
+    from pygrid_amd import Engine
+
+    for vec in (None,) if sys.argv[1] == "median" else (None, "4"):  # (None: the environment as the parent set it)
+        if vec:
+            os.environ["PGH_TRIM_VEC"] = vec
+        with Engine(device()) as made:
+            made.set_layout([P])
+            made.reserve(5)
+            if sys.argv[1] == "median":
+                for k in range(5):
+                    made.ingest(k, np.full(P, k, F))
+                print("median variant", made.effective_variant(MEDIAN))
+            else:
+                made.set_trim(1)
+                print("trimmed variant", made.effective_variant(TRIMMED))
