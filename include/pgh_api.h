@@ -407,7 +407,7 @@ int pgh_stream_finish_secagg(pgh_ctx* ctx, int base, int prec, int64_t* sum_out,
 int pgh_stream_finish_secagg_device(pgh_ctx* ctx, int base, int prec, int64_t* d_sum, float* d_dec, void* stream);
 
 /* ---- tuning and observability -------------------------------------------------------------- */
-/* Kernel variant for A/B measurement (table in csrc/pgh_kernels.hip); -1 = the default, which
+/* Kernel variant for A/B measurement (table in csrc/pgh_variants.def); -1 = the default, which
  * picks by shard size (auto_variant in csrc/pgh_kernels.hip). */
 #define PGH_DEFAULT_VARIANT (-1)
 int pgh_set_variant(pgh_ctx* ctx, int variant);

@@ -379,7 +379,8 @@ int pgh_reset(pgh_ctx* c) {
 int pgh_set_variant(pgh_ctx* c, int variant) {
     if (c && c->grp) return pgh_group_api::set_variant(c, variant);
     if (!c) return PGH_E_ARG;
-    if (variant < -1 || variant > 23) return fail(c, PGH_E_ARG, "variant %d outside [-1,23]", variant);
+    if (variant < -1 || variant >= pgh::N_VARIANTS)
+        return fail(c, PGH_E_ARG, "variant %d outside [-1,%d]", variant, pgh::N_VARIANTS - 1);
     c->variant = variant;
     return PGH_OK;
 }

@@ -445,9 +445,8 @@ inline int trim_variant(const pgh_ctx* c) {
 // The path a median fold of n rows takes: 50 (K9, on chip) or 51 (K9p, one pass per bit).
 inline int median_variant(const pgh_ctx* c, int64_t n) { return c->med.passes || n > pgh::MEDIAN_NCHIP ? 51 : 50; }
 // The whole median fold of a filled FedavgArgs (diffs, map, n_rows, p, ckpt, out; every row of the
-// cycle) on stream s: K9's one launch or K9p's 32 or 33.  The rows: tab, else d_rows (a device table
-// of n_rows entries), else contiguous from a.diffs.
-int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s);
+// cycle) on stream s: K9's one launch or K9p's 32 or 33.
+int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hipStream_t s);
 // slots[k] * parties for k < n, uploaded to d_rowidx on stream s (waits for the copy)
 int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s);
 inline const int32_t* median_rows(const pgh_ctx* c) { return c->med.d_rowidx.as<int32_t>(); }  // that table
@@ -473,12 +472,11 @@ struct FinalArgs {
 // weights of all of them on the device (weighted, clipped), the reciprocal table covering them (iterative).
 int fold_prepare(pgh_ctx* c, int mode, int64_t total, hipStream_t s);
 // The rows of one launch: n contiguous slab rows from `diffs`, or, with diffs = the slab at row 0,
-// the rows of tab or (a median of more rows than a RowTab carries) of the device table d_rows.
+// the rows of a RowTab or (a median of more rows than a RowTab carries) of a device table.
 struct FoldRows {
     const float* diffs;
     int n;
-    const pgh::RowTab* tab = nullptr;
-    const int32_t* d_rows = nullptr;
+    pgh::Rows src;
 };
 // One launch (the median: all of its launches) of `mode` over the shard params [fa.off, fa.off + fa.len)
 // on stream s, timed and accounted; client0 = the fold index of row 0.

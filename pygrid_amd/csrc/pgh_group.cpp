@@ -897,7 +897,8 @@ int stream_finish_secagg(pgh_ctx* c, int base, int prec, int64_t* sum_out, float
 }
 
 int set_variant(pgh_ctx* c, int variant) {
-    if (variant < -1 || variant > 23) return fail(c, PGH_E_ARG, "variant %d outside [-1,23]", variant);
+    if (variant < -1 || variant >= pgh::N_VARIANTS)
+        return fail(c, PGH_E_ARG, "variant %d outside [-1,%d]", variant, pgh::N_VARIANTS - 1);
     return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_variant(k, variant); }, (int)G(c)->kids.size());
 }
 

@@ -48,7 +48,7 @@ struct FedavgArgs {
     float divisor;          // float(N) or sum of weights, FL_FINAL of MEAN / WEIGHTED
     int flags;
     int mode;
-    int variant;            // kernel variant (table in pgh_kernels.hip); < 0 = auto by shard size
+    int variant;            // kernel variant (table in pgh_variants.def); < 0 = auto by shard size
     // MODE_TRIMMED (K8, the streaming definition in include/pgh_api.h): b = trim_b values dropped per
     // side; divisor = float(N - 2b); client0 + r is the fold index k of row r.  The selection state
     // of a param lives in registers for the launch; a launch without FL_FIRST reads it and a launch
@@ -61,26 +61,48 @@ struct FedavgArgs {
 };
 // The column width K8 takes for a shard of p params at b (variant ids 40: 16-byte, 41: one param).
 int auto_trim_vec(int64_t p, int b);
-hipError_t launch_fedavg(const FedavgArgs& a, hipStream_t s);
 
-// Slab rows of one fold launch given by index instead of contiguous from `diffs`: row r of the
-// launch is slab row rows[r] (a.diffs = the slab at row 0).  Report-time aggregation folds the
-// reported diffs where they landed, in assignment order, skipping workers that never reported
+// The fold's and the share sum's variant ids: 0 .. N_VARIANTS - 1, one PGH_FOLD row each, in order.
+constexpr int N_VARIANTS = 0
+#define PGH_FOLD(...) +1
+#include "pgh_variants.def"
+    ;
+constexpr bool variant_ids_in_order() {
+    int next = 0;
+    bool ok = true;
+#define PGH_FOLD(id, ...) ok = ok && id == next++;
+#define PGH_SECAGG(id, ...) ok = ok && id >= 0 && id < next;
+#include "pgh_variants.def"
+    return ok && next == N_VARIANTS;
+}
+static_assert(variant_ids_in_order(), "pgh_variants.def: fold ids 0, 1, 2, ... each once; share-sum ids among them");
+
+// Slab rows given by index instead of contiguous: row r of the launch is slab row rows[r] (the
+// launch's slab pointer = the slab at row 0).  Report-time aggregation folds the reported diffs where
+// they landed, in assignment order, skipping workers that never reported
 // (cycle_manager.py:243-245).  Passed by value as a kernel argument (scalar loads from the
-// kernarg segment), so a launch folds at most ROWTAB_MAX rows.
+// kernarg segment), so a launch covers at most ROWTAB_MAX rows.
 constexpr int ROWTAB_MAX = 512;
 struct RowTab {
     int32_t rows[ROWTAB_MAX];
 };
-hipError_t launch_fedavg_rows(const FedavgArgs& a, const RowTab& t, hipStream_t s);
+// Which slab rows a launch of n_rows rows reads: tab->rows[r], else d_rows[r] (a device table of
+// n_rows entries), else row0 + r.  At most one table is set, and row0 is 0 beside one.  The fold and
+// K7 have no kernel for a device table.  The fold and the median take their contiguous rows from
+// the slab pointer they are given (row0 = 0); K7, whose outputs are indexed by slab row, from row0.
+struct Rows {
+    const RowTab* tab = nullptr;
+    const int32_t* d_rows = nullptr;
+    int row0 = 0;
+};
+// (a row table runs the shapes pgh_variants.def marks rowtab, launch_fedavg in pgh_kernels.hip)
+hipError_t launch_fedavg(const FedavgArgs& a, const Rows& rows, hipStream_t s);
 
 // MODE_MEDIAN (the definition is in include/pgh_api.h): out = ckpt - median over the launch's rows,
 // per param.  Values are compared as u = key(x) ^ 0x80000000 (unsigned order = the key's signed
 // order); the element of rank (n - 1) / 2 is found by bisection on u, most significant bit first:
 // T = prefix | 1 << bit; prefix = T when #{u < T} <= rank.  An even n also needs the next element:
 // with c = #{u <= lower} it is lower when c >= n / 2 + 1 and min{u > lower} otherwise.
-// The rows: tab (at most ROWTAB_MAX, by value), else rowidx (a device table of n_rows slab rows),
-// else n_rows contiguous rows from diffs.
 // K9 launch_median: one pass over HBM.  The rows of a tile of 64 columns come on chip as keys in
 // registers, one column per lane: up to 64 rows in one lane (8 / 16 / 32 / 64 keys), more rows split
 // over the 2 / 4 / 8 / MEDIAN_WAVES waves of a workgroup (64 keys per lane, wave w holding rows w,
@@ -92,17 +114,17 @@ hipError_t launch_fedavg_rows(const FedavgArgs& a, const RowTab& t, hipStream_t 
 constexpr int MEDIAN_WAVES = 16;
 constexpr int MEDIAN_NCHIP = 64 * MEDIAN_WAVES;
 struct MedianArgs {
-    const float* diffs;      // the slab at row 0 (tab / rowidx) or at the first row
+    const float* diffs;      // the slab at row 0 (a table) or at the first row
     SlabMap map;             // map.off = shard param of local column 0
     int n_rows;
     int64_t p;               // params of the launch
-    const int32_t* rowidx;   // device, [n_rows]; nullptr = contiguous rows (or tab)
+    const int32_t* d_rows;   // the launcher's: Rows::d_rows on its way to the kernel
     const float* ckpt;       // [p]
     float* out;              // [p]
     uint32_t* prefix;        // [p], K9p only
 };
-hipError_t launch_median(const MedianArgs& a, const RowTab* tab, hipStream_t s);
-hipError_t launch_median_pass(const MedianArgs& a, const RowTab* tab, int bit, hipStream_t s);
+hipError_t launch_median(const MedianArgs& a, const Rows& rows, hipStream_t s);
+hipError_t launch_median_pass(const MedianArgs& a, const Rows& rows, int bit, hipStream_t s);
 
 struct SecaggArgs {
     const int64_t* shares;  // slab at the first row (rows = clients x parties)
@@ -170,20 +192,20 @@ hipError_t launch_gather_f32(const uint8_t* bytes, const GChunk* chunks, int n_c
 // SUMSQ_TILE params, 256 lane partials per tile (lane l adds the squares of its four 16-byte columns
 // 4(l + 256j) .. + 3, j = 0 .. 3, in index order), a shuffle tree per wave, ((w0 + w1) + w2) + w3,
 // then a left fold of the row's tile partials.  Params at or past p count as +0.0.  The launch
-// covers n_rows slab rows (row0 .. row0 + n_rows - 1, or tab->rows[0 .. n_rows) with tab set;
-// n_rows <= ROWTAB_MAX then), writes part[row * ntiles + t] and then sumsq[row] (row = slab row).
+// covers the n_rows slab rows of its Rows (contiguous from row0, or a RowTab), writes
+// part[row * ntiles + t] and then sumsq[row] (row = slab row).
 constexpr int SUMSQ_TILE = 4096;
 struct SumsqArgs {
     const float* slab;   // the slab at row 0
     SlabMap map;         // map.off = 0
     int64_t p;           // params in the shard
     int64_t ntiles;      // ceil(p / SUMSQ_TILE)
-    int row0;
+    int row0;            // the launcher's: Rows::row0 on its way to the kernel
     int n_rows;
     double* part;        // [slab rows][ntiles]
     double* sumsq;       // [slab rows]
 };
-hipError_t launch_row_sumsq(const SumsqArgs& a, const RowTab* tab, hipStream_t s);
+hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s);
 
 // K10: the server optimizer's step behind a FINAL fold (the definition is in include/pgh_api.h).  The
 // fold ran with ckpt = a plane of -0.0f and out = d, so d = (-0.0f) - g, which is -g bit for bit for

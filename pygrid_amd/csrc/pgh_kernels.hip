@@ -137,13 +137,15 @@ __device__ __forceinline__ f32x4 iter_step(f32x4 acc, f32x4 v, float kf, double 
     return o;
 }
 
-// Slab row of the launch's row r: r itself (contiguous rows from a.diffs), or the r-th entry of
-// the row table (IDX: report-time folds of scattered slots; the index is wave-uniform, so it is a
-// scalar load from the kernarg segment).
-template <bool IDX>
-__device__ __forceinline__ size_t row_at(const RowTab* t, int r) {
-    if constexpr (IDX) return (size_t)(uint32_t)t->rows[r];
-    else return (size_t)r;
+// Slab row of the launch's row r (Rows in pgh_kernels.h; wave-uniform, so a table entry is a scalar
+// load): SRC 0 contiguous from row0, 1 the RowTab (report-time folds of scattered slots: the kernarg
+// segment), 2 the device table.  The device functions hand Rows on by value: behind a reference the
+// deepest iterative row-table fold (U = 64) kept its RowTab in scratch.
+template <int SRC>
+__device__ __forceinline__ size_t row_at(const Rows rows, int r) {
+    if constexpr (SRC == 1) return (size_t)(uint32_t)rows.tab->rows[r];
+    else if constexpr (SRC == 2) return (size_t)(uint32_t)rows.d_rows[r];
+    else return (size_t)(rows.row0 + r);
 }
 
 // Fold rows r .. r + nv - 1 (nv <= U, already loaded in v) into acc, in order.  nv is U for full
@@ -195,8 +197,8 @@ __device__ __forceinline__ void fold_rows(T (&acc)[W], const T (&v)[U][W], const
 
 // W columns per lane (q0, q0 + qstep, ...: each load instruction of a wave still reads one
 // contiguous span), all rows of the chunk, in order.  VEC consecutive params per column.
-template <int MODE, int U, int W, bool NT, int VEC, bool IDX = false>
-__device__ __forceinline__ void fedavg_columns(const FedavgArgs& a, const RowTab* tab, int64_t q0, int64_t qstep) {
+template <int MODE, int U, int W, bool NT, int VEC, int SRC>
+__device__ __forceinline__ void fedavg_columns(const FedavgArgs& a, const Rows rows, int64_t q0, int64_t qstep) {
     using L = Lane<VEC>;
     using T = typename L::T;
     const int n = a.n_rows;
@@ -209,7 +211,7 @@ __device__ __forceinline__ void fedavg_columns(const FedavgArgs& a, const RowTab
     if (a.flags & FL_FIRST) {
 #pragma unroll
         for (int w = 0; w < W; ++w) {
-            acc[w] = L::template load<NT>(col[w] + row_at<IDX>(tab, 0) * ld);  // fold starts at d0, not 0
+            acc[w] = L::template load<NT>(col[w] + row_at<SRC>(rows, 0) * ld);  // fold starts at d0, not 0
             if constexpr (MODE == MODE_WEIGHTED) acc[w] = acc[w] * a.weights[0];
         }
         r = 1;
@@ -224,7 +226,7 @@ __device__ __forceinline__ void fedavg_columns(const FedavgArgs& a, const RowTab
         for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int w = 0; w < W; ++w)
-                v[u][w] = L::template load<NT>(col[w] + row_at<IDX>(tab, r + u) * ld);
+                v[u][w] = L::template load<NT>(col[w] + row_at<SRC>(rows, r + u) * ld);
         fold_rows<MODE, U, W>(acc, v, a, r, U);
     }
     if (r < n) {  // the last partial batch, its loads in flight together
@@ -234,7 +236,7 @@ __device__ __forceinline__ void fedavg_columns(const FedavgArgs& a, const RowTab
         for (int u = 0; u < U; ++u)
             if (u < nv)
 #pragma unroll
-                for (int w = 0; w < W; ++w) v[u][w] = L::template load<NT>(col[w] + row_at<IDX>(tab, r + u) * ld);
+                for (int w = 0; w < W; ++w) v[u][w] = L::template load<NT>(col[w] + row_at<SRC>(rows, r + u) * ld);
         fold_rows<MODE, U, W>(acc, v, a, r, nv);
     }
 #pragma unroll
@@ -330,29 +332,29 @@ __device__ __forceinline__ int64_t tile_of_wg() {
 }
 
 // Grid-stride over tiles of TB x W columns; a partial last tile goes one column per lane.
-template <int MODE, int U, int W, bool NT, int TB, int VEC, bool IDX, bool XMAP = false>
-__device__ __forceinline__ void fedavg_tiles(const FedavgArgs& a, const RowTab* tab, int64_t ncol) {
+template <int MODE, int U, int W, bool NT, int TB, int VEC, int SRC, bool XMAP = false>
+__device__ __forceinline__ void fedavg_tiles(const FedavgArgs& a, const Rows rows, int64_t ncol) {
     const int64_t tile = (int64_t)TB * W;
     for (int64_t t0 = tile_of_wg<XMAP>() * tile; t0 < ncol; t0 += (int64_t)gridDim.x * tile) {
         const int64_t q0 = t0 + threadIdx.x;
         if (t0 + tile <= ncol) {
-            fedavg_columns<MODE, U, W, NT, VEC, IDX>(a, tab, q0, TB);
+            fedavg_columns<MODE, U, W, NT, VEC, SRC>(a, rows, q0, TB);
         } else {
             for (int64_t q = q0; q < ncol && q < t0 + tile; q += TB)
-                fedavg_columns<MODE, U, 1, NT, VEC, IDX>(a, tab, q, TB);
+                fedavg_columns<MODE, U, 1, NT, VEC, SRC>(a, rows, q, TB);
         }
     }
 }
 
 template <int MODE, int U, int W, bool NT, int TB, int VEC, bool XMAP = false>
 __global__ __launch_bounds__(TB) void k_fedavg(FedavgArgs a, int64_t ncol) {
-    fedavg_tiles<MODE, U, W, NT, TB, VEC, false, XMAP>(a, nullptr, ncol);
+    fedavg_tiles<MODE, U, W, NT, TB, VEC, 0, XMAP>(a, Rows{}, ncol);
 }
 
 // The same fold over the slab rows listed in `tab` (report-time aggregation, pgh_fold_slots).
 template <int MODE, int U, int W, bool NT, int TB, int VEC>
 __global__ __launch_bounds__(TB) void k_fedavg_rows(FedavgArgs a, int64_t ncol, RowTab tab) {
-    fedavg_tiles<MODE, U, W, NT, TB, VEC, true>(a, &tab, ncol);
+    fedavg_tiles<MODE, U, W, NT, TB, VEC, 1>(a, Rows{&tab}, ncol);
 }
 
 // K8: coordinate-wise trimmed mean (MODE_TRIMMED; the definition is in include/pgh_api.h).  The same
@@ -422,8 +424,8 @@ __device__ __forceinline__ void trim_plane_store(int32_t* plane, int64_t q, int6
     Lane<VEC>::store_tail(reinterpret_cast<float*>(plane), q, p, v);
 }
 
-template <int B, int U, int VEC, bool IDX>
-__device__ __forceinline__ void trim_column(const FedavgArgs& a, const RowTab* tab, int64_t q) {
+template <int B, int U, int VEC, int SRC>
+__device__ __forceinline__ void trim_column(const FedavgArgs& a, const Rows rows, int64_t q) {
     using L = Lane<VEC>;
     using T = typename L::T;
     const int n = a.n_rows;
@@ -459,13 +461,13 @@ __device__ __forceinline__ void trim_column(const FedavgArgs& a, const RowTab* t
         T v[U];
         if (nv == U && k0 > 2 * B) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = L::template load<true>(col + row_at<IDX>(tab, r + u) * ld);
+            for (int u = 0; u < U; ++u) v[u] = L::template load<true>(col + row_at<SRC>(rows, r + u) * ld);
 #pragma unroll
             for (int u = 0; u < U; ++u) trim_step<B, VEC, true>(s, v[u], k0 + u);
         } else {
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                if (u < nv) v[u] = L::template load<true>(col + row_at<IDX>(tab, r + u) * ld);
+                if (u < nv) v[u] = L::template load<true>(col + row_at<SRC>(rows, r + u) * ld);
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (u < nv) trim_step<B, VEC, false>(s, v[u], k0 + u);
@@ -493,13 +495,13 @@ __device__ __forceinline__ void trim_column(const FedavgArgs& a, const RowTab* t
 template <int B, int U, int TB, int VEC>
 __global__ __launch_bounds__(TB) void k_fedavg_trim(FedavgArgs a, int64_t ncol) {
     const int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x;
-    if (q < ncol) trim_column<B, U, VEC, false>(a, nullptr, q);
+    if (q < ncol) trim_column<B, U, VEC, 0>(a, Rows{}, q);
 }
 
 template <int B, int U, int TB, int VEC>
 __global__ __launch_bounds__(TB) void k_fedavg_trim_rows(FedavgArgs a, int64_t ncol, RowTab tab) {
     const int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x;
-    if (q < ncol) trim_column<B, U, VEC, true>(a, &tab, q);
+    if (q < ncol) trim_column<B, U, VEC, 1>(a, Rows{&tab}, q);
 }
 
 // K9 / K9p: coordinate-wise median (MODE_MEDIAN; the definition is in include/pgh_api.h, the
@@ -510,14 +512,6 @@ __device__ __forceinline__ float med_value(uint32_t u) { return __int_as_float(t
 __device__ __forceinline__ float med_mid(uint32_t lower, uint32_t upper, bool even) {
     const float a = med_value(lower);
     return even ? __fadd_rn(__fmul_rn(0.5f, a), __fmul_rn(0.5f, med_value(upper))) : a;
-}
-
-// Slab row of the launch's row r (wave-uniform): SRC 0 contiguous, 1 the RowTab, 2 the device table.
-template <int SRC>
-__device__ __forceinline__ size_t med_row(const MedianArgs& a, const RowTab* t, int r) {
-    if constexpr (SRC == 1) return (size_t)(uint32_t)t->rows[r];
-    else if constexpr (SRC == 2) return (size_t)(uint32_t)a.rowidx[r];
-    else return (size_t)r;
 }
 
 // K9.  A tile = 64 consecutive columns; lane l of a wave owns column l of its tile, so a wave-wide
@@ -533,7 +527,7 @@ __device__ __forceinline__ size_t med_row(const MedianArgs& a, const RowTab* t, 
 // bit two LDS operations on top.  W = 1 (up to 64 rows): a lane holds its whole column, no LDS and no
 // barrier, four independent tiles per 256-thread workgroup.
 template <int W, int KPL, int SRC>
-__device__ __forceinline__ void median_tile(const MedianArgs& a, const RowTab* tab) {
+__device__ __forceinline__ void median_tile(const MedianArgs& a, const Rows rows) {
     __shared__ uint32_t s_cnt[3][64];
     __shared__ uint32_t s_min[64];
     const int lane = threadIdx.x & 63;
@@ -548,7 +542,7 @@ __device__ __forceinline__ void median_tile(const MedianArgs& a, const RowTab* t
     for (int j = 0; j < KPL; ++j) {
         const int r = w + W * j;
         k[j] = 0x7fffffffu;  // bits of the largest key
-        if (r < n && live) k[j] = __builtin_nontemporal_load(col + med_row<SRC>(a, tab, r) * ld);
+        if (r < n && live) k[j] = __builtin_nontemporal_load(col + row_at<SRC>(rows, r) * ld);
     }
     if constexpr (W > 1) {
         if (w == 0) {
@@ -601,17 +595,17 @@ __device__ __forceinline__ void median_tile(const MedianArgs& a, const RowTab* t
 
 template <int W, int KPL, int SRC>
 __global__ __launch_bounds__(W == 1 ? BLOCK : 64 * W) void k_median(MedianArgs a) {
-    median_tile<W, KPL, SRC>(a, nullptr);
+    median_tile<W, KPL, SRC>(a, Rows{nullptr, a.d_rows});
 }
 template <int W, int KPL>
 __global__ __launch_bounds__(W == 1 ? BLOCK : 64 * W) void k_median_tab(MedianArgs a, RowTab tab) {
-    median_tile<W, KPL, 1>(a, &tab);
+    median_tile<W, KPL, 1>(a, Rows{&tab});
 }
 
 // K9p: one step of the same bisection with the prefix in HBM: the K1 walk (one lane down its
 // column, U loads in flight) counting instead of adding.  3 (key) + 2 ops per float and pass.
 template <int SRC, int U>
-__device__ __forceinline__ void median_pass(const MedianArgs& a, const RowTab* tab, int bit) {
+__device__ __forceinline__ void median_pass(const MedianArgs& a, const Rows rows, int bit) {
     const int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= a.p) return;
     const int n = a.n_rows;
@@ -626,7 +620,7 @@ __device__ __forceinline__ void median_pass(const MedianArgs& a, const RowTab* t
         uint32_t x[U];
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (u < nv) x[u] = __builtin_nontemporal_load(col + med_row<SRC>(a, tab, r + u) * ld);
+            if (u < nv) x[u] = __builtin_nontemporal_load(col + row_at<SRC>(rows, r + u) * ld);
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (u < nv) {
@@ -651,10 +645,10 @@ __device__ __forceinline__ void median_pass(const MedianArgs& a, const RowTab* t
 
 template <int SRC>
 __global__ __launch_bounds__(BLOCK) void k_median_pass(MedianArgs a, int bit) {
-    median_pass<SRC, 16>(a, nullptr, bit);
+    median_pass<SRC, 16>(a, Rows{nullptr, a.d_rows}, bit);
 }
 __global__ __launch_bounds__(BLOCK) void k_median_pass_tab(MedianArgs a, int bit, RowTab tab) {
-    median_pass<1, 16>(a, &tab, bit);
+    median_pass<1, 16>(a, Rows{&tab}, bit);
 }
 
 // Z_2^64 lane element: VEC = 2 (16-byte column of 2 int64) or 1 (one int64 per lane).
@@ -1094,8 +1088,8 @@ __global__ __launch_bounds__(256) void k_varint_decode(const uint8_t* bytes, con
 // bytes); a launch's last row group repeats its last row instead of branching around the loads.
 constexpr int SUMSQ_RB = 4;
 
-template <bool IDX>
-__device__ __forceinline__ void row_sumsq_tile(const SumsqArgs& a, const RowTab* tab) {
+template <int SRC>
+__device__ __forceinline__ void row_sumsq_tile(const SumsqArgs& a, const Rows rows) {
     __shared__ double wsum[SUMSQ_RB][4];
     const int lane = threadIdx.x, wave = lane >> 6;
     const int64_t t = blockIdx.x, base = t * SUMSQ_TILE;
@@ -1113,7 +1107,7 @@ __device__ __forceinline__ void row_sumsq_tile(const SumsqArgs& a, const RowTab*
 #pragma unroll
     for (int rr = 0; rr < SUMSQ_RB; ++rr) {
         const int r = r0 + min(rr, nr - 1);
-        row[rr] = IDX ? (size_t)(uint32_t)tab->rows[r] : (size_t)(a.row0 + r);
+        row[rr] = row_at<SRC>(rows, r);
     }
     f32x4 v[SUMSQ_RB][4];
 #pragma unroll
@@ -1141,17 +1135,17 @@ __device__ __forceinline__ void row_sumsq_tile(const SumsqArgs& a, const RowTab*
             a.part[row[rr] * (size_t)a.ntiles + (size_t)t] = ((wsum[rr][0] + wsum[rr][1]) + wsum[rr][2]) + wsum[rr][3];
 }
 
-__global__ __launch_bounds__(BLOCK) void k_row_sumsq(SumsqArgs a) { row_sumsq_tile<false>(a, nullptr); }
-__global__ __launch_bounds__(BLOCK) void k_row_sumsq_rows(SumsqArgs a, RowTab tab) { row_sumsq_tile<true>(a, &tab); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq(SumsqArgs a) { row_sumsq_tile<0>(a, Rows{nullptr, nullptr, a.row0}); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_rows(SumsqArgs a, RowTab tab) { row_sumsq_tile<1>(a, Rows{&tab}); }
 
 // The row's tile partials, left-folded in ascending tile order by one lane; the workgroup brings
 // them into LDS 1,024 at a time (coalesced) so the serial chain reads LDS, not HBM.
 constexpr int SUMSQ_FOLD_CHUNK = 4 * BLOCK;
 
-template <bool IDX>
-__device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const RowTab* tab) {
+template <int SRC>
+__device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const Rows rows) {
     __shared__ double buf[SUMSQ_FOLD_CHUNK];
-    const size_t row = IDX ? (size_t)(uint32_t)tab->rows[blockIdx.x] : (size_t)(a.row0 + (int)blockIdx.x);
+    const size_t row = row_at<SRC>(rows, (int)blockIdx.x);
     const double* part = a.part + row * (size_t)a.ntiles;
     double acc = 0.0;  // + 0.0 + partial 0 is partial 0 (partials are never -0.0)
     for (int64_t c0 = 0; c0 < a.ntiles; c0 += SUMSQ_FOLD_CHUNK) {
@@ -1165,8 +1159,8 @@ __device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const RowTab*
     if (threadIdx.x == 0) a.sumsq[row] = acc;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold(SumsqArgs a) { row_sumsq_fold<false>(a, nullptr); }
-__global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold_rows(SumsqArgs a, RowTab tab) { row_sumsq_fold<true>(a, &tab); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold(SumsqArgs a) { row_sumsq_fold<0>(a, Rows{nullptr, nullptr, a.row0}); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold_rows(SumsqArgs a, RowTab tab) { row_sumsq_fold<1>(a, Rows{&tab}); }
 
 int cu_count() {
     static int cached[64] = {0};
@@ -1180,36 +1174,14 @@ int cu_count() {
     return cached[dev];
 }
 
-// Variants (A/B in one process: tools/ab_variants.py; profiles/r01*/README.md).
-//   id  loads  U (rows in flight)  W (cols/lane)  block  VEC (params/col)  grid
-//   0   nt     8                   1              256    4                 one lane per column  <- big shards
-//   1   nt     8                   1              256    4                 persistent, 4 blocks/CU
-//   2   plain  8                   1              256    4                 one lane per column
-//   3   plain  8                   1              256    4                 persistent
-//   4   plain  16                  1              256    4                 one lane per column
-//   5   plain  16                  1              256    4                 persistent
-//   6   nt     16                  1              256    4                 one lane per column
-//   7   nt     4                   2              256    4                 one lane per W columns
-//   8   nt     8                   2              256    4                 one lane per W columns
-//   9   nt     8                   1              512    4                 one lane per column
-//   10  nt     4                   1              256    4                 one lane per column
-//   11  nt     16                  1              64     4                 one lane per column
-//   12  nt     16                  1              64     1                 one lane per param
-//   13  nt     8                   1              256    1                 one lane per param
-//   14  nt     32                  1              64     1                 one lane per param
-//   15  nt     32                  1              64     4                 one lane per column
-//   16  nt     48                  1              64     1                 one lane per param
-//   17  nt     64                  1              64     1                 one lane per param
-//   18  nt     32                  1              128    1                 one lane per param
-//   19  nt     16                  1              512    4                 one lane per column
-//   20  nt     8                   1              1024   4                 one lane per column
-//   21  nt     8 (+8 next batch)   1              256    4                 one lane per column, pipelined
-//   22  nt     4 (+4 next batch)   1              256    4                 one lane per column, pipelined
-//   23  nt     8                   1              256    4                 as 0, each XCD a contiguous eighth
+// The launch shapes are the rows of pgh_variants.def; these are the words its columns are written in.
 // nt loads won 2-5 % on the once-read diff stream (r01c).  Small shards are bound by lanes / CU
 // balance, not by the loads: the auto choice (variant -1) picks by shard size and mode
 // (auto_variant below, r01l measurements on the column-blocked slab).
-constexpr int N_VARIANTS = 24;
+namespace shape {
+enum Grid { tile, persistent, pipelined, xmap };
+constexpr bool nt = true, plain = false, rowtab = true, no_rowtab = false;
+}  // namespace shape
 
 inline unsigned grid_for(int64_t ncol, int64_t tile, bool persistent) {
     const int64_t full = (ncol + tile - 1) / tile;
@@ -1218,69 +1190,46 @@ inline unsigned grid_for(int64_t ncol, int64_t tile, bool persistent) {
     return (unsigned)(full < pers ? (full > 0 ? full : 1) : pers);
 }
 
-template <int MODE, int U, int W, bool NT, int TB, int VEC, bool XMAP = false>
-hipError_t go_fedavg(const FedavgArgs& a, bool persistent, hipStream_t s) {
+// One fold shape.  With a row table it runs k_fedavg_rows, which exists for the TAB shapes only
+// (launch_fedavg sends no other shape a table).
+template <int MODE, bool NT, int U, int W, int TB, int VEC, shape::Grid G, bool TAB>
+hipError_t go_fedavg(const FedavgArgs& a, const Rows& rows, hipStream_t s) {
+    static_assert(G != shape::pipelined || W == 1, "the pipelined walk has one column per lane");
+    static_assert(!TAB || G == shape::tile, "k_fedavg_rows has the plain grid");
     const int64_t ncol = (a.p + VEC - 1) / VEC;
-    k_fedavg<MODE, U, W, NT, TB, VEC, XMAP><<<grid_for(ncol, (int64_t)TB * W, persistent), TB, 0, s>>>(a, ncol);
-    return hipGetLastError();
-}
-
-template <int MODE, int U, int W, bool NT, int TB, int VEC>
-hipError_t go_fedavg_rows(const FedavgArgs& a, const RowTab& t, hipStream_t s) {
-    const int64_t ncol = (a.p + VEC - 1) / VEC;
-    k_fedavg_rows<MODE, U, W, NT, TB, VEC><<<grid_for(ncol, (int64_t)TB * W, false), TB, 0, s>>>(a, ncol, t);
-    return hipGetLastError();
-}
-
-// Indexed folds exist for the shapes the auto choice picks (auto_variant); an explicitly chosen
-// variant outside them runs the auto shape for its shard.
-template <int MODE>
-hipError_t dispatch_fedavg_rows(const FedavgArgs& a, const RowTab& t, int variant, hipStream_t s) {
-    switch (variant) {
-    case 11: return go_fedavg_rows<MODE, 16, 1, true, 64, 4>(a, t, s);
-    case 14: return go_fedavg_rows<MODE, 32, 1, true, 64, 1>(a, t, s);
-    case 17: return go_fedavg_rows<MODE, 64, 1, true, 64, 1>(a, t, s);
-    default: return go_fedavg_rows<MODE, 8, 1, true, 256, 4>(a, t, s);  // variant 0
+    const unsigned grid = grid_for(ncol, (int64_t)TB * W, G == shape::persistent);
+    if (rows.tab) {
+        if constexpr (TAB) k_fedavg_rows<MODE, U, W, NT, TB, VEC><<<grid, TB, 0, s>>>(a, ncol, *rows.tab);
+        else return hipErrorInvalidValue;
+    } else if constexpr (G == shape::pipelined) {
+        k_fedavg_pipe<MODE, U, NT, TB, VEC><<<grid, TB, 0, s>>>(a, ncol);
+    } else {
+        k_fedavg<MODE, U, W, NT, TB, VEC, G == shape::xmap><<<grid, TB, 0, s>>>(a, ncol);
     }
-}
-
-template <int MODE, int U, int TB, int VEC>
-hipError_t go_fedavg_pipe(const FedavgArgs& a, hipStream_t s) {
-    const int64_t ncol = (a.p + VEC - 1) / VEC;
-    k_fedavg_pipe<MODE, U, true, TB, VEC><<<grid_for(ncol, TB, false), TB, 0, s>>>(a, ncol);
     return hipGetLastError();
 }
 
 template <int MODE>
-hipError_t dispatch_fedavg(const FedavgArgs& a, int variant, hipStream_t s) {
+hipError_t dispatch_fedavg(const FedavgArgs& a, const Rows& rows, int variant, hipStream_t s) {
+    using namespace shape;
     switch (variant) {
-    case 0: return go_fedavg<MODE, 8, 1, true, 256, 4>(a, false, s);
-    case 1: return go_fedavg<MODE, 8, 1, true, 256, 4>(a, true, s);
-    case 2: return go_fedavg<MODE, 8, 1, false, 256, 4>(a, false, s);
-    case 3: return go_fedavg<MODE, 8, 1, false, 256, 4>(a, true, s);
-    case 4: return go_fedavg<MODE, 16, 1, false, 256, 4>(a, false, s);
-    case 5: return go_fedavg<MODE, 16, 1, false, 256, 4>(a, true, s);
-    case 6: return go_fedavg<MODE, 16, 1, true, 256, 4>(a, false, s);
-    case 7: return go_fedavg<MODE, 4, 2, true, 256, 4>(a, false, s);
-    case 8: return go_fedavg<MODE, 8, 2, true, 256, 4>(a, false, s);
-    case 9: return go_fedavg<MODE, 8, 1, true, 512, 4>(a, false, s);
-    case 10: return go_fedavg<MODE, 4, 1, true, 256, 4>(a, false, s);
-    case 11: return go_fedavg<MODE, 16, 1, true, 64, 4>(a, false, s);
-    case 12: return go_fedavg<MODE, 16, 1, true, 64, 1>(a, false, s);
-    case 13: return go_fedavg<MODE, 8, 1, true, 256, 1>(a, false, s);
-    case 14: return go_fedavg<MODE, 32, 1, true, 64, 1>(a, false, s);
-    case 15: return go_fedavg<MODE, 32, 1, true, 64, 4>(a, false, s);
-    case 16: return go_fedavg<MODE, 48, 1, true, 64, 1>(a, false, s);
-    case 17: return go_fedavg<MODE, 64, 1, true, 64, 1>(a, false, s);
-    case 18: return go_fedavg<MODE, 32, 1, true, 128, 1>(a, false, s);
-    case 19: return go_fedavg<MODE, 16, 1, true, 512, 4>(a, false, s);
-    case 20: return go_fedavg<MODE, 8, 1, true, 1024, 4>(a, false, s);
-    case 21: return go_fedavg_pipe<MODE, 8, 256, 4>(a, s);
-    case 22: return go_fedavg_pipe<MODE, 4, 256, 4>(a, s);
-    case 23: return go_fedavg<MODE, 8, 1, true, 256, 4, true>(a, false, s);
+#define PGH_FOLD(id, loads, U, W, block, VEC, grid, tab) \
+    case id: return go_fedavg<MODE, loads, U, W, block, VEC, grid, tab>(a, rows, s);
+#include "pgh_variants.def"
     default: return hipErrorInvalidValue;
     }
 }
+
+// Whether the fold of that id has a row-table kernel.
+constexpr bool has_rowtab(int variant) {
+    using namespace shape;
+    switch (variant) {
+#define PGH_FOLD(id, loads, U, W, block, VEC, grid, tab) case id: return tab;
+#include "pgh_variants.def"
+    default: return false;
+    }
+}
+static_assert(has_rowtab(0), "a row-table fold without a kernel of its own id runs id 0's shape");
 
 // K8 shapes: 16-byte columns in 256-thread blocks with 8 rows in flight (the mean's big-shard shape,
 // variant 0), or one param per lane in 64-thread blocks with 32 rows in flight (its small-shard
@@ -1359,10 +1308,11 @@ int auto_variant(int64_t p, int mode) {
     return 0;  // r01p (masked last batch): mean 6918, iterative 6910, weighted 6905 (v15 6647)
 }
 
-template <int U, bool NT, int TB, int VEC>
+template <bool NT, int U, int TB, int VEC, shape::Grid G>
 hipError_t go_secagg(const SecaggArgs& a, hipStream_t s) {
+    static_assert(G == shape::tile || G == shape::persistent, "the share sum has these two grids");
     const int64_t ncol = (a.p + VEC - 1) / VEC;
-    k_secagg<U, NT, TB, VEC><<<grid_for(ncol, TB, false), TB, 0, s>>>(a, ncol);
+    k_secagg<U, NT, TB, VEC><<<grid_for(ncol, TB, G == shape::persistent), TB, 0, s>>>(a, ncol);
     return hipGetLastError();
 }
 
@@ -1377,7 +1327,16 @@ bool valid_map(const SlabMap& m, int64_t p) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// MODE_TRIMMED behind the common checks of launch_fedavg / launch_fedavg_rows.
+// What a family takes as its Rows.  device_table: it has a kernel that reads one; from_row0: its
+// contiguous rows may start past the slab pointer (K7).
+static bool valid_rows(const Rows& r, int n_rows, bool device_table, bool from_row0) {
+    if (r.tab && r.d_rows) return false;
+    if (r.tab && n_rows > ROWTAB_MAX) return false;
+    if (r.d_rows && !device_table) return false;
+    return r.row0 == 0 || (from_row0 && r.row0 > 0 && !r.tab && !r.d_rows);
+}
+
+// MODE_TRIMMED behind the common checks of launch_fedavg.
 static hipError_t launch_trim(const FedavgArgs& a, const RowTab* t, hipStream_t s) {
     if (a.trim_b < 1 || a.trim_b > TRIM_MAX || a.client0 < 0) return hipErrorInvalidValue;
     if (a.trim_vec != 0 && a.trim_vec != 1 && a.trim_vec != 4) return hipErrorInvalidValue;
@@ -1389,8 +1348,8 @@ static hipError_t launch_trim(const FedavgArgs& a, const RowTab* t, hipStream_t 
     return vec == 4 ? dispatch_trim<4>(a, t, s) : dispatch_trim<1>(a, t, s);
 }
 
-// What launch_fedavg and launch_fedavg_rows both ask of their arguments.
-static bool valid_fedavg(const FedavgArgs& a) {
+static bool valid_fedavg(const FedavgArgs& a, const Rows& rows) {
+    if (!valid_rows(rows, a.n_rows, false, false)) return false;
     if (a.p <= 0 || a.n_rows < 0 || !valid_map(a.map, a.p)) return false;
     if ((a.flags & FL_FIRST) && a.n_rows < 1) return false;
     if (a.n_rows > 0 && (!a.diffs || !aligned16(a.diffs))) return false;
@@ -1401,73 +1360,72 @@ static bool valid_fedavg(const FedavgArgs& a) {
     return true;
 }
 
-hipError_t launch_fedavg(const FedavgArgs& a, hipStream_t s) {
-    if (!valid_fedavg(a)) return hipErrorInvalidValue;
-    if (a.mode == MODE_TRIMMED) return launch_trim(a, nullptr, s);
-    const int v = a.variant < 0 ? auto_variant(a.p, a.mode) : a.variant;
+// Contiguous rows: a.variant, or the auto choice when it is negative.  A row table: a.variant where
+// that id has a row-table kernel (pgh_variants.def), the auto choice for every other value; an auto
+// choice without such a kernel (12, 13, 18) runs id 0's shape.
+hipError_t launch_fedavg(const FedavgArgs& a, const Rows& rows, hipStream_t s) {
+    if (!valid_fedavg(a, rows)) return hipErrorInvalidValue;
+    if (a.mode == MODE_TRIMMED) return launch_trim(a, rows.tab, s);
+    int v = a.variant;
+    if (rows.tab ? !has_rowtab(v) : v < 0) v = auto_variant(a.p, a.mode);
+    if (rows.tab && !has_rowtab(v)) v = 0;
     switch (a.mode) {
-    case MODE_MEAN: return dispatch_fedavg<MODE_MEAN>(a, v, s);
-    case MODE_ITERATIVE: return dispatch_fedavg<MODE_ITERATIVE>(a, v, s);
-    case MODE_WEIGHTED: return dispatch_fedavg<MODE_WEIGHTED>(a, v, s);
+    case MODE_MEAN: return dispatch_fedavg<MODE_MEAN>(a, rows, v, s);
+    case MODE_ITERATIVE: return dispatch_fedavg<MODE_ITERATIVE>(a, rows, v, s);
+    case MODE_WEIGHTED: return dispatch_fedavg<MODE_WEIGHTED>(a, rows, v, s);
     default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_fedavg_rows(const FedavgArgs& a_, const RowTab& t, hipStream_t s) {
-    const FedavgArgs& a = a_;
-    if (a.n_rows > ROWTAB_MAX || !valid_fedavg(a)) return hipErrorInvalidValue;
-    if (a.mode == MODE_TRIMMED) return launch_trim(a, &t, s);
-    int v = auto_variant(a.p, a.mode);
-    if (a.variant == 0 || a.variant == 11 || a.variant == 14 || a.variant == 17) v = a.variant;
-    switch (a.mode) {
-    case MODE_MEAN: return dispatch_fedavg_rows<MODE_MEAN>(a, t, v, s);
-    case MODE_ITERATIVE: return dispatch_fedavg_rows<MODE_ITERATIVE>(a, t, v, s);
-    case MODE_WEIGHTED: return dispatch_fedavg_rows<MODE_WEIGHTED>(a, t, v, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-static bool valid_median(const MedianArgs& a, const RowTab* t) {
+// The kernel's arguments: a with the device table of rows in it (k_median<.., 2> reads it from there).
+static bool median_args(const MedianArgs& a, const Rows& rows, MedianArgs* k) {
+    if (!valid_rows(rows, a.n_rows, true, false)) return false;
     if (a.p <= 0 || a.n_rows < 1 || !valid_map(a.map, a.p)) return false;
     if (!a.diffs || !aligned16(a.diffs) || !a.ckpt || !a.out) return false;
-    return !t || a.n_rows <= ROWTAB_MAX;
+    *k = a;
+    k->d_rows = rows.d_rows;
+    return true;
 }
 
 template <int W, int KPL>
-static hipError_t go_median(const MedianArgs& a, const RowTab* t, hipStream_t s) {
+static hipError_t go_median(const MedianArgs& k, const RowTab* t, hipStream_t s) {
     constexpr int TB = W == 1 ? BLOCK : 64 * W;
-    const unsigned grid = grid_for(a.p, W == 1 ? BLOCK : 64, false);
-    if (t) k_median_tab<W, KPL><<<grid, TB, 0, s>>>(a, *t);
-    else if (a.rowidx) k_median<W, KPL, 2><<<grid, TB, 0, s>>>(a);
-    else k_median<W, KPL, 0><<<grid, TB, 0, s>>>(a);
+    const unsigned grid = grid_for(k.p, W == 1 ? BLOCK : 64, false);
+    if (t) k_median_tab<W, KPL><<<grid, TB, 0, s>>>(k, *t);
+    else if (k.d_rows) k_median<W, KPL, 2><<<grid, TB, 0, s>>>(k);
+    else k_median<W, KPL, 0><<<grid, TB, 0, s>>>(k);
     return hipGetLastError();
 }
 
 // K9's tiers (waves per tile x keys per lane): up to 64 rows a lane holds its whole column, in 8, 16,
 // 32 or 64 registers; up to 128 / 256 / 512 / 1,024 rows 2 / 4 / 8 / 16 waves hold 64 keys per lane.
-hipError_t launch_median(const MedianArgs& a, const RowTab* t, hipStream_t s) {
-    if (!valid_median(a, t) || a.n_rows > MEDIAN_NCHIP) return hipErrorInvalidValue;
-    if (a.n_rows <= 8) return go_median<1, 8>(a, t, s);
-    if (a.n_rows <= 16) return go_median<1, 16>(a, t, s);
-    if (a.n_rows <= 32) return go_median<1, 32>(a, t, s);
-    if (a.n_rows <= 64) return go_median<1, 64>(a, t, s);
-    if (a.n_rows <= 128) return go_median<2, 64>(a, t, s);
-    if (a.n_rows <= 256) return go_median<4, 64>(a, t, s);
-    if (a.n_rows <= 512) return go_median<8, 64>(a, t, s);
-    return go_median<MEDIAN_WAVES, 64>(a, t, s);
+hipError_t launch_median(const MedianArgs& a, const Rows& rows, hipStream_t s) {
+    MedianArgs k;
+    const RowTab* t = rows.tab;
+    if (!median_args(a, rows, &k) || a.n_rows > MEDIAN_NCHIP) return hipErrorInvalidValue;
+    if (a.n_rows <= 8) return go_median<1, 8>(k, t, s);
+    if (a.n_rows <= 16) return go_median<1, 16>(k, t, s);
+    if (a.n_rows <= 32) return go_median<1, 32>(k, t, s);
+    if (a.n_rows <= 64) return go_median<1, 64>(k, t, s);
+    if (a.n_rows <= 128) return go_median<2, 64>(k, t, s);
+    if (a.n_rows <= 256) return go_median<4, 64>(k, t, s);
+    if (a.n_rows <= 512) return go_median<8, 64>(k, t, s);
+    return go_median<MEDIAN_WAVES, 64>(k, t, s);
 }
 
-hipError_t launch_median_pass(const MedianArgs& a, const RowTab* t, int bit, hipStream_t s) {
-    if (!valid_median(a, t) || !a.prefix || bit < -1 || bit > 31) return hipErrorInvalidValue;
+hipError_t launch_median_pass(const MedianArgs& a, const Rows& rows, int bit, hipStream_t s) {
+    MedianArgs k;
+    if (!median_args(a, rows, &k) || !a.prefix || bit < -1 || bit > 31) return hipErrorInvalidValue;
     if (bit < 0 && (a.n_rows & 1)) return hipErrorInvalidValue;  // an odd n closes at bit 0
     const unsigned grid = grid_for(a.p, BLOCK, false);
-    if (t) k_median_pass_tab<<<grid, BLOCK, 0, s>>>(a, bit, *t);
-    else if (a.rowidx) k_median_pass<2><<<grid, BLOCK, 0, s>>>(a, bit);
-    else k_median_pass<0><<<grid, BLOCK, 0, s>>>(a, bit);
+    if (rows.tab) k_median_pass_tab<<<grid, BLOCK, 0, s>>>(k, bit, *rows.tab);
+    else if (k.d_rows) k_median_pass<2><<<grid, BLOCK, 0, s>>>(k, bit);
+    else k_median_pass<0><<<grid, BLOCK, 0, s>>>(k, bit);
     return hipGetLastError();
 }
 
 hipError_t launch_secagg(const SecaggArgs& a, hipStream_t s) {
+    using namespace shape;
     if (a.p <= 0 || a.n_rows < 0 || !valid_map(a.map, a.p)) return hipErrorInvalidValue;
     if (a.n_rows > 0 && (!a.shares || (reinterpret_cast<uintptr_t>(a.shares) & 15))) return hipErrorInvalidValue;
     if (!(a.flags & FL_FINAL) && !a.acc) return hipErrorInvalidValue;
@@ -1476,28 +1434,10 @@ hipError_t launch_secagg(const SecaggArgs& a, hipStream_t s) {
     // at ResNet-18 x 1,000 x 2 (v16 6886, 16-byte columns v0 6613), 6747 at 311,650 x 2,500 x 2)
     const int v = a.variant < 0 ? SECAGG_AUTO_VARIANT : a.variant;
     if (v >= N_VARIANTS) return hipErrorInvalidValue;
-    switch (v) {  // same load policy / depth / block / lane width as the fedavg variant of that id
-    case 1: case 3: case 5: {  // persistent grids
-        const int64_t ncol = (a.p + 1) / 2;
-        const unsigned g = grid_for(ncol, BLOCK, true);
-        if (v == 1) k_secagg<8, true, BLOCK, 2><<<g, BLOCK, 0, s>>>(a, ncol);
-        else if (v == 3) k_secagg<8, false, BLOCK, 2><<<g, BLOCK, 0, s>>>(a, ncol);
-        else k_secagg<16, false, BLOCK, 2><<<g, BLOCK, 0, s>>>(a, ncol);
-        return hipGetLastError();
-    }
-    case 2: return go_secagg<8, false, 256, 2>(a, s);
-    case 4: return go_secagg<16, false, 256, 2>(a, s);
-    case 6: return go_secagg<16, true, 256, 2>(a, s);
-    case 7: case 10: return go_secagg<4, true, 256, 2>(a, s);
-    case 11: return go_secagg<16, true, 64, 2>(a, s);
-    case 12: return go_secagg<16, true, 64, 1>(a, s);
-    case 13: return go_secagg<8, true, 256, 1>(a, s);
-    case 14: return go_secagg<32, true, 64, 1>(a, s);
-    case 15: return go_secagg<32, true, 64, 2>(a, s);
-    case 16: return go_secagg<48, true, 64, 1>(a, s);
-    case 17: return go_secagg<64, true, 64, 1>(a, s);
-    case 18: return go_secagg<32, true, 128, 1>(a, s);
-    default: return go_secagg<8, true, 256, 2>(a, s);
+    switch (v) {
+#define PGH_SECAGG(id, loads, U, block, VEC, grid) case id: return go_secagg<loads, U, block, VEC, grid>(a, s);
+#define PGH_SECAGG_DEFAULT(loads, U, block, VEC, grid) default: return go_secagg<loads, U, block, VEC, grid>(a, s);
+#include "pgh_variants.def"
     }
 }
 
@@ -1577,17 +1517,17 @@ hipError_t launch_server_opt(const ServerOptArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_row_sumsq(const SumsqArgs& a, const RowTab* tab, hipStream_t s) {
-    if (a.p <= 0 || a.n_rows < 0 || a.row0 < 0 || a.map.off != 0 || !valid_map(a.map, a.p) ||
+hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s) {
+    const RowTab* tab = rows.tab;
+    if (!valid_rows(rows, a.n_rows, false, true) || a.p <= 0 || a.n_rows < 0 || a.map.off != 0 || !valid_map(a.map, a.p) ||
         a.ntiles != (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE || a.ntiles > 0x7fffffff)
         return hipErrorInvalidValue;
     if (a.n_rows == 0) return hipSuccess;
     if (!a.slab || !a.part || !a.sumsq || (reinterpret_cast<uintptr_t>(a.slab) & 15)) return hipErrorInvalidValue;
-    if (tab && a.n_rows > ROWTAB_MAX) return hipErrorInvalidValue;
     const int max_rows = 65535 * SUMSQ_RB;  // grid rows of one launch
     for (int done = 0; done < a.n_rows; done += max_rows) {
         SumsqArgs b = a;
-        b.row0 = a.row0 + done;
+        b.row0 = rows.row0 + done;
         b.n_rows = std::min(max_rows, a.n_rows - done);
         const dim3 grid((unsigned)b.ntiles, (unsigned)((b.n_rows + SUMSQ_RB - 1) / SUMSQ_RB));
         if (tab) {

@@ -92,7 +92,7 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     a.mode = kernel_mode(mode);
     a.variant = c->variant;
     if (mode == PGH_MEDIAN) {  // (its own launches and bytes)
-        RC(median_fold(c, a, rows.tab, rows.d_rows, s));
+        RC(median_fold(c, a, rows.src, s));
         return opt ? server_opt_launch(c, fa, s) : PGH_OK;
     }
     // HBM bytes: the rows; the running state in unless FIRST; the state out, or ckpt in and out when FINAL
@@ -103,8 +103,7 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
         RC(trim_args(c, &a));
         bytes += trim_state_bytes(c, flags, pg);
     }
-    if (rows.tab) RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg_rows(a, *rows.tab, s); }));
-    else RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, s); }));
+    RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, rows.src, s); }));
     return opt ? server_opt_launch(c, fa, s) : PGH_OK;
 }
 

@@ -103,18 +103,17 @@ int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s) {
     return PGH_OK;
 }
 
-int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, const int32_t* d_rows, hipStream_t s) {
+int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hipStream_t s) {
     pgh::MedianArgs m{};
     m.diffs = a.diffs;
     m.map = a.map;
     m.n_rows = a.n_rows;
     m.p = a.p;
-    m.rowidx = tab ? nullptr : d_rows;
     m.ckpt = a.ckpt;
     m.out = a.out;
-    const uint64_t rows = 4ull * (uint64_t)a.n_rows * (uint64_t)a.p, rp = (uint64_t)a.p;
+    const uint64_t slab = 4ull * (uint64_t)a.n_rows * (uint64_t)a.p, rp = (uint64_t)a.p;
     if (median_variant(c, a.n_rows) == 50)  // K9: the slab once, ckpt in, out
-        return timed_launch(c, s, rows + 8 * rp, [&] { return pgh::launch_median(m, tab, s); });
+        return timed_launch(c, s, slab + 8 * rp, [&] { return pgh::launch_median(m, rows, s); });
     if (!c->med.d_prefix.reserve(sizeof(uint32_t) * (size_t)c->pvec))
         return fail(c, PGH_E_OOM, "allocation of the median's prefix plane failed");
     m.prefix = c->med.d_prefix.as<uint32_t>() + a.map.off;
@@ -122,8 +121,8 @@ int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::RowTab* tab, co
     // the prefix plane (not the first) and writes it, or ckpt in and out (the last)
     const int last = (a.n_rows & 1) ? 0 : -1;
     for (int bit = 31; bit >= last; --bit) {
-        const uint64_t bytes = rows + (bit == 31 ? 0 : 4 * rp) + (bit == last ? 8 * rp : 4 * rp);
-        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_median_pass(m, tab, bit, s); }));
+        const uint64_t bytes = slab + (bit == 31 ? 0 : 4 * rp) + (bit == last ? 8 * rp : 4 * rp);
+        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_median_pass(m, rows, bit, s); }));
     }
     return PGH_OK;
 }
@@ -187,16 +186,16 @@ int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n) {
     }
     const auto bytes = [&](size_t rows) { return rows * (4ull * (uint64_t)c->pg + 8ull * (uint64_t)a.ntiles); };
     if (run) {
-        a.row0 = todo[0];
         a.n_rows = (int)todo.size();
-        RC(timed_launch(c, s, bytes(todo.size()), [&] { return pgh::launch_row_sumsq(a, nullptr, s); }));
+        const pgh::Rows rows{nullptr, nullptr, todo[0]};
+        RC(timed_launch(c, s, bytes(todo.size()), [&] { return pgh::launch_row_sumsq(a, rows, s); }));
     } else {
         for (size_t done = 0; done < todo.size(); done += pgh::ROWTAB_MAX) {
             const size_t m = std::min(todo.size() - done, (size_t)pgh::ROWTAB_MAX);
             pgh::RowTab tab;
             for (size_t k = 0; k < m; ++k) tab.rows[k] = todo[done + k];
             a.n_rows = (int)m;
-            RC(timed_launch(c, s, bytes(m), [&] { return pgh::launch_row_sumsq(a, &tab, s); }));
+            RC(timed_launch(c, s, bytes(m), [&] { return pgh::launch_row_sumsq(a, pgh::Rows{&tab}, s); }));
         }
     }
     // entries of other slots inside [lo, hi] are rewritten with what the device holds for them: the

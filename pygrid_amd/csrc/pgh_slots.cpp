@@ -60,8 +60,8 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         const int flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
         // (only a median comes with more rows than the table carries: they are in the device table then)
         FoldRows rows{c->d_slab.as<float>(), m};
-        if (m <= pgh::ROWTAB_MAX) rows.tab = &tab;
-        else rows.d_rows = median_rows(c);
+        if (m <= pgh::ROWTAB_MAX) rows.src.tab = &tab;
+        else rows.src.d_rows = median_rows(c);
         // The FINAL pass of a report-time close (a short fold of the rows left) as ranges of 4 MiB of
         // output, one after another on one stream, a mark behind every second one: each 8 MiB D2H
         // piece starts behind the two ranges that wrote it instead of behind the whole fold.  Ranges

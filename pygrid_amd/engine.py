@@ -510,7 +510,7 @@ class Engine:
         self._check(self._lib.pgh_set_ingest_ranges(self._h, int(bool(on))), "set_ingest_ranges")
 
     def set_variant(self, v: int):
-        """Kernel variant (csrc/pgh_kernels.hip table); -1 restores the default."""
+        """Kernel variant (csrc/pgh_variants.def table); -1 restores the default."""
         self._check(self._lib.pgh_set_variant(self._h, int(v)), "set_variant")
 
     def effective_variant(self, mode: int = MEAN) -> int:

@@ -4,9 +4,10 @@ arithmetic that says which loop regions of a shape a given launch visits.  No HI
 A shape is one template instantiation: U rows in flight, W columns per lane, the block size, VEC
 params per column, the load policy and the grid policy.  Every walk has three code regions: the
 steady-state loop over full batches of U rows, the masked last batch, and the grid-stride trip over
-tiles of block x W columns.  tests/test_launch_shape_table.py holds these tables against the
-dispatch switches of the source and checks that the cases derived here reach every region of every
-shape; tests/test_gpu_launch_shapes.py runs the cases.
+tiles of block x W columns.  tests/test_launch_shape_table.py holds these tables against
+pygrid_amd/csrc/pgh_variants.def, which the dispatch switches are generated from, and checks that
+the cases derived here reach every region of every shape; tests/test_gpu_launch_shapes.py runs the
+cases.
 """
 from collections import namedtuple
 
@@ -23,7 +24,7 @@ def _s(U, W, block, VEC, nt=True, persistent=False, pipelined=False, xmap=False)
     return Shape(U, W, block, VEC, nt, persistent, pipelined, xmap)
 
 
-# dispatch_fedavg (the comment above N_VARIANTS, restated)
+# the fold (the PGH_FOLD rows of pgh_variants.def, restated)
 FOLD_SHAPES = {
     0: _s(8, 1, 256, 4),
     1: _s(8, 1, 256, 4, persistent=True),
@@ -51,7 +52,7 @@ FOLD_SHAPES = {
     23: _s(8, 1, 256, 4, xmap=True),
 }
 
-# dispatch_fedavg_rows: the row-table kernels (any other variant runs the auto shape of its shard)
+# the row-table kernels (any other explicit variant gives the auto choice; one without a kernel, id 0's shape)
 ROW_SHAPES = {
     0: _s(8, 1, 256, 4),
     11: _s(16, 1, 64, 4),

@@ -1,7 +1,8 @@
-"""CPU: tests/launch_shapes.py against the dispatch switches of pygrid_amd/csrc/pgh_kernels.hip, and
-the cases it derives against the loop regions of every shape.
+"""CPU: tests/launch_shapes.py against pygrid_amd/csrc/pgh_variants.def, the table the dispatch
+switches of pgh_kernels.hip are generated from, and the cases it derives against the loop regions of
+every shape.
 
-A shape added to or changed in the source without the tables following fails the first group; a
+A shape added to or changed in the table without launch_shapes.py following fails the first group; a
 case list that no longer reaches a loop region of some shape fails the second.  The second group is
 what keeps tests/test_gpu_launch_shapes.py honest: it runs exactly the cases checked here.
 """
@@ -14,138 +15,85 @@ import pytest
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import launch_shapes as LS  # noqa: E402
 
-SRC = Path(__file__).resolve().parent.parent / "pygrid_amd" / "csrc" / "pgh_kernels.hip"
-B = {"true": True, "false": False}
+CSRC = Path(__file__).resolve().parent.parent / "pygrid_amd" / "csrc"
+NT = {"nt": True, "plain": False}
+GRIDS = ("tile", "persistent", "pipelined", "xmap")
 
 
-def body_of(text, signature):
-    """The braces' contents of the one function whose definition starts with `signature`."""
-    assert text.count(signature) == 1, signature
-    i = text.index("{", text.index(signature))
-    depth, j = 0, i
-    while True:
-        depth += {"{": 1, "}": -1}.get(text[j], 0)
-        if depth == 0:
-            return text[i + 1:j]
-        j += 1
-
-
-def parse_fold(text):
-    body = body_of(text, "hipError_t dispatch_fedavg(const FedavgArgs& a, int variant, hipStream_t s)")
-    out = {}
-    for m in re.finditer(r"case (\d+): return go_fedavg<MODE, (\d+), (\d+), (true|false), (\d+), (\d+)"
-                         r"(?:, (true|false))?>\(a, (true|false), s\);", body):
-        v, U, W, nt, tb, vec, xmap, pers = m.groups()
-        assert int(v) not in out
-        out[int(v)] = LS.Shape(int(U), int(W), int(tb), int(vec), B[nt], B[pers], False, B[xmap or "false"])
-    for m in re.finditer(r"case (\d+): return go_fedavg_pipe<MODE, (\d+), (\d+), (\d+)>\(a, s\);", body):
-        v, U, tb, vec = m.groups()
-        assert int(v) not in out
-        out[int(v)] = LS.Shape(int(U), 1, int(tb), int(vec), True, False, True, False)
-    assert len(out) == len(re.findall(r"\bcase\b", body)), "a case of dispatch_fedavg was not understood"
-    assert "default: return hipErrorInvalidValue;" in body
-    return out
-
-
-def parse_rows(text):
-    body = body_of(text, "hipError_t dispatch_fedavg_rows(const FedavgArgs& a, const RowTab& t, int variant, hipStream_t s)")
-    out = {}
-    for m in re.finditer(r"(case (\d+)|default): return go_fedavg_rows<MODE, (\d+), (\d+), (true|false), (\d+), (\d+)>"
-                         r"\(a, t, s\);", body):
-        _, v, U, W, nt, tb, vec = m.groups()
-        v = 0 if v is None else int(v)  # the default is the shape of variant 0
-        assert v not in out
-        out[v] = LS.Shape(int(U), int(W), int(tb), int(vec), B[nt], False, False, False)
-    assert len(out) == len(re.findall(r"\b(?:case|default)\b", body)), "a case of dispatch_fedavg_rows was not understood"
-    return out
-
-
-def parse_rows_honoured(text):
-    body = body_of(text, "hipError_t launch_fedavg_rows(const FedavgArgs& a_, const RowTab& t, hipStream_t s)")
-    line = next(ln for ln in body.splitlines() if "v = a.variant" in ln)
-    return {int(v) for v in re.findall(r"a\.variant == (\d+)", line)}
-
-
-def parse_secagg(text):
-    body = body_of(text, "hipError_t launch_secagg(const SecaggArgs& a, hipStream_t s)")
-    block = int(re.search(r"constexpr int BLOCK = (\d+);", text).group(1))
-    sw = body[body.index("switch (v)"):]
-    out = {}
-    # the persistent ids share one block: if (v == a) ... else if (v == b) ... else ...
-    m = re.search(r"((?:case \d+: )+)\{(.*?)\n    \}", sw, re.S)
-    ids = [int(v) for v in re.findall(r"case (\d+):", m.group(1))]
-    inner = m.group(2)
-    assert "grid_for(ncol, BLOCK, true)" in inner
-    launches = re.findall(r"(?:if \(v == (\d+)\)|else) k_secagg<(\d+), (true|false), BLOCK, (\d+)><<<g, BLOCK, 0, s>>>", inner)
-    assert len(launches) == len(ids)
-    named = {int(v) for v, *_ in launches if v}
-    for v, U, nt, vec in launches:
-        v = int(v) if v else next(i for i in ids if i not in named)
-        assert v not in out
-        out[v] = LS.Shape(int(U), 1, block, int(vec), B[nt], True, False, False)
-    rest = sw[m.end():]
-    n_labels = 0
-    for m in re.finditer(r"((?:case \d+: )+|default: )return go_secagg<(\d+), (true|false), (\d+), (\d+)>\(a, s\);", rest):
-        labels, U, nt, tb, vec = m.groups()
-        sh = LS.Shape(int(U), 1, int(tb), int(vec), B[nt], False, False, False)
-        if labels.startswith("default"):
-            default = sh
-            n_labels += 1
+def parse_table(text):
+    """pgh_variants.def -> (fold shapes by id, ids with a row-table kernel, share-sum shapes of the
+    ids that have their own, the share sum's default shape)."""
+    fold, tabbed, own, default = {}, set(), {}, []
+    rows = re.findall(r"^PGH_(FOLD|SECAGG|SECAGG_DEFAULT)\(([^()]*)\)$", text, re.M)
+    assert len(rows) == len(re.findall(r"^PGH_", text, re.M)), "a row of the table was not understood"
+    for kind, args in rows:
+        f = [x.strip() for x in args.split(",")]
+        if kind == "FOLD":
+            v, loads, U, W, tb, vec, grid, tab = f
+            assert int(v) not in fold and grid in GRIDS
+            fold[int(v)] = LS.Shape(int(U), int(W), int(tb), int(vec), NT[loads], grid == "persistent",
+                                    grid == "pipelined", grid == "xmap")
+            if {"rowtab": True, "no_rowtab": False}[tab]:
+                tabbed.add(int(v))
             continue
-        for v in re.findall(r"case (\d+):", labels):
-            assert int(v) not in out
-            out[int(v)] = sh
-            n_labels += 1
-    assert n_labels == len(re.findall(r"\b(?:case|default)\b", rest)), "a case of launch_secagg was not understood"
-    assert "if (v >= N_VARIANTS) return hipErrorInvalidValue;" in body
-    n = int(re.search(r"constexpr int N_VARIANTS = (\d+);", text).group(1))
-    return {v: out.get(v, default) for v in range(n)}, {v for v in range(n) if v not in out}
+        v = f.pop(0) if kind == "SECAGG" else None
+        loads, U, tb, vec, grid = f
+        assert grid in GRIDS[:2]
+        sh = LS.Shape(int(U), 1, int(tb), int(vec), NT[loads], grid == "persistent", False, False)
+        if v is None:
+            default.append(sh)
+        else:
+            assert int(v) not in own
+            own[int(v)] = sh
+    assert len(default) == 1
+    return fold, tabbed, own, default[0]
 
 
 @pytest.fixture(scope="module")
 def text():
-    return SRC.read_text()
+    return (CSRC / "pgh_variants.def").read_text()
 
 
-def test_fold_table_is_the_dispatch_switch(text):
-    assert parse_fold(text) == LS.FOLD_SHAPES
-    assert int(re.search(r"constexpr int N_VARIANTS = (\d+);", text).group(1)) == len(LS.FOLD_SHAPES) == 24
+def test_fold_table_is_the_def_file(text):
+    fold = parse_table(text)[0]
+    assert fold == LS.FOLD_SHAPES
+    assert list(fold) == list(range(24))  # N_VARIANTS (pgh_kernels.h counts these rows) == 24
+    assert len(LS.FOLD_SHAPES) == 24
 
 
-def test_fold_table_is_the_comment_above_n_variants(text):
-    """The variant table in the source's comment says the same as the switch (and so as the helper)."""
-    head = text[text.index("//   id  loads  U (rows in flight)"):text.index("constexpr int N_VARIANTS")]
-    rows = re.findall(r"//   (\d+)\s+(nt|plain)\s+(\d+)(?: \(\+\d+ next batch\))?\s+(\d+)\s+(\d+)\s+(\d+)\s+(.*)", head)
-    assert len(rows) == 24
-    for v, loads, U, W, tb, vec, grid in rows:
-        sh = LS.FOLD_SHAPES[int(v)]
-        assert (sh.U, sh.W, sh.block, sh.VEC, sh.nt) == (int(U), int(W), int(tb), int(vec), loads == "nt"), v
-        assert sh.persistent == grid.startswith("persistent"), v
-        assert sh.pipelined == ("pipelined" in grid), v
-        assert sh.xmap == ("each XCD" in grid), v
-
-
-def test_row_table_is_the_dispatch_switch(text):
-    assert parse_rows(text) == LS.ROW_SHAPES
-    assert parse_rows_honoured(text) == set(LS.ROW_SHAPES)
+def test_row_table_is_the_def_file(text):
+    fold, tabbed, _, _ = parse_table(text)
+    assert {v: fold[v] for v in tabbed} == LS.ROW_SHAPES
+    assert tabbed == set(LS.ROW_SHAPES)  # the explicit ids a row-table fold honours
     for v, sh in LS.ROW_SHAPES.items():  # "same shape as the fold variant of that id"
         assert sh == LS.FOLD_SHAPES[v]
 
 
-def test_secagg_table_is_the_launch_switch(text):
-    shapes, defaulted = parse_secagg(text)
+def secagg_shapes(text):
+    fold, _, own, default = parse_table(text)
+    return {v: own.get(v, default) for v in fold}, {v for v in fold if v not in own}
+
+
+def test_secagg_table_is_the_def_file(text):
+    shapes, defaulted = secagg_shapes(text)
     assert shapes == LS.SECAGG_SHAPES
     assert defaulted == set(LS.SECAGG_DEFAULT_IDS)
 
 
 def test_a_changed_template_argument_is_noticed(text):
-    """The parser reads the arguments, not just the labels: one edited number changes its result."""
-    edited = text.replace("case 17: return go_fedavg<MODE, 64, 1, true, 64, 1>", "case 17: return go_fedavg<MODE, 32, 1, true, 64, 1>")
-    assert edited != text and parse_fold(edited) != LS.FOLD_SHAPES
-    edited = text.replace("case 16: return go_secagg<48, true, 64, 1>", "case 16: return go_secagg<48, true, 64, 2>")
-    assert edited != text and parse_secagg(edited)[0] != LS.SECAGG_SHAPES
-    edited = text.replace("case 14: return go_fedavg_rows<MODE, 32,", "case 14: return go_fedavg_rows<MODE, 16,")
-    assert edited != text and parse_rows(edited) != LS.ROW_SHAPES
+    """The parser reads the arguments, not just the ids: one edited number or flag changes its result."""
+    edited = text.replace("PGH_FOLD(17, nt, 64, 1, 64, 1,", "PGH_FOLD(17, nt, 32, 1, 64, 1,")
+    assert edited != text and parse_table(edited)[0] != LS.FOLD_SHAPES
+    edited = text.replace("PGH_SECAGG(16, nt, 48, 64, 1,", "PGH_SECAGG(16, nt, 48, 64, 2,")
+    assert edited != text and secagg_shapes(edited)[0] != LS.SECAGG_SHAPES
+    edited = text.replace("PGH_FOLD(14, nt, 32, 1, 64, 1, tile, rowtab)", "PGH_FOLD(14, nt, 32, 1, 64, 1, tile, no_rowtab)")
+    assert edited != text and parse_table(edited)[1] != set(LS.ROW_SHAPES)
+
+
+def test_no_hand_written_case_beside_the_table():
+    """The switches over variant ids come from the table: the source has no `case <n>: return go_fedavg...`
+    or `go_secagg...` line.  (K8's switch over the trim depth, `return go_trim<b, VEC>`, is no variant id.)"""
+    assert not re.search(r"case\s+\d+\s*:\s*return\s+go_(?!trim<)", (CSRC / "pgh_kernels.hip").read_text())
 
 
 def test_region_arithmetic_on_known_launches():

@@ -5,6 +5,7 @@
                                 [--params P] [--rounds R] [--variants 0,1,2,3,4,5]
 
 Prints per-variant median / min kernel ms and GB/s of algorithmic bytes.
+The variant ids are the rows of pygrid_amd/csrc/pgh_variants.def.
 """
 import argparse
 import json

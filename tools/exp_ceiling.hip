@@ -67,7 +67,7 @@ int main() {
     pgh::FedavgArgs a{};
     a.diffs = slab; a.map = m; a.n_rows = N; a.client0 = 0; a.p = P; a.acc = acc; a.ckpt = ckpt; a.out = out;
     a.divisor = (float)N; a.flags = pgh::FL_FIRST | pgh::FL_FINAL; a.mode = pgh::MODE_MEAN; a.variant = -1;
-    cs.push_back({"fold_auto", alg, [a] { CK(pgh::launch_fedavg(a, 0)); }, {}});
+    cs.push_back({"fold_auto", alg, [a] { CK(pgh::launch_fedavg(a, pgh::Rows{}, 0)); }, {}});
     const int64_t n16 = (int64_t)(bytes / 16);
     for (int64_t C : {65536, 262144, 1048576, 4194304})
         for (int g : {2048, 8192, 32768}) {

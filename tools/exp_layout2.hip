@@ -131,7 +131,7 @@ int main(int argc, char** argv) {
             pgh::FedavgArgs a{};
             a.diffs = slab; a.map = pgh::single_block(ld); a.n_rows = N; a.client0 = 0; a.p = P; a.acc = acc; a.ckpt = ckpt; a.out = out;
             a.divisor = (float)N; a.flags = pgh::FL_FIRST | pgh::FL_FINAL; a.mode = pgh::MODE_MEAN; a.variant = v;
-            cs.push_back({"rowmaj_v" + std::to_string(v), alg, [a] { CK(pgh::launch_fedavg(a, 0)); }, {}});
+            cs.push_back({"rowmaj_v" + std::to_string(v), alg, [a] { CK(pgh::launch_fedavg(a, pgh::Rows{}, 0)); }, {}});
         }
         for (int64_t B : {256, 1024, 2048, 4096, 8192, 16384, 65536}) {
             const int bs = ilog2(B);
