@@ -216,6 +216,60 @@ int pgh_clip_scale(double sumsq, float c, float* scale);
  * got a scale other than 1, and the largest norm (NaN if any was NaN).  Each pointer may be NULL. */
 int pgh_clip_stats(pgh_ctx* ctx, int64_t* n_rows, int64_t* n_clipped, double* max_norm);
 
+/* ---- Gaussian noise on the clipped close (DP-FedAvg; kernel K11) --------------------------------
+ * The published recipe: clip every diff to C, add N(0, (z C)^2 I) to the sum, divide by N.  With a noise
+ * multiplier z set, a PGH_CLIPPED_MEAN FINAL computes g = acc / float(N) exactly as without it and then,
+ * per parameter with flat model index i,
+ *   sigma = ((double)z * (double)C) / (double)N    (on the host, f64, N = the fold's divisor count);
+ *   n_i = (float)(sigma * Z_i)                     (one f64 product, one rounding to f32);
+ *   g'_i = g_i + n_i                               (f32);
+ *   out = ckpt - g'; with a server optimizer K10's formulas take g' for g.
+ * The result depends on (key, round, z, C, N, diffs) and on nothing else -- not on the launch shape, the
+ * range split, the entry point or how often the FINAL runs: a repeated close releases the same noise,
+ * never a second draw (two draws would average the noise away).
+ *
+ * The sampler.  All arithmetic is IEEE, every operation rounded on its own (no FMA); f64 / and sqrt are
+ * correctly rounded; no libm call.
+ * Generator: Philox4x32-10 (Salmon et al. 2011), multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key
+ * increments 0x9E3779B9, 0xBB67AE85.  One round, with (h0, l0) = mulhilo(M0, c0) and (h1, l1) =
+ * mulhilo(M1, c2): c = (h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0); ten rounds, the key bumped between rounds.
+ * (Counter 0 0 0 0, key 0 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.)
+ * Standard normals, two per pair (Marsaglia's polar method).  Parameter i belongs to pair p = i >> 1; an
+ * even i takes Z0, an odd i Z1.  The key words are (key & 0xffffffff, key >> 32).  For attempt a = 0 .. 31:
+ *   counter (p & 0xffffffff, p >> 32, round, a) -> (x0, x1, x2, x3);
+ *   q1 = (int64)((x1 << 32) | x0) >> 11 (arithmetic), v1 = ((double)q1 + 0.5) * 2^-52 (exact, symmetric,
+ *   never 0); q2, v2 the same from (x3 << 32) | x2;
+ *   s = v1 * v1 + v2 * v2; the first attempt with s < 1.0 is accepted:
+ *   L = plog(s), f = sqrt((-2.0 * L) / s), Z0 = v1 * f, Z1 = v2 * f.
+ * If all 32 attempts are rejected (probability below 2^-70 per pair; the bound is there so that the
+ * kernel's loop provably ends) both normals are +0.0.
+ * plog(s), s a normal f64 in (0, 1) (the fdlibm form): b = bits(s), e = ((b >> 52) & 0x7ff) - 1023,
+ * mb = b & 0xfffffffffffff; if mb >= 0x6a09e667f3bcd: e += 1, m = bits(mb | 0x3fe0000000000000), else
+ * m = bits(mb | 0x3ff0000000000000); f = m - 1.0, t = f / (2.0 + f), w = t * t; R = Lg7, then for c in
+ * Lg6 .. Lg1: R = R * w + c, then R = R * w; plog = (double)e * ln2 + (f - t * (f - R)) with
+ * ln2 = 0x1.62e42fefa39efp-1, Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01,
+ * Lg3 = 2.857142874366239149e-01, Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01,
+ * Lg6 = 1.531383769920937332e-01, Lg7 = 1.479819860511658591e-01.
+ * Philox with a 64-bit key is a statistical generator, not a cryptographic one; a floating-point
+ * Gaussian has the known low-bit weakness (Mironov 2012); privacy accounting is the operator's.
+ *
+ * pgh_set_dp_noise: z = 0 turns the noise off and is always accepted; otherwise z must be finite and > 0
+ * (PGH_E_ARG).  PGH_E_UNSUPPORTED with z > 0 wherever pgh_set_clip_norm refuses: a group, a context whose
+ * shard is narrower than the layout, an int64 slab, a streaming context.  pgh_set_layout and pgh_set_shard
+ * clear the setting; pgh_reset and pgh_reserve keep it.  With noise on, an fp32 FINAL fold in any mode
+ * other than PGH_CLIPPED_MEAN is PGH_E_STATE: nothing is launched, the context stays usable, and no
+ * un-noised average leaves it.  Folds that are not FINAL, secure aggregation and pgh_stream_begin are not
+ * affected.  The fold runs against a plane of -0.0f into a delta plane (the server optimizer's when one is
+ * set, else two [P_shard] float planes of the noise's own, allocated by the first noised FINAL), and K11
+ * follows on the same stream over the same range, ahead of K10.
+ * pgh_dp_normals runs K11's sampler on the GPU and returns Z_i for i in [i0, i0 + n) as f64 (tests,
+ * debugging); pgh_dp_normals_host is the same in plain C++, ctx-free, without a GPU.  pgh_dp_stats reports
+ * z and what the last noised FINAL used (sigma, N); each pointer may be NULL. */
+int pgh_set_dp_noise(pgh_ctx* ctx, float z, uint64_t key, uint32_t round);
+int pgh_dp_normals(pgh_ctx* ctx, uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out);
+int pgh_dp_normals_host(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out);
+int pgh_dp_stats(pgh_ctx* ctx, float* z, double* sigma_last, int64_t* n_last);
+
 /* ---- coordinate-wise trimmed mean (PGH_TRIMMED_MEAN) ----------------------------------------
  * Per parameter: drop the b largest and the b smallest of the N values, average the other N - 2b.
  * Up to b arbitrary rows (NaN, infinities, 1e30) then cannot move any parameter outside the range

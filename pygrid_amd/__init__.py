@@ -15,7 +15,7 @@ Importing the package changes nothing in the host process; ``tune_process()`` is
 opt-in for the process-wide settings the engine benefits from (HIP hardware queues, glibc
 thresholds for 47 MB buffers).
 """
-from .exceptions import (AggregationError, ClipUnavailableError, EngineUnavailableError, MedianUnavailableError,
+from .exceptions import (AggregationError, ClipUnavailableError, DpNoiseUnavailableError, EngineUnavailableError, MedianUnavailableError,
                          ModelNotAcceleratedError,
                          PlanNotAcceleratedError, PyGridError, ServerOptUnavailableError, StateParseError,
                          TrimUnavailableError)
@@ -41,7 +41,7 @@ def tune_process(hw_queues: bool = True, malloc: bool = True) -> dict:
 
 __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
-    "StateParseError", "TrimUnavailableError", "MedianUnavailableError", "ServerOptUnavailableError",
+    "StateParseError", "TrimUnavailableError", "MedianUnavailableError", "ServerOptUnavailableError", "DpNoiseUnavailableError",
     "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
     "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "MODE_NAMES", "F32", "I64",
     "tune_process",

@@ -104,6 +104,10 @@ SIGNATURES = {
     "pgh_row_sumsq": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
     "pgh_clip_scale": (_i, [C.c_double, C.c_float, C.POINTER(C.c_float)]),
     "pgh_clip_stats": (_i, [_vp, _P64, _P64, C.POINTER(C.c_double)]),
+    "pgh_set_dp_noise": (_i, [_vp, C.c_float, _u64, C.c_uint32]),
+    "pgh_dp_normals": (_i, [_vp, _u64, C.c_uint32, _i64, _i64, C.POINTER(C.c_double)]),
+    "pgh_dp_normals_host": (_i, [_u64, C.c_uint32, _i64, _i64, C.POINTER(C.c_double)]),
+    "pgh_dp_stats": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_double), _P64]),
     "pgh_set_trim": (_i, [_vp, _i]),
     "pgh_set_server_opt": (_i, [_vp, _i, C.c_float, C.c_float, C.c_float, C.c_float]),
     "pgh_server_opt_commit": (_i, [_vp]),

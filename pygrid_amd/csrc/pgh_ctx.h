@@ -10,7 +10,8 @@
 //   pgh_reduce.cpp  the one fp32 fold launch (fold_prepare, fold_launch); fold_run's ring walk and the share
 //                   sum; the divisors; RESIDENT and STREAM entry points, the resident checkpoint
 //   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: clipping (K7's sums,
-//                   the scales, the tallies), trimming (K8's planes), the median (K9, K9p); the rules' lifecycle
+//                   the scales, the tallies) and the Gaussian noise on the clipped close (K11 behind a FINAL launch),
+//                   trimming (K8's planes), the median (K9, K9p); the rules' lifecycle
 //                   calls (rules_*) and entry points.  Their state: pgh_rules.h
 //   pgh_serveropt.cpp  the server optimizer: K10 behind a FINAL launch, its planes, commit, download, upload
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order): slot_fold
@@ -19,7 +20,8 @@
 // set, reserved, reset, slot written, weights replaced, folds restarted, cycle finished -- and touches
 // check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run, slot_fold) reach the kernels
 // through the last two alone.  The server optimizer (pgh_set_server_opt) hangs on fold_launch too: a FINAL
-// launch with one set is followed by K10 (server_opt_launch).
+// launch with one set is followed by K10 (server_opt_launch).  The noise (pgh_set_dp_noise) is a second tenant of
+// that mechanism: a clipped FINAL launch with it set is followed by K11 (dp_noise_launch), ahead of K10.
 // The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -220,6 +222,7 @@ struct pgh_ctx {
     // What the averaging rules and the server optimizer keep (pgh_rules.h): touched only by their own code
     // (pgh_rules.cpp, pgh_serveropt.cpp), by fold_launch and fedavg_divisor, and through rules_* below.
     pgh_detail::ClipState clip;
+    pgh_detail::NoiseState noise;
     pgh_detail::TrimState trim;
     pgh_detail::MedianState med;
     pgh_detail::ServerOptState opt;
@@ -426,6 +429,20 @@ int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::ve
 int resident_clip_scales(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n)
 // a slot fold of a clipped cycle: the scales and norms of slots[0, n) at fold index c0 (0 begins the cycle)
 int clip_slot_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0);
+
+// ---- Gaussian noise on the clipped close (pgh_rules.cpp) ---------------------------------------------
+inline bool noise_on(const pgh_ctx* c) { return c->noise.z > 0.f; }
+// A FINAL fp32 fold of `mode` is about to be issued: with noise on only PGH_CLIPPED_MEAN may close a cycle
+// (PGH_E_STATE before anything is launched; an un-noised average never leaves a context that noise is set on).
+int check_noise_final(pgh_ctx* c, int mode);
+// The delta planes of a noised FINAL without a server optimizer (-0 and d), allocated on first use; stream s
+// has the -0 plane filled when this returns.
+int noise_planes(pgh_ctx* c, hipStream_t s);
+struct FinalArgs;
+// K11 behind a FINAL clipped launch of n clients over [fa.off, fa.off + fa.len) on stream s.  into_opt: the
+// fold wrote the server optimizer's delta plane and K10 follows -- K11 noises that plane in place; else it
+// reads the noise state's plane and writes the real out = ckpt - g'.
+int dp_noise_launch(pgh_ctx* c, const FinalArgs& fa, int64_t n, bool into_opt, hipStream_t s);
 
 // ---- trimmed-mean FedAvg (pgh_rules.cpp) ------------------------------------------------------------
 // K8's arguments on top of a filled FedavgArgs (map.off = the launch's first shard param): the mode,

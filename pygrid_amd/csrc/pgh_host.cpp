@@ -7,6 +7,7 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -104,6 +105,86 @@ void prefault_parallel(uint8_t* p, size_t n, CopyPool& pool) {
         const uintptr_t lo = a + per * (uintptr_t)i, hi = std::min(b, lo + per);
         if (lo < hi) (void)madvise((void*)lo, hi - lo, MADV_POPULATE_WRITE);
     });
+}
+
+// ---- the DP noise sampler (the definition: include/pgh_api.h) -----------------------------------------------
+
+void philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+double dp_plog(double s) {
+    uint64_t b;
+    std::memcpy(&b, &s, 8);
+    int e = (int)((b >> 52) & 0x7ff) - 1023;
+    uint64_t mb = b & 0xfffffffffffffull;
+    if (mb >= 0x6a09e667f3bcdull) {
+        e += 1;
+        mb |= 0x3fe0000000000000ull;
+    } else {
+        mb |= 0x3ff0000000000000ull;
+    }
+    double m;
+    std::memcpy(&m, &mb, 8);
+    const double f = m - 1.0, t = f / (2.0 + f), w = t * t;
+    static const double lg[7] = {6.666666666666735130e-01, 3.999999999940941908e-01, 2.857142874366239149e-01,
+                                 2.222219843214978396e-01, 1.818357216161805012e-01, 1.531383769920937332e-01,
+                                 1.479819860511658591e-01};
+    double R = lg[6];
+    for (int k = 5; k >= 0; --k) {
+        R = R * w;
+        R = R + lg[k];
+    }
+    R = R * w;
+    const double hi = (double)e * 0x1.62e42fefa39efp-1, u = f - R, tu = t * u, lo = f - tu;
+    return hi + lo;
+}
+
+namespace {
+inline double dp_uniform(uint32_t lo, uint32_t hi) {
+    const uint64_t u = ((uint64_t)hi << 32) | lo;
+    // an arithmetic shift by 11, written without shifting a negative value
+    const int64_t q = (u >> 63) ? (int64_t)((u >> 11) | 0xffe0000000000000ull) : (int64_t)(u >> 11);
+    return ((double)q + 0.5) * 0x1p-52;
+}
+}  // namespace
+
+void dp_pair_normals(uint64_t key, uint32_t round, uint64_t pair, double* z0, double* z1) {
+    const uint32_t kw[2] = {(uint32_t)key, (uint32_t)(key >> 32)};
+    for (uint32_t a = 0; a < 32; ++a) {
+        const uint32_t ctr[4] = {(uint32_t)pair, (uint32_t)(pair >> 32), round, a};
+        uint32_t x[4];
+        philox4x32_10(ctr, kw, x);
+        const double v1 = dp_uniform(x[0], x[1]), v2 = dp_uniform(x[2], x[3]);
+        const double s1 = v1 * v1, s2 = v2 * v2, s = s1 + s2;
+        if (s < 1.0) {
+            const double num = -2.0 * dp_plog(s), quo = num / s, f = std::sqrt(quo);
+            *z0 = v1 * f;
+            *z1 = v2 * f;
+            return;
+        }
+    }
+    *z0 = 0.0;
+    *z1 = 0.0;
+}
+
+void dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out) {
+    for (int64_t i = i0; i < i0 + n;) {
+        double z[2];
+        dp_pair_normals(key, round, (uint64_t)i >> 1, &z[0], &z[1]);
+        for (int64_t e = i & 1; e < 2 && i < i0 + n; ++e, ++i) out[i - i0] = z[e];
+    }
 }
 
 }  // namespace pgh_detail

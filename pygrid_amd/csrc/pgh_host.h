@@ -1,5 +1,6 @@
 // HIP-free host code of libpygrid_hip (not installed): the non-temporal copy, the copy pool, the
-// scatter out of a landed piece, page pre-faulting, the CPU count.  Nothing here may include HIP.
+// scatter out of a landed piece, page pre-faulting, the CPU count, the DP noise sampler's restatement.  Nothing here
+// may include HIP.
 #pragma once
 #include <algorithm>
 #include <condition_variable>
@@ -149,5 +150,15 @@ struct OutPiece {
 void scatter_out(const uint8_t* src, size_t off, size_t len, const std::vector<OutPiece>& pieces, CopyPool& pool);
 void prefault_small_any(uint8_t* p, size_t n);
 void prefault_parallel(uint8_t* p, size_t n, CopyPool& pool);
+
+// The DP noise sampler of include/pgh_api.h ("Gaussian noise on the clipped close") in plain C++, operation
+// by operation: what kernel K11 computes on the GPU (pgh_dp_normals_host; built with -ffp-contract=off).
+void philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+double dp_plog(double s);  // a normal s in (0, 1)
+void dp_pair_normals(uint64_t key, uint32_t round, uint64_t pair, double* z0, double* z1);
+// Z_i for the flat model indices [i0, i0 + n) (i0 >= 0): pair i >> 1, even i takes Z0, odd i Z1
+void dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out);
+// ((double)z * (double)C) / (double)N
+inline double dp_sigma(float z, float c, int64_t n) { return ((double)z * (double)c) / (double)n; }
 
 }  // namespace pgh_detail

@@ -233,6 +233,32 @@ struct ServerOptArgs {
 };
 hipError_t launch_server_opt(const ServerOptArgs& a, hipStream_t s);
 
+// K11: Gaussian noise on the clipped close (the definition is in include/pgh_api.h).  Like K10 it runs
+// behind a FINAL fold that wrote d = -g into a delta plane: g comes back by a sign flip, the param with
+// model index i takes n_i = (float)(sigma * Z_i), g' = g + n_i, and the launch writes out = ckpt - g', or
+// -- ahead of K10, ckpt == NULL -- the delta plane -(g') (out may be d itself: a lane reads its column
+// before it writes it).  Z comes from Philox4x32-10 with the counter (pair, round, attempt) and Marsaglia's
+// polar method, at most DP_ATTEMPTS attempts per pair; pair = i >> 1, so with i0 a multiple of 4 the
+// lane of a 16-byte column owns two whole pairs.  The last column of a ragged p goes scalar.  Integer-
+// and f64-ALU bound (12 bytes of HBM per param); no LDS, no atomics.  Workgroups of DP_WG_PARAMS
+// params, at most DP_MAX_WGS of them (grid-stride beyond).
+constexpr int DP_ATTEMPTS = 32;
+constexpr int DP_WG_PARAMS = 1024;
+constexpr int DP_MAX_WGS = 8192;
+struct DpNoiseArgs {
+    const float* d;      // every pointer at the launch's column 0, 16-byte aligned
+    const float* ckpt;   // NULL: write the delta plane
+    float* out;
+    int64_t p;           // params of the launch
+    int64_t i0;          // model index of column 0, a multiple of 4
+    uint64_t key;
+    uint32_t round;
+    double sigma;
+};
+hipError_t launch_dp_noise(const DpNoiseArgs& a, hipStream_t s);
+// The sampler alone: out[k] = Z_(i0 + k) for k < n (f64, device memory), any i0 >= 0.
+hipError_t launch_dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out, hipStream_t s);
+
 constexpr uint64_t STREAM_DIFF = 0, STREAM_CKPT = 1, STREAM_SECRET = 2, STREAM_SHARE = 3;
 constexpr float DIFF_SCALE = 2.6429e-7f;
 constexpr float CKPT_SCALE = 1.32145e-6f;

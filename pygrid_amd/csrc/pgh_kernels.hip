@@ -16,6 +16,9 @@
 //       order (build-owned: the norms of PGH_CLIPPED_MEAN)
 // K10 k_server_opt             the server optimizer's step behind a FINAL fold: FedAvgM, FedAdagrad,
 //       FedAdam, FedYogi on g = the cycle's average (build-owned: pgh_set_server_opt)
+// K11 k_dp_noise              Gaussian noise on the clipped average behind a FINAL fold, ahead of K10:
+//       Philox4x32-10, Marsaglia's polar method, a libm-free logarithm (build-owned: pgh_set_dp_noise,
+//       DESIGN.md section 5); k_dp_normals returns the sampler's normals alone
 //
 // Design (DESIGN.md "Kernels"): every kernel is a single streaming pass over the slab held in
 // HBM, column-blocked (SlabMap in pgh_kernels.h: blocks of ld columns, each block all rows,
@@ -828,6 +831,115 @@ __global__ __launch_bounds__(BLOCK) void k_server_opt(ServerOptArgs a) {
     }
 }
 
+// K11 (pgh_kernels.h; the sampler is defined operation by operation in include/pgh_api.h and restated
+// for the host in pgh_host.cpp).  Every f64 operation is rounded on its own (-ffp-contract=off); `/` and
+// __builtin_sqrt on doubles are the correctly rounded expansions (v_div_scale / v_div_fmas / v_div_fixup,
+// v_rsq_f64 with its refinement and fix-up), not the OCML *_rn entry points (see K10 above).
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t (&x)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}
+
+__device__ __forceinline__ double dp_uniform(uint32_t lo, uint32_t hi) {
+    const int64_t q = (int64_t)(((uint64_t)hi << 32) | lo) >> 11;  // arithmetic: 53 signed bits
+    return ((double)q + 0.5) * 0x1p-52;                             // exact, symmetric, never 0
+}
+
+__device__ __forceinline__ double dp_plog(double s) {
+    const uint64_t b = (uint64_t)__double_as_longlong(s);
+    int e = (int)((b >> 52) & 0x7ff) - 1023;
+    uint64_t mb = b & 0xfffffffffffffull;
+    const bool big = mb >= 0x6a09e667f3bcdull;
+    e += big ? 1 : 0;
+    mb |= big ? 0x3fe0000000000000ull : 0x3ff0000000000000ull;
+    const double m = __longlong_as_double((long long)mb);
+    const double f = m - 1.0, t = f / (2.0 + f), w = t * t;
+    double R = 1.479819860511658591e-01;
+    R = R * w + 1.531383769920937332e-01;
+    R = R * w + 1.818357216161805012e-01;
+    R = R * w + 2.222219843214978396e-01;
+    R = R * w + 2.857142874366239149e-01;
+    R = R * w + 3.999999999940941908e-01;
+    R = R * w + 6.666666666666735130e-01;
+    R = R * w;
+    return (double)e * 0x1.62e42fefa39efp-1 + (f - t * (f - R));
+}
+
+// The two standard normals of pair `pair`: the first of at most DP_ATTEMPTS polar attempts inside the
+// unit circle (acceptance pi / 4 per attempt, so lanes of a wave retry for 1.3 rounds on average and the
+// loop is bounded whatever the generator returns); +0.0 twice when every attempt was rejected.
+__device__ __forceinline__ void dp_pair_normals(uint32_t k0, uint32_t k1, uint32_t round, uint64_t pair, double& z0,
+                                                double& z1) {
+    z0 = 0.0;
+    z1 = 0.0;
+    for (uint32_t at = 0; at < (uint32_t)DP_ATTEMPTS; ++at) {
+        uint32_t x[4];
+        philox4x32_10((uint32_t)pair, (uint32_t)(pair >> 32), round, at, k0, k1, x);
+        const double v1 = dp_uniform(x[0], x[1]), v2 = dp_uniform(x[2], x[3]);
+        const double s = v1 * v1 + v2 * v2;
+        if (s < 1.0) {
+            const double f = __builtin_sqrt((-2.0 * dp_plog(s)) / s);
+            z0 = v1 * f;
+            z1 = v2 * f;
+            break;
+        }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_dp_noise(DpNoiseArgs a) {
+    const int64_t ncol = (a.p + 3) >> 2;
+    const uint32_t k0 = (uint32_t)a.key, k1 = (uint32_t)(a.key >> 32);
+    const bool to_out = a.ckpt != nullptr;
+    for (int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x; q < ncol; q += (int64_t)gridDim.x * BLOCK) {
+        const int64_t i = 4 * q;
+        const bool whole = i + 4 <= a.p;
+        f32x4 d, ck = {0.f, 0.f, 0.f, 0.f};
+        if (whole) {
+            d = ld4<false>(a.d + i);
+            if (to_out) ck = ld4<false>(a.ckpt + i);
+        } else {
+            d = ld4_tail(a.d, q, a.p);
+            if (to_out) ck = ld4_tail(a.ckpt, q, a.p);
+        }
+        const uint64_t pair = (uint64_t)(a.i0 + i) >> 1;  // i0 + i is a multiple of 4: two whole pairs
+        double z[4] = {0.0, 0.0, 0.0, 0.0};
+        dp_pair_normals(k0, k1, a.round, pair, z[0], z[1]);
+        if (i + 2 < a.p) dp_pair_normals(k0, k1, a.round, pair + 1, z[2], z[3]);
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float g = __uint_as_float(__float_as_uint(d[e]) ^ 0x80000000u);
+            const float n = (float)(a.sigma * z[e]);  // one f64 product, one rounding to f32
+            const float gn = g + n;
+            o[e] = to_out ? ck[e] - gn : __uint_as_float(__float_as_uint(gn) ^ 0x80000000u);
+        }
+        st4_tail(a.out, q, a.p, o);
+    }
+}
+
+// One lane per pair; the pairs that hold out[0] and out[n - 1] may lie half outside [i0, i0 + n).
+__global__ __launch_bounds__(BLOCK) void k_dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out) {
+    const int64_t pair0 = i0 >> 1, npairs = ((i0 + n - 1) >> 1) - pair0 + 1;
+    for (int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (int64_t)gridDim.x * BLOCK) {
+        double z0, z1;
+        dp_pair_normals((uint32_t)key, (uint32_t)(key >> 32), round, (uint64_t)(pair0 + t), z0, z1);
+        const int64_t k = 2 * (pair0 + t) - i0;  // -1 for the first pair of an odd i0
+        if (k >= 0 && k < n) out[k] = z0;
+        if (k + 1 >= 0 && k + 1 < n) out[k + 1] = z1;
+    }
+}
+
 // KIND 0: one splitmix64 word per param -> Irwin-Hall(4 x u16).  KIND 1 ("fast", config 4's
 // on-device data source): one word per 4 consecutive params (global index g >> 2), param g takes
 // u16 number g & 3 of it, centred, times 2 * scale (same sigma ~ 1e-2): a quarter of the integer
@@ -1514,6 +1626,26 @@ hipError_t launch_server_opt(const ServerOptArgs& a, hipStream_t s) {
     case 3: k_server_opt<3><<<g, BLOCK, 0, s>>>(a); break;
     default: k_server_opt<4><<<g, BLOCK, 0, s>>>(a); break;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_dp_noise(const DpNoiseArgs& a, hipStream_t s) {
+    static_assert(DP_WG_PARAMS == 4 * BLOCK, "one 16-byte column per lane");
+    if (a.p <= 0 || a.i0 < 0 || (a.i0 & 3) || !a.d || !a.out) return hipErrorInvalidValue;
+    for (const void* p : {(const void*)a.d, (const void*)a.ckpt, (const void*)a.out})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return hipErrorInvalidValue;
+    const int64_t ncol = (a.p + 3) >> 2;
+    const unsigned g = (unsigned)std::min<int64_t>((ncol + BLOCK - 1) / BLOCK, DP_MAX_WGS);
+    k_dp_noise<<<g, BLOCK, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out, hipStream_t s) {
+    if (i0 < 0 || n < 0 || i0 > INT64_MAX - n || (n > 0 && !out)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const int64_t npairs = ((i0 + n - 1) >> 1) - (i0 >> 1) + 1;
+    const unsigned g = (unsigned)std::min<int64_t>((npairs + BLOCK - 1) / BLOCK, DP_MAX_WGS);
+    k_dp_normals<<<g, BLOCK, 0, s>>>(key, round, i0, n, out);
     return hipGetLastError();
 }
 

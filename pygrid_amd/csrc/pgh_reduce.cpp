@@ -83,9 +83,19 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     // A server optimizer: the FINAL launch, unchanged, subtracts the average from -0 into the delta
     // plane, and K10 behind it on the same stream applies the step to the real ckpt / out.
     const bool opt = c->opt.kind != PGH_OPT_NONE && (flags & pgh::FL_FINAL);
+    // Noise on the clipped close: a second tenant of that mechanism.  K11 follows the FINAL launch and noises
+    // the delta plane in place ahead of K10, or, without an optimizer, reads planes of the noise state's
+    // own and writes the real out.
+    const bool noise = noise_on(c) && (flags & pgh::FL_FINAL);
+    if (noise) RC(check_noise_final(c, mode));  // (the entry points have checked: nothing was launched)
+    if (noise && (!fa.ckpt || !fa.out)) return fail(c, PGH_E_ARG, "a noised FINAL fold needs ckpt and out");
     if (opt) {
         a.ckpt = c->opt.d_nz.as<float>() + off;
         a.out = c->opt.d_d.as<float>() + off;
+    } else if (noise) {
+        RC(noise_planes(c, s));
+        a.ckpt = c->noise.d_nz.as<float>() + off;
+        a.out = c->noise.d_d.as<float>() + off;
     }
     a.divisor = fa.divisor;
     a.flags = flags;
@@ -104,6 +114,7 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
         bytes += trim_state_bytes(c, flags, pg);
     }
     RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, rows.src, s); }));
+    if (noise) RC(dp_noise_launch(c, fa, client0 + rows.n, opt, s));  // the FINAL launch ends the cycle's N rows
     return opt ? server_opt_launch(c, fa, s) : PGH_OK;
 }
 
@@ -491,6 +502,7 @@ int pgh_stream_flush(pgh_ctx* c) {
 namespace {
 int stream_finish(pgh_ctx* c, FinalArgs fa, hipStream_t cs, bool fedavg, int mode_or_base) {
     if (!c->streaming) return fail(c, PGH_E_STATE, "not streaming (call pgh_stream_begin first)");
+    if (fedavg) RC(check_noise_final(c, c->kind));  // (a stream never clips: with noise on it cannot close)
     const int64_t run = ready_run(c, c->folded);
     RC(check_no_gaps(c, c->folded, run));
     const int64_t n = c->folded + run;
@@ -523,6 +535,7 @@ int pgh_stream_finish_resident(pgh_ctx* c) {
     if (c && c->grp) return pgh_group_api::stream_finish_resident(c);
     RC(check_dtype(c, PGH_F32));
     RC(check_ckpt(c, "pgh_stream_finish_resident"));
+    if (c->streaming) RC(check_noise_final(c, c->kind));
     DeviceGuard g(c->device);
     clear_final_marks(c);
     const double t0 = now_ms();
@@ -536,6 +549,7 @@ int pgh_stream_finish(pgh_ctx* c, const float* ckpt, float* out) {
     if (c && c->grp) return pgh_group_api::stream_finish(c, ckpt, out);
     RC(check_dtype(c, PGH_F32));
     if (!ckpt || !out) return fail(c, PGH_E_ARG, "ckpt / out is NULL");
+    if (c->streaming) RC(check_noise_final(c, c->kind));
     DeviceGuard g(c->device);
     const double t0 = now_ms();
     const size_t bytes = sizeof(float) * (size_t)c->pg;

@@ -1,5 +1,6 @@
 // libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); clipping's
-// per-row sums of squares (K7), their host cache, the scales and the tallies; the trimmed mean's state planes
+// per-row sums of squares (K7), their host cache, the scales and the tallies; the Gaussian noise on the clipped
+// close (K11 behind a FINAL launch, its planes, setting and entry points); the trimmed mean's state planes
 // (K8); the median's driver and row table (K9, K9p); and what the rules' state does at each lifecycle event of
 // the context (rules_*: the one call each event's site makes).  The state itself: pgh_rules.h.
 // (struct pgh_ctx and the shared helpers: pgh_ctx.h)
@@ -13,7 +14,24 @@ using namespace pgh_detail;
 
 namespace pgh_detail {
 
+namespace {
+int mode_use_rule(pgh_ctx* c, int mode, ModeUse use);
+}
+
 int check_mode_use(pgh_ctx* c, int mode, ModeUse use) {
+    RC(mode_use_rule(c, mode, use));
+    // a RESIDENT fold and a closing slot fold end in a FINAL launch (noise is never on for a group or a stream)
+    return use == USE_RESIDENT || use == USE_SLOT_FINAL ? check_noise_final(c, mode) : PGH_OK;
+}
+
+int check_noise_final(pgh_ctx* c, int mode) {
+    if (noise_on(c) && mode != PGH_CLIPPED_MEAN)
+        return fail(c, PGH_E_STATE, "DP noise is set (pgh_set_dp_noise): only PGH_CLIPPED_MEAN may close a cycle, not mode %d", mode);
+    return PGH_OK;
+}
+
+namespace {
+int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
     switch (mode) {
     case PGH_MEAN: case PGH_ITERATIVE_MEAN: case PGH_WEIGHTED_MEAN:
         return PGH_OK;
@@ -34,6 +52,7 @@ int check_mode_use(pgh_ctx* c, int mode, ModeUse use) {
         return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
     }
 }
+}  // namespace
 
 // ---- the lifecycle events of the context, as the rules see them -------------------------------------------
 
@@ -52,7 +71,9 @@ void rules_slab_freed(pgh_ctx* c) {  // the streams are idle (free_slab synchron
 }
 
 void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep_opt) {
-    if (!(keep_opt && lo == c->lo && hi == c->hi && pvec == c->opt.pvec)) c->opt.release();
+    const bool same = keep_opt && lo == c->lo && hi == c->hi;
+    if (!(same && pvec == c->opt.pvec)) c->opt.release();
+    if (!(same && pvec == c->noise.pvec)) c->noise.release();  // (free_slab has synchronised the streams)
     if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
 }
 
@@ -260,6 +281,42 @@ int resident_clip_scales(pgh_ctx* c, int64_t n) {
     return PGH_OK;
 }
 
+// ---- Gaussian noise on the clipped close: the planes and K11 behind a FINAL launch ---------------------------
+
+int noise_planes(pgh_ctx* c, hipStream_t s) {
+    NoiseState& ns = c->noise;
+    if (ns.d_nz && ns.d_d) return PGH_OK;
+    const size_t bytes = 4 * (size_t)c->pvec;
+    if (!ns.d_nz.reserve(bytes) || !ns.d_d.reserve(bytes)) {
+        ns.d_nz.reset();
+        ns.d_d.reset();
+        return fail(c, PGH_E_OOM, "allocation of the noise planes (%zu bytes each) failed", bytes);
+    }
+    CK(c, hipMemsetD32Async((hipDeviceptr_t)ns.d_nz.as<void>(), (int)0x80000000u, (size_t)c->pvec, s));
+    CK(c, hipStreamSynchronize(s));  // (a later FINAL may read the plane on another caller's stream)
+    return PGH_OK;
+}
+
+int dp_noise_launch(pgh_ctx* c, const FinalArgs& fa, int64_t n, bool into_opt, hipStream_t s) {
+    NoiseState& ns = c->noise;
+    if (n <= 0) return fail(c, PGH_E_STATE, "a noised close of no diffs");
+    pgh::DpNoiseArgs o{};
+    float* d = (into_opt ? c->opt.d_d : ns.d_d).as<float>() + fa.off;
+    o.d = d;
+    o.ckpt = into_opt ? nullptr : fa.ckpt + fa.off;
+    o.out = into_opt ? d : fa.out + fa.off;
+    o.p = fa.len;
+    o.i0 = c->lo + fa.off;
+    o.key = ns.key;
+    o.round = ns.round;
+    o.sigma = dp_sigma(ns.z, c->clip.c, n);
+    // HBM bytes: d in and out again (ahead of K10), or d and ckpt in and out out
+    RC(timed_launch(c, s, (into_opt ? 8ull : 12ull) * (uint64_t)fa.len, [&] { return pgh::launch_dp_noise(o, s); }));
+    ns.sigma_last = o.sigma;
+    ns.n_last = n;
+    return PGH_OK;
+}
+
 }  // namespace pgh_detail
 
 namespace {
@@ -337,5 +394,52 @@ int pgh_clip_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_clipped, double* max_
     cl.rows = rows0;
     cl.clipped = cl0;
     cl.max_norm = mx0;
+    return PGH_OK;
+}
+
+// ---- Gaussian noise on the clipped close: the setting, the sampler alone, what the last close used ----------
+
+int pgh_set_dp_noise(pgh_ctx* c, float z, uint64_t key, uint32_t round) {
+    if (!c) return PGH_E_ARG;
+    if (z == 0.f) {  // off: always possible (the planes stay for the next noised cycle of this shard)
+        c->noise.z = 0.f;
+        return PGH_OK;
+    }
+    if (!(z > 0.f) || !std::isfinite(z)) return fail(c, PGH_E_ARG, "the noise multiplier must be finite and > 0, or 0 for off");
+    RC(check_clip_ctx(c, "pgh_set_dp_noise"));
+    c->noise.z = z;
+    c->noise.key = key;
+    c->noise.round = round;
+    c->noise.pvec = c->pvec;
+    return PGH_OK;
+}
+
+int pgh_dp_normals(pgh_ctx* c, uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_dp_normals runs on one GPU: call it on pgh_group_child");
+    if (i0 < 0 || n < 0 || i0 > INT64_MAX - n || (n > 0 && !out)) return fail(c, PGH_E_ARG, "bad index range [%lld,+%lld)", (long long)i0, (long long)n);
+    if (n == 0) return PGH_OK;
+    DeviceGuard g(c->device);
+    DeviceBuf d;
+    if (!d.reserve(8 * (size_t)n)) return fail(c, PGH_E_OOM, "allocation of %lld normals failed", (long long)n);
+    const hipError_t e = pgh::launch_dp_normals(key, round, i0, n, d.as<double>(), c->stream);
+    if (e != hipSuccess) return fail(c, PGH_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    CK(c, hipMemcpyAsync(out, d.as<double>(), 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));  // d is freed on return
+    return PGH_OK;
+}
+
+int pgh_dp_normals_host(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out) {
+    if (i0 < 0 || n < 0 || i0 > INT64_MAX - n || (n > 0 && !out)) return fail(nullptr, PGH_E_ARG, "bad index range [%lld,+%lld)", (long long)i0, (long long)n);
+    dp_normals(key, round, i0, n, out);
+    return PGH_OK;
+}
+
+int pgh_dp_stats(pgh_ctx* c, float* z, double* sigma_last, int64_t* n_last) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_dp_stats: group contexts add no noise");
+    if (z) *z = c->noise.z;
+    if (sigma_last) *sigma_last = c->noise.sigma_last;
+    if (n_last) *n_last = c->noise.n_last;
     return PGH_OK;
 }

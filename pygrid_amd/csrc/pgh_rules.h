@@ -1,5 +1,5 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, trim, med and opt.  Their owners release with the context.
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, trim, med and opt.  Their owners release with the context.
 // The code that works on them: pgh_rules.cpp (clip, trim, med and the lifecycle calls rules_*),
 // pgh_serveropt.cpp (opt).  Not installed.
 #pragma once
@@ -46,6 +46,29 @@ struct ClipState {
     // the slot folds of the running cycle into the finished totals: scales[k] beside norms[k]
     void count_cycle(const std::vector<float>& scales) {
         count(scales.data(), norms.data(), (int64_t)std::min(norms.size(), scales.size()));
+    }
+};
+
+// Gaussian noise on the clipped close (pgh_set_dp_noise): a modifier of the clip
+// rule, not a rule of its own.  With z > 0 fold_launch runs every fp32 FINAL -- PGH_CLIPPED_MEAN only,
+// any other mode is refused -- against a -0 plane into a delta plane and K11 behind it: the server
+// optimizer's planes when one is set (K10 follows K11), else the two owned here, allocated by the first
+// noised FINAL.  The setting belongs to the model like the optimizer's: pgh_reset / pgh_reserve keep it,
+// a new layout or shard clears it (rules_shard_set).
+struct NoiseState {
+    float z = 0.f;        // the noise multiplier; 0 = off
+    uint64_t key = 0;
+    uint32_t round = 0;
+    DeviceBuf d_nz, d_d;  // float [pvec]: -0.0f everywhere; d = -g of the last noised FINAL without an optimizer
+    int64_t pvec = 0;     // the planes' length
+    double sigma_last = 0.0;  // what the last noised FINAL used: z * C / N, and N
+    int64_t n_last = 0;
+
+    void release() {  // planes and setting; the caller has waited for the context's work
+        d_nz.reset();
+        d_d.reset();
+        z = 0.f;
+        pvec = 0;
     }
 };
 

@@ -31,7 +31,8 @@ from .engine import ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
 from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, check_trim_count, clip_norm_of, failing_closed, median_of, \
     rule_kwargs, rule_of, set_on_engine, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
-from . import serveropt
+from . import dp, serveropt
+from .dp import DpKeys, dp_noise_of
 from .serveropt import ServerOptStates, server_opt_of
 
 
@@ -284,12 +285,15 @@ class CycleAggregator:
     each GPU's slice of every diff over its own PCIe link, bit-identical results)."""
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
-                 mean_plans: Optional[str] = None, opt_states: Optional[ServerOptStates] = None):
+                 mean_plans: Optional[str] = None, opt_states: Optional[ServerOptStates] = None,
+                 dp_keys: Optional[DpKeys] = None):
         if engine is None:
             engine = Engine(devices=devices) if devices is not None else Engine(device)
         self.engine = engine
         # server-optimizer moments per FL process (serveropt.py); share one between the users of an engine
         self.opt_states = opt_states if opt_states is not None else ServerOptStates()
+        # the noise key per FL process (dp.py); share one between the users of an engine
+        self.dp_keys = dp_keys if dp_keys is not None else DpKeys()
         self.mean_plans = mean_plan_policy(mean_plans)  # non-iterative hosted plans: "decline" | "probe"
         self._numel: tuple = ()
         self._cap = 0
@@ -317,26 +321,37 @@ class CycleAggregator:
     # ---- bytes in / bytes out: the replaceable slice cycle_manager.py:240-303 -------------------
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
-                           plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None) -> bytes:
+                           plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
+                           dp_noise=UNSET, dp_round=None) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
         byte and only replaces the payloads (ids and tags survive).  ``plan_key``: the hosted
         plan's serialized bytes, to probe it once per plan instead of once per cycle.  ``opt_key``: the
         FL process id under which ``server_config["server_optimizer"]``'s moments are kept (required
-        when the key is set); the step is committed once the new checkpoint bytes exist."""
+        when the key is set); the step is committed once the new checkpoint bytes exist.  ``dp_noise`` /
+        ``dp_round``: Gaussian noise on the clipped close (``dp.dp_noise_of``; default
+        ``server_config["dp_noise"]``) and the round it is drawn for -- the cycle's id, required beside it;
+        the key not given in the setting is ``opt_key``'s in ``dp_keys``."""
         if framing not in ("fresh", "template"):
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         rule = rule_of(server_config, clip_norm, trim_count, median)
         opt = server_opt_of(server_config)
-        with serveropt.failing_closed_opt(opt), failing_closed(rule, "the engine cannot average this cycle"):
+        noise = dp_noise_of(server_config, dp_noise)
+        dp.check_rule(noise, rule)
+        with serveropt.failing_closed_opt(opt), dp.failing_closed_dp(noise), \
+                failing_closed(rule, "the engine cannot average this cycle"):
             return self._average_plan_diffs(server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key,
-                                            rule, opt, opt_key)
+                                            rule, opt, opt_key, noise, dp_round)
+
+    def _set_noise(self, noise, opt_key, dp_round):
+        # after the bound is set and before the first ingest: this cycle's noise, or none
+        dp.set_on_engine(self.engine, noise, None if noise is None else self.dp_keys.key_for(opt_key, noise), dp_round)
 
     def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, rule,
-                            opt=None, opt_key=None):
+                            opt=None, opt_key=None, noise=None, dp_round=None):
         mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                            shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), **rule_kwargs(rule))
         _check_diff_count(rule, len(diffs))
@@ -347,6 +362,7 @@ class CycleAggregator:
             raise
         self._prepare(numel, len(diffs))
         set_on_engine(self.engine, rule)  # before the first ingest: each diff's norm pass rides behind its copy
+        self._set_noise(noise, opt_key, dp_round)
         self.opt_states.bind(self.engine, opt_key, opt, sum(numel))  # before the fold: this process's moments
         if checkpoint is not self._resident or self.engine.ckpt_owner is not self:
             self.engine.ckpt_upload_state(checkpoint)  # else: the last cycle's output is still in HBM
@@ -375,12 +391,16 @@ class CycleAggregator:
     # ---- tensor lists in / out (what the reference holds after unserialize) ---------------------
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
-                       weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None) -> List[np.ndarray]:
+                       weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
+                       dp_noise=UNSET, dp_round=None) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         rule = rule_of(server_config, clip_norm, trim_count, median)
         opt = server_opt_of(server_config)
-        with serveropt.failing_closed_opt(opt), failing_closed(rule, "the engine cannot average this cycle"):
+        noise = dp_noise_of(server_config, dp_noise)
+        dp.check_rule(noise, rule)
+        with serveropt.failing_closed_opt(opt), dp.failing_closed_dp(noise), \
+                failing_closed(rule, "the engine cannot average this cycle"):
             shapes = [np.shape(p) for p in model_params]
             mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
                                n_clients=len(diffs), **rule_kwargs(rule))
@@ -388,6 +408,7 @@ class CycleAggregator:
             numel = [int(np.prod(s)) for s in shapes]
             self._prepare(numel, len(diffs))
             set_on_engine(self.engine, rule)
+            self._set_noise(noise, opt_key, dp_round)
             self.opt_states.bind(self.engine, opt_key, opt, sum(numel))
             for i, d in enumerate(diffs):
                 if len(d) != len(numel):
@@ -463,12 +484,16 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
             diffs = [r.diff for r in reports]  # what :247-250 reads, at the query
         rule = rule_of(server_config)  # a malformed setting fails the close
         opt = server_opt_of(server_config)  # likewise
+        noise = dp_noise_of(server_config)  # likewise; it needs the clip bound
+        dp.check_rule(noise, rule)
         # (the key only beside an optimizer: aggregators with the earlier signature keep working without one)
-        opt_kw = {"opt_key": cycle.fl_process_id} if opt is not None else {}
+        opt_kw = {"opt_key": cycle.fl_process_id} if opt is not None or noise is not None else {}
+        if noise is not None:
+            opt_kw["dp_round"] = cycle.id  # the round the noise is drawn for: a retried close draws it again
         try:
-            # a plan whose cached verdict is a decline raises from hosted_plan already: under an optimizer
-            # or a rule that must fail the close too, not reach the fall-back below
-            with serveropt.failing_closed_opt(opt), failing_closed(rule):
+            # a plan whose cached verdict is a decline raises from hosted_plan already: under an optimizer,
+            # a rule or noise that must fail the close too, not reach the fall-back below
+            with serveropt.failing_closed_opt(opt), dp.failing_closed_dp(noise), failing_closed(rule):
                 avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
                                                  getattr(aggregator, "mean_plans", None))
                 new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,

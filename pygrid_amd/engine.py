@@ -310,6 +310,41 @@ class Engine:
         self._check(self._lib.pgh_clip_stats(self._h, C.byref(n), C.byref(k), C.byref(m)), "clip_stats")
         return {"rows": n.value, "clipped": k.value, "max_norm": m.value}
 
+    # ---- Gaussian noise on the clipped close (DP-FedAvg, kernel K11) --------------------------------
+    def set_dp_noise(self, z: float, key: int = 0, rnd: int = 0):
+        """Noise multiplier ``z`` for later CLIPPED_MEAN closes (finite, > 0; ``include/pgh_api.h``): the
+        close adds ``N(0, (z C / N)^2)`` per parameter, drawn from ``(key, rnd)``; 0 turns it off.  With
+        it on, a close in any other mode is refused (PGH_E_STATE).  Refused (PGH_E_UNSUPPORTED) where
+        ``set_clip_norm`` is; a new layout or shard clears it."""
+        self._check(self._lib.pgh_set_dp_noise(self._h, C.c_float(float(z)), C.c_uint64(int(key) & (2 ** 64 - 1)),
+                                               C.c_uint32(int(rnd) & 0xFFFFFFFF)), "set_dp_noise")
+
+    def dp_normals(self, key: int, rnd: int, i0: int, n: int) -> np.ndarray:
+        """K11's standard normals ``Z_i`` for the flat model indices ``[i0, i0 + n)``, float64, sampled
+        on the GPU (tests, debugging)."""
+        out = np.empty(int(n), dtype=np.float64)
+        self._check(self._lib.pgh_dp_normals(self._h, C.c_uint64(int(key) & (2 ** 64 - 1)), C.c_uint32(int(rnd) & 0xFFFFFFFF),
+                                             int(i0), int(n), out.ctypes.data_as(C.POINTER(C.c_double))), "dp_normals")
+        return out
+
+    @staticmethod
+    def dp_normals_host(key: int, rnd: int, i0: int, n: int) -> np.ndarray:
+        """The same normals from the library's plain C++ restatement of the sampler (no GPU)."""
+        lib = _lib.load()
+        out = np.empty(int(n), dtype=np.float64)
+        rc = lib.pgh_dp_normals_host(C.c_uint64(int(key) & (2 ** 64 - 1)), C.c_uint32(int(rnd) & 0xFFFFFFFF), int(i0),
+                                     int(n), out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise AggregationError(f"dp_normals_host: {_lib.STATUS_NAMES.get(rc, rc)}: "
+                                   f"{lib.pgh_last_error(None).decode(errors='replace')}", status=rc)
+        return out
+
+    def dp_stats(self) -> dict:
+        """``multiplier`` (0: off) and what the last noised close used: ``sigma`` = z C / N and ``n``."""
+        z, s, n = C.c_float(0), C.c_double(0), C.c_int64(0)
+        self._check(self._lib.pgh_dp_stats(self._h, C.byref(z), C.byref(s), C.byref(n)), "dp_stats")
+        return {"multiplier": z.value, "sigma": s.value, "n": n.value}
+
     # ---- coordinate-wise trimmed mean (TRIMMED_MEAN) ----------------------------------------------
     def set_trim(self, b: int):
         """Values dropped per side and parameter by later TRIMMED_MEAN folds (1 .. TRIM_MAX); 0 turns

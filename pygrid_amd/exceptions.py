@@ -68,6 +68,14 @@ class ServerOptUnavailableError(AggregationError):
     the close fails closed."""
 
 
+class DpNoiseUnavailableError(AggregationError):
+    """The FL process asks for Gaussian noise on its clipped close (``server_config["dp_noise"]``) and the
+    engine cannot add it this cycle: no ``diff_clip_norm`` beside it, a cycle the engine declines or cannot
+    clip (an unaccelerated or iterative plan, a non-float32 model, weights, a multi-GPU group), an engine
+    without ``set_dp_noise``, or a close without a round.  Like the rules' errors it is NOT a
+    ``PlanNotAcceleratedError``: the node's own averaging adds no noise, so the close fails closed."""
+
+
 class ModelNotAcceleratedError(PlanNotAcceleratedError):
     """The checkpoint or a diff holds well-formed tensors that are not float32 (another dtype, or a
     serializer other than syft's "all").  The reference averages them with torch's type promotion;

@@ -68,7 +68,7 @@ from . import state as state_codec
 from .cycle import _decline_non_float32
 from .engine import F32, MEAN, WEIGHTED_MEAN, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
-from . import serveropt
+from . import dp, serveropt
 from .robust import check_trim_count, failing_closed, rule_of, set_on_engine
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
@@ -85,8 +85,14 @@ class IncrementalCycle:
     def __init__(self, engine: Engine, numel, mode: int = MEAN, slots: Optional[int] = None, fold_batch: int = 8,
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
-                 median: bool = False, server_opt=None, opt_key=None, opt_states=None):
-        """``server_opt``: the FL process's server optimizer (``serveropt.server_opt_of``), its moments
+                 median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
+                 dp_keys=None):
+        """``dp_noise``: the FL process's noise setting (``dp.dp_noise_of``; it needs ``clip_norm``), drawn for
+        ``dp_round`` (the cycle's id) from the key it names or ``opt_key``'s in ``dp_keys`` (share the
+        close-time aggregator's).  Early folds do not involve it: K11 follows the close's FINAL pass alone.
+        ``last_close`` reports ``noise_multiplier`` and ``noise_std`` (z C / N).
+
+        ``server_opt``: the FL process's server optimizer (``serveropt.server_opt_of``), its moments
         kept under ``opt_key`` (the FL process id) in ``opt_states`` (share the close-time aggregator's).
         Early folds do not involve it; the close binds the process's moments before its FINAL pass and
         commits the step once the new checkpoint bytes exist.
@@ -119,6 +125,11 @@ class IncrementalCycle:
         if rule is not None:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
         self._fold_mode = rule.mode if rule else mode
+        self._noise = noise = dp.dp_noise_of({}, dp_noise)
+        dp.check_rule(noise, rule)
+        self._noise_args = (None, None)
+        if noise is not None:
+            self._noise_args = ((dp_keys if dp_keys is not None else dp.DpKeys()).key_for(opt_key, noise), dp_round)
         self._opt, self._opt_key = server_opt, opt_key
         self._opt_states = opt_states if opt_states is not None else serveropt.ServerOptStates()
         if server_opt is not None and opt_key is None:
@@ -169,6 +180,7 @@ class IncrementalCycle:
             # the close overlaps the tail of the last report's copy (pgh_set_ingest_ranges)
             engine.set_ingest_ranges(os.environ.get("PGH_INGEST_RANGES", "1") != "0")
         set_on_engine(engine, rule)  # (the engine was reset above: no slot folds under way)
+        dp.set_on_engine(engine, noise, *self._noise_args)  # set, or cleared: a shared engine carries none over
         self._ckpt: Optional[bytes] = None  # checkpoint bytes whose payloads are resident in HBM
         if checkpoint is not None and getattr(engine, "ckpt_owner", None) is not None \
                 and getattr(engine, "ckpt_bytes", None) is checkpoint:
@@ -478,6 +490,8 @@ class IncrementalCycle:
             self._prepared = None
             # before the FINAL pass: this process's moments (another process may have closed on the engine since)
             self._opt_states.bind(self.engine, self._opt_key, self._opt, sum(self._numel))
+            if self._noise is not None:  # (again, right before the FINAL pass: no un-noised average leaves)
+                dp.set_on_engine(self.engine, self._noise, *self._noise_args)
             stats = self._fold_in_order(rest, fetch)
             del stats["db_rows"]
             stats.update(refold=bool(refold), reason=refold or None, early=k, n=len(order),
@@ -488,6 +502,7 @@ class IncrementalCycle:
             else:
                 stats.update(clipped=0, max_norm=None)
             stats.update(trim=self.trim_count, median=self.median)
+            stats.update(dp.close_stats(self.engine, self._noise))
             self.last_close = stats
             new = (state_codec.fresh_checkpoint(self.engine, checkpoint, prepared=prep) if framing == "fresh"
                    else self.engine.ckpt_patch_state(checkpoint))

@@ -75,9 +75,11 @@ from .checkpoints import Checkpoint, CheckpointStore
 from .cycle import CycleAggregator, _decline_non_float32, finish_cycle, hosted_plan, make_average_plan_diffs, \
     select_mode
 from .engine import MEAN
-from .exceptions import AggregationError, PlanNotAcceleratedError, PyGridError, ServerOptUnavailableError, \
-    StateParseError
+from .exceptions import AggregationError, DpNoiseUnavailableError, PlanNotAcceleratedError, PyGridError, \
+    ServerOptUnavailableError, StateParseError
 from .incremental import IncrementalCycle
+from . import dp
+from .dp import DP_KEY, dp_noise_of
 from .serveropt import OPT_KEY, server_opt_of
 from .robust import failing_closed, rule_kwargs, rule_of
 from .trigger import CycleCloseTrigger
@@ -321,8 +323,19 @@ class NodeEngine:
         rule = rule_of(server_config)  # the process's robust-aggregation rule (a malformed setting raises)
         # under a rule a cycle the engine does not run is not _DECLINED -- the node's own averaging does not
         # apply the rule: the close-time path refuses the cycle again, loudly, when it closes
-        with failing_closed(rule):
+        noise = dp_noise_of(server_config)  # likewise; without the clip bound it raises
+        dp.check_rule(noise, rule)
+        with dp.failing_closed_dp(noise), failing_closed(rule):
             return self._new_cycle_for(cm, cycle, server_config, rule, fresh)
+
+    def _dp_kwargs(self, server_config, cycle) -> dict:
+        """The FL process's noise for its report-time cycle: the setting, the round (the cycle's id) and the
+        keys shared with the close-time path (nothing when none is set)."""
+        noise = dp_noise_of(server_config)
+        if noise is None:
+            return {}
+        return {"dp_noise": noise, "dp_round": cycle.id, "opt_key": cycle.fl_process_id,
+                "dp_keys": self.aggregator.dp_keys}
 
     def _opt_kwargs(self, server_config, cycle) -> dict:
         """The FL process's server optimizer for its report-time cycle: the setting, the key its moments
@@ -348,7 +361,7 @@ class NodeEngine:
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
         inc = IncrementalCycle(self.engine, numel, mode=MEAN if rule else mode, slots=self.slots,
                                fold_batch=self.fold_batch, checkpoint=ckpt, **rule_kwargs(rule),
-                               **self._opt_kwargs(server_config, cycle))
+                               **{**self._dp_kwargs(server_config, cycle), **self._opt_kwargs(server_config, cycle)})
         if not fresh:  # after a restart: the rows assigned before it (a cycle just created has none;
             # an assignment that lands while this state is built is recorded from _pending_assign)
             for row in _rows(cm, cycle_id=cycle.id):
@@ -431,6 +444,10 @@ class NodeEngine:
             original = _refuse_opt(cycle.id)  # fail closed: the node's own averaging applies no optimizer
         if rule is not None:
             original = _refuse(rule, cycle.id)  # fail closed: the node's own averaging does not apply the rule
+        noise = dp_noise_of(server_config)  # (a malformed setting fails the close)
+        dp.check_rule(noise, rule)
+        if noise is not None:
+            original = _refuse_dp(cycle.id)  # fail closed: the node's own averaging adds no noise
         with self._engine_for_close():
             model = ckpt = None
             if isinstance(self._cycles.get(cycle.id), IncrementalCycle):
@@ -495,9 +512,11 @@ class NodeEngine:
                 return close_time(cm, server_config, cycle)
             self.stats["closes_report_time"] += 1
             if rule is not None:
-                log.info("cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)", cycle.id, rule.key,
+                noised = "" if noise is None else "; %s multiplier %s, noise std %s per parameter" % (
+                    DP_KEY, st.last_close.get("noise_multiplier"), st.last_close.get("noise_std"))
+                log.info("cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)%s", cycle.id, rule.key,
                          rule.value, st.last_close.get("n", 0), st.last_close.get("clipped", 0),
-                         st.last_close.get("max_norm"))
+                         st.last_close.get("max_norm"), noised)
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)
             self.aggregator._resident = None
@@ -550,6 +569,14 @@ def _refuse_opt(cycle_id):
     def original(*_a, **_k):
         raise ServerOptUnavailableError(f"{OPT_KEY} is set and the engine does not average cycle {cycle_id}; not "
                                         "falling back to the node's own averaging, which applies no optimizer")
+    return original
+
+
+def _refuse_dp(cycle_id):
+    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for noise."""
+    def original(*_a, **_k):
+        raise DpNoiseUnavailableError(f"{DP_KEY} is set and the engine does not average cycle {cycle_id}; not falling "
+                                      "back to the node's own averaging, which adds no noise")
     return original
 
 
