@@ -30,10 +30,11 @@ from . import state as state_codec
 from .engine import ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
 from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, check_trim_count, clip_norm_of, failing_closed, median_of, \
-    rule_kwargs, rule_of, set_on_engine, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
-from . import dp, serveropt
-from .dp import DpKeys, dp_noise_of
-from .serveropt import ServerOptStates, server_opt_of
+    rule_of, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
+from . import serveropt
+from .dp import DpKeys
+from .serveropt import ServerOptStates
+from .settings import settings_of
 
 
 def ready_to_average(server_config: dict, received_diffs: int, cycle_end=None, now=None) -> bool:
@@ -265,9 +266,13 @@ def _decline_non_float32(pb: bytes, what: str):
         raise ModelNotAcceleratedError(f"{what} holds non-float32 tensors {bad[:8]} (the engine is fp32-only)")
 
 
-def _check_diff_count(rule, n_diffs: int):
-    if rule is not None and rule.key == TRIM_KEY:
-        check_trim_count(rule.value, n_diffs)
+def checkpoint_numels(checkpoint: bytes):
+    """The checkpoint's tensor sizes (``cycle_manager.py:240``); a non-float32 model is declined."""
+    try:
+        return state_codec.tensor_numels(checkpoint)
+    except StateParseError:
+        _decline_non_float32(checkpoint, "the checkpoint")
+        raise
 
 
 def _shapes_or_none(pb: bytes):
@@ -337,33 +342,30 @@ class CycleAggregator:
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        rule = rule_of(server_config, clip_norm, trim_count, median)
-        opt = server_opt_of(server_config)
-        noise = dp_noise_of(server_config, dp_noise)
-        dp.check_rule(noise, rule)
-        with serveropt.failing_closed_opt(opt), dp.failing_closed_dp(noise), \
-                failing_closed(rule, "the engine cannot average this cycle"):
-            return self._average_plan_diffs(server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key,
-                                            rule, opt, opt_key, noise, dp_round)
+        given = (clip_norm, trim_count, median, dp_noise)
+        with self._closing(server_config, given, avg_plan, weights, plan_key, lambda: _shapes_or_none(checkpoint),
+                           lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round) as (settings, mode):
+            return self._average_plan_diffs(checkpoint, diffs, weights, framing, settings, mode)
 
-    def _set_noise(self, noise, opt_key, dp_round):
-        # after the bound is set and before the first ingest: this cycle's noise, or none
-        dp.set_on_engine(self.engine, noise, None if noise is None else self.dp_keys.key_for(opt_key, noise), dp_round)
+    @contextlib.contextmanager
+    def _closing(self, server_config, given, avg_plan, weights, plan_key, shapes, numel_of, n_diffs, opt_key, dp_round):
+        """What both entry points do before their first ingest, and the fail-closed block they fold in:
+        gives ``(settings, mode)`` with the engine laid out for ``numel_of()`` and ``n_diffs`` rows, the rule and the
+        noise set and ``opt_key``'s moments bound.  ``given``: the caller's clip_norm, trim_count, median, dp_noise."""
+        settings = settings_of(server_config, *given)
+        with settings.fail_closed("the engine cannot average this cycle"):
+            mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
+                               shapes=shapes, n_clients=n_diffs, **settings.rule_kwargs())
+            if settings.rule is not None and settings.rule.key == TRIM_KEY:
+                check_trim_count(settings.rule.value, n_diffs)
+            numel = numel_of()
+            self._prepare(numel, n_diffs)
+            # before the first ingest: each diff's norm pass rides behind its copy
+            settings.set_on_engine(self.engine, settings.noise_key(self.dp_keys, opt_key), dp_round)
+            self.opt_states.bind(self.engine, opt_key, settings.opt, sum(numel))  # before the fold: its moments
+            yield settings, mode
 
-    def _average_plan_diffs(self, server_config, checkpoint, diffs, avg_plan, weights, framing, plan_key, rule,
-                            opt=None, opt_key=None, noise=None, dp_round=None):
-        mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
-                           shapes=lambda: _shapes_or_none(checkpoint), n_clients=len(diffs), **rule_kwargs(rule))
-        _check_diff_count(rule, len(diffs))
-        try:
-            numel = state_codec.tensor_numels(checkpoint)  # :240
-        except StateParseError:
-            _decline_non_float32(checkpoint, "the checkpoint")
-            raise
-        self._prepare(numel, len(diffs))
-        set_on_engine(self.engine, rule)  # before the first ingest: each diff's norm pass rides behind its copy
-        self._set_noise(noise, opt_key, dp_round)
-        self.opt_states.bind(self.engine, opt_key, opt, sum(numel))  # before the fold: this process's moments
+    def _average_plan_diffs(self, checkpoint, diffs, weights, framing, settings, mode):
         if checkpoint is not self._resident or self.engine.ckpt_owner is not self:
             self.engine.ckpt_upload_state(checkpoint)  # else: the last cycle's output is still in HBM
         for i, d in enumerate(diffs):  # :247-250
@@ -381,7 +383,7 @@ class CycleAggregator:
         self.engine.fedavg_resident(mode)  # :252-296
         new = (state_codec.fresh_checkpoint(self.engine, checkpoint) if framing == "fresh"  # :303
                else self.engine.ckpt_patch_state(checkpoint))
-        if opt is not None:
+        if settings.opt is not None:
             self.opt_states.commit(self.engine)  # the new checkpoint's bytes exist: the step counts
         self.engine.ckpt_owner = self
         self.engine.ckpt_bytes = new  # the bytes whose params are resident (IncrementalCycle reuses them)
@@ -395,21 +397,11 @@ class CycleAggregator:
                        dp_noise=UNSET, dp_round=None) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        rule = rule_of(server_config, clip_norm, trim_count, median)
-        opt = server_opt_of(server_config)
-        noise = dp_noise_of(server_config, dp_noise)
-        dp.check_rule(noise, rule)
-        with serveropt.failing_closed_opt(opt), dp.failing_closed_dp(noise), \
-                failing_closed(rule, "the engine cannot average this cycle"):
-            shapes = [np.shape(p) for p in model_params]
-            mode = select_mode(server_config, avg_plan, weights, mean_plans=self.mean_plans, shapes=shapes,
-                               n_clients=len(diffs), **rule_kwargs(rule))
-            _check_diff_count(rule, len(diffs))
-            numel = [int(np.prod(s)) for s in shapes]
-            self._prepare(numel, len(diffs))
-            set_on_engine(self.engine, rule)
-            self._set_noise(noise, opt_key, dp_round)
-            self.opt_states.bind(self.engine, opt_key, opt, sum(numel))
+        shapes = [np.shape(p) for p in model_params]
+        numel = [int(np.prod(s)) for s in shapes]
+        given = (clip_norm, trim_count, median, dp_noise)
+        with self._closing(server_config, given, avg_plan, weights, None, shapes, lambda: numel, len(diffs), opt_key,
+                           dp_round) as (settings, mode):
             for i, d in enumerate(diffs):
                 if len(d) != len(numel):
                     raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
@@ -419,7 +411,7 @@ class CycleAggregator:
             flat = np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in model_params])
             self._resident = None  # the host-buffer fold overwrites the resident checkpoint
             out = self.engine.fedavg(mode, flat)
-            if opt is not None:
+            if settings.opt is not None:
                 self.opt_states.commit(self.engine)  # the new parameters are on the host: the step counts
             res, off = [], 0
             for s, n in zip(shapes, numel):
@@ -482,18 +474,15 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
         with gate() if gate is not None else contextlib.nullcontext():
             reports = self._worker_cycles.query(cycle_id=cycle.id, is_completed=True)
             diffs = [r.diff for r in reports]  # what :247-250 reads, at the query
-        rule = rule_of(server_config)  # a malformed setting fails the close
-        opt = server_opt_of(server_config)  # likewise
-        noise = dp_noise_of(server_config)  # likewise; it needs the clip bound
-        dp.check_rule(noise, rule)
-        # (the key only beside an optimizer: aggregators with the earlier signature keep working without one)
-        opt_kw = {"opt_key": cycle.fl_process_id} if opt is not None or noise is not None else {}
-        if noise is not None:
+        settings = settings_of(server_config)  # a malformed setting, or noise without the clip bound, fails the close
+        # (the key only beside an optimizer or noise: aggregators with the earlier signature keep working without one)
+        opt_kw = {"opt_key": cycle.fl_process_id} if settings.opt is not None or settings.noise is not None else {}
+        if settings.noise is not None:
             opt_kw["dp_round"] = cycle.id  # the round the noise is drawn for: a retried close draws it again
         try:
             # a plan whose cached verdict is a decline raises from hosted_plan already: under an optimizer,
             # a rule or noise that must fail the close too, not reach the fall-back below
-            with serveropt.failing_closed_opt(opt), dp.failing_closed_dp(noise), failing_closed(rule):
+            with settings.fail_closed():
                 avg_plan, plan_key = hosted_plan(server_config, cycle, process_manager, plan_manager,
                                                  getattr(aggregator, "mean_plans", None))
                 new_ckpt = aggregator.average_plan_diffs(server_config, _checkpoint.value, diffs, avg_plan,

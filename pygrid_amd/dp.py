@@ -22,7 +22,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .exceptions import AggregationError, ClipUnavailableError, DpNoiseUnavailableError, PlanNotAcceleratedError
+from .exceptions import AggregationError, DpNoiseUnavailableError
 from .robust import CLIP_KEY, UNSET, Rule
 
 DP_KEY = "dp_noise"
@@ -120,29 +120,3 @@ def set_on_engine(engine, spec: Optional[DpNoiseSpec], key: Optional[int] = None
         if e.status != -6:  # PGH_E_UNSUPPORTED
             raise
         raise DpNoiseUnavailableError(f"{DP_KEY} is set but this engine cannot apply it: {e}") from e
-
-
-def close_stats(engine, spec: Optional[DpNoiseSpec]) -> dict:
-    """``noise_multiplier`` and ``noise_std`` (z C / N, what the last noised FINAL used) for ``last_close``."""
-    if spec is None:
-        return {"noise_multiplier": None, "noise_std": None}
-    st = engine.dp_stats()
-    return {"noise_multiplier": float(st["multiplier"]), "noise_std": float(st["sigma"])}
-
-
-class failing_closed_dp:
-    """Under a noise setting, "the engine does not run this cycle" raised in the block -- a
-    ``PlanNotAcceleratedError``, or the clip rule's own refusal -- becomes a ``DpNoiseUnavailableError``:
-    the node's own averaging adds no noise (and does not clip), so the close fails instead."""
-
-    def __init__(self, spec: Optional[DpNoiseSpec]):
-        self.spec = spec
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, et, e, tb):
-        if self.spec is not None and et is not None and issubclass(et, (PlanNotAcceleratedError, ClipUnavailableError)):
-            raise DpNoiseUnavailableError(f"{DP_KEY} is set but the engine does not average this cycle ({e}); "
-                                          "the node's own averaging adds no noise") from e
-        return False

@@ -69,7 +69,8 @@ from .cycle import _decline_non_float32
 from .engine import F32, MEAN, WEIGHTED_MEAN, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
 from . import dp, serveropt
-from .robust import check_trim_count, failing_closed, rule_of, set_on_engine
+from .robust import check_trim_count, failing_closed
+from .settings import CloseSettings, settings_of
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
 MAX_DEFAULT_SLOTS = 4096
@@ -86,8 +87,11 @@ class IncrementalCycle:
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
                  median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
-                 dp_keys=None):
-        """``dp_noise``: the FL process's noise setting (``dp.dp_noise_of``; it needs ``clip_norm``), drawn for
+                 dp_keys=None, settings: Optional[CloseSettings] = None):
+        """``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
+        ``median``, ``server_opt`` and ``dp_noise`` below (both: an error); keys, round and stores go beside either.
+
+        ``dp_noise``: the FL process's noise setting (``dp.dp_noise_of``; it needs ``clip_norm``), drawn for
         ``dp_round`` (the cycle's id) from the key it names or ``opt_key``'s in ``dp_keys`` (share the
         close-time aggregator's).  Early folds do not involve it: K11 follows the close's FINAL pass alone.
         ``last_close`` reports ``noise_multiplier`` and ``noise_std`` (z C / N).
@@ -118,21 +122,22 @@ class IncrementalCycle:
         ``ClipUnavailableError`` instead of being handed back to the node's unclipped averaging."""
         self.engine = engine
         self.mode = mode
-        self._rule = rule = rule_of({}, clip_norm=clip_norm, trim_count=trim_count, median=bool(median))
+        given = {k: v for k, v in dict(clip_norm=clip_norm, trim_count=trim_count, median=bool(median) or None,
+                                       server_opt=server_opt, dp_noise=dp_noise).items() if v is not None}
+        if settings is not None and given:
+            raise AggregationError(f"settings= was given beside {', '.join(given)}")
+        self._settings = settings = settings if settings is not None else settings_of({}, **given)
+        self._rule = rule = settings.rule
         if rule is not None and (mode != MEAN or weights_by_worker is not None):
             raise rule.refuse("applies to the plain mean only (no weights, no iterative plan)")
         self.clip_norm, self.trim_count, self.median = None, None, False
         if rule is not None:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
         self._fold_mode = rule.mode if rule else mode
-        self._noise = noise = dp.dp_noise_of({}, dp_noise)
-        dp.check_rule(noise, rule)
-        self._noise_args = (None, None)
-        if noise is not None:
-            self._noise_args = ((dp_keys if dp_keys is not None else dp.DpKeys()).key_for(opt_key, noise), dp_round)
-        self._opt, self._opt_key = server_opt, opt_key
+        self._noise_args = (settings.noise_key(dp_keys if dp_keys is not None else dp.DpKeys(), opt_key), dp_round)
+        self._opt_key = opt_key
         self._opt_states = opt_states if opt_states is not None else serveropt.ServerOptStates()
-        if server_opt is not None and opt_key is None:
+        if settings.opt is not None and opt_key is None:
             raise AggregationError(f"{serveropt.OPT_KEY} is set but the cycle has no opt_key to keep its state under")
         self._numel = tuple(int(n) for n in numel)
         P = sum(self._numel)
@@ -179,8 +184,7 @@ class IncrementalCycle:
         if hasattr(engine, "set_ingest_ranges"):
             # the close overlaps the tail of the last report's copy (pgh_set_ingest_ranges)
             engine.set_ingest_ranges(os.environ.get("PGH_INGEST_RANGES", "1") != "0")
-        set_on_engine(engine, rule)  # (the engine was reset above: no slot folds under way)
-        dp.set_on_engine(engine, noise, *self._noise_args)  # set, or cleared: a shared engine carries none over
+        settings.set_on_engine(engine, *self._noise_args)  # (the engine was reset above: no slot folds under way)
         self._ckpt: Optional[bytes] = None  # checkpoint bytes whose payloads are resident in HBM
         if checkpoint is not None and getattr(engine, "ckpt_owner", None) is not None \
                 and getattr(engine, "ckpt_bytes", None) is checkpoint:
@@ -192,7 +196,8 @@ class IncrementalCycle:
             try:
                 engine.ckpt_upload_state(checkpoint)
             except StateParseError:
-                self._raise_if_not_float32(checkpoint, "the checkpoint")
+                with failing_closed(rule):
+                    _decline_non_float32(checkpoint, "the checkpoint")
                 raise
             engine.ckpt_owner = self
             self._ckpt = checkpoint
@@ -324,10 +329,6 @@ class IncrementalCycle:
         """Clipping: the row's norm pass goes to the GPU now, behind its copy, not at the close."""
         if self.clip_norm is not None:
             self.engine.row_sumsq([slot], wait=False)
-
-    def _raise_if_not_float32(self, pb: bytes, what: str):
-        with failing_closed(self._rule):
-            _decline_non_float32(pb, what)
 
     def _held(self, worker) -> bool:
         return worker in self._slot_of or worker in self._parked
@@ -489,24 +490,18 @@ class IncrementalCycle:
             prep = self._prepared[1] if self._prepared and self._prepared[0] is checkpoint else None
             self._prepared = None
             # before the FINAL pass: this process's moments (another process may have closed on the engine since)
-            self._opt_states.bind(self.engine, self._opt_key, self._opt, sum(self._numel))
-            if self._noise is not None:  # (again, right before the FINAL pass: no un-noised average leaves)
-                dp.set_on_engine(self.engine, self._noise, *self._noise_args)
+            self._opt_states.bind(self.engine, self._opt_key, self._settings.opt, sum(self._numel))
+            if self._settings.noise is not None:  # (again, right before the FINAL pass: no un-noised average leaves)
+                self._settings.set_on_engine(self.engine, *self._noise_args, noise_only=True)
             stats = self._fold_in_order(rest, fetch)
             del stats["db_rows"]
             stats.update(refold=bool(refold), reason=refold or None, early=k, n=len(order),
                          folded_before_close=folded_before)
-            if self.clip_norm is not None:  # the engine was reset when this cycle took it: its rows only
-                cs = self.engine.clip_stats()
-                stats.update(clipped=int(cs["clipped"]), max_norm=float(cs["max_norm"]))
-            else:
-                stats.update(clipped=0, max_norm=None)
-            stats.update(trim=self.trim_count, median=self.median)
-            stats.update(dp.close_stats(self.engine, self._noise))
+            stats.update(self._settings.close_stats(self.engine))
             self.last_close = stats
             new = (state_codec.fresh_checkpoint(self.engine, checkpoint, prepared=prep) if framing == "fresh"
                    else self.engine.ckpt_patch_state(checkpoint))
-            if self._opt is not None:
+            if self._settings.opt is not None:
                 self._opt_states.commit(self.engine)  # the new checkpoint's bytes exist: the step counts
             self.engine.ckpt_owner = self
             self.engine.ckpt_bytes = new

@@ -66,22 +66,18 @@ Nothing runs at import: ``install`` is the opt-in, ``uninstall`` restores every 
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import logging
 import threading
 from typing import Callable, Dict, Optional, Sequence
 
-from . import state as state_codec
 from .checkpoints import Checkpoint, CheckpointStore
-from .cycle import CycleAggregator, _decline_non_float32, finish_cycle, hosted_plan, make_average_plan_diffs, \
+from .cycle import CycleAggregator, checkpoint_numels, finish_cycle, hosted_plan, make_average_plan_diffs, \
     select_mode
 from .engine import MEAN
-from .exceptions import AggregationError, DpNoiseUnavailableError, PlanNotAcceleratedError, PyGridError, \
-    ServerOptUnavailableError, StateParseError
+from .exceptions import AggregationError, PlanNotAcceleratedError, PyGridError, StateParseError
 from .incremental import IncrementalCycle
-from . import dp
-from .dp import DP_KEY, dp_noise_of
-from .serveropt import OPT_KEY, server_opt_of
-from .robust import failing_closed, rule_kwargs, rule_of
+from .settings import settings_of
 from .trigger import CycleCloseTrigger
 
 log = logging.getLogger(__name__)
@@ -320,48 +316,28 @@ class NodeEngine:
 
     def _new_cycle(self, cm, cycle, fresh: bool = False) -> IncrementalCycle:
         server_config, _ = self.process_manager.get_configs(id=cycle.fl_process_id)
-        rule = rule_of(server_config)  # the process's robust-aggregation rule (a malformed setting raises)
-        # under a rule a cycle the engine does not run is not _DECLINED -- the node's own averaging does not
-        # apply the rule: the close-time path refuses the cycle again, loudly, when it closes
-        noise = dp_noise_of(server_config)  # likewise; without the clip bound it raises
-        dp.check_rule(noise, rule)
-        with dp.failing_closed_dp(noise), failing_closed(rule):
-            return self._new_cycle_for(cm, cycle, server_config, rule, fresh)
+        settings = settings_of(server_config)  # (a malformed setting, or noise without the clip bound, raises)
+        # under a rule or noise a cycle the engine does not run is not _DECLINED -- the node's own averaging applies
+        # neither: the close-time path refuses it again, loudly, when it closes.  Under an optimizer alone (opt=None
+        # below) it is _DECLINED like any plan the engine does not run, and the close's stand-in refuses it.
+        with dataclasses.replace(settings, opt=None).fail_closed():
+            return self._new_cycle_for(cm, cycle, server_config, settings, fresh)
 
-    def _dp_kwargs(self, server_config, cycle) -> dict:
-        """The FL process's noise for its report-time cycle: the setting, the round (the cycle's id) and the
-        keys shared with the close-time path (nothing when none is set)."""
-        noise = dp_noise_of(server_config)
-        if noise is None:
-            return {}
-        return {"dp_noise": noise, "dp_round": cycle.id, "opt_key": cycle.fl_process_id,
-                "dp_keys": self.aggregator.dp_keys}
-
-    def _opt_kwargs(self, server_config, cycle) -> dict:
-        """The FL process's server optimizer for its report-time cycle: the setting, the key its moments
-        are kept under and the states shared with the close-time path (nothing when none is set)."""
-        opt = server_opt_of(server_config)
-        if opt is None:
-            return {}
-        return {"server_opt": opt, "opt_key": cycle.fl_process_id, "opt_states": self.aggregator.opt_states}
-
-    def _new_cycle_for(self, cm, cycle, server_config, rule, fresh: bool) -> IncrementalCycle:
+    def _new_cycle_for(self, cm, cycle, server_config, settings, fresh: bool) -> IncrementalCycle:
         avg_plan, plan_key = hosted_plan(server_config, cycle, self.process_manager, self.plan_manager,
                                          self.aggregator.mean_plans)
         model = self.model_manager.get(fl_process_id=cycle.fl_process_id)
         ckpt = self.model_manager.load(model_id=model.id).value
-        try:
-            numel = state_codec.tensor_numels(ckpt)
-        except StateParseError:
-            _decline_non_float32(ckpt, "the checkpoint")
-            raise
+        numel = checkpoint_numels(ckpt)
         # under a rule: the rule's mode where the plan dispatches to MEAN, the rule's error everywhere else
         mode = select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
-                           shapes=lambda: _shapes(ckpt), **rule_kwargs(rule))
+                           shapes=lambda: _shapes(ckpt), **settings.rule_kwargs())
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
-        inc = IncrementalCycle(self.engine, numel, mode=MEAN if rule else mode, slots=self.slots,
-                               fold_batch=self.fold_batch, checkpoint=ckpt, **rule_kwargs(rule),
-                               **{**self._dp_kwargs(server_config, cycle), **self._opt_kwargs(server_config, cycle)})
+        # the moments under the FL process's id, the noise for the cycle's id; the close-time path's stores
+        inc = IncrementalCycle(self.engine, numel, mode=MEAN if settings.rule else mode, slots=self.slots,
+                               fold_batch=self.fold_batch, checkpoint=ckpt, settings=settings,
+                               opt_key=cycle.fl_process_id, opt_states=self.aggregator.opt_states,
+                               dp_round=cycle.id, dp_keys=self.aggregator.dp_keys)
         if not fresh:  # after a restart: the rows assigned before it (a cycle just created has none;
             # an assignment that lands while this state is built is recorded from _pending_assign)
             for row in _rows(cm, cycle_id=cycle.id):
@@ -439,15 +415,8 @@ class NodeEngine:
     def average_plan_diffs(self, cm, server_config, cycle, close_time: Callable, original: Callable):
         """The close (executor thread).  Holds the engine lock throughout, the report gate only for
         the snapshot of the completed rows (see the module docstring)."""
-        rule = rule_of(server_config)  # a malformed setting, or two rules at once, fails the close
-        if server_opt_of(server_config) is not None:  # (a malformed setting fails the close)
-            original = _refuse_opt(cycle.id)  # fail closed: the node's own averaging applies no optimizer
-        if rule is not None:
-            original = _refuse(rule, cycle.id)  # fail closed: the node's own averaging does not apply the rule
-        noise = dp_noise_of(server_config)  # (a malformed setting fails the close)
-        dp.check_rule(noise, rule)
-        if noise is not None:
-            original = _refuse_dp(cycle.id)  # fail closed: the node's own averaging adds no noise
+        settings = settings_of(server_config)  # a malformed setting, or two rules at once, fails the close
+        original = settings.refusing_original(cycle.id) or original  # fail closed: the node's applies none
         with self._engine_for_close():
             model = ckpt = None
             if isinstance(self._cycles.get(cycle.id), IncrementalCycle):
@@ -511,12 +480,8 @@ class NodeEngine:
                 self.stats["closes_close_time"] += 1
                 return close_time(cm, server_config, cycle)
             self.stats["closes_report_time"] += 1
-            if rule is not None:
-                noised = "" if noise is None else "; %s multiplier %s, noise std %s per parameter" % (
-                    DP_KEY, st.last_close.get("noise_multiplier"), st.last_close.get("noise_std"))
-                log.info("cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)%s", cycle.id, rule.key,
-                         rule.value, st.last_close.get("n", 0), st.last_close.get("clipped", 0),
-                         st.last_close.get("max_norm"), noised)
+            if settings.rule is not None:
+                log.info(settings.close_message(cycle.id, st.last_close))
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)
             self.aggregator._resident = None
@@ -562,30 +527,6 @@ class NodeEngine:
         for k in self._assigned_keys.pop(cycle_id, ()):
             if self._assigned.get(k, (None, None))[1] == cycle_id:
                 del self._assigned[k]
-
-
-def _refuse_opt(cycle_id):
-    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for a server optimizer."""
-    def original(*_a, **_k):
-        raise ServerOptUnavailableError(f"{OPT_KEY} is set and the engine does not average cycle {cycle_id}; not "
-                                        "falling back to the node's own averaging, which applies no optimizer")
-    return original
-
-
-def _refuse_dp(cycle_id):
-    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for noise."""
-    def original(*_a, **_k):
-        raise DpNoiseUnavailableError(f"{DP_KEY} is set and the engine does not average cycle {cycle_id}; not falling "
-                                      "back to the node's own averaging, which adds no noise")
-    return original
-
-
-def _refuse(rule, cycle_id):
-    """Stands in for the node's own ``_average_plan_diffs`` when the FL process asked for a rule."""
-    def original(*_a, **_k):
-        raise rule.refuse(f"is set and the engine does not average cycle {cycle_id}; not falling back to the node's "
-                          f"own averaging, which {rule.lacks}")
-    return original
 
 
 def _only(blobs: dict):

@@ -7,12 +7,13 @@ counterpart) -- and what the host layer does with them, once:
   ``exceptions.py`` only if callers must tell its failures apart);
 * ``rule_of`` parses the settings and gives the single active ``Rule`` (or None).  At most one rule
   applies to a cycle: a combination is refused with the error of the rule earlier in ``KINDS``;
-* ``failing_closed`` is the one fail-closed decision: where a rule is set, "the engine does not run
+* ``failing_closed`` is the rule's fail-closed decision: where a rule is set, "the engine does not run
   this cycle" (``PlanNotAcceleratedError``, on which callers fall back to the node's own averaging)
   becomes the rule's error -- the node's averaging applies no rule, so the close fails instead;
 * ``set_on_engine`` puts a rule onto an engine before a cycle's first ingest.
 
-Sits below ``cycle.py`` and ``incremental.py`` (it imports only ``engine`` and ``exceptions``).
+These two are the rule's part of ``settings.CloseSettings`` -- a cycle's rule, server optimizer and noise,
+parsed once -- which is what the call sites hold.  Sits below it (imports only ``engine`` and ``exceptions``).
 """
 from __future__ import annotations
 
@@ -128,11 +129,6 @@ def rule_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET
     if len(active) > 1:
         raise active[0].refuse(f"cannot be combined with {active[1].key}")
     return active[0] if active else None
-
-
-def rule_kwargs(rule: Optional[Rule]) -> dict:
-    """The rule as the keyword argument that ``select_mode`` and ``IncrementalCycle`` take."""
-    return {} if rule is None else {rule.arg: rule.value}
 
 
 @contextlib.contextmanager

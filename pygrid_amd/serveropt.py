@@ -19,7 +19,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from .engine import OPT_ADAGRAD, OPT_ADAM, OPT_MOMENTUM, OPT_NONE, OPT_YOGI
-from .exceptions import AggregationError, PlanNotAcceleratedError, ServerOptUnavailableError
+from .exceptions import AggregationError, ServerOptUnavailableError
 
 OPT_KEY = "server_optimizer"
 NAMES = {"fedavgm": OPT_MOMENTUM, "fedadagrad": OPT_ADAGRAD, "fedadam": OPT_ADAM, "fedyogi": OPT_YOGI}
@@ -165,19 +165,3 @@ class ServerOptStates:
         engine.server_opt_commit()
         self._held[owner[1]].steps += 1
 
-
-class failing_closed_opt:
-    """Under a server optimizer, a ``PlanNotAcceleratedError`` raised in the block becomes a
-    ``ServerOptUnavailableError``: the node's own averaging applies no optimizer."""
-
-    def __init__(self, spec: Optional[ServerOptSpec]):
-        self.spec = spec
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, et, e, tb):
-        if self.spec is not None and et is not None and issubclass(et, PlanNotAcceleratedError):
-            raise ServerOptUnavailableError(f"{OPT_KEY} is set but the engine does not average this cycle ({e}); "
-                                            "the node's own averaging applies no optimizer") from e
-        return False

@@ -1,0 +1,118 @@
+"""Everything an FL process can ask of a cycle's close in its ``server_config`` -- a robust-aggregation
+rule (``robust.py``), a server optimizer (``serveropt.py``), Gaussian noise beside the clip bound
+(``dp.py``) -- parsed once, by ``settings_of`` alone, into one ``CloseSettings``, which is what the call
+sites hold: its ``fail_closed`` is the one fail-closed decision, ``refusing_original`` the one stand-in for
+the node's own averaging, ``set_on_engine`` the one way onto an engine, ``close_stats`` what ``last_close``
+says.  Of two things set together the noise speaks before the rule, the rule before the optimizer.
+
+Sits below ``cycle.py`` and ``incremental.py`` (it imports only those three, ``engine`` and ``exceptions``).
+"""
+from __future__ import annotations
+
+import contextlib
+import dataclasses
+from typing import Callable, Optional
+
+from . import dp, robust
+from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
+from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, PlanNotAcceleratedError, \
+    ServerOptUnavailableError
+from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
+from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
+
+
+@dataclasses.dataclass(frozen=True)
+class CloseSettings:
+    """A cycle's parsed settings: each in its module's own parsed form, or None."""
+    rule: Optional[Rule] = None
+    opt: Optional[ServerOptSpec] = None
+    noise: Optional[DpNoiseSpec] = None
+
+    def __bool__(self) -> bool:
+        return self.rule is not None or self.opt is not None or self.noise is not None
+
+    def rule_kwargs(self) -> dict:
+        """The rule as the keyword argument that ``select_mode`` takes."""
+        return {} if self.rule is None else {self.rule.arg: self.rule.value}
+
+    @contextlib.contextmanager
+    def fail_closed(self, what: str = "the engine does not average this cycle"):
+        """A ``PlanNotAcceleratedError`` (``ModelNotAcceleratedError`` included) raised in the block must not
+        reach a caller that falls back to the node's own averaging, which clips, trims, steps and noises nothing.
+        Under a rule it becomes the rule's error; under noise that error in turn, like the clip rule's own
+        refusal, a ``DpNoiseUnavailableError``; under an optimizer alone a ``ServerOptUnavailableError``."""
+        try:
+            with robust.failing_closed(self.rule, what):
+                yield
+        except (PlanNotAcceleratedError, ClipUnavailableError) as e:
+            if self.noise is not None:
+                raise DpNoiseUnavailableError(f"{DP_KEY} is set but the engine does not average this cycle ({e}); "
+                                              "the node's own averaging adds no noise") from e
+            if self.opt is not None and isinstance(e, PlanNotAcceleratedError):
+                raise ServerOptUnavailableError(f"{OPT_KEY} is set but the engine does not average this cycle ({e}); "
+                                                "the node's own averaging applies no optimizer") from e
+            raise
+
+    def refusing_original(self, cycle_id) -> Optional[Callable]:
+        """What stands in for the node's own ``_average_plan_diffs`` where the engine does not average the
+        cycle: it raises, since that averaging lacks what was asked for.  None when nothing is set."""
+        if self.noise is not None:
+            key, error, lacks = DP_KEY, DpNoiseUnavailableError, "adds no noise"
+        elif self.rule is not None:
+            key, error, lacks = self.rule.key, self.rule.error, self.rule.lacks
+        elif self.opt is not None:
+            key, error, lacks = OPT_KEY, ServerOptUnavailableError, "applies no optimizer"
+        else:
+            return None
+
+        def original(*_a, **_k):
+            raise error(f"{key} is set and the engine does not average cycle {cycle_id}; not falling back to the "
+                        f"node's own averaging, which {lacks}")
+        return original
+
+    def noise_key(self, dp_keys: dp.DpKeys, process) -> Optional[int]:
+        """The key this FL process's noise is drawn from (None: no noise)."""
+        return None if self.noise is None else dp_keys.key_for(process, self.noise)
+
+    def set_on_engine(self, engine, key: Optional[int] = None, round: Optional[int] = None, noise_only=False) -> None:
+        """Before a cycle's first ingest: the rule, then the noise (it is scaled by the bound) drawn from ``key``
+        for ``round``, each set or cleared -- an engine shared across FL processes carries none over.
+        ``noise_only``: again right before a FINAL pass."""
+        if not noise_only:
+            robust.set_on_engine(engine, self.rule)
+        dp.set_on_engine(engine, self.noise, key, round)
+
+    def _value(self, key: str, off=None):
+        return self.rule.value if self.rule is not None and self.rule.key == key else off
+
+    def close_stats(self, engine) -> dict:
+        """The rule's and the noise's entries of ``last_close``, read from the engine after the FINAL pass (it
+        was reset when the cycle took it: the clip counters are this cycle's rows only; ``noise_std`` is z C / N)."""
+        cs = engine.clip_stats() if self._value(CLIP_KEY) is not None else None
+        ns = engine.dp_stats() if self.noise is not None else None
+        return {"clipped": int(cs["clipped"]) if cs else 0, "max_norm": float(cs["max_norm"]) if cs else None,
+                "trim": self._value(TRIM_KEY), "median": self._value(MEDIAN_KEY, False),
+                "noise_multiplier": float(ns["multiplier"]) if ns else None,
+                "noise_std": float(ns["sigma"]) if ns else None}
+
+    def close_message(self, cycle_id, last_close: dict) -> str:
+        """One log line on a close under a rule, from its ``last_close``."""
+        noised = "" if self.noise is None else "; %s multiplier %s, noise std %s per parameter" % (
+            DP_KEY, last_close.get("noise_multiplier"), last_close.get("noise_std"))
+        return "cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)%s" % (
+            cycle_id, self.rule.key, self.rule.value, last_close.get("n", 0), last_close.get("clipped", 0),
+            last_close.get("max_norm"), noised)
+
+
+def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
+                server_opt=UNSET) -> CloseSettings:
+    """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
+    ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
+    malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
+    the earlier rule's error (``robust.KINDS``), noise without the clip bound ``DpNoiseUnavailableError``."""
+    rule = rule_of(server_config, clip_norm, trim_count, median)
+    if not isinstance(server_opt, ServerOptSpec):
+        server_opt = server_opt_of(server_config if server_opt is UNSET else {OPT_KEY: server_opt})
+    noise = dp_noise_of(server_config, dp_noise)
+    dp.check_rule(noise, rule)
+    return CloseSettings(rule, server_opt, noise)
