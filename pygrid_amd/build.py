@@ -21,7 +21,7 @@ SOURCES = [CSRC / "pgh_kernels.hip", CSRC / "pgh_api.cpp", CSRC / "pgh_host.cpp"
            CSRC / "pgh_serveropt.cpp", CSRC / "pgh_slots.cpp", CSRC / "pgh_group.cpp", CSRC / "pgh_state.cpp",
            CSRC / "pgh_b64.cpp"]
 HEADERS = [CSRC / "pgh_kernels.h", CSRC / "pgh_variants.def", CSRC / "pgh_state.h", CSRC / "pgh_internal.h", CSRC / "pgh_ctx.h",
-           CSRC / "pgh_rules.h", CSRC / "pgh_res.h", CSRC / "pgh_host.h", ROOT / "include" / "pgh_api.h"]
+           CSRC / "pgh_rules.h", CSRC / "pgh_xfer.h", CSRC / "pgh_res.h", CSRC / "pgh_host.h", ROOT / "include" / "pgh_api.h"]
 ARCH = os.environ.get("PGH_OFFLOAD_ARCH", "gfx950")
 
 

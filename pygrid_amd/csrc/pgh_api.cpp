@@ -86,7 +86,7 @@ double now_ms() {
 static void sync_work(pgh_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy) (void)hipStreamSynchronize(c->copy);
-    if (c->dec) (void)hipStreamSynchronize(c->dec);  // a varint decode writes slab rows
+    if (c->vdec.s) (void)hipStreamSynchronize(c->vdec.s);  // a varint decode writes slab rows
     for (auto& fe : c->fold_evs) (void)hipEventSynchronize(fe.second);  // folds on caller streams
 }
 
@@ -184,8 +184,8 @@ int pgh_create(int device, size_t pinned_bytes, pgh_ctx** out) {
     c->device = device;
     DeviceGuard g(device);
     if (pinned_bytes == 0) pinned_bytes = 256ull << 20;
-    c->pin_slot = (pinned_bytes / 2) & ~(size_t)4095;
-    if (c->pin_slot < 4096) c->pin_slot = 4096;
+    c->ring.slot_bytes = (pinned_bytes / 2) & ~(size_t)4095;
+    if (c->ring.slot_bytes < 4096) c->ring.slot_bytes = 4096;
     c->copy_threads = std::min(16, pgh_int::usable_cpus());
     if (const char* e = std::getenv("PGH_COPY_THREADS")) c->copy_threads = std::max(1, std::atoi(e));
     {
@@ -193,16 +193,11 @@ int pgh_create(int device, size_t pinned_bytes, pgh_ctx** out) {
         if (!nu || std::atoi(nu) != 0) c->local_cpus = gpu_local_cpus(device);
     }
     c->pool_copy.reset(new CopyPool(c->copy_threads, c->local_cpus));
-    if (const char* e = std::getenv("PGH_PINNED_GATHER")) c->pinned_gather = std::atoi(e) != 0;
     if (const char* e = std::getenv("PGH_BLOCK_BYTES")) c->block_bytes = (size_t)std::max(0LL, std::atoll(e));
     if (const char* e = std::getenv("PGH_FINAL_RANGES")) c->final_split = std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("PGH_D2H_STREAM")) c->d2h_mode = std::max(0, std::min(1, std::atoi(e)));
-    c->own_d2h = c->d2h_mode > 0;
-    bool ok = c->stream.make() == hipSuccess && c->copy.make() == hipSuccess && c->aux.make() == hipSuccess &&
-              (!c->own_d2h || c->d2h.make() == hipSuccess);  // (dec, a fifth stream, only on first use)
-    for (pgh_ctx::Event* ev : {&c->copy_done, &c->xsync, &c->aux_ev, &c->pin_ev[0], &c->pin_ev[1], &c->gtab_ev,
-                               &c->gdma_ev, &c->vtab_ev, &c->dec_in, &c->vbuf[0].done, &c->vbuf[1].done})
-        ok = ok && ev->make() == hipSuccess;
+    bool ok = c->stream.make() == hipSuccess && c->copy.make() == hipSuccess && c->aux.make() == hipSuccess;
+    ok = ok && xfer_made(c);  // the D2H stream, the transfer owners' events and knobs
+    for (pgh_ctx::Event* ev : {&c->copy_done, &c->xsync, &c->aux_ev}) ok = ok && ev->make() == hipSuccess;
     ok = ok && rules_made(c);
     if (!ok) { pgh_destroy(c); return fail(nullptr, PGH_E_HIP, "stream/event creation failed"); }
     {
@@ -214,14 +209,15 @@ int pgh_create(int device, size_t pinned_bytes, pgh_ctx** out) {
             const unsigned flags = c->local_cpus.empty() ? hipHostMallocDefault : hipHostMallocNumaUser;
             // a placement the runtime refuses is not worth failing the context for
             for (int k = 0; k < 2 && pin_ok; ++k)
-                pin_ok = c->h_pin[k].reserve(c->pin_slot, flags) ||
-                         (flags != hipHostMallocDefault && c->h_pin[k].reserve(c->pin_slot));
+                pin_ok = c->ring.h_pin[k].reserve(c->ring.slot_bytes, flags) ||
+                         (flags != hipHostMallocDefault && c->ring.h_pin[k].reserve(c->ring.slot_bytes));
         };
         if (c->local_cpus.empty()) alloc();
         else std::thread([&] { DeviceGuard g2(device); alloc(); }).join();
         if (!pin_ok) {
+            const size_t bytes = c->ring.slot_bytes;
             pgh_destroy(c);
-            return fail(nullptr, PGH_E_OOM, "pinned host allocation of %zu bytes failed", c->pin_slot);
+            return fail(nullptr, PGH_E_OOM, "pinned host allocation of %zu bytes failed", bytes);
         }
     }
     // Warm-up (PGH_WARMUP=0 skips it): the first kernel launch loads the code object and the first
@@ -230,20 +226,20 @@ int pgh_create(int device, size_t pinned_bytes, pgh_ctx** out) {
     // (profiles/r01am).  One small launch plus an H2D and a D2H of up to 2 MiB on the two streams.
     const char* wu = std::getenv("PGH_WARMUP");
     if (!wu || std::atoi(wu) != 0) {
-        const int64_t n = (int64_t)std::min(c->pin_slot, (size_t)2 << 20) / 8;  // int64 values
+        const int64_t n = (int64_t)std::min(c->ring.slot_bytes, (size_t)2 << 20) / 8;  // int64 values
         void* d = nullptr;
         ok = hipMalloc(&d, 12 * n) == hipSuccess;
         if (ok) {
             int64_t* d_sum = (int64_t*)d;
             float* d_dec = (float*)((uint8_t*)d + 8 * n);
-            void* const pin0 = c->h_pin[0].as<void>();
+            void* const pin0 = c->ring.h_pin[0].as<void>();
             std::memset(pin0, 0, 8 * n);
             ok = hipMemcpyAsync(d_sum, pin0, 8 * n, hipMemcpyHostToDevice, c->copy) == hipSuccess &&
                  hipStreamSynchronize(c->copy) == hipSuccess &&
-                 (!c->d2h || (hipMemcpyAsync(d_sum, pin0, 8 * n, hipMemcpyHostToDevice, c->d2h) == hipSuccess &&
-                              hipStreamSynchronize(c->d2h) == hipSuccess)) &&
+                 (!c->d2h.s || (hipMemcpyAsync(d_sum, pin0, 8 * n, hipMemcpyHostToDevice, c->d2h.s) == hipSuccess &&
+                                hipStreamSynchronize(c->d2h.s) == hipSuccess)) &&
                  pgh::launch_secagg_decode(d_sum, d_dec, n, 1.0f, c->stream) == hipSuccess &&
-                 hipMemcpyAsync(c->h_pin[1].as<void>(), d_sum, 8 * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                 hipMemcpyAsync(c->ring.h_pin[1].as<void>(), d_sum, 8 * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
                  hipStreamSynchronize(c->stream) == hipSuccess;
             (void)hipFree(d);
         }
@@ -263,7 +259,7 @@ void pgh_destroy(pgh_ctx* c) {
     if (c->grp) { pgh_group_api::destroy(c); return; }
     DeviceGuard g(c->device);  // (alive across the delete: the owners release on this device)
     sync_work(c);
-    if (c->d2h) (void)hipStreamSynchronize(c->d2h);
+    if (c->d2h.s) (void)hipStreamSynchronize(c->d2h.s);
     delete c;
 }
 
@@ -439,7 +435,7 @@ int pgh_sync(pgh_ctx* c) {
     if (!c) return PGH_E_ARG;
     DeviceGuard g(c->device);
     CK(c, hipStreamSynchronize(c->copy));
-    if (c->dec) CK(c, hipStreamSynchronize(c->dec));
+    if (c->vdec.s) CK(c, hipStreamSynchronize(c->vdec.s));
     CK(c, hipStreamSynchronize(c->stream));
     return PGH_OK;
 }

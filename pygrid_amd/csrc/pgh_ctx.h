@@ -3,8 +3,10 @@
 //
 // The context's code is split by what it does:
 //   pgh_api.cpp     lifecycle, errors and state checks, observability, the group driver's internals
-//   pgh_host.cpp    host code free of HIP (pgh_host.h): non-temporal copy, copy pool, pre-faulting
-//   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks
+//   pgh_host.cpp    host code free of HIP (pgh_host.h): non-temporal copy, copy pool, pre-faulting, the walk over
+//                   host pieces (PieceCursor), the chunk arithmetic of ranged ingest
+//   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks; the methods of
+//                   the transfer owners.  Their state: pgh_xfer.h
 //   pgh_order.cpp   which stream waits for what, and the timing events
 //   pgh_ingest.cpp  host bytes -> HBM slab rows (raw, State messages, int64 shares, synthetic)
 //   pgh_reduce.cpp  the one fp32 fold launch (fold_prepare, fold_launch); fold_run's ring walk and the share
@@ -22,6 +24,12 @@
 // through the last two alone.  The server optimizer (pgh_set_server_opt) hangs on fold_launch too: a FINAL
 // launch with one set is followed by K10 (server_opt_launch).  The noise (pgh_set_dp_noise) is a second tenant of
 // that mechanism: a clipped FINAL launch with it set is followed by K11 (dp_noise_launch), ahead of K10.
+// A new transfer feature adds its state struct to pgh_xfer.h (a member of pgh_ctx), its events and knobs to
+// xfer_made -- the one call pgh_create makes -- and goes through the owners that keep the shared protocols: a
+// staging slot is taken and handed back through StagingRing (take, sent), every data operation on the copy stream
+// is counted through RangedIngest::copy_issued (what lets a close wait per ingest chunk), a page-locked table is
+// rewritten through HostTable::upload, an H2D is accounted by an H2DTimer, a pre-queued D2H is dropped through
+// D2HState::drop_pre.
 // The context's HIP resources are held by the owners of pgh_res.h: `delete` releases them all.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,6 +57,7 @@
 #include "pgh_res.h"
 #include "pgh_rules.h"
 #include "pgh_state.h"
+#include "pgh_xfer.h"
 
 namespace pgh_detail {
 
@@ -77,7 +86,7 @@ struct pgh_ctx {
     Stream aux;     // second reduction stream: alternate ranges of a split FINAL pass
     Event aux_ev;
     // Every ordering event that comes and goes (fold_evs, slab_evs, slot_ring, marks, final_marks,
-    // d2h_ev, rng_ev) is lent by ev_pool; the timing pairs (pending) by timing_pool, whose events
+    // d2h.ev, ranged.ev) is lent by ev_pool; the timing pairs (pending) by timing_pool, whose events
     // keep hipEventDisableSystemFence (take_event).
     pgh_detail::EventPool ev_pool{hipEventDisableTiming}, timing_pool{hipEventDisableSystemFence};
     // The last fold issued on each stream (folds may run on several caller streams at once, e.g.
@@ -121,85 +130,16 @@ struct pgh_ctx {
     DeviceBuf d_rec;  // double per client
     std::vector<DeviceBuf> rec_old;
 
-    PinnedBuf h_pin[2];
-    size_t pin_slot = 0;
-    Event pin_ev[2];
-    bool pin_used[2] = {false, false};
-    int pin_next = 0;
-    std::vector<hipEvent_t> d2h_ev;  // one per ring cell of a staged D2H (stage_d2h_pieces); ev_pool's
-    // A staged D2H through the pinned ring: pieces of `piece` bytes of [src, src + total) into the
-    // cells of the free pinned slots, each followed by d2h_ev[cell].  piped: src is a fold's result
-    // with range marks; each piece is issued (on the copy stream) once the host sees every mark
-    // covering it complete -- no cross-stream wait on the device, which sent the pieces to blit
-    // kernels that slowed the ranges beside them (profiles/r05k/-r05m/, r05aa/).
-    struct D2HRing {
-        const uint8_t* src = nullptr;
-        size_t total = 0, piece = 0, per_slot = 0, cells = 0, n_pieces = 0, queued = 0, done = 0;
-        int free_slot[2] = {0, 1};
-        int n_free = 0;
-        hipStream_t s = nullptr;
-        bool piped = false;
-        uint8_t* base = nullptr;  // (not owned) the cells of a piped ring: h_d2h (own_d2h), else the free pinned slots
-    };
-    // The new checkpoint's D2H as the FINAL pass of a report-time close starts it: the pieces whose
-    // ranges finished while the later ranges were still being issued (pgh_slots.cpp); the patch /
-    // download that follows adopts the ring.  Dropped with the marks (clear_final_marks) or when a
-    // staging copy takes a pinned slot (take_pin_slot).
-    D2HRing pre_d2h;
-    bool pre_d2h_valid = false;
-    // A piped ring's pieces on a stream and in page-locked cells of their own (PGH_D2H_STREAM,
-    // default 1): on the copy stream they queued behind the last reports' H2D, and they waited for
-    // a staging slot those reports still held -- with reports back to back, until every report had
-    // landed.  The stream is primed with a small H2D when made, so the runtime sends its D2H to an
-    // SDMA engine (r05ae).  (Rounds 6's K6 k_copy_to_host, pieces copied out by a kernel beside an H2D
-    // backlog, was removed: copying a piece right behind the FINAL ranges that wrote it on another
-    // stream, it read ranges that had not run yet -- profiles/r06s/.)
-    bool own_d2h = true;
-    int d2h_mode = 1;
-    Stream d2h;
-    PinnedBuf h_d2h;
+    // The transfer side (pgh_xfer.h): touched only by their own code (pgh_xfer.cpp) and the call sites named there.
+    pgh_detail::StagingRing ring;     // pageable host bytes -> HBM; lends its slots to a D2H without own cells
+    pgh_detail::D2HState d2h;         // HBM -> host: the piped ring's stream and cells, the pre-queued ring
+    pgh_detail::RangedIngest ranged;  // chunk events of the last report, the count of copy-stream operations
+    pgh_detail::VarintDecode vdec;    // int64 shares: byte buffers, the decode stream
+    pgh_detail::PinnedGather gather;  // page-locked fp32 State messages
+
     int copy_threads = 8;
     std::vector<int> local_cpus;  // PGH_NUMA (default on): the GPU's socket, for the copy pool + pinned ring
     std::unique_ptr<CopyPool> pool_copy;
-
-    // secagg shares as State bytes: varint payloads in HBM + their chunk table (k_varint_decode)
-    // Each decode runs on its own stream (dec) behind its message's DMAs, so the copy stream's next
-    // DMA does not queue behind it; the HBM bytes and chunk table alternate between two buffers (the
-    // DMA of one message beside the decode of the one before).
-    struct VarintBuf {
-        DeviceBuf bytes;
-        DeviceBuf tab;  // pgh::VChunk
-        Event done;     // the last decode that read this buffer
-        bool used = false;
-    };
-    VarintBuf vbuf[2];
-    int vbuf_next = 0;
-    Stream dec;                      // made on first use: a context's fifth stream
-    Event dec_in;                    // copy stream -> dec: a message's bytes and table have landed
-    hipEvent_t dec_last = nullptr;   // (a vbuf's `done`, not owned) the last decode issued: folds wait for it
-    PinnedBuf h_vtab;                // host image of a chunk table (pgh::VChunk)
-    Event vtab_ev;                   // the last table upload (h_vtab reusable after it)
-    bool vtab_used = false;
-    // page-locked fp32 State messages (below) stage through this buffer
-    DeviceBuf d_vbytes;
-    // page-locked fp32 State messages (pgh_ingest_state): DMA'd whole into d_vbytes, gathered into the
-    // slab row by k_gather_f32 with this chunk table (PGH_PINNED_GATHER=0: one DMA per payload piece)
-    DeviceBuf d_gtab;  // pgh::GChunk
-    PinnedBuf h_gtab;
-    Event gtab_ev;     // the last table upload (h_gtab reusable after it)
-    Event gdma_ev;     // the last message DMA (the caller's buffer is free after it)
-    bool gtab_used = false;
-    bool pinned_gather = true;
-    // Ranged report ingest (pgh_set_ingest_ranges): a State diff goes to HBM in chunks of
-    // INGEST_CHUNK params, each followed by rng_ev[k] on the copy stream, so that the FINAL pass of
-    // a report-time close that starts while the last report's DMA is still in flight folds each
-    // param range as soon as its bytes have landed.  copy_seq counts the data operations issued on
-    // the copy stream; the ranged close applies only while rng_seq == copy_seq (nothing issued on
-    // the copy stream since the latest ranged ingest) and rng_n chunks cover the shard.
-    bool ingest_ranges = false;
-    std::vector<hipEvent_t> rng_ev;  // ev_pool's
-    uint64_t copy_seq = 0, rng_seq = ~0ull;
-    int rng_n = 0;
     bool warmup_skipped = false;  // pgh_create's warm-up failed (e.g. no device memory left): skipped
     int64_t vec_min = 0;      // [P_shard] device vectors at least this long (group collectives)
     // Pipelined close: a resident fold's FINAL pass runs as final_split param ranges, each followed by
@@ -340,14 +280,30 @@ int timed_launch(pgh_ctx* c, hipStream_t s, uint64_t bytes, F&& launch) {
 }
 
 // ---- host <-> HBM --------------------------------------------------------------------------------
-// HBM -> host results move in pieces of at most D2H_PIECE, the later pieces' DMAs beside the host
-// copy-out of the earlier ones (r01ac: 4, 8, 16 MiB within the noise of the 47 MB report-time close;
-// with the parallel pre-fault, r01ak, 8 MiB pieces closed in 2.3-2.4 ms vs 2.6-2.7 for one piece).
-constexpr size_t D2H_PIECE = 8u << 20;
-constexpr size_t D2H_OWN_CELLS = 8;  // a piped ring's own cells: 64 MiB at most (ResNet-18: 6 pieces)
-// Ranged report ingest (pgh_set_ingest_ranges): one chunk = the params of one D2H piece = two
-// 4 MiB FINAL ranges of a report-time close (pgh_slots.cpp).
-constexpr int64_t INGEST_CHUNK = (int64_t)(D2H_PIECE / 4);
+// (D2H_PIECE and INGEST_CHUNK, with the chunk arithmetic of ranged ingest: pgh_host.h)
+// The two owner methods on the per-piece loops.
+inline int StagingRing::sent(pgh_ctx* c, int slot, hipStream_t s) {
+    CK(c, hipEventRecord(ev[slot], s));
+    used[slot] = true;
+    return PGH_OK;
+}
+inline int RangedIngest::mark(pgh_ctx* c, int k) {
+    CK(c, hipEventRecord(ev[(size_t)k], c->copy));
+    return PGH_OK;
+}
+// The accounting of one H2D: made where it starts; done, on success alone, adds the elapsed host time, the
+// bytes moved and those of them that went through the staging ring.
+struct H2DTimer {
+    pgh_ctx* c;
+    double t0;
+    explicit H2DTimer(pgh_ctx* c_) : c(c_), t0(now_ms()) {}
+    int done(size_t bytes, size_t staged = 0) {
+        c->st.h2d_ms_total += now_ms() - t0;
+        c->st.h2d_bytes_total += bytes;
+        c->st.h2d_staged_bytes_total += staged;
+        return PGH_OK;
+    }
+};
 
 bool is_pinned(const void* p);
 // src_room: bytes readable at src past the n elements (a staging slot's unused rest); a range that
@@ -357,15 +313,12 @@ int h2d_range(pgh_ctx* c, const Dest& d, int64_t i0, const uint8_t* src, int64_t
               size_t src_room = 0);
 int stage_pieces_h2d(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& pieces);
 int stage_pieces_h2d_ranged(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& pieces, size_t total);
-bool ranged_ingest_valid(const pgh_ctx* c);
 int stage_h2d(pgh_ctx* c, const Dest& dst, const uint8_t* src, size_t n, bool pinned_src);
 int stage_d2h_pieces(pgh_ctx* c, const uint8_t* src, const std::vector<OutPiece>& pieces, hipStream_t s,
                      const std::function<void()>& overlap = nullptr, bool marks = false);
 // may_wait = false: both pinned slots still busy -> r->n_free == 0 (nothing set up) instead of waiting
-int d2h_ring_begin(pgh_ctx* c, pgh_ctx::D2HRing* r, const uint8_t* src, size_t total, hipStream_t s, bool piped,
+int d2h_ring_begin(pgh_ctx* c, D2HRing* r, const uint8_t* src, size_t total, hipStream_t s, bool piped,
                    bool may_wait = true);
-int d2h_issue_ready(pgh_ctx* c, pgh_ctx::D2HRing* r);  // piped: every piece whose marks have fired, no wait
-int take_pin_slot(pgh_ctx* c, int* slot);  // the next pinned staging slot, free of earlier DMAs
 int state_shard_spans(pgh_ctx* c, const uint8_t* pb, size_t n, std::vector<std::pair<size_t, size_t>>* out,
                       const char* what);
 // page-locked blocks marked async (pgh_host_async): DMAs from them are recorded, not waited for

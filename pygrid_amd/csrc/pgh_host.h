@@ -1,6 +1,6 @@
 // HIP-free host code of libpygrid_hip (not installed): the non-temporal copy, the copy pool, the
-// scatter out of a landed piece, page pre-faulting, the CPU count, the DP noise sampler's restatement.  Nothing here
-// may include HIP.
+// scatter out of a landed piece, the walk over concatenated host pieces, the chunk arithmetic of ranged ingest,
+// page pre-faulting, the CPU count, the DP noise sampler's restatement.  Nothing here may include HIP.
 #pragma once
 #include <algorithm>
 #include <condition_variable>
@@ -147,7 +147,43 @@ struct OutPiece {
     uint8_t* dst;
     size_t n;
 };
+// The walk over concatenated host pieces: take appends to `segs` the copies that fill `room` bytes at
+// dst, or what is left of the pieces, and returns the bytes taken.  A zero-length piece yields an empty
+// segment when the walk reaches it before the room is full; a piece that ends exactly at the edge is
+// finished by the take that reaches the edge.
+struct PieceCursor {
+    const std::vector<Piece>& pieces;
+    size_t pi = 0, poff = 0;
+    size_t take(uint8_t* dst, size_t room, std::vector<CopyPool::Seg>* segs) {
+        size_t fill = 0;
+        while (fill < room && pi < pieces.size()) {
+            const size_t m = std::min(pieces[pi].n - poff, room - fill);
+            segs->push_back({dst + fill, pieces[pi].src + poff, m});
+            fill += m;
+            poff += m;
+            if (poff == pieces[pi].n) { ++pi; poff = 0; }
+        }
+        return fill;
+    }
+};
 void scatter_out(const uint8_t* src, size_t off, size_t len, const std::vector<OutPiece>& pieces, CopyPool& pool);
+
+// HBM -> host results move in pieces of at most D2H_PIECE, the later pieces' DMAs beside the host
+// copy-out of the earlier ones (r01ac: 4, 8, 16 MiB within the noise of the 47 MB report-time close;
+// with the parallel pre-fault, r01ak, 8 MiB pieces closed in 2.3-2.4 ms vs 2.6-2.7 for one piece).
+constexpr size_t D2H_PIECE = 8u << 20;
+// Ranged report ingest (pgh_set_ingest_ranges): one chunk = the params of one D2H piece = two
+// 4 MiB FINAL ranges of a report-time close (pgh_slots.cpp).
+constexpr int64_t INGEST_CHUNK = (int64_t)(D2H_PIECE / 4);
+inline int ingest_chunks(int64_t pg) { return (int)((pg + INGEST_CHUNK - 1) / INGEST_CHUNK); }  // of a row of pg floats
+// the bytes [*a, *b) of chunk k of a row of pg floats
+inline void ingest_chunk_bytes(int64_t pg, int k, size_t* a, size_t* b) {
+    *a = (size_t)k * INGEST_CHUNK * 4;
+    *b = std::min((size_t)pg * 4, (size_t)(k + 1) * INGEST_CHUNK * 4);
+}
+// params from `at` up to the next chunk boundary: a gather chunk of a ranged ingest is cut there
+inline int64_t ingest_chunk_room(int64_t at) { return (at / INGEST_CHUNK + 1) * INGEST_CHUNK - at; }
+
 void prefault_small_any(uint8_t* p, size_t n);
 void prefault_parallel(uint8_t* p, size_t n, CopyPool& pool);
 

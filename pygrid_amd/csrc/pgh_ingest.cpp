@@ -9,6 +9,15 @@ using namespace pgh_detail;
 
 // (the public entry points take their C linkage from include/pgh_api.h)
 
+namespace {
+// The tail of every fp32 ingest: the row's norm pass behind its copy (clipping on), then the slot is the client's.
+int finish_ingest(pgh_ctx* c, int64_t client, int slot) {
+    RC(sumsq_after_ingest(c, slot));
+    return mark_ingested(c, client, slot);
+}
+int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>& pieces, int slot, bool ranged);
+}  // namespace
+
 int pgh_ingest_raw(pgh_ctx* c, int client, const void* flat, size_t nbytes, int dtype) {
     if (c && c->grp) return pgh_group_api::ingest_raw(c, client, flat, nbytes, dtype);
     RC(check_dtype(c, dtype));
@@ -26,12 +35,7 @@ int pgh_ingest_raw(pgh_ctx* c, int client, const void* flat, size_t nbytes, int 
     const size_t row_elems = nbytes / (es * (size_t)c->parties);  // each party's row: the model's or the shard's
     for (int s = 0; s < c->parties; ++s)
         RC(stage_h2d(c, row_dest(c, slot, s), src + ((size_t)s * row_elems + first) * es, (size_t)c->pg * es, pinned));
-    RC(sumsq_after_ingest(c, slot));
-    return mark_ingested(c, client, slot);
-}
-
-namespace {
-int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>& pieces, int slot, bool ranged);
+    return finish_ingest(c, client, slot);
 }
 
 int pgh_ingest_state(pgh_ctx* c, int client, const uint8_t* pb, size_t n) {
@@ -50,23 +54,20 @@ int pgh_ingest_state(pgh_ctx* c, int client, const uint8_t* pb, size_t n) {
     RC(claim_slot(c, client, &slot));
     // report-time ingest (pgh_set_ingest_ranges): in chunks with an event each, so a close that
     // starts while this DMA is in flight folds each param range as soon as it has landed
-    const bool ranged = c->ingest_ranges && !c->streaming && c->pg >= (1 << 20);
-    if (n && !pieces.empty() && c->pinned_gather && is_pinned(pb)) {
+    const bool ranged = c->ranged.on && !c->streaming && c->pg >= (1 << 20);
+    if (n && !pieces.empty() && c->gather.on && is_pinned(pb)) {
         // Page-locked message (a report decoded straight into pgh_host_alloc memory,
         // pygrid_amd.report.PinnedPool): no staging copy.  The part of the message holding this
         // shard's payloads goes to HBM in ONE DMA (a few hundred bytes of framing ride along) and
         // k_gather_f32 moves the payloads into the slab row; the call waits for the DMA only (the
         // buffer is borrowed), the gather runs on behind it on the copy stream.
-        const double t0 = now_ms();
         RC(pinned_gather_ingest(c, pb, pieces, slot, ranged));
-        c->st.h2d_ms_total += now_ms() - t0;
-        RC(sumsq_after_ingest(c, slot));
-        return mark_ingested(c, client, slot);
+        return finish_ingest(c, client, slot);
     }
     if (n && is_pinned(pb)) {
         // Page-locked message, one DMA per payload piece (PGH_PINNED_GATHER=0).  The buffer is only
         // borrowed for the call, so the call waits for its copies.
-        const double t0 = now_ms();
+        H2DTimer t(c);
         const Dest d = row_dest(c, slot, 0);
         size_t off = 0;
         for (auto& p : pieces) {
@@ -74,19 +75,16 @@ int pgh_ingest_state(pgh_ctx* c, int client, const uint8_t* pb, size_t n) {
             off += p.n;
         }
         CK(c, hipStreamSynchronize(c->copy));
-        c->st.h2d_ms_total += now_ms() - t0;
-        c->st.h2d_bytes_total += off;
-        RC(sumsq_after_ingest(c, slot));
-        return mark_ingested(c, client, slot);
+        RC(t.done(off));
+        return finish_ingest(c, client, slot);
     }
     size_t total = 0;
     for (auto& p : pieces) total += p.n;
-    if (ranged && total == (size_t)c->pg * 4 && total <= c->pin_slot)
+    if (ranged && total == (size_t)c->pg * 4 && total <= c->ring.slot_bytes)
         RC(stage_pieces_h2d_ranged(c, row_dest(c, slot, 0), pieces, total));
     else
         RC(stage_pieces_h2d(c, row_dest(c, slot, 0), pieces));
-    RC(sumsq_after_ingest(c, slot));
-    return mark_ingested(c, client, slot);
+    return finish_ingest(c, client, slot);
 }
 
 namespace {
@@ -169,41 +167,38 @@ int check_share_msg(pgh_ctx* c, ShareMsg* m, int client, int party) {
 // Stage one party message: chunk bytes -> pinned ring (copied and counted by the pool threads)
 // -> its region of the HBM byte buffer `dev`, on the copy stream.  Nothing is decoded yet.
 int stage_share_msg(pgh_ctx* c, ShareMsg& m, uint8_t* dev) {
-    const double t0 = now_ms();
+    H2DTimer t(c);
     const size_t nk = m.chunks.size();
     size_t k = 0;
     while (k < nk) {
         int ps = 0;
-        RC(take_pin_slot(c, &ps));
+        RC(c->ring.take(c, &ps));
         const size_t s0 = (size_t)m.chunks[k].off;
-        const size_t cap = c->pin_slot;  // whole-slot fills (r01z: smaller fills were slower)
+        const size_t cap = c->ring.slot_bytes;  // whole-slot fills (r01z: smaller fills were slower)
         size_t k1 = k;
         while (k1 < nk && (size_t)m.chunks[k1].off + (size_t)m.chunks[k1].n - s0 <= cap) ++k1;
         if (k1 == k) return fail(c, PGH_E_STATE, "pinned slot smaller than one varint chunk");
-        uint8_t* pin = c->h_pin[ps].as<uint8_t>();
+        uint8_t* pin = c->ring.at(ps);
         const size_t fill = (size_t)m.chunks[k1 - 1].off + (size_t)m.chunks[k1 - 1].n - s0;
         c->pool_copy->run_items((int)(k1 - k), fill >= (4u << 20), [&](int i) {
             const size_t q = k + (size_t)i;
             uint8_t* dst = pin + ((size_t)m.chunks[q].off - s0);
             m.st[q] = pgh_state::varint_copy_stats(dst, m.src[q], (size_t)m.chunks[q].n);
         });
-        ++c->copy_seq;
+        c->ranged.copy_issued();
         CK(c, hipMemcpyAsync(dev + s0, pin, fill, hipMemcpyHostToDevice, c->copy));
-        CK(c, hipEventRecord(c->pin_ev[ps], c->copy));
-        c->pin_used[ps] = true;
+        RC(c->ring.sent(c, ps, c->copy));
         k = k1;
     }
-    c->st.h2d_ms_total += now_ms() - t0;
-    c->st.h2d_bytes_total += m.bytes;
-    c->st.h2d_staged_bytes_total += m.bytes;
-    return PGH_OK;
+    return t.done(m.bytes, m.bytes);
 }
 
 // pgh_ingest_state of a page-locked message: [first payload, last payload end) of this shard in one
-// DMA to d_vbytes, the gather table behind it, then k_gather_f32 into the slot's row.  `ranged`
+// DMA to gather.d_bytes, the gather table behind it, then k_gather_f32 into the slot's row.  `ranged`
 // (pgh_set_ingest_ranges): the table's chunks are cut at INGEST_CHUNK param boundaries and the DMA +
-// gather run chunk by chunk, rng_ev[k] behind chunk k's gather.
+// gather run chunk by chunk, chunk k's event behind its gather.
 int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>& pieces, int slot, bool ranged) {
+    H2DTimer t(c);
     const size_t a = (size_t)(pieces.front().src - pb) & ~(size_t)63;
     const size_t b = (size_t)(pieces.back().src - pb) + pieces.back().n;
     std::vector<pgh::GChunk> tab;
@@ -214,7 +209,7 @@ int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>
         const int64_t src = (int64_t)((size_t)(p.src - pb) - a);
         for (int64_t k = 0; k < nf;) {
             int64_t len = std::min<int64_t>(pgh::GATHER_CHUNK, nf - k);
-            if (ranged) len = std::min(len, (((dst + k) / INGEST_CHUNK) + 1) * INGEST_CHUNK - (dst + k));
+            if (ranged) len = std::min(len, ingest_chunk_room(dst + k));
             tab.push_back({src + 4 * k, dst + k, (int32_t)len, 0});
             k += len;
         }
@@ -222,32 +217,22 @@ int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>
         total += p.n;
     }
     ranged = ranged && dst == c->pg;
-    if (tab.empty()) return PGH_OK;
+    if (tab.empty()) return t.done(0);
+    PinnedGather& g = c->gather;
     const size_t tb = tab.size() * sizeof(pgh::GChunk);
     // regrown only behind the copy stream: an earlier gather may still read the old buffers
-    if (b - a + 16 > c->d_vbytes.cap() || tb > c->d_gtab.cap()) CK(c, hipStreamSynchronize(c->copy));
-    if (!c->d_vbytes.reserve_geometric(b - a + 16))
+    if (b - a + 16 > g.d_bytes.cap() || tb > g.d_tab.cap()) CK(c, hipStreamSynchronize(c->copy));
+    if (!g.d_bytes.reserve_geometric(b - a + 16))
         return fail(c, PGH_E_OOM, "pinned message buffer: device allocation of %zu bytes failed", b - a + 16);
-    if (c->gtab_used) CK(c, hipEventSynchronize(c->gtab_ev));  // the previous table upload read h_gtab
-    if (tb > c->d_gtab.cap()) {
-        if (!c->d_gtab.reserve(tb) || !c->h_gtab.reserve(tb)) {
-            c->d_gtab.reset();  // (the test above: both or neither)
-            return fail(c, PGH_E_OOM, "gather chunk table of %zu bytes failed", tb);
-        }
-        c->gtab_used = false;
-    }
-    pgh::GChunk* const d_gtab = c->d_gtab.as<pgh::GChunk>();
-    uint8_t* const d_vbytes = c->d_vbytes.as<uint8_t>();
-    std::memcpy(c->h_gtab.as<void>(), tab.data(), tb);
-    ++c->copy_seq;
-    CK(c, hipMemcpyAsync(d_gtab, c->h_gtab.as<void>(), tb, hipMemcpyHostToDevice, c->copy));
-    CK(c, hipEventRecord(c->gtab_ev, c->copy));
-    c->gtab_used = true;
+    if (!g.d_tab.reserve(tb)) return fail(c, PGH_E_OOM, "gather chunk table of %zu bytes failed", tb);
+    pgh::GChunk* const d_gtab = g.d_tab.as<pgh::GChunk>();
+    uint8_t* const d_vbytes = g.d_bytes.as<uint8_t>();
+    RC(g.tab.upload(c, d_gtab, tab.data(), tb, c->copy));
     const Dest d = row_dest(c, slot, 0);
     const bool async = host_async(pb + a, b - a);
     if (ranged) {
-        const int K = (int)((c->pg + INGEST_CHUNK - 1) / INGEST_CHUNK);
-        if (!c->ev_pool.fill(c->rng_ev, (size_t)K)) return fail(c, PGH_E_HIP, "hipEventCreate failed");
+        int K = 0;
+        RC(c->ranged.begin(c, c->pg, &K));
         size_t e0 = 0;
         for (int k = 0; k < K; ++k) {
             size_t e1 = e0;
@@ -257,34 +242,32 @@ int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>
                 CK(c, hipMemcpyAsync(d_vbytes + lo, pb + a + lo, hi - lo, hipMemcpyHostToDevice, c->copy));
                 if (e1 == tab.size()) {  // the message's last DMA: the host block is read once this is done
                     if (async) RC(host_dma_queued(c, pb + a, b - a, c->copy));
-                    else CK(c, hipEventRecord(c->gdma_ev, c->copy));
+                    else CK(c, hipEventRecord(g.dma_ev, c->copy));
                 }
                 const hipError_t e = pgh::launch_gather_f32(d_vbytes, d_gtab + e0, (int)(e1 - e0),
                                                             (float*)d.base, d.map, c->copy);
                 if (e != hipSuccess) return fail(c, PGH_E_HIP, "gather launch failed: %s", hipGetErrorString(e));
             }
-            CK(c, hipEventRecord(c->rng_ev[(size_t)k], c->copy));
+            RC(c->ranged.mark(c, k));
             e0 = e1;
         }
-        c->rng_seq = c->copy_seq;
-        c->rng_n = K;
+        c->ranged.commit(K);
     } else {
         CK(c, hipMemcpyAsync(d_vbytes, pb + a, b - a, hipMemcpyHostToDevice, c->copy));
         if (async) RC(host_dma_queued(c, pb + a, b - a, c->copy));  // the block's owner waits (pgh_host_wait)
-        else CK(c, hipEventRecord(c->gdma_ev, c->copy));
+        else CK(c, hipEventRecord(g.dma_ev, c->copy));
         const hipError_t e = pgh::launch_gather_f32(d_vbytes, d_gtab, (int)tab.size(), (float*)d.base, d.map,
                                                     c->copy);
         if (e != hipSuccess) return fail(c, PGH_E_HIP, "gather launch failed: %s", hipGetErrorString(e));
     }
-    if (!async) CK(c, hipEventSynchronize(c->gdma_ev));
-    c->st.h2d_bytes_total += total;
-    return PGH_OK;
+    if (!async) CK(c, hipEventSynchronize(g.dma_ev));
+    return t.done(total);
 }
 
 // A varint buffer holding `bytes` of messages and a table of `tab_bytes` (grown when short, after
 // the decode that last read it).  The dec stream is made on the first use.
-int prepare_vbuf(pgh_ctx* c, pgh_ctx::VarintBuf& b, size_t bytes, size_t tab_bytes) {
-    if (!c->dec) CK(c, c->dec.make());
+int prepare_vbuf(pgh_ctx* c, VarintBuf& b, size_t bytes, size_t tab_bytes) {
+    if (!c->vdec.s) CK(c, c->vdec.s.make());
     if (bytes > b.bytes.cap() || tab_bytes > b.tab.cap()) {  // regrown behind its last decode and the copy stream
         if (b.used) CK(c, hipEventSynchronize(b.done));
         CK(c, hipStreamSynchronize(c->copy));
@@ -298,40 +281,29 @@ int prepare_vbuf(pgh_ctx* c, pgh_ctx::VarintBuf& b, size_t bytes, size_t tab_byt
 
 // Every party validated: one chunk table for all of them (uploaded behind the payload DMAs), then
 // one decode per party into its slab row (the shard's range), on the dec stream.
-int decode_share_msgs(pgh_ctx* c, std::vector<ShareMsg>& msgs, int slot, pgh_ctx::VarintBuf& b) {
+int decode_share_msgs(pgh_ctx* c, std::vector<ShareMsg>& msgs, int slot, VarintBuf& b) {
     size_t nk = 0;
     for (auto& m : msgs) nk += m.chunks.size();
     if (nk == 0) return PGH_OK;  // every tensor empty
     const size_t tb = nk * sizeof(pgh::VChunk);
-    if (c->vtab_used) CK(c, hipEventSynchronize(c->vtab_ev));  // the previous table upload read h_vtab
-    if (tb > c->h_vtab.cap()) {
-        if (!c->h_vtab.reserve(b.tab.cap())) return fail(c, PGH_E_OOM, "pinned chunk table of %zu bytes failed", b.tab.cap());
-        c->vtab_used = false;
-    }
-    pgh::VChunk* const h_vtab = c->h_vtab.as<pgh::VChunk>();
     pgh::VChunk* const d_tab = b.tab.as<pgh::VChunk>();
+    std::vector<pgh::VChunk> all;  // (several parties: their tables one after another)
+    if (msgs.size() > 1)
+        for (auto& m : msgs) all.insert(all.end(), m.chunks.begin(), m.chunks.end());
+    RC(c->vdec.tab.upload(c, d_tab, msgs.size() > 1 ? all.data() : msgs[0].chunks.data(), tb, c->copy));
+    CK(c, hipEventRecord(c->vdec.in, c->copy));
+    CK(c, hipStreamWaitEvent(c->vdec.s, c->vdec.in, 0));
     size_t at = 0;
-    for (auto& m : msgs) {
-        std::memcpy(h_vtab + at, m.chunks.data(), m.chunks.size() * sizeof(pgh::VChunk));
-        at += m.chunks.size();
-    }
-    ++c->copy_seq;
-    CK(c, hipMemcpyAsync(d_tab, h_vtab, tb, hipMemcpyHostToDevice, c->copy));
-    CK(c, hipEventRecord(c->vtab_ev, c->copy));
-    c->vtab_used = true;
-    CK(c, hipEventRecord(c->dec_in, c->copy));
-    CK(c, hipStreamWaitEvent(c->dec, c->dec_in, 0));
-    at = 0;
     for (size_t s = 0; s < msgs.size(); ++s) {
         const int n = (int)msgs[s].chunks.size();
         const hipError_t e = pgh::launch_varint_decode(b.bytes.as<uint8_t>(), d_tab + at, n, (int64_t*)slot_row(c, slot, (int)s),
-                                                       slab_map(c), c->lo, c->hi, c->dec);
+                                                       slab_map(c), c->lo, c->hi, c->vdec.s);
         if (e != hipSuccess) return fail(c, PGH_E_HIP, "varint decode launch failed: %s", hipGetErrorString(e));
         at += (size_t)n;
     }
-    CK(c, hipEventRecord(b.done, c->dec));
+    CK(c, hipEventRecord(b.done, c->vdec.s));
     b.used = true;
-    c->dec_last = b.done;
+    c->vdec.last = b.done;
     return PGH_OK;
 }
 }  // namespace
@@ -357,8 +329,7 @@ int pgh_ingest_state_shares(pgh_ctx* c, int client, int n_parties, const uint8_t
     DeviceGuard g(c->device);
     int slot = 0;
     RC(claim_slot(c, client, &slot));
-    pgh_ctx::VarintBuf& b = c->vbuf[c->vbuf_next];
-    c->vbuf_next ^= 1;
+    VarintBuf& b = c->vdec.take();
     RC(prepare_vbuf(c, b, total + 16, std::max<size_t>(nk, 1) * sizeof(pgh::VChunk)));
     for (auto& m : msgs) RC(stage_share_msg(c, m, b.bytes.as<uint8_t>()));
     for (int s = 0; s < n_parties; ++s) RC(check_share_msg(c, &msgs[(size_t)s], client, s));
@@ -394,7 +365,7 @@ int pgh_synth_ingest(pgh_ctx* c, uint64_t seed, int client0, int n) {
         // (beside the fold on the copy stream, the write-heavy fill and the read-only fold shared
         // HBM 13 % worse, r02p), grid capped at 8192 workgroups (r01t), non-temporal stores
         const hipStream_t gs = c->streaming ? c->stream : c->copy;
-        ++c->copy_seq;
+        c->ranged.copy_issued();
         if (c->dtype == PGH_F32)
             e = pgh::launch_synth_f32((float*)slot_row(c, slot, 0), slab_map(c), c->nb * c->bw, run, c->pg, seed,
                                       pgh::STREAM_DIFF, c->client_base + client, c->lo, pgh::DIFF_SCALE, gs,
@@ -425,7 +396,7 @@ int pgh_set_synth_kind(pgh_ctx* c, int kind) {
 int pgh_set_ingest_ranges(pgh_ctx* c, int on) {
     if (c && c->grp) return pgh_group_api::set_ingest_ranges(c, on);
     if (!c) return PGH_E_ARG;
-    c->ingest_ranges = on != 0;
+    c->ranged.on = on != 0;
     return PGH_OK;
 }
 

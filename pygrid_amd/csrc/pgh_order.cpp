@@ -48,7 +48,7 @@ int collect_timings(pgh_ctx* c) {
 void clear_final_marks(pgh_ctx* c) {
     for (auto& m : c->final_marks) c->ev_pool.give(m.ev);
     c->final_marks.clear();
-    c->pre_d2h_valid = false;
+    c->d2h.drop_pre();
 }
 
 int add_final_mark(pgh_ctx* c, hipStream_t s, int64_t end) {
@@ -85,7 +85,7 @@ int64_t range_edge(const pgh_ctx* c, int k, int K) { return k >= K ? c->pg : (c-
 int order_after_ingest(pgh_ctx* c, hipStream_t s) {
     CK(c, hipEventRecord(c->copy_done, c->copy));
     CK(c, hipStreamWaitEvent(s, c->copy_done, 0));
-    if (c->dec_last) CK(c, hipStreamWaitEvent(s, c->dec_last, 0));
+    if (hipEvent_t dec = c->vdec.last_decode()) CK(c, hipStreamWaitEvent(s, dec, 0));
     return PGH_OK;
 }
 

@@ -44,10 +44,10 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     // chunk of the last report it reads instead of after the whole copy stream
     // (never a clipped pass: a scale needs the last report's whole row, so it takes the whole-stream wait)
     const bool clipped = mode == PGH_CLIPPED_MEAN;
-    const bool ranged = final && !clipped && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && ranged_ingest_valid(c);
+    const bool ranged = final && !clipped && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && c->ranged.valid(c->pg);
     if (clipped && n > 0) RC(clip_slot_scales(c, slots, n, c0));  // the sums still missing in one batch, then the scales in fold order
     if (!ranged) RC(order_after_ingest(c, s));
-    else if (c->dec_last) CK(c, hipStreamWaitEvent(s, c->dec_last, 0));  // the copy stream: per range below
+    else if (hipEvent_t dec = c->vdec.last_decode()) CK(c, hipStreamWaitEvent(s, dec, 0));  // the copy stream: per range below
     if (n > 0) RC(fold_prepare(c, mode, total, s));
     if (median && n > pgh::ROWTAB_MAX) RC(median_row_table(c, slots, n, s));  // more rows than a RowTab carries
     int done = 0;
@@ -74,7 +74,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         // the new checkpoint's D2H starts here: after each mark, the pieces whose ranges have
         // finished go out while the later ranges are still being issued (stage_d2h_pieces adopts the
         // ring).  The result is d_out until the swap below.
-        pgh_ctx::D2HRing& pre = c->pre_d2h;
+        D2HRing& pre = c->d2h.pre;
         bool prequeue = false;
         if (K > 1 && (flags & pgh::FL_FINAL)) {
             RC(d2h_ring_begin(c, &pre, c->d_out.as<uint8_t>(), 4 * (size_t)c->pg, s, true, false));
@@ -83,24 +83,14 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         for (int r = 0; r < K; ++r) {
             const hipStream_t rs = s;
             const int64_t lo = std::min(c->pg, RF * r), hi = K == 1 ? c->pg : std::min(c->pg, RF * (r + 1));
-            if (ranged && K > 1) {  // every chunk this range reads has landed ...
-                for (int64_t k = lo / INGEST_CHUNK; k <= (hi - 1) / INGEST_CHUNK; ++k)
-                    CK(c, hipStreamWaitEvent(rs, c->rng_ev[(size_t)k], 0));
-            } else if (ranged && r == 0) {
-                CK(c, hipStreamWaitEvent(rs, c->rng_ev[(size_t)(c->rng_n - 1)], 0));  // ... or all of it
-            }
+            if (ranged && K > 1) RC(c->ranged.wait_range(c, rs, lo, hi));  // every chunk this range reads has landed ...
+            else if (ranged && r == 0) RC(c->ranged.wait_all(c, rs));     // ... or all of it
             fa.off = lo;
             fa.len = hi - lo;
             RC(fold_launch(c, mode, rows, c0 + done, flags, fa, rs));
             if (K > 1 && (hi % (2 * RF) == 0 || hi == c->pg)) {
                 RC(add_final_mark(c, rs, hi));
-                const size_t before = prequeue ? pre.queued : 0;
-                if (prequeue) RC(d2h_issue_ready(c, &pre));
-                if (prequeue && pre.queued > before)  // its slots are busy until these pieces land
-                    for (int k = 0; k < pre.n_free; ++k) {
-                        CK(c, hipEventRecord(c->pin_ev[pre.free_slot[k]], pre.s));
-                        c->pin_used[pre.free_slot[k]] = true;
-                    }
+                if (prequeue) RC(c->d2h.issue_pre(c));
             }
         }
         prequeued = prequeued || prequeue;
@@ -114,7 +104,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     c->slot_mode = mode;
     if (final) {
         std::swap(c->d_ckpt, c->d_out);  // the new checkpoint is the next cycle's input
-        c->pre_d2h_valid = prequeued && c->pre_d2h.src == c->d_ckpt.as<uint8_t>();
+        c->d2h.keep_pre(prequeued, c->d_ckpt.as<uint8_t>());
         c->folded = 0;  // the next cycle folds from scratch
         c->slot_mode = -1;
         if (clipped) rules_clipped_cycle_finished(c);  // the cycle's rows join the finished totals (pgh_clip_stats)

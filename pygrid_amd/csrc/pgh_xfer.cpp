@@ -1,6 +1,7 @@
 // libpygrid_hip: host <-> HBM movement -- H2D through the pinned staging ring (or straight from
 // page-locked memory), the D2H rings, the shard's spans of a State message, and the page-locked host
-// blocks whose DMAs may outlive the call.  (struct pgh_ctx and the shared helpers: pgh_ctx.h)
+// blocks whose DMAs may outlive the call; the methods of the transfer owners (pgh_xfer.h).
+// (struct pgh_ctx and the shared helpers: pgh_ctx.h)
 #include "pgh_ctx.h"
 
 namespace pgh_detail {
@@ -11,7 +12,7 @@ int h2d_range(pgh_ctx* c, const Dest& d, int64_t i0, const uint8_t* src, int64_t
               size_t src_room) {
     const size_t es = d.es;
     if (n <= 0) return PGH_OK;
-    ++c->copy_seq;
+    c->ranged.copy_issued();
     if (d.map.bshift == 62) {
         CK(c, hipMemcpyAsync(d.base + (size_t)i0 * es, src, (size_t)n * es, hipMemcpyHostToDevice, s));
         return PGH_OK;
@@ -45,77 +46,122 @@ bool is_pinned(const void* p) {
     return attr.type == hipMemoryTypeHost;
 }
 
-// Ranged report ingest (pgh_set_ingest_ranges) of concatenated fp32 host pieces holding the whole
-// shard row: one pinned slot, filled and DMA'd chunk by chunk (INGEST_CHUNK params each, the host
-// copy of chunk k + 1 beside the DMA of chunk k), rng_ev[k] behind chunk k's DMA.
-int stage_pieces_h2d_ranged(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& pieces, size_t total) {
-    const double t0 = now_ms();
-    const int K = (int)((c->pg + INGEST_CHUNK - 1) / INGEST_CHUNK);
-    if (!c->ev_pool.fill(c->rng_ev, (size_t)K)) return fail(c, PGH_E_HIP, "hipEventCreate failed");
-    int slot = 0;
-    RC(take_pin_slot(c, &slot));
-    size_t pi = 0, poff = 0;
-    for (int k = 0; k < K; ++k) {
-        const size_t a = (size_t)k * INGEST_CHUNK * 4, b = std::min(total, (size_t)(k + 1) * INGEST_CHUNK * 4);
-        std::vector<CopyPool::Seg> segs;
-        for (size_t at = a; at < b;) {
-            const size_t m = std::min(pieces[pi].n - poff, b - at);
-            segs.push_back({c->h_pin[slot].as<uint8_t>() + at, pieces[pi].src + poff, m});
-            at += m;
-            poff += m;
-            if (poff == pieces[pi].n) { ++pi; poff = 0; }
-        }
-        c->pool_copy->run(segs);
-        RC(h2d_range(c, dst, (int64_t)(a / 4), c->h_pin[slot].as<uint8_t>() + a, (int64_t)((b - a) / 4), c->copy,
-                     b == total ? c->pin_slot - b : 0));
-        CK(c, hipEventRecord(c->rng_ev[(size_t)k], c->copy));
-    }
-    CK(c, hipEventRecord(c->pin_ev[slot], c->copy));
-    c->pin_used[slot] = true;
-    c->rng_seq = c->copy_seq;
-    c->rng_n = K;
-    c->st.h2d_ms_total += now_ms() - t0;
-    c->st.h2d_bytes_total += total;
-    c->st.h2d_staged_bytes_total += total;
+// ---- the transfer owners (pgh_xfer.h) ---------------------------------------------------------------
+bool xfer_made(pgh_ctx* c) {
+    if (const char* e = std::getenv("PGH_PINNED_GATHER")) c->gather.on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("PGH_D2H_STREAM")) c->d2h.mode = std::max(0, std::min(1, std::atoi(e)));
+    c->d2h.own = c->d2h.mode > 0;
+    bool ok = !c->d2h.own || c->d2h.s.make() == hipSuccess;  // (vdec.s, a fifth stream, only on first use)
+    for (Event* ev : {&c->ring.ev[0], &c->ring.ev[1], &c->gather.tab.ev, &c->gather.dma_ev, &c->vdec.tab.ev,
+                      &c->vdec.in, &c->vdec.buf[0].done, &c->vdec.buf[1].done})
+        ok = ok && ev->make() == hipSuccess;
+    return ok;
+}
+
+int StagingRing::take(pgh_ctx* c, int* slot) {
+    *slot = next;
+    next ^= 1;
+    if (used[*slot]) CK(c, hipEventSynchronize(ev[*slot]));
+    c->d2h.drop_pre();
     return PGH_OK;
 }
 
-// Whether the FINAL pass of a slot fold may wait per param range on the latest ranged ingest
-// instead of on every copy issued (order_after_ingest): nothing else went to the copy stream since.
-bool ranged_ingest_valid(const pgh_ctx* c) {
-    return c->ingest_ranges && c->rng_seq == c->copy_seq && c->rng_n == (int)((c->pg + INGEST_CHUNK - 1) / INGEST_CHUNK);
+int StagingRing::poll_free(pgh_ctx* c, int out[2], int* n) {
+    for (int k = 0; k < 2; ++k) {
+        if (used[k]) {
+            const hipError_t q = hipEventQuery(ev[k]);
+            if (q == hipErrorNotReady) continue;
+            CK(c, q);
+            used[k] = false;
+        }
+        out[(*n)++] = k;
+    }
+    return PGH_OK;
+}
+
+int StagingRing::wait_all(pgh_ctx* c) {
+    for (int k = 0; k < 2; ++k) {
+        CK(c, hipEventSynchronize(ev[k]));
+        used[k] = false;
+    }
+    return PGH_OK;
+}
+
+int HostTable::upload(pgh_ctx* c, void* dev_dst, const void* src, size_t bytes, hipStream_t s) {
+    if (used) CK(c, hipEventSynchronize(ev));  // the previous upload read the image
+    if (bytes > h.cap()) {
+        if (!h.reserve(bytes)) return fail(c, PGH_E_OOM, "%s of %zu bytes failed", what, bytes);
+        used = false;
+    }
+    std::memcpy(h.as<void>(), src, bytes);
+    c->ranged.copy_issued();
+    CK(c, hipMemcpyAsync(dev_dst, h.as<void>(), bytes, hipMemcpyHostToDevice, s));
+    CK(c, hipEventRecord(ev, s));
+    used = true;
+    return PGH_OK;
+}
+
+int RangedIngest::begin(pgh_ctx* c, int64_t pg, int* K) {
+    *K = chunks(pg);
+    if (!c->ev_pool.fill(ev, (size_t)*K)) return fail(c, PGH_E_HIP, "hipEventCreate failed");
+    return PGH_OK;
+}
+
+int RangedIngest::wait_range(pgh_ctx* c, hipStream_t s, int64_t lo, int64_t hi) {
+    for (int64_t k = lo / INGEST_CHUNK; k <= (hi - 1) / INGEST_CHUNK; ++k) CK(c, hipStreamWaitEvent(s, ev[(size_t)k], 0));
+    return PGH_OK;
+}
+
+int RangedIngest::wait_all(pgh_ctx* c, hipStream_t s) {
+    CK(c, hipStreamWaitEvent(s, ev[(size_t)(n - 1)], 0));
+    return PGH_OK;
+}
+
+// Ranged report ingest (pgh_set_ingest_ranges) of concatenated fp32 host pieces holding the whole
+// shard row: one pinned slot, filled and DMA'd chunk by chunk (INGEST_CHUNK params each, the host
+// copy of chunk k + 1 beside the DMA of chunk k), the chunk's event behind its DMA.
+int stage_pieces_h2d_ranged(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& pieces, size_t total) {
+    H2DTimer t(c);
+    int K = 0, slot = 0;
+    RC(c->ranged.begin(c, c->pg, &K));
+    RC(c->ring.take(c, &slot));
+    uint8_t* const pin = c->ring.at(slot);
+    PieceCursor cur{pieces};
+    for (int k = 0; k < K; ++k) {
+        size_t a, b;
+        ingest_chunk_bytes(c->pg, k, &a, &b);  // (total == 4 pg: the caller's condition)
+        std::vector<CopyPool::Seg> segs;
+        cur.take(pin + a, b - a, &segs);
+        c->pool_copy->run(segs);
+        RC(h2d_range(c, dst, (int64_t)(a / 4), pin + a, (int64_t)((b - a) / 4), c->copy,
+                     b == total ? c->ring.slot_bytes - b : 0));
+        RC(c->ranged.mark(c, k));
+    }
+    RC(c->ring.sent(c, slot, c->copy));
+    c->ranged.commit(K);
+    return t.done(total, total);
 }
 
 // Concatenated host pieces -> HBM at `dst`, through the pinned ring: each slot is filled by
 // (multi-threaded) host copies of as many pieces as fit, then DMA'd while the next slot fills.
 int stage_pieces_h2d(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& pieces) {
-    const double t0 = now_ms();
-    size_t total = 0, done = 0, pi = 0, poff = 0;
+    H2DTimer t(c);
+    size_t total = 0, done = 0;
     for (auto& p : pieces) total += p.n;
+    PieceCursor cur{pieces};
     while (done < total) {
         int slot = 0;
-        RC(take_pin_slot(c, &slot));
-        size_t fill = 0;
+        RC(c->ring.take(c, &slot));
         std::vector<CopyPool::Seg> segs;
-        while (fill < c->pin_slot && pi < pieces.size()) {
-            const size_t m = std::min(pieces[pi].n - poff, c->pin_slot - fill);
-            segs.push_back({c->h_pin[slot].as<uint8_t>() + fill, pieces[pi].src + poff, m});
-            fill += m;
-            poff += m;
-            if (poff == pieces[pi].n) { ++pi; poff = 0; }
-        }
+        const size_t fill = cur.take(c->ring.at(slot), c->ring.slot_bytes, &segs);
         c->pool_copy->run(segs);
         // slot fills are whole multiples of 4 KiB but the last, so `done` stays element-aligned
-        RC(h2d_range(c, dst, (int64_t)(done / dst.es), c->h_pin[slot].as<uint8_t>(), (int64_t)(fill / dst.es), c->copy,
-                     c->pin_slot - fill));
-        CK(c, hipEventRecord(c->pin_ev[slot], c->copy));
-        c->pin_used[slot] = true;
+        RC(h2d_range(c, dst, (int64_t)(done / dst.es), c->ring.at(slot), (int64_t)(fill / dst.es), c->copy,
+                     c->ring.slot_bytes - fill));
+        RC(c->ring.sent(c, slot, c->copy));
         done += fill;
     }
-    c->st.h2d_ms_total += now_ms() - t0;
-    c->st.h2d_bytes_total += total;
-    c->st.h2d_staged_bytes_total += total;
-    return PGH_OK;
+    return t.done(total, total);
 }
 
 // host bytes -> HBM on the copy stream.  Page-locked sources are DMA'd directly (the call
@@ -123,97 +169,64 @@ int stage_pieces_h2d(pgh_ctx* c, const Dest& dst, const std::vector<Piece>& piec
 // the pinned ring, so the host memcpy of one slot overlaps the DMA of the other.
 int stage_h2d(pgh_ctx* c, const Dest& dst, const uint8_t* src, size_t n, bool pinned_src) {
     if (!pinned_src) return stage_pieces_h2d(c, dst, {Piece{src, n}});
-    const double t0 = now_ms();
+    H2DTimer t(c);
     RC(h2d_range(c, dst, 0, src, (int64_t)(n / dst.es), c->copy));
     CK(c, hipStreamSynchronize(c->copy));
-    c->st.h2d_ms_total += now_ms() - t0;
-    c->st.h2d_bytes_total += n;
-    return PGH_OK;
+    return t.done(n);
 }
 
-int take_pin_slot(pgh_ctx* c, int* slot) {
-    *slot = c->pin_next;
-    c->pin_next ^= 1;
-    if (c->pin_used[*slot]) CK(c, hipEventSynchronize(c->pin_ev[*slot]));
-    c->pre_d2h_valid = false;  // (conservative) its cells may be overwritten now
-    return PGH_OK;
-}
-
-// The stream and page-locked cells of piped rings (own_d2h): at least `bytes` of cells.  Made on
-// first use; grown only after every piece already on the stream has landed.
+// The page-locked cells of piped rings on their own stream (d2h.own): at least `bytes` of cells.  Made
+// on first use; grown only after every piece already on the stream has landed.  (The stream itself is made
+// with the context -- pgh_create fails without it -- and primed by its warm-up.)
 static int ensure_d2h_cells(pgh_ctx* c, size_t bytes) {
-    if (!c->d2h) {  // (made with the context, primed by its warm-up; here only if that failed)
-        CK(c, c->d2h.make());
-        // prime the stream with a small H2D: the runtime then runs its D2H copies on an SDMA engine
-        // (an unprimed stream's D2H went to blit kernels that share the CUs with the fold, r05k/-r05x/)
-        void* d = nullptr;
-        CK(c, hipMalloc(&d, 64));
-        const hipError_t e1 = hipMemcpyAsync(d, c->h_pin[0].as<uint8_t>(), 64, hipMemcpyHostToDevice, c->d2h);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamSynchronize(c->d2h) : e1;
-        (void)hipFree(d);
-        CK(c, e2);
-    }
-    if (c->h_d2h.cap() >= bytes) return PGH_OK;
-    CK(c, hipStreamSynchronize(c->d2h));
-    if (!c->h_d2h.reserve(bytes)) return fail(c, PGH_E_OOM, "page-locked D2H cells of %zu bytes failed", bytes);
+    if (c->d2h.h.cap() >= bytes) return PGH_OK;
+    CK(c, hipStreamSynchronize(c->d2h.s));
+    if (!c->d2h.h.reserve(bytes)) return fail(c, PGH_E_OOM, "page-locked D2H cells of %zu bytes failed", bytes);
     return PGH_OK;
 }
 
-int d2h_ring_begin(pgh_ctx* c, pgh_ctx::D2HRing* r, const uint8_t* src, size_t total, hipStream_t s, bool piped,
-                   bool may_wait) {
-    *r = pgh_ctx::D2HRing{};
+int d2h_ring_begin(pgh_ctx* c, D2HRing* r, const uint8_t* src, size_t total, hipStream_t s, bool piped, bool may_wait) {
+    *r = D2HRing{};
     r->src = src;
     r->total = total;
     r->piped = piped;
-    if (piped && c->own_d2h) {  // up to D2H_OWN_CELLS pieces in flight, none of the staging slots held
+    if (piped && c->d2h.own) {  // up to D2H_OWN_CELLS pieces in flight, none of the staging slots held
         r->piece = D2H_PIECE;
         r->n_pieces = (total + r->piece - 1) / r->piece;
         RC(ensure_d2h_cells(c, std::min(r->n_pieces, D2H_OWN_CELLS) * r->piece));
-        r->base = c->h_d2h.as<uint8_t>();
-        r->cells = c->h_d2h.cap() / r->piece;
+        r->base = c->d2h.h.as<uint8_t>();
+        r->cells = c->d2h.h.cap() / r->piece;
         r->per_slot = r->cells;
-        r->s = c->d2h;
-        if (!c->ev_pool.fill(c->d2h_ev, std::min(r->cells, r->n_pieces)))
+        r->s = c->d2h.s;
+        if (!c->ev_pool.fill(c->d2h.ev, std::min(r->cells, r->n_pieces)))
             return fail(c, PGH_E_HIP, "hipEventCreate failed");
         return PGH_OK;
     }
     r->s = piped ? c->copy : s;
-    r->piece = std::min(c->pin_slot, D2H_PIECE);
-    r->per_slot = c->pin_slot / r->piece;  // >= 1 (pin_slot >= 4096)
+    r->piece = std::min(c->ring.slot_bytes, D2H_PIECE);
+    r->per_slot = c->ring.slot_bytes / r->piece;  // >= 1 (slot_bytes >= 4096)
     // an earlier staged ingest may still read a slot: use the free ones, wait only if neither is
-    for (int k = 0; k < 2; ++k) {
-        if (c->pin_used[k]) {
-            const hipError_t q = hipEventQuery(c->pin_ev[k]);
-            if (q == hipErrorNotReady) continue;
-            CK(c, q);
-            c->pin_used[k] = false;
-        }
-        r->free_slot[r->n_free++] = k;
-    }
+    RC(c->ring.poll_free(c, r->free_slot, &r->n_free));
     if (r->n_free == 0 && !may_wait) return PGH_OK;
     if (r->n_free == 0) {
-        for (int k = 0; k < 2; ++k) {
-            CK(c, hipEventSynchronize(c->pin_ev[k]));
-            c->pin_used[k] = false;
-            r->free_slot[k] = k;
-        }
-        r->n_free = 2;
+        RC(c->ring.wait_all(c));
+        r->n_free = 2;  // (free_slot is {0, 1} still)
     }
     r->cells = (size_t)r->n_free * r->per_slot;  // ring cells, one piece each
     r->n_pieces = (total + r->piece - 1) / r->piece;
-    if (!c->ev_pool.fill(c->d2h_ev, std::min(r->cells, r->n_pieces))) return fail(c, PGH_E_HIP, "hipEventCreate failed");
+    if (!c->ev_pool.fill(c->d2h.ev, std::min(r->cells, r->n_pieces))) return fail(c, PGH_E_HIP, "hipEventCreate failed");
     return PGH_OK;
 }
 
-static uint8_t* d2h_cell(const pgh_ctx* c, const pgh_ctx::D2HRing& r, size_t j) {
+static uint8_t* d2h_cell(const pgh_ctx* c, const D2HRing& r, size_t j) {
     if (r.base) return r.base + (j % r.cells) * r.piece;
-    return c->h_pin[r.free_slot[(j % r.cells) / r.per_slot]].as<uint8_t>() + (j % r.per_slot) * r.piece;
+    return c->ring.at(r.free_slot[(j % r.cells) / r.per_slot]) + (j % r.per_slot) * r.piece;
 }
 
 // Piece j of a piped ring: have all the fold ranges its floats come from finished?  (wait: block
 // until they have.)  Marks may come from two streams (a split resident FINAL pass): every mark
 // overlapping the piece is checked.
-static int d2h_piece_ready(pgh_ctx* c, const pgh_ctx::D2HRing& r, size_t j, bool wait, bool* ready) {
+static int d2h_piece_ready(pgh_ctx* c, const D2HRing& r, size_t j, bool wait, bool* ready) {
     *ready = true;
     if (!r.piped) return PGH_OK;
     const size_t off = j * r.piece, len = std::min(r.piece, r.total - off);
@@ -235,16 +248,16 @@ static int d2h_piece_ready(pgh_ctx* c, const pgh_ctx::D2HRing& r, size_t j, bool
     return PGH_OK;
 }
 
-static int d2h_issue(pgh_ctx* c, pgh_ctx::D2HRing* r) {
+static int d2h_issue(pgh_ctx* c, D2HRing* r) {
     const size_t j = r->queued, off = j * r->piece, len = std::min(r->piece, r->total - off);
     CK(c, hipMemcpyAsync(d2h_cell(c, *r, j), r->src + off, len, hipMemcpyDeviceToHost, r->s));
     c->st.d2h_bytes_total += len;
-    CK(c, hipEventRecord(c->d2h_ev[j % r->cells], r->s));
+    CK(c, hipEventRecord(c->d2h.ev[j % r->cells], r->s));
     ++r->queued;
     return PGH_OK;
 }
 
-int d2h_issue_ready(pgh_ctx* c, pgh_ctx::D2HRing* r) {
+static int d2h_issue_ready(pgh_ctx* c, D2HRing* r) {  // piped: every piece whose marks have fired, no wait
     while (r->queued < r->n_pieces && r->queued < r->done + r->cells) {
         bool ok = false;
         RC(d2h_piece_ready(c, *r, r->queued, false, &ok));
@@ -266,20 +279,20 @@ int d2h_issue_ready(pgh_ctx* c, pgh_ctx::D2HRing* r) {
 // blit kernels (__amd_rocclr_copyBuffer) -- on the copy stream only after a stall, on any other
 // stream always -- and each blit held the fold range beside it to a quarter of its speed (48 ->
 // 182 us, profiles/r05d/, r05k/-r05m/).  The FINAL pass of a report-time close starts this itself
-// (pre_d2h), issuing the pieces whose ranges are done while it issues the rest.
+// (d2h.pre), issuing the pieces whose ranges are done while it issues the rest.
 int stage_d2h_pieces(pgh_ctx* c, const uint8_t* src, const std::vector<OutPiece>& pieces, hipStream_t s,
                      const std::function<void()>& overlap, bool marks) {
     size_t total = 0;
     for (auto& p : pieces) total += p.n;
     if (total == 0) return PGH_OK;
     const bool piped = marks && !c->final_marks.empty();
-    pgh_ctx::D2HRing r;
-    if (piped && c->pre_d2h_valid && c->pre_d2h.src == src && c->pre_d2h.total == total) {
-        r = c->pre_d2h;  // started by the FINAL pass (its slots marked busy until now)
+    D2HRing r;
+    if (piped && c->d2h.adopts(src, total)) {
+        r = c->d2h.pre;  // started by the FINAL pass (its slots marked busy until now)
     } else {
         RC(d2h_ring_begin(c, &r, src, total, s, piped));
     }
-    c->pre_d2h_valid = false;
+    c->d2h.drop_pre();
     auto copy_out = [&](size_t j) {
         const size_t off = j * r.piece, len = std::min(r.piece, total - off);
         scatter_out(d2h_cell(c, r, j), off, len, pieces, *c->pool_copy);
@@ -289,7 +302,7 @@ int stage_d2h_pieces(pgh_ctx* c, const uint8_t* src, const std::vector<OutPiece>
             while (r.queued < r.n_pieces && r.queued < r.cells) RC(d2h_issue(c, &r));
             if (overlap) overlap();
             for (; r.done < r.n_pieces; ++r.done) {
-                CK(c, hipEventSynchronize(c->d2h_ev[r.done % r.cells]));
+                CK(c, hipEventSynchronize(c->d2h.ev[r.done % r.cells]));
                 copy_out(r.done);
                 if (r.queued < r.n_pieces) RC(d2h_issue(c, &r));  // into the cell just copied out
             }
@@ -304,7 +317,7 @@ int stage_d2h_pieces(pgh_ctx* c, const uint8_t* src, const std::vector<OutPiece>
             while (r.done < r.n_pieces) {
                 RC(d2h_issue_ready(c, &r));  // whatever finished, before a copy-out takes the thread
                 if (r.done < r.queued) {
-                    const hipError_t q = hipEventQuery(c->d2h_ev[r.done % r.cells]);
+                    const hipError_t q = hipEventQuery(c->d2h.ev[r.done % r.cells]);
                     if (q == hipSuccess) {
                         copy_out(r.done++);
                         continue;
@@ -321,8 +334,16 @@ int stage_d2h_pieces(pgh_ctx* c, const uint8_t* src, const std::vector<OutPiece>
         return PGH_OK;
     }();
     if (rc != PGH_OK) (void)hipStreamSynchronize(r.s);  // no piece may still land in a slot handed out later
-    for (int k = 0; k < r.n_free; ++k) c->pin_used[r.free_slot[k]] = false;  // every piece landed
+    for (int k = 0; k < r.n_free; ++k) c->ring.release(r.free_slot[k]);  // every piece landed
     return rc;
+}
+
+int D2HState::issue_pre(pgh_ctx* c) {
+    const size_t before = pre.queued;
+    RC(d2h_issue_ready(c, &pre));
+    if (pre.queued > before)  // its slots are busy until these pieces land
+        for (int k = 0; k < pre.n_free; ++k) RC(c->ring.sent(c, pre.free_slot[k], pre.s));
+    return PGH_OK;
 }
 
 // The shard's slice of every tensor payload of a State message, as byte ranges of the message.

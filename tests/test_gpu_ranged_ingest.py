@@ -88,9 +88,11 @@ def test_ranged_report_close_is_bit_exact(engine, mode, pinned):
 
 
 def test_ranged_off_and_on_agree_and_a_copy_in_between_falls_back(engine, monkeypatch):
-    """PGH_INGEST_RANGES=0 (whole-copy ingest) and the default give the same bytes; a checkpoint
-    upload issued after the last ranged report (a copy the ranges do not cover) makes the close
-    wait on the whole copy stream, still bit-exact."""
+    """PGH_INGEST_RANGES=0 (whole-copy ingest) and the default give the same bytes; a copy issued
+    after the last ranged report (one the ranges do not cover) makes the close wait on the whole copy
+    stream, still bit-exact -- every kind of counted copy the engine can issue there without changing
+    the result: a checkpoint upload from State bytes, one from raw floats, and a raw ingest into a slot
+    the cycle never assigned and the close does not fold."""
     from pygrid_amd.incremental import IncrementalCycle
     from pygrid_amd.state_schema import build_state_fast, parse_state
 
@@ -111,18 +113,27 @@ def test_ranged_off_and_on_agree_and_a_copy_in_between_falls_back(engine, monkey
         outs.append(inc.close(ck))
     for off, on, w_ in zip(parse_state(outs[0]), parse_state(outs[1]), want):  # (fresh ids: not the bytes)
         assert np.array_equal(bits(off), bits(w_)) and np.array_equal(bits(on), bits(w_))
-    # the checkpoint re-uploaded between the last report and the close
     monkeypatch.setenv("PGH_INGEST_RANGES", "1")
-    ck = build_state_fast(ckpt)
-    inc = IncrementalCycle(engine, numel, slots=4, fold_batch=8, checkpoint=ck)
-    for w in range(4):
-        inc.assigned(w)
-    for w in (1, 3, 0, 2):
-        inc.reported(w, build_state_fast(diffs[w]))
-    engine.ckpt_upload_state(ck)
-    new = inc.close(ck)
-    for g, w_ in zip(parse_state(new), want):
-        assert np.array_equal(bits(g), bits(w_))
+    flat_ckpt = np.concatenate([t.reshape(-1) for t in ckpt])
+    stray = (rng.standard_normal(flat_ckpt.size) * 1e-2).astype(F)
+    copies = {
+        # the checkpoint re-uploaded between the last report and the close, as State bytes and as raw floats
+        "ckpt_upload_state": lambda ck: engine.ckpt_upload_state(ck),
+        "ckpt_upload": lambda ck: engine.ckpt_upload(flat_ckpt),
+        # slot 4: one more than the cycle's four workers take; nobody reported it, the close leaves it alone
+        "ingest_raw": lambda ck: engine.ingest(4, stray),
+    }
+    for what, copy_in_between in copies.items():
+        ck = build_state_fast(ckpt)
+        inc = IncrementalCycle(engine, numel, slots=5 if what == "ingest_raw" else 4, fold_batch=8, checkpoint=ck)
+        for w in range(4):
+            inc.assigned(w)
+        for w in (1, 3, 0, 2):
+            inc.reported(w, build_state_fast(diffs[w]))
+        copy_in_between(ck)
+        new = inc.close(ck)
+        for g, w_ in zip(parse_state(new), want):
+            assert np.array_equal(bits(g), bits(w_)), what
 
 
 def test_ranged_report_close_on_a_group():
