@@ -53,14 +53,18 @@ typedef enum {
  * b smallest (coordinate-wise trimmed mean, Yin et al. 2018; b from pgh_set_trim; no reference
  * counterpart).
  * PGH_MEDIAN: per parameter, the median of the N reported values (coordinate-wise median, Yin et al.
- * 2018; no parameter; no reference counterpart; defined below, before the reductions). */
+ * 2018; no parameter; no reference counterpart; defined below, before the reductions).
+ * PGH_GEOMETRIC_MEDIAN: the smoothed Weiszfeld approximation of the geometric median of the N diffs
+ * (Pillutla, Kakade, Harchaoui, "Robust Aggregation for Federated Learning"; settings from
+ * pgh_set_geomed; no reference counterpart; defined below). */
 typedef enum {
     PGH_MEAN = 0,
     PGH_ITERATIVE_MEAN = 1,
     PGH_WEIGHTED_MEAN = 2,
     PGH_CLIPPED_MEAN = 3,
     PGH_TRIMMED_MEAN = 4,
-    PGH_MEDIAN = 5
+    PGH_MEDIAN = 5,
+    PGH_GEOMETRIC_MEDIAN = 6
 } pgh_mode;
 /* Stream kind for pgh_stream_begin besides the three averaging modes. */
 #define PGH_STREAM_SECAGG 16
@@ -321,6 +325,62 @@ int pgh_set_trim(pgh_ctx* ctx, int b);
  * PGH_MEDIAN) reports 50 or 51 for the diffs currently held; pgh_set_variant does not affect
  * median folds. */
 #define PGH_MEDIAN_NCHIP 1024
+
+/* ---- geometric-median FedAvg (PGH_GEOMETRIC_MEDIAN, RFA; kernel K12) ----------------------------
+ * The geometric median of the diffs -- the point with the smallest sum of L2 distances to them --
+ * approximated by a fixed number of smoothed Weiszfeld steps.  It tolerates any hostile minority in norm
+ * (not per coordinate), is rotation invariant and returns a point in the convex hull of the diffs.
+ * All arithmetic is IEEE, every operation rounded on its own (no FMA contraction); f64 / and sqrt are
+ * correctly rounded; no libm call besides sqrt.  Rows d_0 .. d_{N-1} in fold order, iters and nu from
+ * pgh_set_geomed:
+ *   1. Included rows.  s_c = the sum of squares of row c in the order of "clipped FedAvg" above (K7,
+ *      cached at ingest).  A row whose s_c is not finite (a NaN, an infinity, an overflow) is excluded:
+ *      no fold and no distance pass reads it (0 * inf cannot poison a parameter).  The included rows
+ *      keep their relative order; the k-th of them is fold client k.  No row included: PGH_E_STATE,
+ *      nothing is launched, the context stays usable.
+ *   2. Iterate.  v^(0) = +0.0.  For t = 0 .. iters - 1, on the host in f64, over the included rows:
+ *        D_c = s_c for t = 0, else K12's sum against v^(t) (below);
+ *        dist_c = sqrt(D_c);
+ *        beta_c = D_c finite ? 1.0 / max((double)nu, dist_c) : 0.0;
+ *        B = the left fold of beta_c in fold order (f64); B == 0 is PGH_E_STATE;
+ *        w_c = (float)(beta_c / B);  W = the f32 left fold of w_c;
+ *        acc = d_0 * w_0; acc = acc + d_c * w_c (the product rounded to f32, then the sum, fold order:
+ *        the weighted fold);  v^(t+1) = acc / W (f32).
+ *      Iteration 0 needs no distance pass (the norms are there from ingest), and a row of 1e30 cannot
+ *      overflow the starting point the way a plain mean would.
+ *   3. Close.  out = ckpt - v^(iters); with a server optimizer K10 takes g = v^(iters).
+ *   4. K12.  D_c = K7's sum in K7's exact order (tiles of 4,096 params, 256 lane partials over j and e,
+ *      the shuffle tree per wave, the four wave sums left to right, the tile partials left to right) over
+ *      x_i = d_c[i] - v[i], ONE f32 subtraction, so that the square is exact in f64.  The engine holds -v
+ *      (the fold against a -0.0 plane yields it exactly) and adds: d + (-v) is the same IEEE operation.
+ * The result is a function of the rows and (iters, nu) alone: not of the launch shape, the slots, the
+ * slab's block width, the range split or the entry point; a repeated close gives identical bits.
+ *
+ * pgh_set_geomed: iters = 0 turns the rule off (always accepted), 1 .. PGH_GEOMED_MAX_ITERS turns it on
+ * with nu finite and > 0; anything else is PGH_E_ARG.  PGH_E_UNSUPPORTED wherever pgh_set_clip_norm
+ * refuses (a group, a shard narrower than the layout, an int64 slab, a streaming context).
+ * pgh_set_layout and pgh_set_shard clear the setting; pgh_reset and pgh_reserve keep it.  With the rule
+ * on every ingest queues the row's K7 behind its copy, as clipping does.  The mode takes every row of
+ * the cycle in one call: pgh_fedavg, pgh_fedavg_device[_range], pgh_fedavg_resident and
+ * pgh_fold_slots_finish_resident (any slot list, no earlier slot fold in the cycle: PGH_E_STATE
+ * otherwise) accept it on one GPU holding whole rows; pgh_fold_slots, pgh_stream_begin, groups and
+ * narrower shards refuse it (PGH_E_UNSUPPORTED); the mode without the setting is PGH_E_STATE, and so
+ * is the mode beside DP noise.  pgh_set_weights is not used (the close replaces the weights).  The
+ * inner iterations run whole-shard on the context's stream and are finished when the call that
+ * computed them returns; the final weights are computed once per state of the slab (range calls and
+ * repeated closes reuse them), and only the last fold is a FINAL one.  Two [P_shard] float planes in
+ * HBM (-0.0 and -v), allocated by the first close with iters >= 2.  pgh_effective_variant(ctx,
+ * PGH_GEOMETRIC_MEDIAN) reports what the weighted fold would run.
+ * pgh_row_distsq: K12 alone against `point` (host, P floats), the counterpart of pgh_row_sumsq: the n
+ * listed occupied slots' D_c into out (n doubles).
+ * pgh_geomed_stats: the setting's iters and, of the last computation of the weights: the rows given, how
+ * many were excluded, the f64 left fold of dist_c over the included rows in the last iteration
+ * (the objective) and the largest w_c of it.  Each pointer may be NULL. */
+#define PGH_GEOMED_MAX_ITERS 16
+int pgh_set_geomed(pgh_ctx* ctx, int iters, float nu);
+int pgh_row_distsq(pgh_ctx* ctx, const int32_t* slots, int n, const float* point, double* out);
+int pgh_geomed_stats(pgh_ctx* ctx, int* iters, int64_t* n_rows, int64_t* n_excluded, double* objective,
+                     float* max_weight);
 
 /* ---- server optimizers: how the average is applied (FedAvgM, FedAdagrad, FedAdam, FedYogi) ------
  * Without one, a close writes out = ckpt - g, g being the cycle's average as its mode defines it

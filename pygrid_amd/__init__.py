@@ -15,11 +15,12 @@ Importing the package changes nothing in the host process; ``tune_process()`` is
 opt-in for the process-wide settings the engine benefits from (HIP hardware queues, glibc
 thresholds for 47 MB buffers).
 """
-from .exceptions import (AggregationError, ClipUnavailableError, DpNoiseUnavailableError, EngineUnavailableError, MedianUnavailableError,
+from .exceptions import (AggregationError, ClipUnavailableError, DpNoiseUnavailableError, EngineUnavailableError, GeometricMedianUnavailableError,
+                         MedianUnavailableError,
                          ModelNotAcceleratedError,
                          PlanNotAcceleratedError, PyGridError, ServerOptUnavailableError, StateParseError,
                          TrimUnavailableError)
-from .engine import (CLIPPED_MEAN, F32, I64, ITERATIVE_MEAN, MEAN, MEDIAN, MEDIAN_NCHIP, MODE_NAMES, STREAM_SECAGG,
+from .engine import (CLIPPED_MEAN, F32, GEOMETRIC_MEDIAN, I64, ITERATIVE_MEAN, MEAN, MEDIAN, MEDIAN_NCHIP, MODE_NAMES, STREAM_SECAGG,
                      TRIMMED_MEAN, TRIM_MAX,
                      WEIGHTED_MEAN, Engine, PinnedBuffer, device_count)
 
@@ -43,7 +44,7 @@ __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
     "StateParseError", "TrimUnavailableError", "MedianUnavailableError", "ServerOptUnavailableError", "DpNoiseUnavailableError",
     "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
-    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "MODE_NAMES", "F32", "I64",
+    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "GEOMETRIC_MEDIAN", "GeometricMedianUnavailableError", "MODE_NAMES", "F32", "I64",
     "tune_process",
 ]
 __version__ = "0.3.0"

@@ -109,6 +109,9 @@ SIGNATURES = {
     "pgh_dp_normals_host": (_i, [_u64, C.c_uint32, _i64, _i64, C.POINTER(C.c_double)]),
     "pgh_dp_stats": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_double), _P64]),
     "pgh_set_trim": (_i, [_vp, _i]),
+    "pgh_set_geomed": (_i, [_vp, _i, C.c_float]),
+    "pgh_row_distsq": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "pgh_geomed_stats": (_i, [_vp, C.POINTER(C.c_int), _P64, _P64, C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "pgh_set_server_opt": (_i, [_vp, _i, C.c_float, C.c_float, C.c_float, C.c_float]),
     "pgh_server_opt_commit": (_i, [_vp]),
     "pgh_server_opt_steps": (_i, [_vp, _P64]),

@@ -4,7 +4,7 @@
 // The context's code is split by what it does:
 //   pgh_api.cpp     lifecycle, errors and state checks, observability, the group driver's internals
 //   pgh_host.cpp    host code free of HIP (pgh_host.h): non-temporal copy, copy pool, pre-faulting, the walk over
-//                   host pieces (PieceCursor), the chunk arithmetic of ranged ingest
+//                   host pieces (PieceCursor), the chunk arithmetic of ranged ingest, the geometric median's host step
 //   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks; the methods of
 //                   the transfer owners.  Their state: pgh_xfer.h
 //   pgh_order.cpp   which stream waits for what, and the timing events
@@ -13,7 +13,7 @@
 //                   sum; the divisors; RESIDENT and STREAM entry points, the resident checkpoint
 //   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: clipping (K7's sums,
 //                   the scales, the tallies) and the Gaussian noise on the clipped close (K11 behind a FINAL launch),
-//                   trimming (K8's planes), the median (K9, K9p); the rules' lifecycle
+//                   trimming (K8's planes), the median (K9, K9p), the geometric median (its weights, K12); the rules' lifecycle
 //                   calls (rules_*) and entry points.  Their state: pgh_rules.h
 //   pgh_serveropt.cpp  the server optimizer: K10 behind a FINAL launch, its planes, commit, download, upload
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order): slot_fold
@@ -63,7 +63,7 @@ namespace pgh_detail {
 
 constexpr int KIND_SECAGG = PGH_STREAM_SECAGG;  // fold kind besides the pgh_mode values (none of which it equals)
 static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KIND_SECAGG != PGH_WEIGHTED_MEAN &&
-                  KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN && KIND_SECAGG != PGH_MEDIAN,
+                  KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN && KIND_SECAGG != PGH_MEDIAN && KIND_SECAGG != PGH_GEOMETRIC_MEDIAN,
               "the secagg fold kind must not collide with an averaging mode");
 
 // CPUs on the GPU's own socket (its PCI device's local_cpulist) that this process may run on; empty
@@ -165,6 +165,7 @@ struct pgh_ctx {
     pgh_detail::NoiseState noise;
     pgh_detail::TrimState trim;
     pgh_detail::MedianState med;
+    pgh_detail::GeomedState geo;
     pgh_detail::ServerOptState opt;
 
     bool streaming = false;
@@ -219,12 +220,13 @@ double now_ms();
 inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
 inline bool valid_mode(int m) {  // (pgh_effective_variant's alone: check_mode_use has its own switch)
     return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN ||
-           m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN;
+           m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN || m == PGH_GEOMETRIC_MEDIAN;
 }
 static_assert(PGH_TRIMMED_MEAN == pgh::MODE_TRIMMED && PGH_TRIM_MAX == pgh::TRIM_MAX, "the kernels' numbering");
 static_assert(PGH_MEDIAN == pgh::MODE_MEDIAN && PGH_MEDIAN_NCHIP == pgh::MEDIAN_NCHIP, "the kernels' numbering");
-// The kernels' mode: a clipped mean is the weighted fold with the scales as weights.
-inline int kernel_mode(int m) { return m == PGH_CLIPPED_MEAN ? PGH_WEIGHTED_MEAN : m; }
+// The kernels' mode: a clipped mean is the weighted fold with the scales as weights, a geometric median the
+// weighted fold with the last Weiszfeld weights.
+inline int kernel_mode(int m) { return m == PGH_CLIPPED_MEAN || m == PGH_GEOMETRIC_MEDIAN ? PGH_WEIGHTED_MEAN : m; }
 // May `mode` be folded this way on this context?  The one place that says so, in this order: an unknown
 // mode (PGH_E_ARG); a rule that the use or a group cannot serve -- a stream neither clips, trims nor
 // takes a median, a median folds nothing early, a group does not clip (PGH_E_UNSUPPORTED); a rule whose
@@ -376,12 +378,26 @@ float clip_scale_of(double sumsq, float c);
 // K7 on the copy stream for those of `slots` that have no sum yet, and the D2H of the sums
 int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n);
 int sumsq_wait(pgh_ctx* c);                // the queued sums are in sq_host afterwards
-int sumsq_after_ingest(pgh_ctx* c, int slot);  // clipping on: queue the row's K7 behind its copy
+int sumsq_after_ingest(pgh_ctx* c, int slot);  // norms wanted (below): queue the row's K7 behind its copy
 // weights[c0 + k] = the scale of slots[k] (waits for the sums); norms (nullable) receives sqrt(sumsq)
 int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms);
 int resident_clip_scales(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n)
 // a slot fold of a clipped cycle: the scales and norms of slots[0, n) at fold index c0 (0 begins the cycle)
 int clip_slot_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0);
+
+// ---- geometric-median FedAvg (pgh_rules.cpp) ---------------------------------------------------------
+inline bool geomed_on(const pgh_ctx* c) { return c->geo.iters > 0 && c->dtype == PGH_F32 && !c->streaming; }
+// K7 behind every ingest: clipping or the geometric median is on
+inline bool norms_wanted(const pgh_ctx* c) { return clip_on(c) || geomed_on(c); }
+// The final weights of a close over slots[0, n) in fold order (the included rows and their weights into
+// geo.rows / weights / geo.W): the inner iterations run whole-shard on the context's stream and are finished
+// when this returns.  PGH_E_STATE with no row included; nothing is launched then.
+int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n);
+int geomed_resident_weights(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n), once per slab state
+// One launch per run of the included rows (contiguous: one; else RowTabs) of the weighted fold over
+// [fa.off, fa.off + fa.len) on stream s: FIRST on the first, FINAL (when `final`) on the last.
+struct FinalArgs;
+int geomed_fold(pgh_ctx* c, bool final, const FinalArgs& fa, hipStream_t s);
 
 // ---- Gaussian noise on the clipped close (pgh_rules.cpp) ---------------------------------------------
 inline bool noise_on(const pgh_ctx* c) { return c->noise.z > 0.f; }
@@ -436,6 +452,7 @@ struct FinalArgs {
     float divisor = 1.f;
     int64_t off = 0;   // param range within the shard
     int64_t len = -1;  // -1 = to the end of the shard
+    bool plain = false;  // a FINAL that is an inner step (the geometric median's iterate): no K10 / K11 behind it
 };
 // The two steps every fp32 fold driver takes (fold_run, slot_fold; nothing else calls them).
 // Before the launches of a fold that brings the cycle to `total` clients, on the fold's stream: the

@@ -187,6 +187,28 @@ void dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out
     }
 }
 
+bool geomed_step(const double* D, int64_t n, float nu, float* w, float* W, double* objective, float* max_w) {
+    std::vector<double> beta((size_t)n);
+    double B = 0.0, obj = 0.0;
+    for (int64_t k = 0; k < n; ++k) {
+        const double dist = std::sqrt(D[k]);
+        beta[(size_t)k] = std::isfinite(D[k]) ? 1.0 / std::max((double)nu, dist) : 0.0;
+        B = k == 0 ? beta[0] : B + beta[(size_t)k];
+        obj = k == 0 ? dist : obj + dist;
+    }
+    if (objective) *objective = obj;
+    if (!(B != 0.0)) return false;
+    float tot = 0.f, mx = 0.f;
+    for (int64_t k = 0; k < n; ++k) {
+        w[k] = (float)(beta[(size_t)k] / B);
+        tot = k == 0 ? w[0] : tot + w[k];
+        mx = k == 0 || w[k] > mx ? w[k] : mx;
+    }
+    *W = tot;
+    if (max_w) *max_w = mx;
+    return true;
+}
+
 }  // namespace pgh_detail
 
 namespace pgh_int {

@@ -1,6 +1,7 @@
 // HIP-free host code of libpygrid_hip (not installed): the non-temporal copy, the copy pool, the
 // scatter out of a landed piece, the walk over concatenated host pieces, the chunk arithmetic of ranged ingest,
-// page pre-faulting, the CPU count, the DP noise sampler's restatement.  Nothing here may include HIP.
+// page pre-faulting, the CPU count, the DP noise sampler's restatement, the geometric median's host step.
+// Nothing here may include HIP.
 #pragma once
 #include <algorithm>
 #include <condition_variable>
@@ -196,5 +197,11 @@ void dp_pair_normals(uint64_t key, uint32_t round, uint64_t pair, double* z0, do
 void dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n, double* out);
 // ((double)z * (double)C) / (double)N
 inline double dp_sigma(float z, float c, int64_t n) { return ((double)z * (double)c) / (double)n; }
+
+// One host step of the geometric median (include/pgh_api.h, "Geometric-median FedAvg"): from the squared
+// distances D[0, n) of the included rows, in fold order, the weights w[0, n), their f32 left fold *W, the
+// f64 left fold of sqrt(D) (*objective) and the largest weight (*max_w; both nullable).  False when the
+// f64 left fold of the betas is 0 (every D non-finite): w and *W are not written then.
+bool geomed_step(const double* D, int64_t n, float nu, float* w, float* W, double* objective, float* max_w);
 
 }  // namespace pgh_detail

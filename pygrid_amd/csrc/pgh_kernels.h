@@ -207,6 +207,18 @@ struct SumsqArgs {
 };
 hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s);
 
+// K12: the geometric median's squared distances (the definition is in include/pgh_api.h): K7's sum, in
+// K7's order, over x = d_c[i] + negv[i], one f32 addition per param (negv = -v: d + (-v) is d - v in
+// IEEE).  A workgroup owns one tile and DISTSQ_RC rows: the plane tile is read once per DISTSQ_RC rows,
+// not once per K7 row group.  The launch writes s.part[row * ntiles + t] and then s.sumsq[row] like K7
+// (s.sumsq is the distances' buffer here); negv holds at least p floats rounded up to 4, 16-byte aligned.
+constexpr int DISTSQ_RC = 32;
+struct DistsqArgs {
+    SumsqArgs s;
+    const float* negv;   // [p], -v
+};
+hipError_t launch_row_distsq(const DistsqArgs& a, const Rows& rows, hipStream_t s);
+
 // K10: the server optimizer's step behind a FINAL fold (the definition is in include/pgh_api.h).  The
 // fold ran with ckpt = a plane of -0.0f and out = d, so d = (-0.0f) - g, which is -g bit for bit for
 // every non-NaN g: x - y = x + (-y) in IEEE 754, so d = (-0) + (-g); a finite non-zero or infinite

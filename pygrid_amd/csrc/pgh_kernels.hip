@@ -19,6 +19,9 @@
 // K11 k_dp_noise              Gaussian noise on the clipped average behind a FINAL fold, ahead of K10:
 //       Philox4x32-10, Marsaglia's polar method, a libm-free logarithm (build-owned: pgh_set_dp_noise,
 //       DESIGN.md section 5); k_dp_normals returns the sampler's normals alone
+// K12 k_row_distsq             K7's sum over d_c[i] - v[i]: every row's squared distance to a moving point,
+//       a tile of the point held in registers over a chunk of rows (build-owned: PGH_GEOMETRIC_MEDIAN,
+//       DESIGN.md section 5)
 //
 // Design (DESIGN.md "Kernels"): every kernel is a single streaming pass over the slab held in
 // HBM, column-blocked (SlabMap in pgh_kernels.h: blocks of ld columns, each block all rows,
@@ -1274,6 +1277,68 @@ __device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const Rows ro
 __global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold(SumsqArgs a) { row_sumsq_fold<0>(a, Rows{nullptr, nullptr, a.row0}); }
 __global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold_rows(SumsqArgs a, RowTab tab) { row_sumsq_fold<1>(a, Rows{&tab}); }
 
+// K12: K7's sums over x = d_c[i] + negv[i] (one f32 addition; negv holds -v, so this is d - v), in K7's
+// order, for the geometric median's distances to a moving point.  The other way round from K7: a workgroup
+// owns one tile and a chunk of DISTSQ_RC rows.  It brings its 16 KiB of the plane into registers once
+// (16 floats per lane, plain loads: the workgroups of the other row chunks read the same tile) and streams
+// its rows past it in K7's groups of SUMSQ_RB (4 RB non-temporal loads in flight), so the plane costs
+// 1 / DISTSQ_RC of the slab's bytes instead of 1 / SUMSQ_RB.  The wave sums of every row of the chunk meet
+// in LDS behind one barrier; the tile partials go where K7's go and k_row_sumsq_fold[_rows] finishes the
+// rows.  K7's clamp and mask for the last tile (the plane is clamped the same way: it is at least p long),
+// and the last row group repeats the chunk's last row.
+template <int SRC>
+__device__ __forceinline__ void row_distsq_tile(const DistsqArgs& d, const Rows rows) {
+    __shared__ double wsum[DISTSQ_RC][4];
+    const SumsqArgs& a = d.s;
+    const int lane = threadIdx.x, wave = lane >> 6;
+    const int64_t t = blockIdx.x, base = t * SUMSQ_TILE;
+    const int r0 = (int)blockIdx.y * DISTSQ_RC;
+    const int nr = min(DISTSQ_RC, a.n_rows - r0);
+    const bool full = base + SUMSQ_TILE <= a.p;
+    const int64_t last4 = (a.p - 1) & ~int64_t(3);
+    int64_t idx[4], off[4];
+    f32x4 nv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        idx[j] = base + 4 * (lane + BLOCK * j);
+        const int64_t i = full ? idx[j] : min(idx[j], last4);
+        off[j] = a.map.at(i);
+        nv[j] = ld4<false>(d.negv + i);
+    }
+    for (int g = 0; g < nr; g += SUMSQ_RB) {  // (nr is uniform over the workgroup)
+        size_t row[SUMSQ_RB];
+#pragma unroll
+        for (int rr = 0; rr < SUMSQ_RB; ++rr) row[rr] = row_at<SRC>(rows, r0 + min(g + rr, nr - 1));
+        f32x4 v[SUMSQ_RB][4];
+#pragma unroll
+        for (int rr = 0; rr < SUMSQ_RB; ++rr)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[rr][j] = ld4<true>(a.slab + row[rr] * (size_t)a.map.ld + off[j]);
+#pragma unroll
+        for (int rr = 0; rr < SUMSQ_RB; ++rr) {
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xf = v[rr][j][e] + nv[j][e];
+                    const double x = (full || idx[j] + e < a.p) ? (double)xf : 0.0;
+                    acc = __builtin_fma(x, x, acc);
+                }
+#pragma unroll
+            for (int h = 32; h >= 1; h >>= 1) acc += __shfl_down(acc, h, 64);
+            if ((lane & 63) == 0) wsum[g + rr][wave] = acc;  // (g + rr < DISTSQ_RC: a multiple of SUMSQ_RB)
+        }
+    }
+    __syncthreads();
+    if (lane < nr)
+        a.part[row_at<SRC>(rows, r0 + lane) * (size_t)a.ntiles + (size_t)t] =
+            ((wsum[lane][0] + wsum[lane][1]) + wsum[lane][2]) + wsum[lane][3];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_row_distsq(DistsqArgs d) { row_distsq_tile<0>(d, Rows{nullptr, nullptr, d.s.row0}); }
+__global__ __launch_bounds__(BLOCK) void k_row_distsq_rows(DistsqArgs d, RowTab tab) { row_distsq_tile<1>(d, Rows{&tab}); }
+
 int cu_count() {
     static int cached[64] = {0};
     int dev = 0;
@@ -1668,6 +1733,36 @@ hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s)
         } else {
             k_row_sumsq<<<grid, BLOCK, 0, s>>>(b);
             k_row_sumsq_fold<<<(unsigned)b.n_rows, BLOCK, 0, s>>>(b);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+static_assert(DISTSQ_RC % SUMSQ_RB == 0 && DISTSQ_RC <= BLOCK, "K12's row chunk: whole row groups, one lane per row at the end");
+
+hipError_t launch_row_distsq(const DistsqArgs& d, const Rows& rows, hipStream_t s) {
+    const SumsqArgs& a = d.s;
+    const RowTab* tab = rows.tab;
+    if (!valid_rows(rows, a.n_rows, false, true) || a.p <= 0 || a.n_rows < 0 || a.map.off != 0 || !valid_map(a.map, a.p) ||
+        a.ntiles != (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE || a.ntiles > 0x7fffffff)
+        return hipErrorInvalidValue;
+    if (a.n_rows == 0) return hipSuccess;
+    if (!a.slab || !a.part || !a.sumsq || !d.negv || ((reinterpret_cast<uintptr_t>(a.slab) | reinterpret_cast<uintptr_t>(d.negv)) & 15))
+        return hipErrorInvalidValue;
+    const int max_rows = 65535 * DISTSQ_RC;  // grid rows of one launch
+    for (int done = 0; done < a.n_rows; done += max_rows) {
+        DistsqArgs b = d;
+        b.s.row0 = rows.row0 + done;
+        b.s.n_rows = std::min(max_rows, a.n_rows - done);
+        const dim3 grid((unsigned)a.ntiles, (unsigned)((b.s.n_rows + DISTSQ_RC - 1) / DISTSQ_RC));
+        if (tab) {
+            k_row_distsq_rows<<<grid, BLOCK, 0, s>>>(b, *tab);
+            k_row_sumsq_fold_rows<<<(unsigned)b.s.n_rows, BLOCK, 0, s>>>(b.s, *tab);
+        } else {
+            k_row_distsq<<<grid, BLOCK, 0, s>>>(b);
+            k_row_sumsq_fold<<<(unsigned)b.s.n_rows, BLOCK, 0, s>>>(b.s);
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

@@ -82,11 +82,11 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     a.out = fa.out ? fa.out + off : nullptr;
     // A server optimizer: the FINAL launch, unchanged, subtracts the average from -0 into the delta
     // plane, and K10 behind it on the same stream applies the step to the real ckpt / out.
-    const bool opt = c->opt.kind != PGH_OPT_NONE && (flags & pgh::FL_FINAL);
+    const bool opt = c->opt.kind != PGH_OPT_NONE && (flags & pgh::FL_FINAL) && !fa.plain;
     // Noise on the clipped close: a second tenant of that mechanism.  K11 follows the FINAL launch and noises
     // the delta plane in place ahead of K10, or, without an optimizer, reads planes of the noise state's
     // own and writes the real out.
-    const bool noise = noise_on(c) && (flags & pgh::FL_FINAL);
+    const bool noise = noise_on(c) && (flags & pgh::FL_FINAL) && !fa.plain;
     if (noise) RC(check_noise_final(c, mode));  // (the entry points have checked: nothing was launched)
     if (noise && (!fa.ckpt || !fa.out)) return fail(c, PGH_E_ARG, "a noised FINAL fold needs ckpt and out");
     if (opt) {
@@ -123,8 +123,11 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
 int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const FinalArgs& fa, hipStream_t s) {
     // (resident only, check_mode_use: the scales of clients [0, n) become the fold's weights)
     if (kind == PGH_CLIPPED_MEAN) RC(resident_clip_scales(c, n));
+    // (resident only too: the included rows and their final weights; the fold below runs over those rows)
+    const bool geomed = kind == PGH_GEOMETRIC_MEDIAN;
+    if (geomed) RC(geomed_resident_weights(c, n));
     RC(order_after_ingest(c, s));
-    if (kind != KIND_SECAGG && n > 0) RC(fold_prepare(c, kind, c0 + n, s));
+    if (kind != KIND_SECAGG && n > 0) RC(fold_prepare(c, kind, geomed ? (int64_t)c->geo.rows.size() : c0 + n, s));
     const int R = c->slots;
     FinalArgs r = fa;  // the launches' param range, its length resolved
     if (r.len < 0) r.len = c->pg - r.off;
@@ -133,7 +136,8 @@ int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const Fina
         return fail(c, PGH_E_ARG, "param range [%lld,+%lld) outside the shard or not 4-aligned", (long long)off,
                     (long long)len);
     int64_t done = 0;
-    do {
+    if (geomed) RC(geomed_fold(c, final, r, s));
+    else do {
         const int slot = (int)((c0 + done) % R);
         const int64_t seg = std::min<int64_t>(n - done, (int64_t)(R - slot));
         const bool first = (c0 + done == 0);
@@ -244,6 +248,9 @@ int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
         const float t = weight_total(c->weights, n);
         if (!(t != 0.f)) return fail(c, PGH_E_ARG, "sum of weights is zero");
         *div = t;
+    } else if (mode == PGH_GEOMETRIC_MEDIAN) {  // (resident folds; a slot close takes W from its own weights)
+        RC(geomed_resident_weights(c, n));
+        *div = c->geo.W;
     } else {
         *div = (float)n;  // th.div(sum, len(diffs)), cycle_manager.py:288
     }

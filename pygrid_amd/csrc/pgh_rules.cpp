@@ -1,7 +1,8 @@
 // libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); clipping's
 // per-row sums of squares (K7), their host cache, the scales and the tallies; the Gaussian noise on the clipped
 // close (K11 behind a FINAL launch, its planes, setting and entry points); the trimmed mean's state planes
-// (K8); the median's driver and row table (K9, K9p); and what the rules' state does at each lifecycle event of
+// (K8); the median's driver and row table (K9, K9p); the geometric median's included rows, inner iterations and
+// final weights (K12 between weighted folds); and what the rules' state does at each lifecycle event of
 // the context (rules_*: the one call each event's site makes).  The state itself: pgh_rules.h.
 // (struct pgh_ctx and the shared helpers: pgh_ctx.h)
 #include "pgh_ctx.h"
@@ -48,6 +49,14 @@ int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
         if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no median: it needs every row at once");
         if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a median needs every row at once: nothing can be folded early");
         return PGH_OK;
+    case PGH_GEOMETRIC_MEDIAN:  // every row at once like the median, the whole row of each like clipping
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no geometric median: it needs every row at once");
+        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a geometric median needs every row at once: nothing can be folded early");
+        if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts take no geometric median: the shards each hold part of a row");
+        if (c->layout && c->pg != c->P)
+            return fail(c, PGH_E_UNSUPPORTED, "a geometric median needs whole rows: the shard [%lld,%lld) is narrower than the model", (long long)c->lo, (long long)c->hi);
+        if (c->geo.iters == 0) return fail(c, PGH_E_STATE, "PGH_GEOMETRIC_MEDIAN needs its setting: call pgh_set_geomed first");
+        return PGH_OK;
     default:
         return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
     }
@@ -63,7 +72,11 @@ bool rules_made(pgh_ctx* c) {
 }
 
 void rules_slab_freed(pgh_ctx* c) {  // the streams are idle (free_slab synchronised them)
-    for (auto* v : {&c->trim.d_planes, &c->med.d_prefix, &c->med.d_rowidx, &c->clip.d_sq_part, &c->clip.d_sq}) v->reset();
+    for (auto* v : {&c->trim.d_planes, &c->med.d_prefix, &c->med.d_rowidx, &c->clip.d_sq_part, &c->clip.d_sq, &c->geo.d_nz, &c->geo.d_negv,
+                    &c->geo.d_dist})
+        v->reset();
+    c->geo.h_dist.reset();
+    c->geo.forget();
     c->clip.h_sq.reset();
     c->clip.sq_state.clear();
     c->clip.sq_host.clear();
@@ -75,6 +88,7 @@ void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep
     if (!(same && pvec == c->opt.pvec)) c->opt.release();
     if (!(same && pvec == c->noise.pvec)) c->noise.release();  // (free_slab has synchronised the streams)
     if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
+    c->geo.release();  // (free_slab has dropped the planes; the setting goes with the layout or shard)
 }
 
 void rules_reserved(pgh_ctx* c, int slots) {
@@ -82,11 +96,17 @@ void rules_reserved(pgh_ctx* c, int slots) {
     c->clip.sq_host.assign((size_t)slots, 0.0);
 }
 
-void rules_reset(pgh_ctx* c) { c->clip.forget(); }
+void rules_reset(pgh_ctx* c) {
+    c->clip.forget();
+    c->geo.forget();
+}
 
-void rules_slot_written(pgh_ctx* c, int slot, int n) { c->clip.slot_written(slot, n); }
+void rules_slot_written(pgh_ctx* c, int slot, int n) {
+    c->clip.slot_written(slot, n);
+    c->geo.weights_valid = false;
+}
 
-void rules_weights_replaced(pgh_ctx* c) { c->clip.scales_valid = false; }
+void rules_weights_replaced(pgh_ctx* c) { c->clip.scales_valid = c->geo.weights_valid = false; }
 
 void rules_folds_restarted(pgh_ctx* c) { c->clip.norms.clear(); }
 
@@ -243,7 +263,7 @@ int sumsq_wait(pgh_ctx* c) {
 }
 
 int sumsq_after_ingest(pgh_ctx* c, int slot) {
-    if (!clip_on(c)) return PGH_OK;
+    if (!norms_wanted(c)) return PGH_OK;
     const int32_t sl = slot;
     return sumsq_queue(c, &sl, 1);
 }
@@ -251,6 +271,7 @@ int sumsq_after_ingest(pgh_ctx* c, int slot) {
 int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms) {
     RC(sumsq_queue(c, slots, n));
     RC(sumsq_wait(c));
+    c->geo.weights_valid = false;  // (the context's weights become the scales)
     c->weights.resize((size_t)(c0 + n));
     if (norms) norms->resize((size_t)(c0 + n));
     for (int k = 0; k < n; ++k) {
@@ -278,6 +299,146 @@ int resident_clip_scales(pgh_ctx* c, int64_t n) {
     RC(clip_set_scales(c, slots.data(), (int)n, 0, &norms));
     c->clip.count(c->weights.data(), norms.data(), n);
     c->clip.scales_valid = true;
+    return PGH_OK;
+}
+
+// ---- geometric-median FedAvg: the included rows, K12, the inner iterations, the final weights -----------------
+
+namespace {
+// f(rows, k0, m) for each run of the listed slots a launch can take: all of them when they are consecutive,
+// else RowTabs of at most ROWTAB_MAX; k0 = the fold index of the run's first row.
+template <class F>
+int for_row_runs(pgh_ctx* c, const std::vector<int32_t>& slots, F&& f) {
+    bool run = true;
+    for (size_t k = 0; k < slots.size(); ++k) run = run && slots[k] == slots[0] + (int32_t)k;
+    if (run) return f(pgh::Rows{nullptr, nullptr, slots[0] * c->parties}, (size_t)0, slots.size());
+    for (size_t done = 0; done < slots.size(); done += pgh::ROWTAB_MAX) {
+        const size_t m = std::min(slots.size() - done, (size_t)pgh::ROWTAB_MAX);
+        pgh::RowTab tab;
+        for (size_t k = 0; k < m; ++k) tab.rows[k] = slots[done + k] * c->parties;
+        RC(f(pgh::Rows{&tab}, done, m));
+    }
+    return PGH_OK;
+}
+
+int geomed_planes(pgh_ctx* c, hipStream_t s) {
+    GeomedState& g = c->geo;
+    if (g.d_nz && g.d_negv) return PGH_OK;
+    const size_t bytes = 4 * (size_t)c->pvec;
+    if (!g.d_nz.reserve(bytes) || !g.d_negv.reserve(bytes)) {
+        g.d_nz.reset();
+        g.d_negv.reset();
+        return fail(c, PGH_E_OOM, "allocation of the geometric median's planes (%zu bytes each) failed", bytes);
+    }
+    CK(c, hipMemsetD32Async((hipDeviceptr_t)g.d_nz.as<void>(), (int)0x80000000u, (size_t)c->pvec, s));
+    // (the -0 plane is only ever read on the context's stream, behind this)
+    return hipMemsetD32Async((hipDeviceptr_t)g.d_negv.as<void>(), (int)0x80000000u, (size_t)c->pvec, s) == hipSuccess
+               ? PGH_OK
+               : fail(c, PGH_E_HIP, "hipMemsetD32Async of the iterate plane failed");
+}
+
+// K12 over the listed slots against d_negv on stream s, the D2H of the sums and the wait: D[k] = the
+// squared distance of slots[k].  (K7's tile partials are free: every queued K7 has been waited for.)
+int distsq_run(pgh_ctx* c, const std::vector<int32_t>& slots, hipStream_t s, double* D) {
+    GeomedState& g = c->geo;
+    RC(sumsq_wait(c));
+    RC(ensure_sumsq_buffers(c));
+    if (!g.d_dist.reserve(8 * (size_t)c->slots) || !g.h_dist.reserve(8 * (size_t)c->slots))
+        return fail(c, PGH_E_OOM, "allocation of the geometric median's distances (%d rows) failed", c->slots);
+    pgh::DistsqArgs a{};
+    a.s.slab = c->d_slab.as<float>();
+    a.s.map = slab_map(c);
+    a.s.p = c->pg;
+    a.s.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
+    a.s.part = c->clip.d_sq_part.as<double>();
+    a.s.sumsq = g.d_dist.as<double>();
+    a.negv = g.d_negv.as<float>();
+    // HBM bytes: the rows, the partials out and in again; the plane once per row chunk (from L2 mostly)
+    RC(for_row_runs(c, slots, [&](const pgh::Rows& rows, size_t, size_t m) {
+        a.s.n_rows = (int)m;
+        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
+        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_distsq(a, rows, s); });
+    }));
+    int32_t lo = slots[0], hi = slots[0];
+    for (int32_t sl : slots) {
+        lo = std::min(lo, sl);
+        hi = std::max(hi, sl);
+    }
+    CK(c, hipMemcpyAsync(g.h_dist.as<double>() + lo, g.d_dist.as<double>() + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
+    CK(c, hipStreamSynchronize(s));
+    for (size_t k = 0; k < slots.size(); ++k) D[k] = g.h_dist.as<double>()[slots[k]];
+    return PGH_OK;
+}
+}  // namespace
+
+int geomed_fold(pgh_ctx* c, bool final, const FinalArgs& fa, hipStream_t s) {
+    const std::vector<int32_t>& inc = c->geo.rows;
+    return for_row_runs(c, inc, [&](const pgh::Rows& rows, size_t k0, size_t m) {
+        const int flags = (k0 == 0 ? pgh::FL_FIRST : 0) | (final && k0 + m == inc.size() ? pgh::FL_FINAL : 0);
+        FoldRows fr{rows.tab ? c->d_slab.as<float>() : (const float*)slot_row(c, inc[0], 0), (int)m, rows};
+        fr.src.row0 = 0;  // (the fold takes contiguous rows from its slab pointer)
+        return fold_launch(c, PGH_GEOMETRIC_MEDIAN, fr, (int64_t)k0, flags, fa, s);
+    });
+}
+
+int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
+    GeomedState& g = c->geo;
+    g.weights_valid = false;
+    c->clip.scales_valid = false;  // (the context's weights become this rule's)
+    RC(sumsq_queue(c, slots, n));
+    RC(sumsq_wait(c));
+    std::vector<int32_t> inc;
+    std::vector<double> D;
+    for (int k = 0; k < n; ++k) {
+        const double ss = c->clip.sq_host[(size_t)slots[k]];
+        if (!std::isfinite(ss)) continue;  // excluded: no fold and no distance pass reads the row
+        inc.push_back(slots[k]);
+        D.push_back(ss);
+    }
+    if (inc.empty()) return fail(c, PGH_E_STATE, "geometric median: none of the %d diffs is finite", n);
+    const hipStream_t s = c->stream;
+    std::vector<float> w(inc.size());
+    float W = 0.f, mx = 0.f;
+    double obj = 0.0;
+    g.rows = inc;
+    for (int t = 0;; ++t) {
+        if (!geomed_step(D.data(), (int64_t)D.size(), g.nu, w.data(), &W, &obj, &mx))
+            return fail(c, PGH_E_STATE, "geometric median: no finite distance in iteration %d", t);
+        c->weights = w;
+        c->weights_on_device = false;
+        if (t == g.iters - 1) break;
+        // v^(t+1) as -v: the weighted fold against the -0 plane, whole shard; then every row's distance to it
+        if (t == 0) {
+            RC(order_after_ingest(c, s));
+            RC(geomed_planes(c, s));
+        }
+        RC(fold_prepare(c, PGH_GEOMETRIC_MEDIAN, (int64_t)inc.size(), s));
+        FinalArgs fa;
+        fa.ckpt = g.d_nz.as<float>();
+        fa.out = g.d_negv.as<float>();
+        fa.divisor = W;
+        fa.off = 0;
+        fa.len = c->pg;
+        fa.plain = true;
+        RC(geomed_fold(c, true, fa, s));
+        RC(distsq_run(c, inc, s, D.data()));
+    }
+    g.W = W;
+    g.n_rows = n;
+    g.n_excluded = n - (int64_t)inc.size();
+    g.objective = obj;
+    g.max_weight = mx;
+    return PGH_OK;
+}
+
+int geomed_resident_weights(pgh_ctx* c, int64_t n) {
+    GeomedState& g = c->geo;
+    if (g.weights_valid && g.n_valid == n && c->weights.size() == g.rows.size()) return PGH_OK;
+    std::vector<int32_t> slots((size_t)n);
+    for (int64_t k = 0; k < n; ++k) slots[(size_t)k] = (int32_t)k;
+    RC(geomed_slot_weights(c, slots.data(), (int)n));
+    g.weights_valid = true;
+    g.n_valid = n;
     return PGH_OK;
 }
 
@@ -370,6 +531,55 @@ int pgh_row_sumsq(pgh_ctx* c, const int32_t* slots, int n, double* out) {
     if (!out) return PGH_OK;
     RC(sumsq_wait(c));
     for (int k = 0; k < n; ++k) out[k] = c->clip.sq_host[(size_t)slots[k]];
+    return PGH_OK;
+}
+
+// ---- geometric-median FedAvg: the setting, K12 alone, what the last close saw ---------------------------------
+
+int pgh_set_geomed(pgh_ctx* c, int iters, float nu) {
+    if (!c) return PGH_E_ARG;
+    if (iters == 0) {  // off: always possible
+        c->geo.iters = 0;
+        c->geo.weights_valid = false;
+        return PGH_OK;
+    }
+    RC(check_clip_ctx(c, "pgh_set_geomed"));
+    if (iters < 0 || iters > PGH_GEOMED_MAX_ITERS) return fail(c, PGH_E_ARG, "geometric median: %d iterations outside [0,%d]", iters, PGH_GEOMED_MAX_ITERS);
+    if (!(nu > 0.f) || !std::isfinite(nu)) return fail(c, PGH_E_ARG, "geometric median: the smoothing must be finite and > 0");
+    if (iters != c->geo.iters || nu != c->geo.nu) c->geo.weights_valid = false;
+    c->geo.iters = iters;
+    c->geo.nu = nu;
+    return PGH_OK;
+}
+
+int pgh_row_distsq(pgh_ctx* c, const int32_t* slots, int n, const float* point, double* out) {
+    RC(check_clip_ctx(c, "pgh_row_distsq"));
+    RC(check_dtype(c, PGH_F32));
+    if (n < 0 || (n > 0 && (!slots || !point || !out))) return fail(c, PGH_E_ARG, "bad slot list, point or out (n=%d)", n);
+    for (int k = 0; k < n; ++k) {
+        if (slots[k] < 0 || slots[k] >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", slots[k], c->slots);
+        if (c->slot_client[(size_t)slots[k]] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", slots[k]);
+    }
+    if (n == 0) return PGH_OK;
+    DeviceGuard g(c->device);
+    const hipStream_t s = c->stream;
+    RC(order_after_ingest(c, s));
+    RC(geomed_planes(c, s));
+    std::vector<float> neg((size_t)c->pg);
+    for (int64_t i = 0; i < c->pg; ++i) neg[(size_t)i] = -point[i];
+    CK(c, hipMemcpyAsync(c->geo.d_negv.as<float>(), neg.data(), 4 * (size_t)c->pg, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // neg is pageable: the copy has left it
+    return distsq_run(c, std::vector<int32_t>(slots, slots + n), s, out);
+}
+
+int pgh_geomed_stats(pgh_ctx* c, int* iters, int64_t* n_rows, int64_t* n_excluded, double* objective, float* max_weight) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_geomed_stats: group contexts take no geometric median");
+    if (iters) *iters = c->geo.iters;
+    if (n_rows) *n_rows = c->geo.n_rows;
+    if (n_excluded) *n_excluded = c->geo.n_excluded;
+    if (objective) *objective = c->geo.objective;
+    if (max_weight) *max_weight = c->geo.max_weight;
     return PGH_OK;
 }
 

@@ -1,6 +1,6 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, trim, med and opt.  Their owners release with the context.
-// The code that works on them: pgh_rules.cpp (clip, trim, med and the lifecycle calls rules_*),
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trim, med and opt.  Their owners release with the context.
+// The code that works on them: pgh_rules.cpp (clip, geo, trim, med and the lifecycle calls rules_*),
 // pgh_serveropt.cpp (opt).  Not installed.
 #pragma once
 #include <algorithm>
@@ -69,6 +69,46 @@ struct NoiseState {
         d_d.reset();
         z = 0.f;
         pvec = 0;
+    }
+};
+
+// Geometric-median FedAvg (pgh_set_geomed, PGH_GEOMETRIC_MEDIAN): the smoothed
+// Weiszfeld iteration.  With the rule on every ingest queues K7 like clipping (the cached sums are iteration
+// 0's squared distances and say which rows are excluded).  A close computes the final weights on the
+// context's stream -- per inner iteration a weighted fold against the -0 plane into d_negv (= -v), K12
+// against it, a D2H of the distances, the host step -- and leaves them in the context's `weights` (fold
+// order of the included rows) for the one FINAL fold, which is the weighted fold over `rows`.  Both planes
+// are float [pvec], allocated by the first close that iterates (iters >= 2) or by pgh_row_distsq.
+struct GeomedState {
+    int iters = 0;                  // 0 = the rule is off
+    float nu = 0.f;
+    std::vector<int32_t> rows;      // the included slots, in fold order
+    float W = 0.f;                  // the f32 left fold of the final weights
+    // Resident folds: weights[0, rows.size()) are the final weights of the slab as it is, computed for
+    // clients [0, n_valid) -- range folds and repeated closes reuse them.
+    bool weights_valid = false;
+    int64_t n_valid = 0;
+    DeviceBuf d_nz, d_negv;         // -0.0f everywhere; -v of the last inner iteration (or -point)
+    DeviceBuf d_dist;               // double [slots]: K12's sums, by slab row
+    PinnedBuf h_dist;               // double [slots]
+    // what the last computation of the weights saw (pgh_geomed_stats)
+    int64_t n_rows = 0, n_excluded = 0;
+    double objective = 0.0;
+    float max_weight = 0.f;
+
+    void forget() {  // the weights and the tallies (pgh_reset); the setting stays
+        weights_valid = false;
+        rows.clear();
+        n_rows = n_excluded = 0;
+        objective = 0.0;
+        max_weight = 0.f;
+    }
+    void release() {  // planes and setting; the caller has waited for the context's work
+        d_nz.reset();
+        d_negv.reset();
+        iters = 0;
+        nu = 0.f;
+        forget();
     }
 };
 

@@ -27,6 +27,10 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     const bool median = mode == PGH_MEDIAN;  // every row of the cycle in this one call (check_mode_use: final)
     if (median && c->folded > 0)
         return fail(c, PGH_E_STATE, "a median closes a cycle without earlier slot folds (%lld diffs folded)", (long long)c->folded);
+    // a geometric median too: the weights need every row (check_mode_use: final)
+    const bool geomed = mode == PGH_GEOMETRIC_MEDIAN;
+    if (geomed && c->folded > 0)
+        return fail(c, PGH_E_STATE, "a geometric median closes a cycle without earlier slot folds (%lld diffs folded)", (long long)c->folded);
     const int64_t c0 = c->folded, total = c0 + n;
     FinalArgs fa;
     fa.ckpt = c->d_ckpt.as<float>();
@@ -34,7 +38,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     if (final) {
         RC(check_ckpt(c, "pgh_fold_slots_finish_resident"));
         if (total == 0) return fail(c, PGH_E_STATE, "no diffs folded");
-        RC(fedavg_divisor(c, mode, total, &fa.divisor));
+        if (!geomed) RC(fedavg_divisor(c, mode, total, &fa.divisor));
     } else if (n == 0) {
         return PGH_OK;
     }
@@ -44,11 +48,22 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     // chunk of the last report it reads instead of after the whole copy stream
     // (never a clipped pass: a scale needs the last report's whole row, so it takes the whole-stream wait)
     const bool clipped = mode == PGH_CLIPPED_MEAN;
-    const bool ranged = final && !clipped && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && c->ranged.valid(c->pg);
+    const bool ranged = final && !clipped && !geomed && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && c->ranged.valid(c->pg);
     if (clipped && n > 0) RC(clip_slot_scales(c, slots, n, c0));  // the sums still missing in one batch, then the scales in fold order
+    // the included rows and their final weights (the inner iterations are finished on return); the fold
+    // below runs over the included rows alone, fold client k = the k-th of them
+    const int32_t* const all_slots = slots;
+    const int n_all = n;
+    if (geomed) {
+        RC(geomed_slot_weights(c, slots, n));
+        fa.divisor = c->geo.W;
+        slots = c->geo.rows.data();
+        n = (int)c->geo.rows.size();
+    }
+    const int64_t nfold = geomed ? (int64_t)n : total;
     if (!ranged) RC(order_after_ingest(c, s));
     else if (hipEvent_t dec = c->vdec.last_decode()) CK(c, hipStreamWaitEvent(s, dec, 0));  // the copy stream: per range below
-    if (n > 0) RC(fold_prepare(c, mode, total, s));
+    if (n > 0) RC(fold_prepare(c, mode, nfold, s));
     if (median && n > pgh::ROWTAB_MAX) RC(median_row_table(c, slots, n, s));  // more rows than a RowTab carries
     int done = 0;
     bool prequeued = false;
@@ -97,8 +112,8 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         done += m;
     } while (done < n);
     RC(record_fold(c, c->fold_evs, s));
-    RC(record_slot_fold(c, slots, n));
-    for (int k = 0; k < n; ++k) c->slot_client[(size_t)slots[k]] = -1;  // free for the next ingests
+    RC(record_slot_fold(c, all_slots, n_all));
+    for (int k = 0; k < n_all; ++k) c->slot_client[(size_t)all_slots[k]] = -1;  // free for the next ingests
     c->folded = total;
     c->st.n_folded = total;
     c->slot_mode = mode;

@@ -184,14 +184,15 @@ def cached_mode(server_config: dict, plan_key, mean_plans: Optional[str] = None)
 
 def select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
                 mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None,
-                trim_count=None, median: bool = False) -> int:
-    """The dispatch rule below; under a rule (``robust.rule_of`` of ``clip_norm``, ``trim_count`` and
-    ``median``, parsed values; ``server_config``'s own keys are not read): the rule's mode --
-    ``CLIPPED_MEAN``, ``TRIMMED_MEAN``, ``MEDIAN`` -- exactly where the dispatch gives ``MEAN`` (no
+                trim_count=None, median: bool = False, geometric_median=None) -> int:
+    """The dispatch rule below; under a rule (``robust.rule_of`` of ``clip_norm``, ``trim_count``,
+    ``median`` and ``geometric_median``, parsed values; ``server_config``'s own keys are not read): the rule's
+    mode -- ``CLIPPED_MEAN``, ``TRIMMED_MEAN``, ``MEDIAN``, ``GEOMETRIC_MEDIAN`` -- exactly where the dispatch gives ``MEAN`` (no
     hosted plan, or a plan probed equal to the mean) and the rule's error everywhere else -- weights,
     the iterative plan, a plan the engine declines -- so that the caller cannot fall back to an
     average that does not apply the rule."""
-    rule = rule_of(server_config, clip_norm=clip_norm, trim_count=trim_count, median=median)
+    rule = rule_of(server_config, clip_norm=clip_norm, trim_count=trim_count, median=median,
+                   geometric_median=geometric_median)
     if rule is None:
         return _select_mode(server_config, avg_plan, weights, plan_key, mean_plans, shapes, n_clients)
     if weights is not None:
@@ -327,7 +328,7 @@ class CycleAggregator:
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
                            plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
-                           dp_noise=UNSET, dp_round=None) -> bytes:
+                           dp_noise=UNSET, dp_round=None, geometric_median=UNSET) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -342,7 +343,7 @@ class CycleAggregator:
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        given = (clip_norm, trim_count, median, dp_noise)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median)
         with self._closing(server_config, given, avg_plan, weights, plan_key, lambda: _shapes_or_none(checkpoint),
                            lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round) as (settings, mode):
             return self._average_plan_diffs(checkpoint, diffs, weights, framing, settings, mode)
@@ -351,8 +352,9 @@ class CycleAggregator:
     def _closing(self, server_config, given, avg_plan, weights, plan_key, shapes, numel_of, n_diffs, opt_key, dp_round):
         """What both entry points do before their first ingest, and the fail-closed block they fold in:
         gives ``(settings, mode)`` with the engine laid out for ``numel_of()`` and ``n_diffs`` rows, the rule and the
-        noise set and ``opt_key``'s moments bound.  ``given``: the caller's clip_norm, trim_count, median, dp_noise."""
-        settings = settings_of(server_config, *given)
+        noise set and ``opt_key``'s moments bound.  ``given``: the caller's clip_norm, trim_count, median, dp_noise,
+        geometric_median."""
+        settings = settings_of(server_config, *given[:4], geometric_median=given[4])
         with settings.fail_closed("the engine cannot average this cycle"):
             mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                                shapes=shapes, n_clients=n_diffs, **settings.rule_kwargs())
@@ -394,12 +396,12 @@ class CycleAggregator:
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
                        weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
-                       dp_noise=UNSET, dp_round=None) -> List[np.ndarray]:
+                       dp_noise=UNSET, dp_round=None, geometric_median=UNSET) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         shapes = [np.shape(p) for p in model_params]
         numel = [int(np.prod(s)) for s in shapes]
-        given = (clip_norm, trim_count, median, dp_noise)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median)
         with self._closing(server_config, given, avg_plan, weights, None, shapes, lambda: numel, len(diffs), opt_key,
                            dp_round) as (settings, mode):
             for i, d in enumerate(diffs):

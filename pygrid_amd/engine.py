@@ -15,7 +15,8 @@ import numpy as np
 from . import _lib
 from .exceptions import AggregationError, EngineUnavailableError, StateParseError
 
-MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN = 0, 1, 2, 3, 4, 5
+MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN, GEOMETRIC_MEDIAN = 0, 1, 2, 3, 4, 5, 6
+GEOMED_MAX_ITERS = 16  # PGH_GEOMED_MAX_ITERS
 TRIM_MAX = 8  # PGH_TRIM_MAX
 MEDIAN_NCHIP = 1024  # PGH_MEDIAN_NCHIP: rows the on-chip median kernel takes
 STREAM_SECAGG = 16
@@ -23,7 +24,8 @@ DEFAULT_VARIANT = -1  # PGH_DEFAULT_VARIANT: auto by shard size
 F32, I64 = 0, 1
 OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4  # pgh_server_opt
 MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
-              CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean", MEDIAN: "median"}
+              CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean", MEDIAN: "median",
+              GEOMETRIC_MEDIAN: "geometric_median"}
 
 
 def device_count() -> int:
@@ -344,6 +346,37 @@ class Engine:
         z, s, n = C.c_float(0), C.c_double(0), C.c_int64(0)
         self._check(self._lib.pgh_dp_stats(self._h, C.byref(z), C.byref(s), C.byref(n)), "dp_stats")
         return {"multiplier": z.value, "sigma": s.value, "n": n.value}
+
+    # ---- geometric median (GEOMETRIC_MEDIAN, RFA; kernel K12) ---------------------------------------
+    def set_geomed(self, iters: int = 3, nu: float = 1e-6):
+        """Smoothed Weiszfeld steps (1 .. GEOMED_MAX_ITERS) and smoothing (finite, > 0) of later
+        GEOMETRIC_MEDIAN closes (``include/pgh_api.h``); ``iters=0`` turns the rule off.  With it on every
+        ingest queues the row's norm pass.  Refused (PGH_E_UNSUPPORTED) where ``set_clip_norm`` is; a new
+        layout or shard clears it."""
+        self._check(self._lib.pgh_set_geomed(self._h, int(iters), C.c_float(float(nu))), "set_geomed")
+
+    def row_distsq(self, slots: Sequence[int], point) -> np.ndarray:
+        """float64 squared distances of the diffs in ``slots`` to ``point`` (P floats): K12 alone, in the
+        order of ``row_sumsq`` (tests, debugging)."""
+        a = np.ascontiguousarray(slots, dtype=np.int32)
+        pt = np.ascontiguousarray(point, dtype=np.float32).reshape(-1)
+        if pt.size != self.P:
+            raise AggregationError(f"row_distsq: the point has {pt.size} values, the model {self.P}")
+        out = np.empty(a.size, dtype=np.float64)
+        self._check(self._lib.pgh_row_distsq(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
+                                             pt.ctypes.data_as(C.POINTER(C.c_float)),
+                                             out.ctypes.data_as(C.POINTER(C.c_double))), "row_distsq")
+        return out
+
+    def geomed_stats(self) -> dict:
+        """``iterations`` (0: off) and what the last GEOMETRIC_MEDIAN close saw: ``rows``, ``excluded``
+        (non-finite rows left out), ``objective`` (the sum of distances in its last iteration) and
+        ``max_weight``."""
+        it, n, x, o, m = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_double(0), C.c_float(0)
+        self._check(self._lib.pgh_geomed_stats(self._h, C.byref(it), C.byref(n), C.byref(x), C.byref(o), C.byref(m)),
+                    "geomed_stats")
+        return {"iterations": it.value, "rows": n.value, "excluded": x.value, "objective": o.value,
+                "max_weight": m.value}
 
     # ---- coordinate-wise trimmed mean (TRIMMED_MEAN) ----------------------------------------------
     def set_trim(self, b: int):

@@ -60,6 +60,15 @@ class MedianUnavailableError(AggregationError):
     no median, so the close fails closed."""
 
 
+class GeometricMedianUnavailableError(AggregationError):
+    """The FL process asks for the geometric median (``server_config["diff_geometric_median"]``) and the
+    engine cannot take it this cycle: a hosted iterative or unaccelerated plan, a non-float32 model,
+    aggregation weights or another rule given together with it, a multi-GPU group or a sub-range shard
+    (the distances need whole rows), more diffs at the close than the slab has slots, or no finite diff
+    at all.  Like the other rules' errors it is NOT a ``PlanNotAcceleratedError``: the node's own
+    averaging takes no geometric median, so the close fails closed."""
+
+
 class ServerOptUnavailableError(AggregationError):
     """The FL process asks for a server optimizer (``server_config["server_optimizer"]``) and the
     engine cannot apply it this cycle: it declines the cycle (an unaccelerated plan, a non-float32

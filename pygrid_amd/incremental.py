@@ -87,9 +87,16 @@ class IncrementalCycle:
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
                  median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
-                 dp_keys=None, settings: Optional[CloseSettings] = None):
+                 dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None):
         """``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
-        ``median``, ``server_opt`` and ``dp_noise`` below (both: an error); keys, round and stores go beside either.
+        ``median``, ``geometric_median``, ``server_opt`` and ``dp_noise`` below (both: an error); keys, round and
+        stores go beside either.
+
+        ``geometric_median``: the FL process asks for the geometric median (``robust.geomed_of``: ``True``, the
+        setting's dict or its parsed pair).  Wired like the median -- ``mode`` MEAN, no weights, no other rule,
+        nothing folded early, one GEOMETRIC_MEDIAN finish over every held slot in the close's order, at most as
+        many diffs as slots -- with ``GeometricMedianUnavailableError`` where the median raises its own.  Each
+        diff's norm pass is queued right behind its ingest, as under ``clip_norm``.
 
         ``dp_noise``: the FL process's noise setting (``dp.dp_noise_of``; it needs ``clip_norm``), drawn for
         ``dp_round`` (the cycle's id) from the key it names or ``opt_key``'s in ``dp_keys`` (share the
@@ -123,16 +130,20 @@ class IncrementalCycle:
         self.engine = engine
         self.mode = mode
         given = {k: v for k, v in dict(clip_norm=clip_norm, trim_count=trim_count, median=bool(median) or None,
-                                       server_opt=server_opt, dp_noise=dp_noise).items() if v is not None}
+                                       server_opt=server_opt, dp_noise=dp_noise,
+                                       geometric_median=None if geometric_median is False else geometric_median
+                                       ).items() if v is not None}
         if settings is not None and given:
             raise AggregationError(f"settings= was given beside {', '.join(given)}")
         self._settings = settings = settings if settings is not None else settings_of({}, **given)
         self._rule = rule = settings.rule
         if rule is not None and (mode != MEAN or weights_by_worker is not None):
             raise rule.refuse("applies to the plain mean only (no weights, no iterative plan)")
-        self.clip_norm, self.trim_count, self.median = None, None, False
+        self.clip_norm, self.trim_count, self.median, self.geometric_median = None, None, False, None
         if rule is not None:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
+        # a rule that needs every row of the cycle in one call: nothing folds early, no partial fold at the close
+        self._whole = bool(self.median) or self.geometric_median is not None
         self._fold_mode = rule.mode if rule else mode
         self._noise_args = (settings.noise_key(dp_keys if dp_keys is not None else dp.DpKeys(), opt_key), dp_round)
         self._opt_key = opt_key
@@ -145,7 +156,7 @@ class IncrementalCycle:
         if self.slots < 2:
             raise AggregationError("report-time aggregation needs at least 2 HBM slots")
         self.fold_batch = max(1, int(fold_batch))
-        self.early_fold = bool(early_fold) and not self.median
+        self.early_fold = bool(early_fold) and not self._whole
         self._seq = itertools.count()
         self._order: List[object] = []      # assigned workers, sorted by assignment key
         self._keys: List[tuple] = []        # their keys (sorted, parallel to _order)
@@ -285,7 +296,7 @@ class IncrementalCycle:
             self._queue_norm(self._slot_of[worker])
             return
         # a diff that cannot fold yet leaves one slot free for the fold front
-        if self._free and (self.median or len(self._free) > 1 or self._is_front(worker)):
+        if self._free and (self._whole or len(self._free) > 1 or self._is_front(worker)):
             self._to_hbm(worker, diff)  # raises StateParseError on a malformed diff: nothing recorded
             self._parked.pop(worker, None)
         else:
@@ -433,9 +444,9 @@ class IncrementalCycle:
                 raise AggregationError("no diffs to average")
             if self.trim_count is not None:
                 check_trim_count(self.trim_count, len(order))
-            if self.median and len(order) > self.slots:  # every row at once: no partial fold, no slot given up
+            if self._whole and len(order) > self.slots:  # every row at once: no partial fold, no slot given up
                 raise self._rule.refuse(f"is set and the cycle has {len(order)} diffs, the slab {self.slots} slots: a "
-                                        "median needs every diff in HBM at once")
+                                        f"{'median' if self.median else 'geometric median'} needs every diff in HBM at once")
             if self._weights_by_worker is not None:
                 missing = [w for w in order if w not in self._weights_by_worker]
                 if missing:
@@ -561,7 +572,7 @@ class IncrementalCycle:
                     diff = fetch(w)
             else:
                 from_host += 1
-            if not free and self.median:  # (seal refused a close with more diffs than slots)
+            if not free and self._whole:  # (seal refused a close with more diffs than slots)
                 raise self._rule.refuse("is set and no slot is free for a diff of the close")
             if not free:
                 if batch:

@@ -1,6 +1,6 @@
 """The robust-aggregation rules an FL process can ask for in its ``server_config`` -- per-client L2
-clipping, the coordinate-wise trimmed mean, the coordinate-wise median (none has a reference
-counterpart) -- and what the host layer does with them, once:
+clipping, the coordinate-wise trimmed mean, the coordinate-wise median, the geometric median (none has a
+reference counterpart) -- and what the host layer does with them, once:
 
 * ``KINDS`` is the only place that ties a rule to its config key, the engine mode it turns ``MEAN``
   into, its error class and its engine setter.  A new defence is a new row (and a new class in
@@ -23,9 +23,9 @@ from typing import Optional
 
 import numpy as np
 
-from .engine import CLIPPED_MEAN, MEDIAN, TRIMMED_MEAN, TRIM_MAX
-from .exceptions import AggregationError, ClipUnavailableError, MedianUnavailableError, PlanNotAcceleratedError, \
-    TrimUnavailableError
+from .engine import CLIPPED_MEAN, GEOMED_MAX_ITERS, GEOMETRIC_MEDIAN, MEDIAN, TRIMMED_MEAN, TRIM_MAX
+from .exceptions import AggregationError, ClipUnavailableError, GeometricMedianUnavailableError, \
+    MedianUnavailableError, PlanNotAcceleratedError, TrimUnavailableError
 
 CLIP_KEY = "diff_clip_norm"  # optional server_config key: the per-client L2 bound (no reference counterpart)
 
@@ -91,6 +91,46 @@ def median_of(server_config: dict) -> bool:
     raise AggregationError(f"{MEDIAN_KEY} must be True or False, not {m!r}")
 
 
+GEOMED_KEY = "diff_geometric_median"  # optional server_config key: the geometric median, RFA (no reference counterpart)
+GEOMED_DEFAULTS = (3, 1e-6)  # (iterations, smoothing): the RFA paper's
+_GEOMED_FIELDS = ("iterations", "smoothing")
+
+
+def geomed_of(server_config: dict) -> Optional[tuple]:
+    """The FL process's geometric-median setting, ``server_config["diff_geometric_median"]``, as
+    ``(iterations, smoothing)``: ``True`` gives the defaults (3, 1e-6); a dict may set ``"iterations"``
+    (an int in 1 .. 16) and ``"smoothing"`` (a finite float32 > 0), either optional.  Absent, ``None`` or
+    ``False``: None (off).  Anything else -- another type, an unknown dict key, a bool where a number
+    belongs, a float with a fraction for the iterations, a value out of range -- raises
+    ``AggregationError``: a mistyped setting must not quietly mean "the plain mean"."""
+    g = server_config.get(GEOMED_KEY, None)
+    if g is None or (isinstance(g, (bool, np.bool_)) and not g):
+        return None
+    if isinstance(g, (bool, np.bool_)):
+        return GEOMED_DEFAULTS
+    if not isinstance(g, dict):
+        raise AggregationError(f"{GEOMED_KEY} must be True, False or a dict of {_GEOMED_FIELDS}, not {g!r}")
+    unknown = [k for k in g if k not in _GEOMED_FIELDS]
+    if unknown:
+        raise AggregationError(f"{GEOMED_KEY} has unknown keys {unknown!r} (known: {_GEOMED_FIELDS})")
+    it, nu = g.get("iterations", GEOMED_DEFAULTS[0]), g.get("smoothing", GEOMED_DEFAULTS[1])
+    bad_it = AggregationError(f"{GEOMED_KEY}['iterations'] must be an integer in 1..{GEOMED_MAX_ITERS}, not {it!r}")
+    if isinstance(it, (bool, np.bool_)) or not isinstance(it, (int, float, np.integer, np.floating)):
+        raise bad_it
+    if isinstance(it, (float, np.floating)) and not (np.isfinite(it) and float(it) == int(it)):
+        raise bad_it
+    if not 1 <= int(it) <= GEOMED_MAX_ITERS:
+        raise bad_it
+    if isinstance(nu, (bool, np.bool_)) or not isinstance(nu, (int, float, np.integer, np.floating)):
+        raise AggregationError(f"{GEOMED_KEY}['smoothing'] must be a finite float32 > 0, not {nu!r}")
+    nu = float(nu)
+    with np.errstate(over="ignore", under="ignore"):
+        nu32 = np.float32(nu)  # the engine takes the smoothing as a float32
+    if not np.isfinite(nu) or nu <= 0 or not np.isfinite(nu32) or nu32 <= 0:
+        raise AggregationError(f"{GEOMED_KEY}['smoothing'] must be a finite float32 > 0, not {nu!r}")
+    return (int(it), nu)
+
+
 @dataclasses.dataclass(frozen=True)
 class Rule:
     """One kind of robust aggregation (a row of ``KINDS``) or, with ``value``, a cycle's active rule."""
@@ -99,7 +139,8 @@ class Rule:
     mode: int     # the engine mode the rule turns MEAN into
     error: type   # raised wherever the engine cannot apply the rule to a cycle
     lacks: str    # what the node's own averaging, the fall-back a rule forbids, lacks
-    setter: Optional[str] = None  # the Engine method that takes the value (None: the mode alone carries the rule)
+    # the Engine method that takes the value -- a tuple: its arguments -- (None: the mode alone carries the rule)
+    setter: Optional[str] = None
     off: object = None            # what that method takes for "no rule"
     value: object = None          # the parsed setting
 
@@ -110,6 +151,8 @@ class Rule:
 
 # in order of precedence: of two rules set together the earlier one refuses the combination
 KINDS = (
+    Rule(GEOMED_KEY, "geometric_median", GEOMETRIC_MEDIAN, GeometricMedianUnavailableError, "takes no geometric median",
+         "set_geomed", (0, GEOMED_DEFAULTS[1])),
     Rule(MEDIAN_KEY, "median", MEDIAN, MedianUnavailableError, "takes no median"),
     Rule(TRIM_KEY, "trim_count", TRIMMED_MEAN, TrimUnavailableError, "does not trim", "set_trim", 0),
     Rule(CLIP_KEY, "clip_norm", CLIPPED_MEAN, ClipUnavailableError, "does not clip", "set_clip_norm", 0.0),
@@ -118,13 +161,16 @@ KINDS = (
 UNSET = object()  # an argument left out: the setting comes from server_config
 
 
-def rule_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET) -> Optional[Rule]:
+def rule_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, geometric_median=UNSET) -> Optional[Rule]:
     """The cycle's rule, or None.  An argument that is given overrides its ``server_config`` key
     (``None``: off).  Every setting is parsed, so a malformed one raises ``AggregationError`` even
     beside a rule that would win; two valid ones raise the error of the rule earlier in ``KINDS``."""
-    given = {CLIP_KEY: clip_norm, TRIM_KEY: trim_count, MEDIAN_KEY: median}
+    if isinstance(geometric_median, tuple):  # the parsed form (a Rule's value) back as the setting
+        geometric_median = dict(zip(_GEOMED_FIELDS, geometric_median))
+    given = {CLIP_KEY: clip_norm, TRIM_KEY: trim_count, MEDIAN_KEY: median, GEOMED_KEY: geometric_median}
     cfg = {k: server_config.get(k, None) if v is UNSET else v for k, v in given.items()}
-    values = {CLIP_KEY: clip_norm_of(cfg), TRIM_KEY: trim_count_of(cfg), MEDIAN_KEY: median_of(cfg) or None}
+    values = {CLIP_KEY: clip_norm_of(cfg), TRIM_KEY: trim_count_of(cfg), MEDIAN_KEY: median_of(cfg) or None,
+              GEOMED_KEY: geomed_of(cfg)}
     active = [dataclasses.replace(k, value=values[k.key]) for k in KINDS if values[k.key] is not None]
     if len(active) > 1:
         raise active[0].refuse(f"cannot be combined with {active[1].key}")
@@ -149,15 +195,18 @@ def set_on_engine(engine, rule: Optional[Rule]):
     shared across FL processes never carries one over.  An engine without a setter that the cycle
     does not need is left alone; one that lacks the setter the cycle needs, or answers it with
     PGH_E_UNSUPPORTED (a multi-GPU group, a sub-range shard), fails the cycle with the rule's error."""
+    def args(v):
+        return v if isinstance(v, tuple) else (v,)
+
     for kind in reversed(KINDS):  # the bound first, then the trim count, as engines have always been called
         if kind.setter is None:
             continue
         if rule is None or rule.key != kind.key:
             if hasattr(engine, kind.setter):
-                getattr(engine, kind.setter)(kind.off)
+                getattr(engine, kind.setter)(*args(kind.off))
             continue
         try:
-            getattr(engine, kind.setter)(rule.value)
+            getattr(engine, kind.setter)(*args(rule.value))
         except AttributeError as e:
             raise rule.refuse(f"is set but the engine has no {kind.setter}") from e
         except AggregationError as e:

@@ -17,7 +17,7 @@ from . import dp, robust
 from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
 from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, PlanNotAcceleratedError, \
     ServerOptUnavailableError
-from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
+from .robust import CLIP_KEY, GEOMED_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
 
 
@@ -90,27 +90,37 @@ class CloseSettings:
         was reset when the cycle took it: the clip counters are this cycle's rows only; ``noise_std`` is z C / N)."""
         cs = engine.clip_stats() if self._value(CLIP_KEY) is not None else None
         ns = engine.dp_stats() if self.noise is not None else None
-        return {"clipped": int(cs["clipped"]) if cs else 0, "max_norm": float(cs["max_norm"]) if cs else None,
-                "trim": self._value(TRIM_KEY), "median": self._value(MEDIAN_KEY, False),
-                "noise_multiplier": float(ns["multiplier"]) if ns else None,
-                "noise_std": float(ns["sigma"]) if ns else None}
+        stats = {"clipped": int(cs["clipped"]) if cs else 0, "max_norm": float(cs["max_norm"]) if cs else None,
+                 "trim": self._value(TRIM_KEY), "median": self._value(MEDIAN_KEY, False),
+                 "noise_multiplier": float(ns["multiplier"]) if ns else None,
+                 "noise_std": float(ns["sigma"]) if ns else None}
+        if self._value(GEOMED_KEY) is not None:  # one more key, under this rule alone
+            gs = engine.geomed_stats()
+            stats["geometric_median"] = {"iterations": int(gs["iterations"]), "excluded": int(gs["excluded"]),
+                                         "objective": float(gs["objective"]), "max_weight": float(gs["max_weight"])}
+        return stats
 
     def close_message(self, cycle_id, last_close: dict) -> str:
         """One log line on a close under a rule, from its ``last_close``."""
         noised = "" if self.noise is None else "; %s multiplier %s, noise std %s per parameter" % (
             DP_KEY, last_close.get("noise_multiplier"), last_close.get("noise_std"))
+        gm = last_close.get("geometric_median")
+        if gm is not None:
+            return "cycle %s closed with %s=%r over %d diffs (%d excluded, sum of distances %s, largest weight %s)" % (
+                cycle_id, self.rule.key, self.rule.value, last_close.get("n", 0), gm["excluded"], gm["objective"],
+                gm["max_weight"])
         return "cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)%s" % (
             cycle_id, self.rule.key, self.rule.value, last_close.get("n", 0), last_close.get("clipped", 0),
             last_close.get("max_norm"), noised)
 
 
 def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
-                server_opt=UNSET) -> CloseSettings:
+                server_opt=UNSET, geometric_median=UNSET) -> CloseSettings:
     """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
     ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
     malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
     the earlier rule's error (``robust.KINDS``), noise without the clip bound ``DpNoiseUnavailableError``."""
-    rule = rule_of(server_config, clip_norm, trim_count, median)
+    rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median)
     if not isinstance(server_opt, ServerOptSpec):
         server_opt = server_opt_of(server_config if server_opt is UNSET else {OPT_KEY: server_opt})
     noise = dp_noise_of(server_config, dp_noise)
