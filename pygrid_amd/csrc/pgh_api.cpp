@@ -92,7 +92,8 @@ static void sync_work(pgh_ctx* c) {
 
 void free_slab(pgh_ctx* c) {
     sync_work(c);
-    for (auto* v : {&c->d_slab, &c->d_ckpt, &c->d_out, &c->d_acc, &c->d_uacc, &c->d_sum, &c->d_dec, &c->d_w}) v->reset();
+    for (auto* v : {&c->d_slab, &c->d_ckpt, &c->d_out, &c->d_acc, &c->d_uacc, &c->d_sum, &c->d_dec}) v->reset();
+    c->fw.slab_freed();
     c->ckpt_valid = false;
     clear_final_marks(c);
     rules_slab_freed(c);
@@ -106,7 +107,6 @@ void free_slab(pgh_ctx* c) {
     c->fold_evs.clear();
     release_slot_fold_events(c);
     c->slot_read_seq.clear();
-    c->weights_on_device = false;
 }
 
 int check_ready(pgh_ctx* c) {
@@ -119,6 +119,19 @@ int check_ready(pgh_ctx* c) {
 int check_dtype(pgh_ctx* c, int dtype) {
     RC(check_ready(c));
     if (c->dtype != dtype) return fail(c, PGH_E_STATE, "slab holds dtype %d, call needs %d", c->dtype, dtype);
+    return PGH_OK;
+}
+
+int check_slot_list(pgh_ctx* c, const int32_t* slots, int n, bool no_twice) {
+    std::vector<char> seen(no_twice ? (size_t)c->slots : 0, 0);
+    for (int k = 0; k < n; ++k) {
+        const int32_t sl = slots[k];
+        if (sl < 0 || sl >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", sl, c->slots);
+        if (c->slot_client[(size_t)sl] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", sl);
+        if (!no_twice) continue;
+        if (seen[(size_t)sl]) return fail(c, PGH_E_ARG, "slot %d listed twice", sl);
+        seen[(size_t)sl] = 1;
+    }
     return PGH_OK;
 }
 
@@ -340,8 +353,7 @@ int pgh_reserve(pgh_ctx* c, int max_clients, int dtype, int n_parties) {
     c->slot_client.assign((size_t)max_clients, -1);
     c->slot_read_seq.assign((size_t)max_clients, 0);
     rules_reserved(c, max_clients);
-    c->weights.clear();
-    c->weights_on_device = false;
+    c->fw.clear();
     c->st.max_clients = max_clients;
     c->st.n_clients = 0;
     c->st.n_folded = 0;
@@ -360,8 +372,7 @@ int pgh_reset(pgh_ctx* c) {
     release_slot_fold_events(c);  // c->stream is idle (synchronised above)
     std::fill(c->slot_client.begin(), c->slot_client.end(), -1);
     rules_reset(c);
-    c->weights.clear();
-    c->weights_on_device = false;
+    c->fw.clear();
     c->streaming = false;
     c->slot_mode = -1;
     c->folded = 0;

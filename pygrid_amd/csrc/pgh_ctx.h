@@ -9,19 +9,23 @@
 //                   the transfer owners.  Their state: pgh_xfer.h
 //   pgh_order.cpp   which stream waits for what, and the timing events
 //   pgh_ingest.cpp  host bytes -> HBM slab rows (raw, State messages, int64 shares, synthetic)
-//   pgh_reduce.cpp  the one fp32 fold launch (fold_prepare, fold_launch); fold_run's ring walk and the share
-//                   sum; the divisors; RESIDENT and STREAM entry points, the resident checkpoint
-//   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: clipping (K7's sums,
-//                   the scales, the tallies) and the Gaussian noise on the clipped close (K11 behind a FINAL launch),
-//                   trimming (K8's planes), the median (K9, K9p), the geometric median (its weights, K12); the rules' lifecycle
-//                   calls (rules_*) and entry points.  Their state: pgh_rules.h
+//   pgh_reduce.cpp  the one fp32 fold launch (fold_prepare, fold_launch), the fold over listed slots (fold_listed);
+//                   fold_run's ring walk and the share sum; the divisors; the weights' upload; RESIDENT and STREAM
+//                   entry points, the resident checkpoint
+//   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: the row sums (RowSums:
+//                   K7 and its cache, K12), clipping (the scales, the tallies) and the Gaussian noise on the clipped
+//                   close (K11 behind a FINAL launch), trimming (K8's planes), the median (K9, K9p), the geometric
+//                   median (its weights); the -0 plane; the rules' lifecycle calls (rules_*), the fold plans the
+//                   two drivers ask for (rules_slot_plan, rules_resident_plan) and the entry points.  Their state:
+//                   pgh_rules.h
 //   pgh_serveropt.cpp  the server optimizer: K10 behind a FINAL launch, its planes, commit, download, upload
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order): slot_fold
 // A new averaging rule adds its state struct to pgh_rules.h (a member of pgh_ctx), its lines to the lifecycle
 // functions rules_* in pgh_rules.cpp -- the one call each event of the context makes: made, slab freed, shard
-// set, reserved, reset, slot written, weights replaced, folds restarted, cycle finished -- and touches
-// check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run, slot_fold) reach the kernels
-// through the last two alone.  The server optimizer (pgh_set_server_opt) hangs on fold_launch too: a FINAL
+// set, reserved, reset, slot written, row ingested, folds restarted, cycle finished -- and to the two plan
+// functions, and touches check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run, slot_fold)
+// ask for the plan and reach the kernels through the last two alone.  A row-wise rule takes its sums from RowSums,
+// writes its weights through FoldWeights::replace and folds against the one -0 plane (NegZeroPlane).  The server optimizer (pgh_set_server_opt) hangs on fold_launch too: a FINAL
 // launch with one set is followed by K10 (server_opt_launch).  The noise (pgh_set_dp_noise) is a second tenant of
 // that mechanism: a clipped FINAL launch with it set is followed by K11 (dp_noise_launch), ahead of K10.
 // A new transfer feature adds its state struct to pgh_xfer.h (a member of pgh_ctx), its events and knobs to
@@ -124,7 +128,6 @@ struct pgh_ctx {
     // uninitialised memory, which a resident fold / download / patch must refuse to read
     bool ckpt_valid = false;
     DeviceBuf d_acc, d_uacc, d_sum, d_dec;  // [pvec]: float, uint64, int64, float
-    DeviceBuf d_w;                          // float per client
     // iterative plan: rec[k] = 1 / (double)(float)(k + 1), grown on demand, kept for the context's
     // life (a superseded table may still be read by an in-flight fold: freed at destroy)
     DeviceBuf d_rec;  // double per client
@@ -156,11 +159,16 @@ struct pgh_ctx {
     int64_t client_base = 0;  // synthetic client k is generated as global client client_base + k
 
     std::vector<int64_t> slot_client;  // client held by each slot and not yet folded, or -1
-    std::vector<float> weights;
-    bool weights_on_device = false;
+    // The fold's weights: every writer replaces them through FoldWeights::replace, fold_prepare uploads them.
+    pgh_detail::FoldWeights fw;
 
     // What the averaging rules and the server optimizer keep (pgh_rules.h): touched only by their own code
-    // (pgh_rules.cpp, pgh_serveropt.cpp), by fold_launch and fedavg_divisor, and through rules_* below.
+    // (pgh_rules.cpp, pgh_serveropt.cpp) and by fold_launch's lines for the optimizer and noise tenants.  The
+    // lifecycle files (pgh_api.cpp, pgh_ingest.cpp, pgh_slots.cpp, pgh_xfer.cpp, pgh_order.cpp) reach them
+    // through rules_* and the fold plans below alone:
+    //   grep -n 'c->\(clip\|geo\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
+    pgh_detail::RowSums rowsums;   // K7's per-slot cache, the buffers of K7 and K12 (clip, geo)
+    pgh_detail::NegZeroPlane nz;   // the one plane of -0.0f (opt, noise, geo)
     pgh_detail::ClipState clip;
     pgh_detail::NoiseState noise;
     pgh_detail::TrimState trim;
@@ -236,6 +244,8 @@ int check_mode_use(pgh_ctx* c, int mode, ModeUse use);
 int check_ready(pgh_ctx* c);
 int check_dtype(pgh_ctx* c, int dtype);
 int check_ckpt(pgh_ctx* c, const char* what);
+// Every listed slot is inside the slab and holds an unfolded diff; no_twice: and none is listed twice.
+int check_slot_list(pgh_ctx* c, const int32_t* slots, int n, bool no_twice);
 // A host vector of nbytes given as the whole model or as this shard alone, `unit` bytes per param: *first =
 // the param of it at which this shard's part starts.  Any other length: PGH_E_ARG, `what` leading the message.
 int shard_start(pgh_ctx* c, const char* what, size_t nbytes, size_t unit, size_t* first);
@@ -367,46 +377,62 @@ void rules_reset(pgh_ctx* c);                // pgh_reset: the cycle's sums, sca
 // (pgh_stream_begin resets; only a resident clipped fold sets them), so clearing them here for every slot of
 // a run changes nothing a caller can see.
 void rules_slot_written(pgh_ctx* c, int slot, int n = 1);
-void rules_weights_replaced(pgh_ctx* c);        // pgh_set_weights: they are no longer the slab's scales
 void rules_folds_restarted(pgh_ctx* c);         // pgh_fold_slots_restart (the caller clears the weights)
-void rules_clipped_cycle_finished(pgh_ctx* c);  // a clipped slot close: the cycle's rows join the finished totals
+void rules_cycle_finished(pgh_ctx* c, int mode);  // a slot close: a clipped cycle's rows join the finished totals
+int rules_row_ingested(pgh_ctx* c, int slot);   // the tail of an fp32 ingest: a rule that wants norms queues the row's K7
+
+// What a fold driver asks the rules before its launches: which rows the fold of `mode` takes and with what.
+// For PGH_MEAN, ITERATIVE, WEIGHTED, TRIMMED and MEDIAN (and a share sum) the plan is the input unchanged and
+// nothing is launched.  A clipped fold gets its scales as the weights (K7 for the sums still missing); a
+// geometric median its included rows, their final weights and W (the inner iterations are finished on return).
+struct FoldPlan {
+    const int32_t* slots = nullptr;  // the rows to fold, in order: the given ones or the included ones.
+                                     // rules_resident_plan: null = clients [0, n) where the slab holds them
+    int n = 0;
+    int64_t total = 0;               // the cycle's clients for fold_prepare, this fold included
+    bool has_divisor = false;        // the rule supplies the FINAL divisor
+    float divisor = 1.f;
+    bool whole_rows = false;         // the rule read every row landed whole: no ranged wait
+};
+int rules_slot_plan(pgh_ctx* c, int mode, const int32_t* slots, int n, int64_t c0, FoldPlan* p);  // slot_fold
+int rules_resident_plan(pgh_ctx* c, int mode, int64_t c0, int64_t n, FoldPlan* p);                // fold_run
+// A rule that closes a cycle in one slot fold only (median, geometric median): its name for the refusal; else null.
+const char* rules_one_fold_cycle(int mode);
+int trim_divisor(pgh_ctx* c, int64_t n, float* div);  // n - 2b; PGH_E_STATE with fewer than 2b + 1 diffs
+
+// ---- the row walker of RowSums and of every fold over listed slots ---------------------------------------
+// f(rows, k0, m) for each run of the listed slots a launch can take: all of them when they are consecutive,
+// else RowTabs of at most ROWTAB_MAX; k0 = the index in the list of the run's first row.
+template <class F>
+int for_row_runs(pgh_ctx* c, const int32_t* slots, size_t n, F&& f) {
+    bool run = true;
+    for (size_t k = 0; k < n; ++k) run = run && slots[k] == slots[0] + (int32_t)k;
+    if (run) return f(pgh::Rows{nullptr, nullptr, slots[0] * c->parties}, (size_t)0, n);
+    for (size_t done = 0; done < n; done += pgh::ROWTAB_MAX) {
+        const size_t m = std::min(n - done, (size_t)pgh::ROWTAB_MAX);
+        pgh::RowTab tab;
+        for (size_t k = 0; k < m; ++k) tab.rows[k] = slots[done + k] * c->parties;
+        RC(f(pgh::Rows{&tab}, done, m));
+    }
+    return PGH_OK;
+}
 
 // ---- clipped FedAvg (pgh_rules.cpp) ----------------------------------------------------------------
 inline bool clip_on(const pgh_ctx* c) { return c->clip.c > 0.f && c->dtype == PGH_F32 && !c->streaming; }
 // scale = norm <= C ? 1 : (float)(C / norm), norm = sqrt(sumsq) in f64 (IEEE: NaN -> NaN, inf -> 0)
 float clip_scale_of(double sumsq, float c);
-// K7 on the copy stream for those of `slots` that have no sum yet, and the D2H of the sums
-int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n);
-int sumsq_wait(pgh_ctx* c);                // the queued sums are in sq_host afterwards
-int sumsq_after_ingest(pgh_ctx* c, int slot);  // norms wanted (below): queue the row's K7 behind its copy
-// weights[c0 + k] = the scale of slots[k] (waits for the sums); norms (nullable) receives sqrt(sumsq)
-int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms);
-int resident_clip_scales(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n)
-// a slot fold of a clipped cycle: the scales and norms of slots[0, n) at fold index c0 (0 begins the cycle)
-int clip_slot_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0);
 
 // ---- geometric-median FedAvg (pgh_rules.cpp) ---------------------------------------------------------
 inline bool geomed_on(const pgh_ctx* c) { return c->geo.iters > 0 && c->dtype == PGH_F32 && !c->streaming; }
 // K7 behind every ingest: clipping or the geometric median is on
 inline bool norms_wanted(const pgh_ctx* c) { return clip_on(c) || geomed_on(c); }
-// The final weights of a close over slots[0, n) in fold order (the included rows and their weights into
-// geo.rows / weights / geo.W): the inner iterations run whole-shard on the context's stream and are finished
-// when this returns.  PGH_E_STATE with no row included; nothing is launched then.
-int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n);
-int geomed_resident_weights(pgh_ctx* c, int64_t n);  // resident folds: clients [0, n) in slots [0, n), once per slab state
-// One launch per run of the included rows (contiguous: one; else RowTabs) of the weighted fold over
-// [fa.off, fa.off + fa.len) on stream s: FIRST on the first, FINAL (when `final`) on the last.
-struct FinalArgs;
-int geomed_fold(pgh_ctx* c, bool final, const FinalArgs& fa, hipStream_t s);
 
 // ---- Gaussian noise on the clipped close (pgh_rules.cpp) ---------------------------------------------
 inline bool noise_on(const pgh_ctx* c) { return c->noise.z > 0.f; }
 // A FINAL fp32 fold of `mode` is about to be issued: with noise on only PGH_CLIPPED_MEAN may close a cycle
 // (PGH_E_STATE before anything is launched; an un-noised average never leaves a context that noise is set on).
 int check_noise_final(pgh_ctx* c, int mode);
-// The delta planes of a noised FINAL without a server optimizer (-0 and d), allocated on first use; stream s
-// has the -0 plane filled when this returns.
-int noise_planes(pgh_ctx* c, hipStream_t s);
+int noise_plane(pgh_ctx* c);  // the delta plane of a noised FINAL without a server optimizer, allocated on first use
 struct FinalArgs;
 // K11 behind a FINAL clipped launch of n clients over [fa.off, fa.off + fa.len) on stream s.  into_opt: the
 // fold wrote the server optimizer's delta plane and K10 follows -- K11 noises that plane in place; else it
@@ -456,7 +482,8 @@ struct FinalArgs {
 };
 // The two steps every fp32 fold driver takes (fold_run, slot_fold; nothing else calls them).
 // Before the launches of a fold that brings the cycle to `total` clients, on the fold's stream: the
-// weights of all of them on the device (weighted, clipped), the reciprocal table covering them (iterative).
+// weights of all of them on the device (weighted, clipped, geometric median: FoldWeights::upload), the reciprocal
+// table covering them (iterative).
 int fold_prepare(pgh_ctx* c, int mode, int64_t total, hipStream_t s);
 // The rows of one launch: n contiguous slab rows from `diffs`, or, with diffs = the slab at row 0,
 // the rows of a RowTab or (a median of more rows than a RowTab carries) of a device table.
@@ -468,6 +495,9 @@ struct FoldRows {
 // One launch (the median: all of its launches) of `mode` over the shard params [fa.off, fa.off + fa.len)
 // on stream s, timed and accounted; client0 = the fold index of row 0.
 int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int flags, const FinalArgs& fa, hipStream_t s);
+// One launch per run of the listed slots (for_row_runs) of `mode` over [fa.off, fa.off + fa.len) on stream s:
+// FIRST on the first, FINAL (when `final`) on the last; fold client k = the k-th listed slot.
+int fold_listed(pgh_ctx* c, int mode, const int32_t* slots, size_t n, bool final, const FinalArgs& fa, hipStream_t s);
 int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const FinalArgs& fa, hipStream_t s);
 int64_t ready_run(pgh_ctx* c, int64_t from);
 int check_no_gaps(pgh_ctx* c, int64_t from, int64_t run);

@@ -12,7 +12,7 @@ using namespace pgh_detail;
 namespace {
 // The tail of every fp32 ingest: the row's norm pass behind its copy (clipping on), then the slot is the client's.
 int finish_ingest(pgh_ctx* c, int64_t client, int slot) {
-    RC(sumsq_after_ingest(c, slot));
+    RC(rules_row_ingested(c, slot));
     return mark_ingested(c, client, slot);
 }
 int pinned_gather_ingest(pgh_ctx* c, const uint8_t* pb, const std::vector<Piece>& pieces, int slot, bool ranged);
@@ -438,14 +438,12 @@ int pgh_set_weights(pgh_ctx* c, const float* w, int n) {
     if (!c) return PGH_E_ARG;
     if (!w || n <= 0) return fail(c, PGH_E_ARG, "need a non-empty weight vector");
     if (c->folded > 0) {  // stream or slot folds: clients [0, folded) are in the running state
-        for (int64_t k = 0; k < c->folded && k < n && k < (int64_t)c->weights.size(); ++k)
-            if (std::memcmp(&w[k], &c->weights[(size_t)k], 4) != 0)
+        for (int64_t k = 0; k < c->folded && k < n && k < (int64_t)c->fw.v.size(); ++k)
+            if (std::memcmp(&w[k], &c->fw.v[(size_t)k], 4) != 0)
                 return fail(c, PGH_E_STATE, "weight of already folded client %lld changed", (long long)k);
         if (n < c->folded) return fail(c, PGH_E_STATE, "fewer weights than folded clients");
     }
-    c->weights.assign(w, w + n);
-    c->weights_on_device = false;
-    rules_weights_replaced(c);
+    c->fw.replace(FoldWeights::CALLER).assign(w, w + n);  // (no longer a rule's: its next resident fold computes anew)
     return PGH_OK;
 }
 

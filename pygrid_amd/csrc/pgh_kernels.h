@@ -210,7 +210,7 @@ hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s)
 // K12: the geometric median's squared distances (the definition is in include/pgh_api.h): K7's sum, in
 // K7's order, over x = d_c[i] + negv[i], one f32 addition per param (negv = -v: d + (-v) is d - v in
 // IEEE).  A workgroup owns one tile and DISTSQ_RC rows: the plane tile is read once per DISTSQ_RC rows,
-// not once per K7 row group.  The launch writes s.part[row * ntiles + t] and then s.sumsq[row] like K7
+// not once per K7 row group (the tile body is K7's, pgh_kernels.hip row_sq_tile, and so is the launcher).  The launch writes s.part[row * ntiles + t] and then s.sumsq[row] like K7
 // (s.sumsq is the distances' buffer here); negv holds at least p floats rounded up to 4, 16-byte aligned.
 constexpr int DISTSQ_RC = 32;
 struct DistsqArgs {

@@ -20,8 +20,8 @@
 //       Philox4x32-10, Marsaglia's polar method, a libm-free logarithm (build-owned: pgh_set_dp_noise,
 //       DESIGN.md section 5); k_dp_normals returns the sampler's normals alone
 // K12 k_row_distsq             K7's sum over d_c[i] - v[i]: every row's squared distance to a moving point,
-//       a tile of the point held in registers over a chunk of rows (build-owned: PGH_GEOMETRIC_MEDIAN,
-//       DESIGN.md section 5)
+//       a tile of the point held in registers over a chunk of rows; one tile body with K7, row_sq_tile
+//       (build-owned: PGH_GEOMETRIC_MEDIAN)
 //
 // Design (DESIGN.md "Kernels"): every kernel is a single streaming pass over the slab held in
 // HBM, column-blocked (SlabMap in pgh_kernels.h: blocks of ld columns, each block all rows,
@@ -1193,65 +1193,82 @@ __global__ __launch_bounds__(256) void k_varint_decode(const uint8_t* bytes, con
     }
 }
 
-// K7: sums of squares along slab rows (the clipping norm), the one reduction here that runs along
-// a client's row instead of down a param column.  One workgroup per tile of SUMSQ_TILE params and
-// group of RB rows: every lane issues its four 16-byte columns of all RB rows (4 RB non-temporal
-// loads in flight) before it squares any, then each row is reduced on its own in the fixed order of
-// pgh_kernels.h (lane partial -> shuffle tree per wave -> four wave sums through LDS).  The squares
-// are exact in f64, so the fma below is the rounded add of the definition.  Addresses past the
-// shard clamp to its last column and are masked to +0.0 (the slab's padding columns hold stale
-// bytes); a launch's last row group repeats its last row instead of branching around the loads.
+// K7 and K12: sums of squares along slab rows (the clipping norm; the geometric median's distances to a moving
+// point), the reductions here that run along a client's row instead of down a param column.  One tile body:
+// a workgroup owns one tile of SUMSQ_TILE params and a chunk of RC rows, which it walks in groups of SUMSQ_RB
+// rows.  Per group every lane issues its four 16-byte columns of all RB rows (4 RB non-temporal loads in
+// flight) before it squares any, then each row is reduced on its own in the fixed order of pgh_kernels.h (lane
+// partial -> shuffle tree per wave -> four wave sums through LDS).  The squares are exact in f64, so the fma
+// below is the rounded add of the definition.  Addresses past the shard clamp to its last column and are masked
+// to +0.0 (the slab's padding columns hold stale bytes); a chunk's last row group repeats its last row instead
+// of branching around the loads.  The wave sums of every row of the chunk meet in LDS behind one barrier.
+//   K7  (RC = SUMSQ_RB, DIST = false): x = d_c[i]; one row group per workgroup.
+//   K12 (RC = DISTSQ_RC, DIST = true): x = d_c[i] + negv[i] (one f32 addition; negv holds -v, so this is d - v).
+//       The workgroup brings its 16 KiB of the plane into registers once (16 floats per lane, plain loads: the
+//       workgroups of the other row chunks read the same tile; clamped like the rows: the plane is at least p
+//       long) and streams its rows past it, so the plane costs 1 / DISTSQ_RC of the slab's bytes instead of
+//       1 / SUMSQ_RB.  The tile partials go where K7's go and k_row_sumsq_fold[_rows] finishes the rows.
 constexpr int SUMSQ_RB = 4;
 
-template <int SRC>
-__device__ __forceinline__ void row_sumsq_tile(const SumsqArgs& a, const Rows rows) {
-    __shared__ double wsum[SUMSQ_RB][4];
+template <int SRC, int RC, bool DIST>
+__device__ __forceinline__ void row_sq_tile(const SumsqArgs& a, const float* negv, const Rows rows) {
+    __shared__ double wsum[RC][4];
     const int lane = threadIdx.x, wave = lane >> 6;
     const int64_t t = blockIdx.x, base = t * SUMSQ_TILE;
-    const int r0 = (int)blockIdx.y * SUMSQ_RB;
-    const int nr = min(SUMSQ_RB, a.n_rows - r0);
+    const int r0 = (int)blockIdx.y * RC;
+    const int nr = min(RC, a.n_rows - r0);
     const bool full = base + SUMSQ_TILE <= a.p;
     const int64_t last4 = (a.p - 1) & ~int64_t(3);
     int64_t idx[4], off[4];
+    f32x4 nv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         idx[j] = base + 4 * (lane + BLOCK * j);
-        off[j] = a.map.at(full ? idx[j] : min(idx[j], last4));
+        const int64_t i = full ? idx[j] : min(idx[j], last4);
+        off[j] = a.map.at(i);
+        if constexpr (DIST) nv[j] = ld4<false>(negv + i);
     }
-    size_t row[SUMSQ_RB];
+    const int ng = RC == SUMSQ_RB ? SUMSQ_RB : nr;  // (nr is uniform over the workgroup; K7: one trip)
+#pragma unroll 1
+    for (int g = 0; g < ng; g += SUMSQ_RB) {
+        size_t row[SUMSQ_RB];
 #pragma unroll
-    for (int rr = 0; rr < SUMSQ_RB; ++rr) {
-        const int r = r0 + min(rr, nr - 1);
-        row[rr] = row_at<SRC>(rows, r);
-    }
-    f32x4 v[SUMSQ_RB][4];
+        for (int rr = 0; rr < SUMSQ_RB; ++rr) row[rr] = row_at<SRC>(rows, r0 + min(g + rr, nr - 1));
+        f32x4 v[SUMSQ_RB][4];
 #pragma unroll
-    for (int rr = 0; rr < SUMSQ_RB; ++rr)
+        for (int rr = 0; rr < SUMSQ_RB; ++rr)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[rr][j] = ld4<true>(a.slab + row[rr] * (size_t)a.map.ld + off[j]);
+            for (int j = 0; j < 4; ++j) v[rr][j] = ld4<true>(a.slab + row[rr] * (size_t)a.map.ld + off[j]);
 #pragma unroll
-    for (int rr = 0; rr < SUMSQ_RB; ++rr) {
-        double acc = 0.0;
+        for (int rr = 0; rr < SUMSQ_RB; ++rr) {
+            double acc = 0.0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const double x = (full || idx[j] + e < a.p) ? (double)v[rr][j][e] : 0.0;
-                acc = __builtin_fma(x, x, acc);
-            }
+                for (int e = 0; e < 4; ++e) {
+                    const float xf = DIST ? v[rr][j][e] + nv[j][e] : v[rr][j][e];
+                    const double x = (full || idx[j] + e < a.p) ? (double)xf : 0.0;
+                    acc = __builtin_fma(x, x, acc);
+                }
 #pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) acc += __shfl_down(acc, h, 64);
-        if ((lane & 63) == 0) wsum[rr][wave] = acc;
+            for (int h = 32; h >= 1; h >>= 1) acc += __shfl_down(acc, h, 64);
+            if ((lane & 63) == 0) wsum[g + rr][wave] = acc;  // (g + rr < RC: a multiple of SUMSQ_RB)
+        }
     }
     __syncthreads();
-#pragma unroll
-    for (int rr = 0; rr < SUMSQ_RB; ++rr)
-        if (lane == rr && rr < nr)
-            a.part[row[rr] * (size_t)a.ntiles + (size_t)t] = ((wsum[rr][0] + wsum[rr][1]) + wsum[rr][2]) + wsum[rr][3];
+    if (lane < nr)
+        a.part[row_at<SRC>(rows, r0 + lane) * (size_t)a.ntiles + (size_t)t] =
+            ((wsum[lane][0] + wsum[lane][1]) + wsum[lane][2]) + wsum[lane][3];
 }
 
-__global__ __launch_bounds__(BLOCK) void k_row_sumsq(SumsqArgs a) { row_sumsq_tile<0>(a, Rows{nullptr, nullptr, a.row0}); }
-__global__ __launch_bounds__(BLOCK) void k_row_sumsq_rows(SumsqArgs a, RowTab tab) { row_sumsq_tile<1>(a, Rows{&tab}); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq(SumsqArgs a) {
+    row_sq_tile<0, SUMSQ_RB, false>(a, nullptr, Rows{nullptr, nullptr, a.row0});
+}
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_rows(SumsqArgs a, RowTab tab) { row_sq_tile<1, SUMSQ_RB, false>(a, nullptr, Rows{&tab}); }
+__global__ __launch_bounds__(BLOCK) void k_row_distsq(DistsqArgs d) {
+    row_sq_tile<0, DISTSQ_RC, true>(d.s, d.negv, Rows{nullptr, nullptr, d.s.row0});
+}
+__global__ __launch_bounds__(BLOCK) void k_row_distsq_rows(DistsqArgs d, RowTab tab) { row_sq_tile<1, DISTSQ_RC, true>(d.s, d.negv, Rows{&tab}); }
 
 // The row's tile partials, left-folded in ascending tile order by one lane; the workgroup brings
 // them into LDS 1,024 at a time (coalesced) so the serial chain reads LDS, not HBM.
@@ -1276,68 +1293,6 @@ __device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const Rows ro
 
 __global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold(SumsqArgs a) { row_sumsq_fold<0>(a, Rows{nullptr, nullptr, a.row0}); }
 __global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold_rows(SumsqArgs a, RowTab tab) { row_sumsq_fold<1>(a, Rows{&tab}); }
-
-// K12: K7's sums over x = d_c[i] + negv[i] (one f32 addition; negv holds -v, so this is d - v), in K7's
-// order, for the geometric median's distances to a moving point.  The other way round from K7: a workgroup
-// owns one tile and a chunk of DISTSQ_RC rows.  It brings its 16 KiB of the plane into registers once
-// (16 floats per lane, plain loads: the workgroups of the other row chunks read the same tile) and streams
-// its rows past it in K7's groups of SUMSQ_RB (4 RB non-temporal loads in flight), so the plane costs
-// 1 / DISTSQ_RC of the slab's bytes instead of 1 / SUMSQ_RB.  The wave sums of every row of the chunk meet
-// in LDS behind one barrier; the tile partials go where K7's go and k_row_sumsq_fold[_rows] finishes the
-// rows.  K7's clamp and mask for the last tile (the plane is clamped the same way: it is at least p long),
-// and the last row group repeats the chunk's last row.
-template <int SRC>
-__device__ __forceinline__ void row_distsq_tile(const DistsqArgs& d, const Rows rows) {
-    __shared__ double wsum[DISTSQ_RC][4];
-    const SumsqArgs& a = d.s;
-    const int lane = threadIdx.x, wave = lane >> 6;
-    const int64_t t = blockIdx.x, base = t * SUMSQ_TILE;
-    const int r0 = (int)blockIdx.y * DISTSQ_RC;
-    const int nr = min(DISTSQ_RC, a.n_rows - r0);
-    const bool full = base + SUMSQ_TILE <= a.p;
-    const int64_t last4 = (a.p - 1) & ~int64_t(3);
-    int64_t idx[4], off[4];
-    f32x4 nv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        idx[j] = base + 4 * (lane + BLOCK * j);
-        const int64_t i = full ? idx[j] : min(idx[j], last4);
-        off[j] = a.map.at(i);
-        nv[j] = ld4<false>(d.negv + i);
-    }
-    for (int g = 0; g < nr; g += SUMSQ_RB) {  // (nr is uniform over the workgroup)
-        size_t row[SUMSQ_RB];
-#pragma unroll
-        for (int rr = 0; rr < SUMSQ_RB; ++rr) row[rr] = row_at<SRC>(rows, r0 + min(g + rr, nr - 1));
-        f32x4 v[SUMSQ_RB][4];
-#pragma unroll
-        for (int rr = 0; rr < SUMSQ_RB; ++rr)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[rr][j] = ld4<true>(a.slab + row[rr] * (size_t)a.map.ld + off[j]);
-#pragma unroll
-        for (int rr = 0; rr < SUMSQ_RB; ++rr) {
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float xf = v[rr][j][e] + nv[j][e];
-                    const double x = (full || idx[j] + e < a.p) ? (double)xf : 0.0;
-                    acc = __builtin_fma(x, x, acc);
-                }
-#pragma unroll
-            for (int h = 32; h >= 1; h >>= 1) acc += __shfl_down(acc, h, 64);
-            if ((lane & 63) == 0) wsum[g + rr][wave] = acc;  // (g + rr < DISTSQ_RC: a multiple of SUMSQ_RB)
-        }
-    }
-    __syncthreads();
-    if (lane < nr)
-        a.part[row_at<SRC>(rows, r0 + lane) * (size_t)a.ntiles + (size_t)t] =
-            ((wsum[lane][0] + wsum[lane][1]) + wsum[lane][2]) + wsum[lane][3];
-}
-
-__global__ __launch_bounds__(BLOCK) void k_row_distsq(DistsqArgs d) { row_distsq_tile<0>(d, Rows{nullptr, nullptr, d.s.row0}); }
-__global__ __launch_bounds__(BLOCK) void k_row_distsq_rows(DistsqArgs d, RowTab tab) { row_distsq_tile<1>(d, Rows{&tab}); }
 
 int cu_count() {
     static int cached[64] = {0};
@@ -1714,61 +1669,40 @@ hipError_t launch_dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n
     return hipGetLastError();
 }
 
-hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s) {
+static_assert(DISTSQ_RC % SUMSQ_RB == 0 && DISTSQ_RC <= BLOCK, "K12's row chunk: whole row groups, one lane per row at the end");
+
+// K7 (negv null) or K12 over the launch's rows, RC rows per workgroup, and the fold of the tile partials behind it.
+template <int RC>
+static hipError_t launch_row_sq(const SumsqArgs& a, const float* negv, const Rows& rows, hipStream_t s) {
+    constexpr bool DIST = RC == DISTSQ_RC;
     const RowTab* tab = rows.tab;
     if (!valid_rows(rows, a.n_rows, false, true) || a.p <= 0 || a.n_rows < 0 || a.map.off != 0 || !valid_map(a.map, a.p) ||
         a.ntiles != (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE || a.ntiles > 0x7fffffff)
         return hipErrorInvalidValue;
     if (a.n_rows == 0) return hipSuccess;
-    if (!a.slab || !a.part || !a.sumsq || (reinterpret_cast<uintptr_t>(a.slab) & 15)) return hipErrorInvalidValue;
-    const int max_rows = 65535 * SUMSQ_RB;  // grid rows of one launch
+    if (!a.slab || !a.part || !a.sumsq || (DIST && !negv) ||
+        ((reinterpret_cast<uintptr_t>(a.slab) | reinterpret_cast<uintptr_t>(negv)) & 15))
+        return hipErrorInvalidValue;
+    const int max_rows = 65535 * RC;  // grid rows of one launch
     for (int done = 0; done < a.n_rows; done += max_rows) {
         SumsqArgs b = a;
         b.row0 = rows.row0 + done;
         b.n_rows = std::min(max_rows, a.n_rows - done);
-        const dim3 grid((unsigned)b.ntiles, (unsigned)((b.n_rows + SUMSQ_RB - 1) / SUMSQ_RB));
-        if (tab) {
-            k_row_sumsq_rows<<<grid, BLOCK, 0, s>>>(b, *tab);
-            k_row_sumsq_fold_rows<<<(unsigned)b.n_rows, BLOCK, 0, s>>>(b, *tab);
-        } else {
-            k_row_sumsq<<<grid, BLOCK, 0, s>>>(b);
-            k_row_sumsq_fold<<<(unsigned)b.n_rows, BLOCK, 0, s>>>(b);
-        }
+        const dim3 grid((unsigned)b.ntiles, (unsigned)((b.n_rows + RC - 1) / RC));
+        if (DIST && tab) k_row_distsq_rows<<<grid, BLOCK, 0, s>>>(DistsqArgs{b, negv}, *tab);
+        else if (DIST) k_row_distsq<<<grid, BLOCK, 0, s>>>(DistsqArgs{b, negv});
+        else if (tab) k_row_sumsq_rows<<<grid, BLOCK, 0, s>>>(b, *tab);
+        else k_row_sumsq<<<grid, BLOCK, 0, s>>>(b);
+        if (tab) k_row_sumsq_fold_rows<<<(unsigned)b.n_rows, BLOCK, 0, s>>>(b, *tab);
+        else k_row_sumsq_fold<<<(unsigned)b.n_rows, BLOCK, 0, s>>>(b);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-static_assert(DISTSQ_RC % SUMSQ_RB == 0 && DISTSQ_RC <= BLOCK, "K12's row chunk: whole row groups, one lane per row at the end");
-
-hipError_t launch_row_distsq(const DistsqArgs& d, const Rows& rows, hipStream_t s) {
-    const SumsqArgs& a = d.s;
-    const RowTab* tab = rows.tab;
-    if (!valid_rows(rows, a.n_rows, false, true) || a.p <= 0 || a.n_rows < 0 || a.map.off != 0 || !valid_map(a.map, a.p) ||
-        a.ntiles != (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE || a.ntiles > 0x7fffffff)
-        return hipErrorInvalidValue;
-    if (a.n_rows == 0) return hipSuccess;
-    if (!a.slab || !a.part || !a.sumsq || !d.negv || ((reinterpret_cast<uintptr_t>(a.slab) | reinterpret_cast<uintptr_t>(d.negv)) & 15))
-        return hipErrorInvalidValue;
-    const int max_rows = 65535 * DISTSQ_RC;  // grid rows of one launch
-    for (int done = 0; done < a.n_rows; done += max_rows) {
-        DistsqArgs b = d;
-        b.s.row0 = rows.row0 + done;
-        b.s.n_rows = std::min(max_rows, a.n_rows - done);
-        const dim3 grid((unsigned)a.ntiles, (unsigned)((b.s.n_rows + DISTSQ_RC - 1) / DISTSQ_RC));
-        if (tab) {
-            k_row_distsq_rows<<<grid, BLOCK, 0, s>>>(b, *tab);
-            k_row_sumsq_fold_rows<<<(unsigned)b.s.n_rows, BLOCK, 0, s>>>(b.s, *tab);
-        } else {
-            k_row_distsq<<<grid, BLOCK, 0, s>>>(b);
-            k_row_sumsq_fold<<<(unsigned)b.s.n_rows, BLOCK, 0, s>>>(b.s);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
+hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s) { return launch_row_sq<SUMSQ_RB>(a, nullptr, rows, s); }
+hipError_t launch_row_distsq(const DistsqArgs& d, const Rows& rows, hipStream_t s) { return launch_row_sq<DISTSQ_RC>(d.s, d.negv, rows, s); }
 
 hipError_t launch_synth_shares(int64_t* out, const SlabMap& m, int64_t ncols, int n_clients, int n_parties,
                                int64_t p, uint64_t seed, int64_t client0, int64_t idx0, float enc_scale,

@@ -15,12 +15,12 @@ using namespace pgh_detail;
 
 namespace pgh_detail {
 
-static int sync_weights(pgh_ctx* c, hipStream_t s) {
-    if (c->weights_on_device || c->weights.empty()) return PGH_OK;
-    if (!c->d_w.reserve(sizeof(float) * c->weights.size())) return fail(c, PGH_E_OOM, "weight vector allocation failed");
-    CK(c, hipMemcpyAsync(c->d_w.as<float>(), c->weights.data(), sizeof(float) * c->weights.size(), hipMemcpyHostToDevice, s));
-    CK(c, hipStreamSynchronize(s));  // c->weights may change after return
-    c->weights_on_device = true;
+int FoldWeights::upload(pgh_ctx* c, hipStream_t s) {
+    if (on_device || v.empty()) return PGH_OK;
+    if (!d.reserve(sizeof(float) * v.size())) return fail(c, PGH_E_OOM, "weight vector allocation failed");
+    CK(c, hipMemcpyAsync(d.as<float>(), v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // v may change after return
+    on_device = true;
     return PGH_OK;
 }
 
@@ -58,9 +58,9 @@ float weight_total(const std::vector<float>& w, int64_t n) {  // left fold, floa
 
 int fold_prepare(pgh_ctx* c, int mode, int64_t total, hipStream_t s) {
     if (kernel_mode(mode) == PGH_WEIGHTED_MEAN) {
-        if ((int64_t)c->weights.size() < total)
-            return fail(c, PGH_E_STATE, "weighted mean: %zu weights for %lld clients", c->weights.size(), (long long)total);
-        RC(sync_weights(c, s));
+        if ((int64_t)c->fw.v.size() < total)
+            return fail(c, PGH_E_STATE, "weighted mean: %zu weights for %lld clients", c->fw.v.size(), (long long)total);
+        RC(c->fw.upload(c, s));
     }
     if (mode == PGH_ITERATIVE_MEAN) RC(ensure_recips(c, total, s));
     return PGH_OK;
@@ -75,7 +75,7 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     a.n_rows = rows.n;
     a.client0 = client0;
     a.p = fa.len;
-    a.weights = c->d_w ? c->d_w.as<float>() + client0 : nullptr;
+    a.weights = c->fw.d ? c->fw.d.as<float>() + client0 : nullptr;
     a.recips = c->d_rec ? c->d_rec.as<double>() + client0 : nullptr;
     a.acc = c->d_acc.as<float>() + off;
     a.ckpt = fa.ckpt ? fa.ckpt + off : nullptr;
@@ -89,13 +89,11 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     const bool noise = noise_on(c) && (flags & pgh::FL_FINAL) && !fa.plain;
     if (noise) RC(check_noise_final(c, mode));  // (the entry points have checked: nothing was launched)
     if (noise && (!fa.ckpt || !fa.out)) return fail(c, PGH_E_ARG, "a noised FINAL fold needs ckpt and out");
-    if (opt) {
-        a.ckpt = c->opt.d_nz.as<float>() + off;
-        a.out = c->opt.d_d.as<float>() + off;
-    } else if (noise) {
-        RC(noise_planes(c, s));
-        a.ckpt = c->noise.d_nz.as<float>() + off;
-        a.out = c->noise.d_d.as<float>() + off;
+    if (opt || noise) {  // (the lines that name the two tenants' delta planes: fold_launch's own)
+        RC(c->nz.ensure(c, s));
+        if (!opt) RC(noise_plane(c));
+        a.ckpt = c->nz.get() + off;
+        a.out = (opt ? c->opt.d_d : c->noise.d_d).as<float>() + off;
     }
     a.divisor = fa.divisor;
     a.flags = flags;
@@ -118,25 +116,32 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     return opt ? server_opt_launch(c, fa, s) : PGH_OK;
 }
 
+int fold_listed(pgh_ctx* c, int mode, const int32_t* slots, size_t n, bool final, const FinalArgs& fa, hipStream_t s) {
+    return for_row_runs(c, slots, n, [&](const pgh::Rows& rows, size_t k0, size_t m) {
+        const int flags = (k0 == 0 ? pgh::FL_FIRST : 0) | (final && k0 + m == n ? pgh::FL_FINAL : 0);
+        FoldRows fr{rows.tab ? c->d_slab.as<float>() : (const float*)slot_row(c, slots[0], 0), (int)m, rows};
+        fr.src.row0 = 0;  // (the fold takes contiguous rows from its slab pointer)
+        return fold_launch(c, mode, fr, (int64_t)k0, flags, fa, s);
+    });
+}
+
 // Fold slots holding clients [c0, c0 + n) (slot order may wrap) into the running state.
 // FIRST when c0 == 0; FINAL writes out (fedavg: ckpt - avg; secagg: sum/dec) instead of the state.
 int fold_run(pgh_ctx* c, int kind, int64_t c0, int64_t n, bool final, const FinalArgs& fa, hipStream_t s) {
-    // (resident only, check_mode_use: the scales of clients [0, n) become the fold's weights)
-    if (kind == PGH_CLIPPED_MEAN) RC(resident_clip_scales(c, n));
-    // (resident only too: the included rows and their final weights; the fold below runs over those rows)
-    const bool geomed = kind == PGH_GEOMETRIC_MEDIAN;
-    if (geomed) RC(geomed_resident_weights(c, n));
+    FoldPlan plan;  // a rule's weights, and the rows it folds where they are not all n
+    RC(rules_resident_plan(c, kind, c0, n, &plan));
     RC(order_after_ingest(c, s));
-    if (kind != KIND_SECAGG && n > 0) RC(fold_prepare(c, kind, geomed ? (int64_t)c->geo.rows.size() : c0 + n, s));
+    if (kind != KIND_SECAGG && n > 0) RC(fold_prepare(c, kind, plan.total, s));
     const int R = c->slots;
-    FinalArgs r = fa;  // the launches' param range, its length resolved
+    FinalArgs r = fa;  // the launches' param range, its length resolved, and the rule's divisor
+    if (plan.has_divisor) r.divisor = plan.divisor;
     if (r.len < 0) r.len = c->pg - r.off;
     const int64_t off = r.off, len = r.len;
     if (off < 0 || (off & 3) || len <= 0 || off + len > c->pg)
         return fail(c, PGH_E_ARG, "param range [%lld,+%lld) outside the shard or not 4-aligned", (long long)off,
                     (long long)len);
     int64_t done = 0;
-    if (geomed) RC(geomed_fold(c, final, r, s));
+    if (plan.slots) RC(fold_listed(c, kind, plan.slots, (size_t)plan.n, final, r, s));
     else do {
         const int slot = (int)((c0 + done) % R);
         const int64_t seg = std::min<int64_t>(n - done, (int64_t)(R - slot));
@@ -237,21 +242,15 @@ int resident_count(pgh_ctx* c, int64_t* n_out) {
 }
 
 int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
-    if (mode == PGH_TRIMMED_MEAN) {  // b dropped per side; at least one value must be left
-        if (n < 2 * (int64_t)c->trim.b + 1)
-            return fail(c, PGH_E_STATE, "trimmed mean with b = %d needs at least %d diffs, have %lld", c->trim.b,
-                        2 * c->trim.b + 1, (long long)n);
-        *div = (float)(n - 2 * (int64_t)c->trim.b);
+    if (mode == PGH_TRIMMED_MEAN) {
+        RC(trim_divisor(c, n, div));
     } else if (mode == PGH_WEIGHTED_MEAN) {
-        if ((int64_t)c->weights.size() < n)
-            return fail(c, PGH_E_STATE, "weighted mean needs %lld weights, have %zu", (long long)n, c->weights.size());
-        const float t = weight_total(c->weights, n);
+        if ((int64_t)c->fw.v.size() < n)
+            return fail(c, PGH_E_STATE, "weighted mean needs %lld weights, have %zu", (long long)n, c->fw.v.size());
+        const float t = weight_total(c->fw.v, n);
         if (!(t != 0.f)) return fail(c, PGH_E_ARG, "sum of weights is zero");
         *div = t;
-    } else if (mode == PGH_GEOMETRIC_MEDIAN) {  // (resident folds; a slot close takes W from its own weights)
-        RC(geomed_resident_weights(c, n));
-        *div = c->geo.W;
-    } else {
+    } else {  // (a geometric median's comes with the plan that computed its weights)
         *div = (float)n;  // th.div(sum, len(diffs)), cycle_manager.py:288
     }
     return PGH_OK;

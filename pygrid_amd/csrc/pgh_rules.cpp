@@ -1,9 +1,11 @@
-// libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); clipping's
-// per-row sums of squares (K7), their host cache, the scales and the tallies; the Gaussian noise on the clipped
-// close (K11 behind a FINAL launch, its planes, setting and entry points); the trimmed mean's state planes
-// (K8); the median's driver and row table (K9, K9p); the geometric median's included rows, inner iterations and
-// final weights (K12 between weighted folds); and what the rules' state does at each lifecycle event of
-// the context (rules_*: the one call each event's site makes).  The state itself: pgh_rules.h.
+// libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); the per-row
+// sums of squares and distances (RowSums: K7 with its host cache, K12); clipping's scales and tallies; the
+// Gaussian noise on the clipped close (K11 behind a FINAL launch, its plane, setting and entry points); the
+// trimmed mean's state planes (K8); the median's driver and row table (K9, K9p); the geometric median's included
+// rows, inner iterations and final weights (K12 between weighted folds); the context's -0 plane; what the rules'
+// state does at each lifecycle event of the context (rules_*: the one call each event's site makes) and what
+// they hand a fold driver before its launches (rules_slot_plan, rules_resident_plan).  The state itself:
+// pgh_rules.h.
 // (struct pgh_ctx and the shared helpers: pgh_ctx.h)
 #include "pgh_ctx.h"
 
@@ -68,51 +70,65 @@ int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
 bool rules_made(pgh_ctx* c) {
     if (const char* e = std::getenv("PGH_TRIM_VEC")) c->trim.vec = std::atoi(e) == 4 ? 4 : std::atoi(e) == 1 ? 1 : 0;
     if (const char* e = std::getenv("PGH_MEDIAN_PATH")) c->med.passes = std::strcmp(e, "passes") == 0;
-    return c->clip.sq_ev.make() == hipSuccess;
+    return c->rowsums.ev.make() == hipSuccess;
 }
 
 void rules_slab_freed(pgh_ctx* c) {  // the streams are idle (free_slab synchronised them)
-    for (auto* v : {&c->trim.d_planes, &c->med.d_prefix, &c->med.d_rowidx, &c->clip.d_sq_part, &c->clip.d_sq, &c->geo.d_nz, &c->geo.d_negv,
-                    &c->geo.d_dist})
-        v->reset();
-    c->geo.h_dist.reset();
+    for (auto* v : {&c->trim.d_planes, &c->med.d_prefix, &c->med.d_rowidx, &c->geo.d_negv}) v->reset();
+    c->rowsums.slab_freed();
     c->geo.forget();
-    c->clip.h_sq.reset();
-    c->clip.sq_state.clear();
-    c->clip.sq_host.clear();
     c->clip.forget();
 }
 
 void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep_opt) {
-    const bool same = keep_opt && lo == c->lo && hi == c->hi;
+    const bool same_shard = lo == c->lo && hi == c->hi;
+    const bool same = keep_opt && same_shard;
     if (!(same && pvec == c->opt.pvec)) c->opt.release();
     if (!(same && pvec == c->noise.pvec)) c->noise.release();  // (free_slab has synchronised the streams)
+    if (!(same_shard && pvec == c->pvec)) c->nz.d.reset();     // (its tenants above and below are gone with it)
     if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
-    c->geo.release();  // (free_slab has dropped the planes; the setting goes with the layout or shard)
+    c->geo.release();  // (free_slab has dropped the plane; the setting goes with the layout or shard)
 }
 
-void rules_reserved(pgh_ctx* c, int slots) {
-    c->clip.sq_state.assign((size_t)slots, (uint8_t)ClipState::SQ_NONE);
-    c->clip.sq_host.assign((size_t)slots, 0.0);
-}
+void rules_reserved(pgh_ctx* c, int slots) { c->rowsums.reserved(slots); }
 
 void rules_reset(pgh_ctx* c) {
+    c->rowsums.forget();
     c->clip.forget();
     c->geo.forget();
 }
 
 void rules_slot_written(pgh_ctx* c, int slot, int n) {
-    c->clip.slot_written(slot, n);
-    c->geo.weights_valid = false;
+    c->rowsums.slot_written(slot, n);
+    c->fw.stale();  // the slab is no longer the one a rule's resident weights were computed for
 }
-
-void rules_weights_replaced(pgh_ctx* c) { c->clip.scales_valid = c->geo.weights_valid = false; }
 
 void rules_folds_restarted(pgh_ctx* c) { c->clip.norms.clear(); }
 
-void rules_clipped_cycle_finished(pgh_ctx* c) {
-    c->clip.count_cycle(c->weights);
+void rules_cycle_finished(pgh_ctx* c, int mode) {
+    if (mode != PGH_CLIPPED_MEAN) return;
+    c->clip.count_cycle(c->fw.v);  // the cycle's rows join the finished totals (pgh_clip_stats)
     c->clip.norms.clear();
+}
+
+int rules_row_ingested(pgh_ctx* c, int slot) {
+    if (!norms_wanted(c)) return PGH_OK;
+    const int32_t sl = slot;
+    return c->rowsums.queue(c, &sl, 1);
+}
+
+const char* rules_one_fold_cycle(int mode) {
+    return mode == PGH_MEDIAN ? "a median" : mode == PGH_GEOMETRIC_MEDIAN ? "a geometric median" : nullptr;
+}
+
+int NegZeroPlane::ensure(pgh_ctx* c, hipStream_t s) {
+    if (d) return PGH_OK;
+    if (!d.reserve(4 * (size_t)c->pvec)) return fail(c, PGH_E_OOM, "allocation of the -0 plane (%zu bytes) failed", 4 * (size_t)c->pvec);
+    const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)d.as<void>(), (int)0x80000000u, (size_t)c->pvec, s);
+    // (complete before any tenant reads it, on whichever stream: paid once per shard)
+    if (e == hipSuccess && hipStreamSynchronize(s) == hipSuccess) return PGH_OK;
+    d.reset();
+    return fail(c, PGH_E_HIP, "filling the -0 plane failed: %s", hipGetErrorString(e));
 }
 
 // ---- trimmed mean: K8's arguments and state planes ---------------------------------------------------------
@@ -168,20 +184,7 @@ int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hip
     return PGH_OK;
 }
 
-// ---- clipped FedAvg: per-row sums of squares (K7), their host cache, the scales, the tallies ---------------
-
-float clip_scale_of(double sumsq, float c) {
-    const double norm = std::sqrt(sumsq);
-    return norm <= (double)c ? 1.0f : (float)((double)c / norm);
-}
-
-void ClipState::forget() {
-    slot_written(0, (int)sq_state.size());
-    sq_queued.clear();
-    norms.clear();
-    rows = clipped = 0;
-    max_norm = 0.0;
-}
+// ---- clipped FedAvg: the tallies -------------------------------------------------------------------------------
 
 void ClipState::count(const float* scales, const double* row_norms, int64_t n) {
     for (int64_t k = 0; k < n; ++k) {
@@ -191,206 +194,162 @@ void ClipState::count(const float* scales, const double* row_norms, int64_t n) {
     }
 }
 
-namespace {
-int ensure_sumsq_buffers(pgh_ctx* c) {
-    if (c->clip.d_sq_part) return PGH_OK;
+// ---- the row sums: K7 and its host cache, K12 (RowSums) -------------------------------------------------------
+
+int RowSums::ensure(pgh_ctx* c) {
+    if (d_part) return PGH_OK;
     const size_t ntiles = (size_t)((c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE);
     const size_t rows = (size_t)c->slots;
-    if (!c->clip.d_sq_part.reserve(8 * rows * ntiles) || !c->clip.d_sq.reserve(8 * rows) || !c->clip.h_sq.reserve(8 * rows)) {
-        c->clip.d_sq_part.reset();  // (the test above: all three or none)
+    if (!d_part.reserve(8 * rows * ntiles) || !d_sq.reserve(8 * rows) || !h_sq.reserve(8 * rows)) {
+        d_part.reset();  // (the test above: all three or none)
         return fail(c, PGH_E_OOM, "allocation of the clipping sums (%zu rows x %zu tiles) failed", rows, ntiles);
     }
     return PGH_OK;
 }
-}  // namespace
 
-int sumsq_queue(pgh_ctx* c, const int32_t* slots, int n) {
-    std::vector<int32_t> todo;
-    for (int k = 0; k < n; ++k)
-        if (c->clip.sq_state[(size_t)slots[k]] == ClipState::SQ_NONE) todo.push_back(slots[k]);
-    if (todo.empty()) return PGH_OK;
-    RC(ensure_sumsq_buffers(c));
+pgh::SumsqArgs RowSums::args(pgh_ctx* c, double* sums) const {
     pgh::SumsqArgs a{};
     a.slab = c->d_slab.as<float>();
     a.map = slab_map(c);
     a.p = c->pg;
     a.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
-    a.part = c->clip.d_sq_part.as<double>();
-    a.sumsq = c->clip.d_sq.as<double>();
-    const hipStream_t s = c->copy;
-    bool run = true;  // consecutive slots: one launch over contiguous rows
-    int32_t lo = todo[0], hi = todo[0];
-    for (size_t k = 0; k < todo.size(); ++k) {
-        run = run && todo[k] == todo[0] + (int32_t)k;
-        lo = std::min(lo, todo[k]);
-        hi = std::max(hi, todo[k]);
-    }
-    const auto bytes = [&](size_t rows) { return rows * (4ull * (uint64_t)c->pg + 8ull * (uint64_t)a.ntiles); };
-    if (run) {
-        a.n_rows = (int)todo.size();
-        const pgh::Rows rows{nullptr, nullptr, todo[0]};
-        RC(timed_launch(c, s, bytes(todo.size()), [&] { return pgh::launch_row_sumsq(a, rows, s); }));
-    } else {
-        for (size_t done = 0; done < todo.size(); done += pgh::ROWTAB_MAX) {
-            const size_t m = std::min(todo.size() - done, (size_t)pgh::ROWTAB_MAX);
-            pgh::RowTab tab;
-            for (size_t k = 0; k < m; ++k) tab.rows[k] = todo[done + k];
-            a.n_rows = (int)m;
-            RC(timed_launch(c, s, bytes(m), [&] { return pgh::launch_row_sumsq(a, pgh::Rows{&tab}, s); }));
-        }
-    }
-    // entries of other slots inside [lo, hi] are rewritten with what the device holds for them: the
-    // same value an earlier copy brought (same stream), or one nobody reads
-    CK(c, hipMemcpyAsync(c->clip.h_sq.as<double>() + lo, c->clip.d_sq.as<double>() + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
-    CK(c, hipEventRecord(c->clip.sq_ev, s));
-    for (int32_t sl : todo) {
-        c->clip.sq_state[(size_t)sl] = ClipState::SQ_QUEUED;
-        c->clip.sq_queued.push_back(sl);
-    }
-    return PGH_OK;
+    a.part = d_part.as<double>();
+    a.sumsq = sums;
+    return a;
 }
-
-int sumsq_wait(pgh_ctx* c) {
-    if (c->clip.sq_queued.empty()) return PGH_OK;
-    CK(c, hipEventSynchronize(c->clip.sq_ev));
-    for (int32_t sl : c->clip.sq_queued)
-        if (c->clip.sq_state[(size_t)sl] == ClipState::SQ_QUEUED) {
-            c->clip.sq_host[(size_t)sl] = c->clip.h_sq.as<double>()[sl];
-            c->clip.sq_state[(size_t)sl] = ClipState::SQ_VALID;
-        }
-    c->clip.sq_queued.clear();
-    return PGH_OK;
-}
-
-int sumsq_after_ingest(pgh_ctx* c, int slot) {
-    if (!norms_wanted(c)) return PGH_OK;
-    const int32_t sl = slot;
-    return sumsq_queue(c, &sl, 1);
-}
-
-int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms) {
-    RC(sumsq_queue(c, slots, n));
-    RC(sumsq_wait(c));
-    c->geo.weights_valid = false;  // (the context's weights become the scales)
-    c->weights.resize((size_t)(c0 + n));
-    if (norms) norms->resize((size_t)(c0 + n));
-    for (int k = 0; k < n; ++k) {
-        const double ss = c->clip.sq_host[(size_t)slots[k]];
-        c->weights[(size_t)(c0 + k)] = clip_scale_of(ss, c->clip.c);
-        if (norms) (*norms)[(size_t)(c0 + k)] = std::sqrt(ss);
-    }
-    c->weights_on_device = false;
-    return PGH_OK;
-}
-
-int clip_slot_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0) {
-    if (c0 == 0) c->clip.norms.clear();
-    c->clip.scales_valid = false;
-    return clip_set_scales(c, slots, n, c0, &c->clip.norms);
-}
-
-// Resident folds in PGH_CLIPPED_MEAN: the scales of clients [0, n) (slot k holds client k), computed
-// once per state of the slab -- the range form and repeated folds reuse them.
-int resident_clip_scales(pgh_ctx* c, int64_t n) {
-    if (c->clip.scales_valid && (int64_t)c->weights.size() == n) return PGH_OK;
-    std::vector<int32_t> slots((size_t)n);
-    for (int64_t k = 0; k < n; ++k) slots[(size_t)k] = (int32_t)k;
-    std::vector<double> norms;
-    RC(clip_set_scales(c, slots.data(), (int)n, 0, &norms));
-    c->clip.count(c->weights.data(), norms.data(), n);
-    c->clip.scales_valid = true;
-    return PGH_OK;
-}
-
-// ---- geometric-median FedAvg: the included rows, K12, the inner iterations, the final weights -----------------
 
 namespace {
-// f(rows, k0, m) for each run of the listed slots a launch can take: all of them when they are consecutive,
-// else RowTabs of at most ROWTAB_MAX; k0 = the fold index of the run's first row.
-template <class F>
-int for_row_runs(pgh_ctx* c, const std::vector<int32_t>& slots, F&& f) {
-    bool run = true;
-    for (size_t k = 0; k < slots.size(); ++k) run = run && slots[k] == slots[0] + (int32_t)k;
-    if (run) return f(pgh::Rows{nullptr, nullptr, slots[0] * c->parties}, (size_t)0, slots.size());
-    for (size_t done = 0; done < slots.size(); done += pgh::ROWTAB_MAX) {
-        const size_t m = std::min(slots.size() - done, (size_t)pgh::ROWTAB_MAX);
-        pgh::RowTab tab;
-        for (size_t k = 0; k < m; ++k) tab.rows[k] = slots[done + k] * c->parties;
-        RC(f(pgh::Rows{&tab}, done, m));
+// sums[lo, hi] of the listed slots from the device to their pinned image on stream s.  Entries of other slots
+// inside [lo, hi] are rewritten with what the device holds for them: the same value an earlier copy brought
+// (same stream), or one nobody reads.
+int sums_d2h(pgh_ctx* c, const int32_t* slots, size_t n, double* h, const double* d, hipStream_t s) {
+    const auto mm = std::minmax_element(slots, slots + n);
+    const int32_t lo = *mm.first, hi = *mm.second;
+    CK(c, hipMemcpyAsync(h + lo, d + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
+    return PGH_OK;
+}
+}  // namespace
+
+int RowSums::queue(pgh_ctx* c, const int32_t* slots, int n) {
+    std::vector<int32_t> todo;
+    for (int k = 0; k < n; ++k)
+        if (state[(size_t)slots[k]] == NONE) todo.push_back(slots[k]);
+    if (todo.empty()) return PGH_OK;
+    RC(ensure(c));
+    pgh::SumsqArgs a = args(c, d_sq.as<double>());
+    const hipStream_t s = c->copy;
+    // HBM bytes: the rows, the tile partials out
+    RC(for_row_runs(c, todo.data(), todo.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
+        a.n_rows = (int)m;
+        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 8ull * (uint64_t)a.ntiles);
+        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_sumsq(a, rows, s); });
+    }));
+    RC(sums_d2h(c, todo.data(), todo.size(), h_sq.as<double>(), d_sq.as<double>(), s));
+    CK(c, hipEventRecord(ev, s));
+    for (int32_t sl : todo) {
+        state[(size_t)sl] = QUEUED;
+        queued.push_back(sl);
     }
     return PGH_OK;
 }
 
-int geomed_planes(pgh_ctx* c, hipStream_t s) {
-    GeomedState& g = c->geo;
-    if (g.d_nz && g.d_negv) return PGH_OK;
-    const size_t bytes = 4 * (size_t)c->pvec;
-    if (!g.d_nz.reserve(bytes) || !g.d_negv.reserve(bytes)) {
-        g.d_nz.reset();
-        g.d_negv.reset();
-        return fail(c, PGH_E_OOM, "allocation of the geometric median's planes (%zu bytes each) failed", bytes);
+int RowSums::wait(pgh_ctx* c) {
+    if (queued.empty()) return PGH_OK;
+    CK(c, hipEventSynchronize(ev));
+    for (int32_t sl : queued)
+        if (state[(size_t)sl] == QUEUED) {
+            value[(size_t)sl] = h_sq.as<double>()[sl];
+            state[(size_t)sl] = VALID;
+        }
+    queued.clear();
+    return PGH_OK;
+}
+
+// (K7's tile partials are free: every queued K7 has been waited for.)
+int RowSums::distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* negv, hipStream_t s, double* D) {
+    RC(wait(c));
+    RC(ensure(c));
+    if (!d_dist.reserve(8 * (size_t)c->slots) || !h_dist.reserve(8 * (size_t)c->slots))
+        return fail(c, PGH_E_OOM, "allocation of the geometric median's distances (%d rows) failed", c->slots);
+    pgh::DistsqArgs a{args(c, d_dist.as<double>()), negv};
+    // HBM bytes: the rows, the partials out and in again; the plane once per row chunk (from L2 mostly)
+    RC(for_row_runs(c, slots.data(), slots.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
+        a.s.n_rows = (int)m;
+        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
+        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_distsq(a, rows, s); });
+    }));
+    RC(sums_d2h(c, slots.data(), slots.size(), h_dist.as<double>(), d_dist.as<double>(), s));
+    CK(c, hipStreamSynchronize(s));
+    for (size_t k = 0; k < slots.size(); ++k) D[k] = h_dist.as<double>()[slots[k]];
+    return PGH_OK;
+}
+
+// ---- clipped FedAvg: the scales and the tallies ------------------------------------------------------------
+
+float clip_scale_of(double sumsq, float c) {
+    const double norm = std::sqrt(sumsq);
+    return norm <= (double)c ? 1.0f : (float)((double)c / norm);
+}
+
+namespace {
+// weights[c0 + k] = the scale of slots[k] (K7 for the sums still missing in one batch, then the wait); norms
+// receives sqrt(sumsq) beside them
+int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms) {
+    RC(c->rowsums.queue(c, slots, n));
+    RC(c->rowsums.wait(c));
+    std::vector<float>& w = c->fw.replace(FoldWeights::CLIP);
+    w.resize((size_t)(c0 + n));
+    norms->resize((size_t)(c0 + n));
+    for (int k = 0; k < n; ++k) {
+        const double ss = c->rowsums.at(slots[k]);
+        w[(size_t)(c0 + k)] = clip_scale_of(ss, c->clip.c);
+        (*norms)[(size_t)(c0 + k)] = std::sqrt(ss);
     }
-    CK(c, hipMemsetD32Async((hipDeviceptr_t)g.d_nz.as<void>(), (int)0x80000000u, (size_t)c->pvec, s));
-    // (the -0 plane is only ever read on the context's stream, behind this)
+    return PGH_OK;
+}
+
+std::vector<int32_t> first_slots(int64_t n) {  // resident folds: client k is in slot k
+    std::vector<int32_t> slots((size_t)n);
+    for (int64_t k = 0; k < n; ++k) slots[(size_t)k] = (int32_t)k;
+    return slots;
+}
+
+// Resident folds in PGH_CLIPPED_MEAN: the scales of clients [0, n), computed once per state of the slab --
+// the range form and repeated folds reuse them.
+int resident_clip_scales(pgh_ctx* c, int64_t n) {
+    if (c->fw.valid(FoldWeights::CLIP, n)) return PGH_OK;
+    std::vector<double> norms;
+    RC(clip_set_scales(c, first_slots(n).data(), (int)n, 0, &norms));
+    c->clip.count(c->fw.v.data(), norms.data(), n);
+    c->fw.validate(n);
+    return PGH_OK;
+}
+
+// ---- geometric-median FedAvg: the included rows, the inner iterations, the final weights ---------------------
+
+int geomed_plane(pgh_ctx* c, hipStream_t s) {  // the iterate plane, -0 until something is written to it
+    GeomedState& g = c->geo;
+    RC(c->nz.ensure(c, s));
+    if (g.d_negv) return PGH_OK;
+    if (!g.d_negv.reserve(4 * (size_t)c->pvec))
+        return fail(c, PGH_E_OOM, "allocation of the geometric median's planes (%zu bytes each) failed", 4 * (size_t)c->pvec);
     return hipMemsetD32Async((hipDeviceptr_t)g.d_negv.as<void>(), (int)0x80000000u, (size_t)c->pvec, s) == hipSuccess
                ? PGH_OK
                : fail(c, PGH_E_HIP, "hipMemsetD32Async of the iterate plane failed");
 }
 
-// K12 over the listed slots against d_negv on stream s, the D2H of the sums and the wait: D[k] = the
-// squared distance of slots[k].  (K7's tile partials are free: every queued K7 has been waited for.)
-int distsq_run(pgh_ctx* c, const std::vector<int32_t>& slots, hipStream_t s, double* D) {
-    GeomedState& g = c->geo;
-    RC(sumsq_wait(c));
-    RC(ensure_sumsq_buffers(c));
-    if (!g.d_dist.reserve(8 * (size_t)c->slots) || !g.h_dist.reserve(8 * (size_t)c->slots))
-        return fail(c, PGH_E_OOM, "allocation of the geometric median's distances (%d rows) failed", c->slots);
-    pgh::DistsqArgs a{};
-    a.s.slab = c->d_slab.as<float>();
-    a.s.map = slab_map(c);
-    a.s.p = c->pg;
-    a.s.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
-    a.s.part = c->clip.d_sq_part.as<double>();
-    a.s.sumsq = g.d_dist.as<double>();
-    a.negv = g.d_negv.as<float>();
-    // HBM bytes: the rows, the partials out and in again; the plane once per row chunk (from L2 mostly)
-    RC(for_row_runs(c, slots, [&](const pgh::Rows& rows, size_t, size_t m) {
-        a.s.n_rows = (int)m;
-        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
-        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_distsq(a, rows, s); });
-    }));
-    int32_t lo = slots[0], hi = slots[0];
-    for (int32_t sl : slots) {
-        lo = std::min(lo, sl);
-        hi = std::max(hi, sl);
-    }
-    CK(c, hipMemcpyAsync(g.h_dist.as<double>() + lo, g.d_dist.as<double>() + lo, 8 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, s));
-    CK(c, hipStreamSynchronize(s));
-    for (size_t k = 0; k < slots.size(); ++k) D[k] = g.h_dist.as<double>()[slots[k]];
-    return PGH_OK;
-}
-}  // namespace
-
-int geomed_fold(pgh_ctx* c, bool final, const FinalArgs& fa, hipStream_t s) {
-    const std::vector<int32_t>& inc = c->geo.rows;
-    return for_row_runs(c, inc, [&](const pgh::Rows& rows, size_t k0, size_t m) {
-        const int flags = (k0 == 0 ? pgh::FL_FIRST : 0) | (final && k0 + m == inc.size() ? pgh::FL_FINAL : 0);
-        FoldRows fr{rows.tab ? c->d_slab.as<float>() : (const float*)slot_row(c, inc[0], 0), (int)m, rows};
-        fr.src.row0 = 0;  // (the fold takes contiguous rows from its slab pointer)
-        return fold_launch(c, PGH_GEOMETRIC_MEDIAN, fr, (int64_t)k0, flags, fa, s);
-    });
-}
-
+// The final weights of a close over slots[0, n) in fold order (the included rows into geo.rows, their weights
+// into the context's, W into geo.W): the inner iterations run whole-shard on the context's stream and are
+// finished when this returns.  PGH_E_STATE with no row included; nothing is launched then.
 int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
     GeomedState& g = c->geo;
-    g.weights_valid = false;
-    c->clip.scales_valid = false;  // (the context's weights become this rule's)
-    RC(sumsq_queue(c, slots, n));
-    RC(sumsq_wait(c));
+    c->fw.stale();  // (the context's weights become this rule's, whatever happens below)
+    RC(c->rowsums.queue(c, slots, n));
+    RC(c->rowsums.wait(c));
     std::vector<int32_t> inc;
     std::vector<double> D;
     for (int k = 0; k < n; ++k) {
-        const double ss = c->clip.sq_host[(size_t)slots[k]];
+        const double ss = c->rowsums.at(slots[k]);
         if (!std::isfinite(ss)) continue;  // excluded: no fold and no distance pass reads the row
         inc.push_back(slots[k]);
         D.push_back(ss);
@@ -404,24 +363,23 @@ int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
     for (int t = 0;; ++t) {
         if (!geomed_step(D.data(), (int64_t)D.size(), g.nu, w.data(), &W, &obj, &mx))
             return fail(c, PGH_E_STATE, "geometric median: no finite distance in iteration %d", t);
-        c->weights = w;
-        c->weights_on_device = false;
+        c->fw.replace(FoldWeights::GEOMED) = w;
         if (t == g.iters - 1) break;
         // v^(t+1) as -v: the weighted fold against the -0 plane, whole shard; then every row's distance to it
         if (t == 0) {
             RC(order_after_ingest(c, s));
-            RC(geomed_planes(c, s));
+            RC(geomed_plane(c, s));
         }
         RC(fold_prepare(c, PGH_GEOMETRIC_MEDIAN, (int64_t)inc.size(), s));
         FinalArgs fa;
-        fa.ckpt = g.d_nz.as<float>();
+        fa.ckpt = c->nz.get();
         fa.out = g.d_negv.as<float>();
         fa.divisor = W;
         fa.off = 0;
         fa.len = c->pg;
         fa.plain = true;
-        RC(geomed_fold(c, true, fa, s));
-        RC(distsq_run(c, inc, s, D.data()));
+        RC(fold_listed(c, PGH_GEOMETRIC_MEDIAN, inc.data(), inc.size(), true, fa, s));
+        RC(c->rowsums.distsq(c, inc, g.d_negv.as<float>(), s, D.data()));
     }
     g.W = W;
     g.n_rows = n;
@@ -431,31 +389,69 @@ int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
     return PGH_OK;
 }
 
-int geomed_resident_weights(pgh_ctx* c, int64_t n) {
-    GeomedState& g = c->geo;
-    if (g.weights_valid && g.n_valid == n && c->weights.size() == g.rows.size()) return PGH_OK;
-    std::vector<int32_t> slots((size_t)n);
-    for (int64_t k = 0; k < n; ++k) slots[(size_t)k] = (int32_t)k;
-    RC(geomed_slot_weights(c, slots.data(), (int)n));
-    g.weights_valid = true;
-    g.n_valid = n;
+int geomed_resident_weights(pgh_ctx* c, int64_t n) {  // clients [0, n) in slots [0, n), once per slab state
+    if (c->fw.valid(FoldWeights::GEOMED, n) && c->fw.v.size() == c->geo.rows.size()) return PGH_OK;
+    RC(geomed_slot_weights(c, first_slots(n).data(), (int)n));
+    c->fw.validate(n);
+    return PGH_OK;
+}
+}  // namespace
+
+// ---- the fold plans: what the drivers ask before their launches ------------------------------------------------
+
+namespace {
+void geomed_plan(pgh_ctx* c, FoldPlan* p) {  // the included rows alone, fold client k = the k-th of them
+    p->slots = c->geo.rows.data();
+    p->n = (int)c->geo.rows.size();
+    p->total = p->n;
+    p->has_divisor = true;
+    p->divisor = c->geo.W;
+    p->whole_rows = true;
+}
+}  // namespace
+
+int rules_slot_plan(pgh_ctx* c, int mode, const int32_t* slots, int n, int64_t c0, FoldPlan* p) {
+    *p = FoldPlan{slots, n, c0 + n};
+    if (mode == PGH_CLIPPED_MEAN) {  // a scale needs the whole row of the last report
+        p->whole_rows = true;
+        if (n == 0) return PGH_OK;
+        if (c0 == 0) c->clip.norms.clear();
+        return clip_set_scales(c, slots, n, c0, &c->clip.norms);  // scales and norms at fold index c0
+    }
+    if (mode == PGH_GEOMETRIC_MEDIAN) {
+        RC(geomed_slot_weights(c, slots, n));
+        geomed_plan(c, p);
+    }
+    return PGH_OK;
+}
+
+int rules_resident_plan(pgh_ctx* c, int mode, int64_t c0, int64_t n, FoldPlan* p) {
+    *p = FoldPlan{nullptr, (int)n, c0 + n};
+    // (resident only, check_mode_use: clients [0, n) -- their scales become the fold's weights)
+    if (mode == PGH_CLIPPED_MEAN) {
+        p->whole_rows = true;
+        return resident_clip_scales(c, n);
+    }
+    if (mode == PGH_GEOMETRIC_MEDIAN) {
+        RC(geomed_resident_weights(c, n));
+        geomed_plan(c, p);
+    }
+    return PGH_OK;
+}
+
+int trim_divisor(pgh_ctx* c, int64_t n, float* div) {  // b dropped per side; at least one value must be left
+    if (n < 2 * (int64_t)c->trim.b + 1)
+        return fail(c, PGH_E_STATE, "trimmed mean with b = %d needs at least %d diffs, have %lld", c->trim.b,
+                    2 * c->trim.b + 1, (long long)n);
+    *div = (float)(n - 2 * (int64_t)c->trim.b);
     return PGH_OK;
 }
 
 // ---- Gaussian noise on the clipped close: the planes and K11 behind a FINAL launch ---------------------------
 
-int noise_planes(pgh_ctx* c, hipStream_t s) {
-    NoiseState& ns = c->noise;
-    if (ns.d_nz && ns.d_d) return PGH_OK;
-    const size_t bytes = 4 * (size_t)c->pvec;
-    if (!ns.d_nz.reserve(bytes) || !ns.d_d.reserve(bytes)) {
-        ns.d_nz.reset();
-        ns.d_d.reset();
-        return fail(c, PGH_E_OOM, "allocation of the noise planes (%zu bytes each) failed", bytes);
-    }
-    CK(c, hipMemsetD32Async((hipDeviceptr_t)ns.d_nz.as<void>(), (int)0x80000000u, (size_t)c->pvec, s));
-    CK(c, hipStreamSynchronize(s));  // (a later FINAL may read the plane on another caller's stream)
-    return PGH_OK;
+int noise_plane(pgh_ctx* c) {
+    if (c->noise.d_d || c->noise.d_d.reserve(4 * (size_t)c->pvec)) return PGH_OK;
+    return fail(c, PGH_E_OOM, "allocation of the noise planes (%zu bytes each) failed", 4 * (size_t)c->pvec);
 }
 
 int dp_noise_launch(pgh_ctx* c, const FinalArgs& fa, int64_t n, bool into_opt, hipStream_t s) {
@@ -496,12 +492,12 @@ int pgh_set_clip_norm(pgh_ctx* c, float bound) {
     if (!c) return PGH_E_ARG;
     if (bound == 0.f) {  // off: always possible (a group never clips)
         c->clip.c = 0.f;
-        c->clip.scales_valid = false;
+        c->fw.stale(FoldWeights::CLIP);
         return PGH_OK;
     }
     RC(check_clip_ctx(c, "pgh_set_clip_norm"));
     if (!(bound > 0.f) || !std::isfinite(bound)) return fail(c, PGH_E_ARG, "the clipping bound must be finite and > 0, or 0 for off");
-    if (bound != c->clip.c) c->clip.scales_valid = false;
+    if (bound != c->clip.c) c->fw.stale(FoldWeights::CLIP);
     c->clip.c = bound;
     return PGH_OK;
 }
@@ -522,15 +518,12 @@ int pgh_row_sumsq(pgh_ctx* c, const int32_t* slots, int n, double* out) {
     RC(check_dtype(c, PGH_F32));
     if (c->streaming) return fail(c, PGH_E_UNSUPPORTED, "pgh_row_sumsq: the context is streaming");
     if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
-    for (int k = 0; k < n; ++k) {
-        if (slots[k] < 0 || slots[k] >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", slots[k], c->slots);
-        if (c->slot_client[(size_t)slots[k]] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", slots[k]);
-    }
+    RC(check_slot_list(c, slots, n, false));
     DeviceGuard g(c->device);
-    RC(sumsq_queue(c, slots, n));
+    RC(c->rowsums.queue(c, slots, n));
     if (!out) return PGH_OK;
-    RC(sumsq_wait(c));
-    for (int k = 0; k < n; ++k) out[k] = c->clip.sq_host[(size_t)slots[k]];
+    RC(c->rowsums.wait(c));
+    for (int k = 0; k < n; ++k) out[k] = c->rowsums.at(slots[k]);
     return PGH_OK;
 }
 
@@ -540,13 +533,13 @@ int pgh_set_geomed(pgh_ctx* c, int iters, float nu) {
     if (!c) return PGH_E_ARG;
     if (iters == 0) {  // off: always possible
         c->geo.iters = 0;
-        c->geo.weights_valid = false;
+        c->fw.stale(FoldWeights::GEOMED);
         return PGH_OK;
     }
     RC(check_clip_ctx(c, "pgh_set_geomed"));
     if (iters < 0 || iters > PGH_GEOMED_MAX_ITERS) return fail(c, PGH_E_ARG, "geometric median: %d iterations outside [0,%d]", iters, PGH_GEOMED_MAX_ITERS);
     if (!(nu > 0.f) || !std::isfinite(nu)) return fail(c, PGH_E_ARG, "geometric median: the smoothing must be finite and > 0");
-    if (iters != c->geo.iters || nu != c->geo.nu) c->geo.weights_valid = false;
+    if (iters != c->geo.iters || nu != c->geo.nu) c->fw.stale(FoldWeights::GEOMED);
     c->geo.iters = iters;
     c->geo.nu = nu;
     return PGH_OK;
@@ -556,20 +549,17 @@ int pgh_row_distsq(pgh_ctx* c, const int32_t* slots, int n, const float* point, 
     RC(check_clip_ctx(c, "pgh_row_distsq"));
     RC(check_dtype(c, PGH_F32));
     if (n < 0 || (n > 0 && (!slots || !point || !out))) return fail(c, PGH_E_ARG, "bad slot list, point or out (n=%d)", n);
-    for (int k = 0; k < n; ++k) {
-        if (slots[k] < 0 || slots[k] >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", slots[k], c->slots);
-        if (c->slot_client[(size_t)slots[k]] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", slots[k]);
-    }
+    RC(check_slot_list(c, slots, n, false));
     if (n == 0) return PGH_OK;
     DeviceGuard g(c->device);
     const hipStream_t s = c->stream;
     RC(order_after_ingest(c, s));
-    RC(geomed_planes(c, s));
+    RC(geomed_plane(c, s));
     std::vector<float> neg((size_t)c->pg);
     for (int64_t i = 0; i < c->pg; ++i) neg[(size_t)i] = -point[i];
     CK(c, hipMemcpyAsync(c->geo.d_negv.as<float>(), neg.data(), 4 * (size_t)c->pg, hipMemcpyHostToDevice, s));
     CK(c, hipStreamSynchronize(s));  // neg is pageable: the copy has left it
-    return distsq_run(c, std::vector<int32_t>(slots, slots + n), s, out);
+    return c->rowsums.distsq(c, std::vector<int32_t>(slots, slots + n), c->geo.d_negv.as<float>(), s, out);
 }
 
 int pgh_geomed_stats(pgh_ctx* c, int* iters, int64_t* n_rows, int64_t* n_excluded, double* objective, float* max_weight) {
@@ -597,7 +587,7 @@ int pgh_clip_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_clipped, double* max_
     ClipState& cl = c->clip;
     const int64_t rows0 = cl.rows, cl0 = cl.clipped;
     const double mx0 = cl.max_norm;
-    cl.count_cycle(c->weights);
+    cl.count_cycle(c->fw.v);
     if (n_rows) *n_rows = cl.rows;
     if (n_clipped) *n_clipped = cl.clipped;
     if (max_norm) *max_norm = cl.max_norm;

@@ -1,5 +1,7 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trim, med and opt.  Their owners release with the context.
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trim, med and opt, and what they share: the row
+// sums (RowSums, rowsums), the fold's weights (FoldWeights, fw) and the -0 plane (NegZeroPlane, nz).  Their owners
+// release with the context.
 // The code that works on them: pgh_rules.cpp (clip, geo, trim, med and the lifecycle calls rules_*),
 // pgh_serveropt.cpp (opt).  Not installed.
 #pragma once
@@ -8,40 +10,123 @@
 #include <utility>
 #include <vector>
 
+#include <hip/hip_runtime.h>
+
+#include "pgh_kernels.h"
 #include "pgh_res.h"
+
+struct pgh_ctx;
 
 namespace pgh_detail {
 
-// Clipped FedAvg (pgh_set_clip_norm, PGH_CLIPPED_MEAN).  K7 (k_row_sumsq)
-// runs on the copy stream -- behind the row's ingest, ahead of any later overwrite of the slot --
-// and its sum comes back through h_sq in a small D2H on the same stream, followed by sq_ev.
-// sq_state: NONE (no sum of the slot's present diff), QUEUED (K7 + D2H issued, value lands in
-// h_sq before the latest sq_ev), VALID (sq_host holds it).  Any ingest into a slot resets it.
+// What the row-wise rules share (clipping and the geometric median today): the per-slot cache of K7's sums of
+// squares and everything device-side that either row reduction (K7, K12) needs.  K7 (k_row_sumsq) runs on the
+// copy stream -- behind the row's ingest, ahead of any later overwrite of the slot -- and its sum comes back
+// through h_sq in a small D2H on the same stream, followed by ev.  K12 runs on the stream its caller gives and
+// its sums come back through h_dist behind a wait.  A slot's state: NONE (no sum of the slot's present diff),
+// QUEUED (K7 + D2H issued, the value lands in h_sq before the latest ev), VALID (at() holds it).  Any ingest
+// into a slot resets it.  The methods are in pgh_rules.cpp.
+struct RowSums {
+    enum : uint8_t { NONE = 0, QUEUED = 1, VALID = 2 };
+    std::vector<uint8_t> state;     // per slot
+    std::vector<double> value;      // per slot: the cached sum of squares
+    std::vector<int32_t> queued;    // slots that went QUEUED since the last harvest
+    DeviceBuf d_part;               // double [slots][ceil(pg / SUMSQ_TILE)] tile partials, K7's and K12's
+    DeviceBuf d_sq, d_dist;         // double [slots]: K7's sums; K12's, by slab row
+    PinnedBuf h_sq, h_dist;         // double [slots]
+    Event ev;
+
+    double at(int slot) const { return value[(size_t)slot]; }  // after wait(): the sum of a slot queued before it
+    void reserved(int slots) {  // pgh_reserve: the cache at its new length
+        state.assign((size_t)slots, (uint8_t)NONE);
+        value.assign((size_t)slots, 0.0);
+    }
+    // The diffs in slots [slot, slot + n) are being replaced: their cached sums were the old diffs'.  The one
+    // place a sum goes to NONE slot by slot.
+    void slot_written(int slot, int n) { std::fill_n(state.begin() + slot, n, (uint8_t)NONE); }
+    void forget() {  // every slot back to NONE (pgh_reset)
+        slot_written(0, (int)state.size());
+        queued.clear();
+    }
+    void slab_freed() {  // the streams are idle: every buffer sized by the slab goes, and the cache
+        for (auto* v : {&d_part, &d_sq, &d_dist}) v->reset();
+        h_sq.reset();
+        h_dist.reset();
+        state.clear();
+        value.clear();
+        queued.clear();
+    }
+    // f(rows, k0, m) for each run of the listed slots a launch can take: all of them when they are consecutive,
+    // else RowTabs of at most ROWTAB_MAX; k0 = the fold index of the run's first row.  (pgh_ctx.h)
+    template <class F>
+    static int for_runs(pgh_ctx* c, const int32_t* slots, size_t n, F&& f);
+    // the kernel arguments of either reduction from the context, the sums going to `sums`
+    pgh::SumsqArgs args(pgh_ctx* c, double* sums) const;
+    int ensure(pgh_ctx* c);  // the tile partials, the sums buffer and its pinned image: all three or none
+    // K7 on the copy stream for those of `slots` that have no sum yet, and the D2H of the sums
+    int queue(pgh_ctx* c, const int32_t* slots, int n);
+    int wait(pgh_ctx* c);  // the queued sums are in at() afterwards
+    // K12 over the listed slots against negv on stream s, the D2H of the sums and the wait: D[k] = the squared
+    // distance of slots[k]
+    int distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* negv, hipStream_t s, double* D);
+};
+
+// The fold's per-client weights (fold order) and their device copy.  Three writers: the caller
+// (pgh_set_weights), the clip scales, the geometric median's final weights.  A rule that wrote them for the
+// resident slab as it is marks them valid for clients [0, n): range folds and repeated closes reuse them.
+// PGH_WEIGHTED_MEAN folds with whatever the vector holds, whoever wrote it.
+struct FoldWeights {
+    enum Writer : uint8_t { CALLER = 0, CLIP = 1, GEOMED = 2 };
+    std::vector<float> v;
+    DeviceBuf d;             // float per client
+    bool on_device = false;
+    Writer writer = CALLER;  // who replaced the contents last
+    int64_t n_valid = -1;    // >= 0: `writer`'s weights of resident clients [0, n_valid) of the slab as it is
+
+    // The contents are about to be replaced (or were): the one place that drops the device copy's claim and
+    // the validity.  Returns the vector to write.
+    std::vector<float>& replace(Writer w) {
+        on_device = false;
+        writer = w;
+        n_valid = -1;
+        return v;
+    }
+    void clear() { replace(CALLER).clear(); }
+    // the slab or a rule's setting changed under the contents: they stay, a resident fold of the rule computes anew
+    void stale() { n_valid = -1; }
+    void stale(Writer w) { if (writer == w) stale(); }
+    bool valid(Writer w, int64_t n) const { return writer == w && n_valid == n; }
+    void validate(int64_t n) { n_valid = n; }
+    void slab_freed() {  // the device copy goes with the slab's other buffers; the contents stay
+        d.reset();
+        replace(writer);
+    }
+    int upload(pgh_ctx* c, hipStream_t s);  // the contents on the device when this returns (pgh_reduce.cpp)
+};
+
+// The context's plane of -0.0f, float [pvec]: a FINAL fold against it writes -avg (the server optimizer's and the
+// noise's delta planes, the geometric median's iterate).  Allocated and filled by the first tenant that needs it,
+// complete before ensure returns; released where the shard or pvec changes and with the context, never when
+// a tenant is switched off or the slab is reserved again.
+struct NegZeroPlane {
+    DeviceBuf d;
+    int ensure(pgh_ctx* c, hipStream_t s);  // pgh_rules.cpp
+    const float* get() const { return d.as<float>(); }
+};
+
+// Clipped FedAvg (pgh_set_clip_norm, PGH_CLIPPED_MEAN): the bound, the norms of the running
+// cycle's slot folds and the tallies.  The sums: RowSums; the scales: FoldWeights (writer CLIP).
 struct ClipState {
-    enum : uint8_t { SQ_NONE = 0, SQ_QUEUED = 1, SQ_VALID = 2 };
     float c = 0.f;                    // the L2 bound; 0 = clipping off
-    std::vector<uint8_t> sq_state;    // per slot
-    std::vector<double> sq_host;      // per slot: the cached sum of squares
-    std::vector<int32_t> sq_queued;   // slots that went QUEUED since the last harvest
-    DeviceBuf d_sq_part;              // double [slots][ceil(pg / SUMSQ_TILE)] tile partials
-    DeviceBuf d_sq;                   // double [slots]
-    PinnedBuf h_sq;                   // double [slots]
-    Event sq_ev;
-    // the scales live in the context's `weights` (fold order) and go to the device like weights.  Resident
-    // folds: scales_valid says weights[0, n) are the scales of the slab as it is (range folds reuse them).
-    bool scales_valid = false;
-    std::vector<double> norms;        // slot folds of the running cycle, in fold order (beside weights)
+    std::vector<double> norms;        // slot folds of the running cycle, in fold order (beside the weights)
     int64_t rows = 0, clipped = 0;    // folds finished since pgh_reset / pgh_reserve
     double max_norm = 0.0;
 
-    // The diffs in slots [slot, slot + n) are being replaced: their cached sums were the old diffs', and the
-    // slab is no longer the one the resident scales were computed for.  The one place a sum goes to NONE
-    // slot by slot.
-    void slot_written(int slot, int n = 1) {
-        std::fill_n(sq_state.begin() + slot, n, (uint8_t)SQ_NONE);
-        scales_valid = false;
+    void forget() {  // the running cycle and the totals (pgh_reset)
+        norms.clear();
+        rows = clipped = 0;
+        max_norm = 0.0;
     }
-    void forget();  // every slot back to SQ_NONE, the scales, the running cycle and the totals (pgh_reset)
     void count(const float* scales, const double* row_norms, int64_t n);  // rows into the finished totals
     // the slot folds of the running cycle into the finished totals: scales[k] beside norms[k]
     void count_cycle(const std::vector<float>& scales) {
@@ -51,21 +136,20 @@ struct ClipState {
 
 // Gaussian noise on the clipped close (pgh_set_dp_noise): a modifier of the clip
 // rule, not a rule of its own.  With z > 0 fold_launch runs every fp32 FINAL -- PGH_CLIPPED_MEAN only,
-// any other mode is refused -- against a -0 plane into a delta plane and K11 behind it: the server
-// optimizer's planes when one is set (K10 follows K11), else the two owned here, allocated by the first
+// any other mode is refused -- against the context's -0 plane into a delta plane and K11 behind it: the server
+// optimizer's delta plane when one is set (K10 follows K11), else the one owned here, allocated by the first
 // noised FINAL.  The setting belongs to the model like the optimizer's: pgh_reset / pgh_reserve keep it,
 // a new layout or shard clears it (rules_shard_set).
 struct NoiseState {
     float z = 0.f;        // the noise multiplier; 0 = off
     uint64_t key = 0;
     uint32_t round = 0;
-    DeviceBuf d_nz, d_d;  // float [pvec]: -0.0f everywhere; d = -g of the last noised FINAL without an optimizer
-    int64_t pvec = 0;     // the planes' length
+    DeviceBuf d_d;        // float [pvec]: d = -g of the last noised FINAL without an optimizer
+    int64_t pvec = 0;     // the plane's length
     double sigma_last = 0.0;  // what the last noised FINAL used: z * C / N, and N
     int64_t n_last = 0;
 
-    void release() {  // planes and setting; the caller has waited for the context's work
-        d_nz.reset();
+    void release() {  // plane and setting; the caller has waited for the context's work
         d_d.reset();
         z = 0.f;
         pvec = 0;
@@ -73,38 +157,30 @@ struct NoiseState {
 };
 
 // Geometric-median FedAvg (pgh_set_geomed, PGH_GEOMETRIC_MEDIAN): the smoothed
-// Weiszfeld iteration.  With the rule on every ingest queues K7 like clipping (the cached sums are iteration
-// 0's squared distances and say which rows are excluded).  A close computes the final weights on the
+// Weiszfeld iteration.  With the rule on every ingest queues K7 like clipping (RowSums: the cached sums are
+// iteration 0's squared distances and say which rows are excluded).  A close computes the final weights on the
 // context's stream -- per inner iteration a weighted fold against the -0 plane into d_negv (= -v), K12
-// against it, a D2H of the distances, the host step -- and leaves them in the context's `weights` (fold
-// order of the included rows) for the one FINAL fold, which is the weighted fold over `rows`.  Both planes
-// are float [pvec], allocated by the first close that iterates (iters >= 2) or by pgh_row_distsq.
+// against it, a D2H of the distances, the host step -- and leaves them in the context's FoldWeights (writer
+// GEOMED, fold order of the included rows) for the one FINAL fold, which is the weighted fold over `rows`.
+// The iterate plane is float [pvec], allocated by the first close that iterates (iters >= 2) or by pgh_row_distsq.
 struct GeomedState {
     int iters = 0;                  // 0 = the rule is off
     float nu = 0.f;
     std::vector<int32_t> rows;      // the included slots, in fold order
     float W = 0.f;                  // the f32 left fold of the final weights
-    // Resident folds: weights[0, rows.size()) are the final weights of the slab as it is, computed for
-    // clients [0, n_valid) -- range folds and repeated closes reuse them.
-    bool weights_valid = false;
-    int64_t n_valid = 0;
-    DeviceBuf d_nz, d_negv;         // -0.0f everywhere; -v of the last inner iteration (or -point)
-    DeviceBuf d_dist;               // double [slots]: K12's sums, by slab row
-    PinnedBuf h_dist;               // double [slots]
+    DeviceBuf d_negv;               // -v of the last inner iteration (or -point)
     // what the last computation of the weights saw (pgh_geomed_stats)
     int64_t n_rows = 0, n_excluded = 0;
     double objective = 0.0;
     float max_weight = 0.f;
 
-    void forget() {  // the weights and the tallies (pgh_reset); the setting stays
-        weights_valid = false;
+    void forget() {  // the included rows and the tallies (pgh_reset); the setting stays
         rows.clear();
         n_rows = n_excluded = 0;
         objective = 0.0;
         max_weight = 0.f;
     }
-    void release() {  // planes and setting; the caller has waited for the context's work
-        d_nz.reset();
+    void release() {  // plane and setting; the caller has waited for the context's work
         d_negv.reset();
         iters = 0;
         nu = 0.f;
@@ -132,14 +208,14 @@ struct MedianState {
 };
 
 // Server optimizer (pgh_set_server_opt).  With one set, fold_launch runs every
-// fp32 FINAL against the -0 plane into the delta plane and K10 behind it, which reads the committed
+// fp32 FINAL against the context's -0 plane into the delta plane and K10 behind it, which reads the committed
 // moments and writes the pending ones; pgh_server_opt_commit swaps the two.  All planes are
 // float [pvec] and belong to the model: pgh_reset / pgh_reserve keep them (rules_slab_freed does not
 // touch them), a new layout or shard drops them and the setting (rules_shard_set -> release).
 struct ServerOptState {
     int kind = 0;  // pgh_server_opt; 0 = off
     float lr = 0.f, beta1 = 0.f, beta2 = 0.f, tau = 0.f, c1 = 0.f, c2 = 0.f;
-    DeviceBuf d_nz, d_d;          // -0.0f everywhere; d = -g of the last FINAL
+    DeviceBuf d_d;                // d = -g of the last FINAL
     DeviceBuf d_m, d_v;           // committed
     DeviceBuf d_m2, d_v2;         // pending: written by K10, committed by the swap
     bool pending = false;         // a FINAL has run since the last commit / upload / (re)initialisation

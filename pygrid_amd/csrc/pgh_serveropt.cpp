@@ -38,7 +38,7 @@ int server_opt_launch(pgh_ctx* c, const FinalArgs& fa, hipStream_t s) {
 }
 
 void ServerOptState::release() {
-    for (auto* v : {&d_nz, &d_d, &d_m, &d_v, &d_m2, &d_v2}) v->reset();
+    for (auto* v : {&d_d, &d_m, &d_v, &d_m2, &d_v2}) v->reset();
     kind = PGH_OPT_NONE;
     nothing_pending();
     steps = 0;
@@ -112,7 +112,7 @@ int pgh_set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2,
     so.release();
     const size_t bytes = 4 * (size_t)c->pvec;
     const bool adaptive = kind != PGH_OPT_MOMENTUM;
-    if (!so.d_nz.reserve(bytes) || !so.d_d.reserve(bytes) || !so.d_m.reserve(bytes) || !so.d_m2.reserve(bytes) ||
+    if (!so.d_d.reserve(bytes) || !so.d_m.reserve(bytes) || !so.d_m2.reserve(bytes) ||
         (adaptive && (!so.d_v.reserve(bytes) || !so.d_v2.reserve(bytes)))) {
         so.release();
         return fail(c, PGH_E_OOM, "allocation of the server optimizer's planes (%zu bytes each) failed", bytes);
@@ -121,8 +121,8 @@ int pgh_set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2,
     so.lr = lr; so.beta1 = beta1; so.beta2 = beta2; so.tau = tau;
     so.c1 = 1.0f - beta1;
     so.c2 = 1.0f - beta2;
-    const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)so.d_nz.as<void>(), (int)0x80000000u, (size_t)c->pvec, c->stream);
-    const int rc = e == hipSuccess ? opt_init_state(c) : fail(c, PGH_E_HIP, "hipMemsetD32Async failed: %s", hipGetErrorString(e));
+    int rc = c->nz.ensure(c, c->stream);
+    if (!rc) rc = opt_init_state(c);
     if (rc) {
         so.release();
         return rc;

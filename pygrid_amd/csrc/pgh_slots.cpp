@@ -16,21 +16,12 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
     if (c->slot_mode >= 0 && c->slot_mode != mode)
         return fail(c, PGH_E_STATE, "averaging mode changed from %d to %d within a cycle", c->slot_mode, mode);
-    std::vector<char> seen((size_t)c->slots, 0);
-    for (int k = 0; k < n; ++k) {
-        const int32_t sl = slots[k];
-        if (sl < 0 || sl >= c->slots) return fail(c, PGH_E_ARG, "slot %d outside [0,%d)", sl, c->slots);
-        if (c->slot_client[(size_t)sl] < 0) return fail(c, PGH_E_STATE, "slot %d holds no unfolded diff", sl);
-        if (seen[(size_t)sl]) return fail(c, PGH_E_ARG, "slot %d listed twice", sl);
-        seen[(size_t)sl] = 1;
-    }
-    const bool median = mode == PGH_MEDIAN;  // every row of the cycle in this one call (check_mode_use: final)
-    if (median && c->folded > 0)
-        return fail(c, PGH_E_STATE, "a median closes a cycle without earlier slot folds (%lld diffs folded)", (long long)c->folded);
-    // a geometric median too: the weights need every row (check_mode_use: final)
-    const bool geomed = mode == PGH_GEOMETRIC_MEDIAN;
-    if (geomed && c->folded > 0)
-        return fail(c, PGH_E_STATE, "a geometric median closes a cycle without earlier slot folds (%lld diffs folded)", (long long)c->folded);
+    RC(check_slot_list(c, slots, n, true));
+    // a median takes every row of the cycle in this one call, a geometric median's weights need them (check_mode_use: final)
+    const char* const one_fold = rules_one_fold_cycle(mode);
+    if (one_fold && c->folded > 0)
+        return fail(c, PGH_E_STATE, "%s closes a cycle without earlier slot folds (%lld diffs folded)", one_fold, (long long)c->folded);
+    const bool median = mode == PGH_MEDIAN;
     const int64_t c0 = c->folded, total = c0 + n;
     FinalArgs fa;
     fa.ckpt = c->d_ckpt.as<float>();
@@ -38,7 +29,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     if (final) {
         RC(check_ckpt(c, "pgh_fold_slots_finish_resident"));
         if (total == 0) return fail(c, PGH_E_STATE, "no diffs folded");
-        if (!geomed) RC(fedavg_divisor(c, mode, total, &fa.divisor));
+        RC(fedavg_divisor(c, mode, total, &fa.divisor));
     } else if (n == 0) {
         return PGH_OK;
     }
@@ -46,24 +37,21 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     const hipStream_t s = c->stream;
     // a close right behind a ranged ingest (pgh_set_ingest_ranges) orders each FINAL range after the
     // chunk of the last report it reads instead of after the whole copy stream
-    // (never a clipped pass: a scale needs the last report's whole row, so it takes the whole-stream wait)
-    const bool clipped = mode == PGH_CLIPPED_MEAN;
-    const bool ranged = final && !clipped && !geomed && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && c->ranged.valid(c->pg);
-    if (clipped && n > 0) RC(clip_slot_scales(c, slots, n, c0));  // the sums still missing in one batch, then the scales in fold order
-    // the included rows and their final weights (the inner iterations are finished on return); the fold
-    // below runs over the included rows alone, fold client k = the k-th of them
+    // (never where a rule needs the last report's whole row, a scale for one: it takes the whole-stream wait)
+    const bool may_range = final && n > 0 && n <= pgh::ROWTAB_MAX && c->pg >= (1 << 20) && c->ranged.valid(c->pg);
+    // the rule's part: a clipped fold's scales in fold order, a geometric median's included rows with their
+    // final weights and divisor -- the fold below runs over the plan's rows, fold client k = the k-th of them
     const int32_t* const all_slots = slots;
     const int n_all = n;
-    if (geomed) {
-        RC(geomed_slot_weights(c, slots, n));
-        fa.divisor = c->geo.W;
-        slots = c->geo.rows.data();
-        n = (int)c->geo.rows.size();
-    }
-    const int64_t nfold = geomed ? (int64_t)n : total;
+    FoldPlan plan;
+    RC(rules_slot_plan(c, mode, slots, n, c0, &plan));
+    slots = plan.slots;
+    n = plan.n;
+    if (plan.has_divisor) fa.divisor = plan.divisor;
+    const bool ranged = may_range && !plan.whole_rows;
     if (!ranged) RC(order_after_ingest(c, s));
     else if (hipEvent_t dec = c->vdec.last_decode()) CK(c, hipStreamWaitEvent(s, dec, 0));  // the copy stream: per range below
-    if (n > 0) RC(fold_prepare(c, mode, nfold, s));
+    if (n > 0) RC(fold_prepare(c, mode, plan.total, s));
     if (median && n > pgh::ROWTAB_MAX) RC(median_row_table(c, slots, n, s));  // more rows than a RowTab carries
     int done = 0;
     bool prequeued = false;
@@ -122,7 +110,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         c->d2h.keep_pre(prequeued, c->d_ckpt.as<uint8_t>());
         c->folded = 0;  // the next cycle folds from scratch
         c->slot_mode = -1;
-        if (clipped) rules_clipped_cycle_finished(c);  // the cycle's rows join the finished totals (pgh_clip_stats)
+        rules_cycle_finished(c, mode);
     }
     return PGH_OK;
 }
@@ -162,8 +150,7 @@ int pgh_fold_slots_restart(pgh_ctx* c) {
     c->folded = 0;
     c->st.n_folded = 0;
     c->slot_mode = -1;
-    c->weights.clear();  // (a clipped cycle's scales among them)
+    c->fw.clear();  // (a clipped cycle's scales among them)
     rules_folds_restarted(c);
-    c->weights_on_device = false;
     return PGH_OK;
 }

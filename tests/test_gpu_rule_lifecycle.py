@@ -1,7 +1,10 @@
 """GPU: what the averaging rules' state does at each lifecycle event of a context -- a slot written, the
 weights replaced, a reset, a reserve, slot folds restarted, a shard set, the context made -- for clipping,
-trimming and the median, bit-exact against tests/clip_oracle.py, tests/trim_oracle.py and
-tests/median_oracle.py.  (The server optimizer's events: test_gpu_serveropt.py::test_state_lifetime.)
+trimming, the median and the geometric median, bit-exact against tests/clip_oracle.py, tests/trim_oracle.py,
+tests/median_oracle.py and tests/geomed_oracle.py; and what the rules share: the fold's weights as clipping, the
+caller and the geometric median write them in turn, and the one plane of -0.0f under the server optimizer, the
+noise (tests/serveropt_oracle.py, tests/dp_oracle.py) and the geometric median's inner folds.
+(The server optimizer's events: test_gpu_serveropt.py::test_state_lifetime.)
 
     python tests/test_gpu_rule_lifecycle.py median | trimmed     (the child processes)
 """
@@ -18,16 +21,21 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 import clip_oracle as CO  # noqa: E402
+import dp_oracle as DO  # noqa: E402
+import geomed_oracle as GO  # noqa: E402
 import median_oracle as MO  # noqa: E402
+import serveropt_oracle as SO  # noqa: E402
 import trim_oracle as TO  # noqa: E402
 from gen_trim_golden import special_rows  # noqa: E402
+from oracle import oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-CLIPPED, TRIMMED, MEDIAN = 3, 4, 5
-STATE = -3
+MEAN, WEIGHTED, CLIPPED, TRIMMED, MEDIAN, GEOMED = 0, 2, 3, 4, 5, 6
+STATE, UNSUPPORTED = -3, -6
 P = 4101  # one full SUMSQ_TILE (4096) and a ragged tile of 5: not a multiple of 4
 BOUND = 1.0
+NU = 1e-6
 
 
 def device():
@@ -170,6 +178,192 @@ def test_clip_shard_clears_the_bound_for_good(eng):
         assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(CO.fedavg_clipped(ckpt, diffs, BOUND)))
     finally:
         eng.set_clip_norm(0)
+
+
+# ---- geometric median: a slot written, the weights replaced ------------------------------------------------------
+
+def geomed_saw(eng, rows, iters):
+    """geomed_stats() is what the oracle gives for these rows: the counts, the objective and the largest weight by bits."""
+    st, g = eng.geomed_stats(), GO.geomed(rows, iters, NU)
+    return (st["iterations"] == iters and st["rows"] == len(rows) and st["excluded"] == g["excluded"] and
+            u64([st["objective"]])[0] == u64([g["objective"]])[0] and u32([st["max_weight"]])[0] == u32([g["max_weight"]])[0])
+
+
+def test_geomed_slot_written(eng):
+    diffs, ckpt = clip_rows(6, 44)
+    other = (diffs[0][::-1] * F(3)).astype(F)  # another norm than the row it replaces: other weights for every row
+    diffs2 = diffs.copy()
+    diffs2[2] = other
+    diffs3 = diffs2.copy()
+    diffs3[4, 1234] = np.inf
+    eng.set_layout([P])
+    eng.reserve(6)
+    eng.set_geomed(3, NU)
+    try:
+        for k, d in enumerate(diffs):
+            eng.ingest(k, d)
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(GO.fedavg_geomed(ckpt, diffs, 3, NU)))
+        assert geomed_saw(eng, diffs, 3)
+        # the slot's sum went with its diff and the slab's weights are computed again
+        eng.ingest(2, other)
+        want2 = GO.fedavg_geomed(ckpt, diffs2, 3, NU)
+        assert not np.array_equal(u32(want2), u32(GO.fedavg_geomed(ckpt, diffs, 3, NU)))
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(want2))
+        assert geomed_saw(eng, diffs2, 3)
+        # a row with one inf: its sum says so, the row is excluded
+        eng.ingest(4, diffs3[4])
+        want3 = GO.fedavg_geomed(ckpt, diffs3, 3, NU)
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(want3))
+        assert eng.geomed_stats()["excluded"] == 1 and geomed_saw(eng, diffs3, 3)
+        # weights replaced: they took the place of the rule's, which the next fold computes again
+        eng.set_weights([5.0] * 6)
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(want3))
+    finally:
+        eng.set_geomed(0)
+
+
+# ---- geometric median: reset, reserve, a shard set ----------------------------------------------------------------
+
+def test_geomed_reset_reserve_shard(eng):
+    diffs, ckpt = clip_rows(9, 45)
+    eng.set_layout([P])
+    eng.reserve(6)
+    eng.set_geomed(3, NU)
+    try:
+        for k in range(6):
+            eng.ingest(k, diffs[k])
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(GO.fedavg_geomed(ckpt, diffs[:6], 3, NU)))
+        assert geomed_saw(eng, diffs[:6], 3)
+        eng.reset()  # the tallies go, the setting stays
+        assert eng.geomed_stats() == {"iterations": 3, "rows": 0, "excluded": 0, "objective": 0.0, "max_weight": 0.0}
+        # another slot count: the sum cache has its length; the iterate plane and the distances are allocated anew
+        eng.reserve(9)
+        eng.set_geomed(2, NU)
+        for k in range(9):
+            eng.ingest(k, diffs[k])
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(GO.fedavg_geomed(ckpt, diffs, 2, NU)))
+        assert geomed_saw(eng, diffs, 2)
+        # a sub-range shard drops the setting: the distances need whole rows
+        eng.set_shard(0, 2048)
+        assert eng.geomed_stats()["iterations"] == 0
+        eng.reserve(3)
+        for k in range(3):
+            eng.ingest(k, diffs[k][:2048])
+        refused(UNSUPPORTED, "a geometric median needs whole rows: the shard [0,2048) is narrower than the model", eng.fedavg, GEOMED,
+                ckpt[:2048])
+        refused(UNSUPPORTED, "pgh_set_geomed: the shard [0,2048) is narrower than the model", eng.set_geomed, 3, NU)
+        eng.set_shard(0, P)  # the whole model again: the setting does not come back by itself
+        eng.reserve(3)
+        for k in range(3):
+            eng.ingest(k, diffs[k])
+        refused(STATE, "PGH_GEOMETRIC_MEDIAN needs its setting: call pgh_set_geomed first", eng.fedavg, GEOMED, ckpt)
+        eng.set_geomed(2, NU)
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(GO.fedavg_geomed(ckpt, diffs[:3], 2, NU)))
+    finally:
+        eng.set_layout([P])
+
+
+# ---- the fold's weights: clipping, the caller and the geometric median write them in turn ---------------------------
+
+def test_weights_change_hands(eng):
+    """37 rows: one K12 chunk of 32 and one of 5 whose second row group repeats its last row; ten K7 row groups."""
+    n, iters = 37, 3
+    diffs, ckpt = clip_rows(n, 46)
+    rows = list(diffs)
+    w = (np.random.default_rng(47).random(n) + 0.5).astype(F)
+    norms = np.sqrt(sums(rows))
+    n_clipped = int(np.sum(CO.scales(rows, BOUND) != 1))
+    assert 0 < n_clipped < n
+    want_clip = CO.fedavg_clipped(ckpt, rows, BOUND)
+    want_w = O.fedavg_weighted([ckpt], [[d] for d in rows], w)[0]
+    want_geo = GO.fedavg_geomed(ckpt, rows, iters, NU)
+    assert len({u32(x).tobytes() for x in (want_clip, want_w, want_geo)}) == 3
+
+    def clip_saw(closes):  # every close that computed the slab's scales counted its rows
+        return eng.clip_stats() == {"rows": closes * n, "clipped": closes * n_clipped, "max_norm": norms.max()}
+
+    eng.set_layout([P])
+    eng.reserve(n)
+    eng.set_clip_norm(BOUND)
+    eng.set_geomed(iters, NU)
+    try:
+        for k, d in enumerate(rows):
+            eng.ingest(k, d)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(want_clip))  # 1: the scales
+        assert clip_saw(1)
+        eng.set_weights(w)                                                     # 2: the caller's
+        assert np.array_equal(u32(eng.fedavg(WEIGHTED, ckpt)), u32(want_w))
+        assert clip_saw(1)
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(want_geo))    # 3: the Weiszfeld weights
+        assert geomed_saw(eng, rows, iters) and clip_saw(1)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(want_clip))  # 4: the scales, computed again
+        assert clip_saw(2)
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(want_geo))    # 5
+        assert geomed_saw(eng, rows, iters) and clip_saw(2)
+        # 6: the same rows in shuffled slots, the clipped close as slot folds in two calls
+        slot_of = np.random.default_rng(48).permutation(n)
+        assert np.any(np.diff(slot_of) != 1)
+        eng.reset()
+        for k, d in enumerate(rows):
+            eng.ingest(int(slot_of[k]), d)
+        eng.ckpt_upload(ckpt)
+        eng.fold_slots(CLIPPED, slot_of[:20])
+        eng.fold_slots_finish_resident(CLIPPED, slot_of[20:])
+        assert np.array_equal(u32(eng.ckpt_download()), u32(want_clip))
+        assert clip_saw(1)
+        # 7: again, the geometric median as one slot close: a list that is no run of slots goes as RowTabs
+        for k, d in enumerate(rows):
+            eng.ingest(int(slot_of[k]), d)
+        eng.ckpt_upload(ckpt)
+        eng.fold_slots_finish_resident(GEOMED, slot_of)
+        assert np.array_equal(u32(eng.ckpt_download()), u32(want_geo))
+        assert geomed_saw(eng, rows, iters) and clip_saw(1)
+    finally:
+        eng.set_clip_norm(0)
+        eng.set_geomed(0)
+
+
+# ---- the -0 plane: one for the server optimizer, the noise and the geometric median ---------------------------------
+
+def test_one_negative_zero_plane(eng):
+    """Every tenant folds its FINAL against the context's one plane of -0.0f: it is still -0 after each of them, and
+    a tenant switched off does not take it along."""
+    n, key, rnd, z = 5, 0xDEADBEEF0BADF00D, 0xFFFFFFFE, 1.1
+    lr, beta1 = 0.3, 0.9
+    diffs, ckpt = clip_rows(n, 49)
+    rows = list(diffs)
+    g_clip = SO.avg_from(lambda ck: CO.fedavg_clipped(ck, rows, BOUND), P)
+    g_mean = SO.avg_from(lambda ck: O.fedavg_mean([ck], [[d] for d in rows])[0], P)
+    m0, v0 = SO.init_state(P, 0.0)
+
+    def momentum(g):
+        return SO.step(SO.MOMENTUM, ckpt, g, m0, v0, lr, beta1, 0.0, 0.0)[0]
+
+    eng.set_layout([P])
+    eng.reserve(n)
+    eng.set_clip_norm(BOUND)
+    eng.set_geomed(2, NU)
+    try:
+        for k, d in enumerate(rows):
+            eng.ingest(k, d)
+        # FedAvgM behind the noise behind the clipped fold
+        eng.set_server_opt(SO.MOMENTUM, lr, beta1)
+        eng.set_dp_noise(z, key, rnd)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(momentum(DO.noised_avg(g_clip, key, rnd, z, BOUND, n))))
+        # the optimizer off: the noise alone
+        eng.set_server_opt(SO.NONE)
+        assert np.array_equal(u32(eng.fedavg(CLIPPED, ckpt)), u32(DO.close(ckpt, g_clip, key, rnd, z, BOUND, n)))
+        # the noise off: the geometric median's inner fold
+        eng.set_dp_noise(0.0)
+        assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(GO.fedavg_geomed(ckpt, rows, 2, NU)))
+        # the optimizer on again (its moments begin anew) under a plain mean
+        eng.set_server_opt(SO.MOMENTUM, lr, beta1)
+        assert np.array_equal(u32(eng.fedavg(MEAN, ckpt)), u32(momentum(g_mean)))
+    finally:
+        eng.set_server_opt(SO.NONE)
+        eng.set_dp_noise(0.0)
+        eng.set_clip_norm(0)
+        eng.set_geomed(0)
 
 
 # ---- trim: the state planes over a reserve; b and the slot folds -----------------------------------------------
