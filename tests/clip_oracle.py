@@ -9,12 +9,26 @@ The order of the sum (f64 throughout; a square of an f32 is exact in f64):
 * lane l of 256: ``a = +0.0; for j in 0..3: for e in 0..3: a += sq(4096 t + 4 (l + 256 j) + e)``;
 * per wave of 64 consecutive lanes: ``for h in 32, 16, 8, 4, 2, 1: v[l] += v[l + h]`` for l < h;
 * tile partial ``((w0 + w1) + w2) + w3``; row sum = left fold of the tile partials, ascending.
+
+The engine's fold kernel brings a row's partials into LDS ``FOLD_CHUNK`` = 1,024 at a time (``SUMSQ_FOLD_CHUNK``
+in pgh_kernels.hip) and one lane carries the sum across the chunks; the definition above knows no chunks.  Three
+widths in tests/gen_clip_golden.py (``WIDE_P``) are cut to that number and move with it:
+
+* ``P_A`` = 1024 x 4096 = 4,194,304: exactly one full chunk, the loop ends on ``c0 == ntiles``;
+* ``P_B`` = 1026 x 4096 - 4095 = 4,198,401: 1,026 tiles, a second chunk of two, one param in the last tile
+  (``p % 4 == 1``: the clamp to the last column and the +0.0 mask);
+* ``P_C`` = 2 x 1024 x 4096 + 5 x 4096 + 3 = 8,409,091: 2,054 tiles, two full chunks and one of six, a ragged
+  last tile.
+
+tests/test_row_sums_wide.py (CPU: the inputs tell a wrong chunking from the right one) and
+tests/test_gpu_row_sums_wide.py (K7, K12 and the closes on them) use no other widths.
 """
 from __future__ import annotations
 
 import numpy as np
 
 TILE = 4096
+FOLD_CHUNK = 1024  # the engine's SUMSQ_FOLD_CHUNK: not part of the definition, only of where the tests look
 F32 = np.float32
 F64 = np.float64
 

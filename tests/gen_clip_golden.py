@@ -8,6 +8,7 @@ cannot move the definition unnoticed.  Run from the repository root:
 Only when the definition itself changes (the oracle and this file together)."""
 from __future__ import annotations
 
+import functools
 import sys
 from pathlib import Path
 
@@ -30,6 +31,66 @@ def mixed_rows(p: int, n: int = 3) -> np.ndarray:
     """n rows of p floats of mixed magnitude (1e-3 .. 1e3 per element)."""
     rng = np.random.default_rng(7000 + p)
     return (rng.standard_normal((n, p)) * 10.0 ** rng.integers(-3, 4, (n, p))).astype(F)
+
+
+# The widths at which a row's tile partials fill more than one chunk of the engine's fold (clip_oracle's
+# docstring says why these three); tests/gen_row_sums_wide_golden.py pins their sums, not this file's main().
+CH = CO.FOLD_CHUNK
+P_A = CH * CO.TILE
+P_B = (CH + 2) * CO.TILE - (CO.TILE - 1)
+P_C = 2 * CH * CO.TILE + 5 * CO.TILE + 3
+WIDE_P = (P_A, P_B, P_C)
+assert WIDE_P == (4_194_304, 4_198_401, 8_409_091)
+WIDE_N = 5  # one K7 row group of 4 and a remainder of 1; one K12 row chunk
+WIDE_GAIN = (1.0, 0.01, 3.0, 0.001)  # per random row, so that one bound clips some rows and not others
+# chosen so that tests/test_row_sums_wide.py holds: the oracle alone tells every wrong chunking from the right one
+WIDE_SEED = {P_A: 91000, P_B: 91025, P_C: 91009}
+SENTINEL = WIDE_N - 1  # the sparse row
+SENTINEL_BIG, SENTINEL_SMALL = 2.0 ** 27, 1.5  # squares 2**54 (one ulp is 4 there) and 2.25
+
+
+def n_tiles(p: int) -> int:
+    return -(-p // CO.TILE)
+
+
+def sentinel_at(p: int) -> dict:
+    """index -> value of the sparse row: 2**27 in tile 0, 1.5 in tile 1,024 (the first tile of the fold's second
+    chunk, where the width has one) and 1.5 in the row's last param."""
+    at = {5: SENTINEL_BIG, p - 1: SENTINEL_SMALL}
+    if n_tiles(p) > CH:
+        at[CH * CO.TILE + 777] = SENTINEL_SMALL
+    return at
+
+
+def sentinel_sumsq(p: int) -> float:
+    """The sparse row's sum in the definition's order, by hand: 2**54 + 2.25 rounds up to 2**54 + 4 and that
+    + 2.25 to 2**54 + 8.  (Not the real sum, 2**54 + 4.5: folding 2.25 + 2.25 first gives 2**54 + 4, folding
+    without either 2.25 gives 2**54 + 4 or 2**54.)"""
+    return 2.0 ** 54 + 4.0 * (len(sentinel_at(p)) - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_rows(p: int) -> np.ndarray:
+    """WIDE_N rows of p floats (cached, read-only).  Rows 0..3: standard normals scaled per tile by 10**k, k drawn
+    from -3..3, times the row's WIDE_GAIN; every fold chunk of two or more tiles opens with a k = -3 tile followed
+    by a k = 3 tile, so each chunk holds large and small partials.  Row 4: sentinel_at(p), zero elsewhere."""
+    rng = np.random.default_rng(WIDE_SEED[p])
+    nt = n_tiles(p)
+    rows = np.zeros((WIDE_N, p), F)
+    for r, gain in enumerate(WIDE_GAIN):
+        k = rng.integers(-3, 4, nt)
+        for c0 in range(0, nt - 1, CH):
+            k[c0], k[c0 + 1] = -3, 3
+        rows[r] = (rng.standard_normal(p) * np.repeat(gain * 10.0 ** k, CO.TILE)[:p]).astype(F)
+    for i, x in sentinel_at(p).items():
+        rows[SENTINEL, i] = x
+    rows.setflags(write=False)
+    return rows
+
+
+def wide_other(p: int) -> np.ndarray:
+    """Another row of that width, for a second ingest into a slot."""
+    return (wide_rows(p)[0][::-1] * F(3)).astype(F)
 
 
 def fold_inputs():
