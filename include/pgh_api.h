@@ -382,6 +382,58 @@ int pgh_row_distsq(pgh_ctx* ctx, const int32_t* slots, int n, const float* point
 int pgh_geomed_stats(pgh_ctx* ctx, int* iters, int64_t* n_rows, int64_t* n_excluded, double* objective,
                      float* max_weight);
 
+/* ---- Multi-Krum selection of diffs ahead of the average (Blanchard et al. 2017; kernel K13) --------
+ * A stage, not an averaging mode: it decides WHICH diffs a cycle averages.  Each diff is scored by its
+ * distance to its nearest neighbours, the m most central diffs are kept and the others leave the cycle;
+ * the cycle's mode (any of pgh_mode, with or without a server optimizer) then runs over the picked slots
+ * through pgh_fold_slots_finish_resident exactly as if they were the only reports.  The selection is a
+ * call, not a context setting.  All arithmetic is IEEE, every operation rounded on its own, no libm call.
+ * Rows d_0 .. d_{n-1} in the caller's list order (distinct occupied slots), an assumed hostile count
+ * f >= 0 and a keep count m:
+ *   1. Included rows.  s_c = the sum of squares of row c (K7, cached at ingest or computed now, as
+ *      pgh_row_sumsq does).  A row whose s_c is not finite -- exactly the rows holding a NaN or an
+ *      infinity -- is excluded: no distance pass reads it.  The n' included rows keep their relative
+ *      order.  f is not reduced by the excluded rows (the conservative reading).  n' >= 2f + 3, else
+ *      PGH_E_STATE: nothing is launched after the sums and the context stays usable.
+ *   2. Distances.  For included a != b, D[a][b] = K7's sum in K7's exact order (tiles of 4,096 params,
+ *      256 lane partials over j and e, the shuffle tree per wave, ((w0 + w1) + w2) + w3, the tile partials
+ *      left to right, params at or past P as +0.0) over x_i = d_a[i] - d_b[i], ONE f32 subtraction, so
+ *      that the square is exact in f64.  d_a - d_b = -(d_b - d_a) exactly, so D is symmetric by
+ *      construction: the kernel computes one triangle.  D[a][a] = +0.0.  Between included rows D is never
+ *      NaN; it may be +inf (the f32 difference of 3e38 and -3e38 overflows), which orders like any other
+ *      value.  D[a][b] is the same f64 bits as pgh_row_distsq of row a against the point d_b.
+ *   3. Scores.  k = n' - f - 2; score_a = the f64 left fold, in ascending order of value, of the k
+ *      smallest of the n' - 1 values D[a][b], b != a.
+ *   4. Selection.  The included rows ordered by (score, list position) ascending -- equal scores break
+ *      towards the earlier row, +inf included -- and the first m taken.  m = 0 means n' - f (Multi-Krum);
+ *      m = 1 is Krum; m > n' - f is PGH_E_STATE.  The picked rows are reported in list order, so the fold
+ *      order of the close is the cycle's order with the others left out.
+ * The result is a function of the rows, their order, f and m alone: not of the slots, the slab's block
+ * width or the batching of the distance passes.
+ *
+ * pgh_row_pairdist: the raw n x n matrix (row-major) over the listed occupied slots: K13 alone.  Like
+ * pgh_row_distsq it does not sanitise and a slot may repeat.
+ * pgh_krum_select_host: steps 3 and 4 over the n x n matrix of the included rows, no context and no GPU:
+ * positions into picked (room for n), their count, and the n scores when `scores` is not NULL.  A NaN or
+ * negative off-diagonal entry, f < 0 or m < 0 is PGH_E_ARG; n < 2f + 3 or m > n - f is PGH_E_STATE.
+ * pgh_krum_select: steps 1 to 4 over the listed slots; the picked SLOTS in list order into picked (room
+ * for n).  A duplicate or unoccupied slot, f < 0 or m < 0 is PGH_E_ARG.
+ * Both context calls: n > PGH_KRUM_MAX_ROWS is PGH_E_UNSUPPORTED, and so is every context pgh_row_sumsq
+ * refuses (a group, a shard narrower than the layout, an int64 slab, a streaming context).  The tile
+ * partials of the distance passes take at most 1 GiB of HBM whatever n and the model: the anchors go in
+ * batches (PGH_PAIRDIST_BUDGET, bytes, read at pgh_create, lowers the budget).
+ * pgh_krum_stats: of the last pgh_krum_select that selected: the rows given, how many were excluded, how
+ * many were picked, the largest score among the picked and the smallest among the dropped (+inf when
+ * none was dropped).  Each pointer may be NULL. */
+#define PGH_KRUM_MAX_ROWS 1024
+int pgh_row_pairdist(pgh_ctx* ctx, const int32_t* slots, int n, double* out);
+int pgh_krum_select_host(const double* dist, int n, int f, int m, int32_t* picked, int* n_picked,
+                         double* scores);
+int pgh_krum_select(pgh_ctx* ctx, const int32_t* slots, int n, int f, int m, int32_t* picked,
+                    int* n_picked);
+int pgh_krum_stats(pgh_ctx* ctx, int64_t* n_rows, int64_t* n_excluded, int64_t* n_picked,
+                   double* max_picked_score, double* min_dropped_score);
+
 /* ---- server optimizers: how the average is applied (FedAvgM, FedAdagrad, FedAdam, FedYogi) ------
  * Without one, a close writes out = ckpt - g, g being the cycle's average as its mode defines it
  * (acc / divisor; the iterative mean's acc; the trimmed mean; the median).  With one set, every

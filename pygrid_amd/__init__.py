@@ -16,7 +16,7 @@ opt-in for the process-wide settings the engine benefits from (HIP hardware queu
 thresholds for 47 MB buffers).
 """
 from .exceptions import (AggregationError, ClipUnavailableError, DpNoiseUnavailableError, EngineUnavailableError, GeometricMedianUnavailableError,
-                         MedianUnavailableError,
+                         KrumUnavailableError, MedianUnavailableError,
                          ModelNotAcceleratedError,
                          PlanNotAcceleratedError, PyGridError, ServerOptUnavailableError, StateParseError,
                          TrimUnavailableError)
@@ -44,7 +44,7 @@ __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
     "StateParseError", "TrimUnavailableError", "MedianUnavailableError", "ServerOptUnavailableError", "DpNoiseUnavailableError",
     "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
-    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "GEOMETRIC_MEDIAN", "GeometricMedianUnavailableError", "MODE_NAMES", "F32", "I64",
+    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "GEOMETRIC_MEDIAN", "GeometricMedianUnavailableError", "KrumUnavailableError", "MODE_NAMES", "F32", "I64",
     "tune_process",
 ]
 __version__ = "0.3.0"

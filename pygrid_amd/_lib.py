@@ -112,6 +112,11 @@ SIGNATURES = {
     "pgh_set_geomed": (_i, [_vp, _i, C.c_float]),
     "pgh_row_distsq": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "pgh_geomed_stats": (_i, [_vp, C.POINTER(C.c_int), _P64, _P64, C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "pgh_row_pairdist": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
+    "pgh_krum_select_host": (_i, [C.POINTER(C.c_double), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_double)]),
+    "pgh_krum_select": (_i, [_vp, C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "pgh_krum_stats": (_i, [_vp, _P64, _P64, _P64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pgh_set_server_opt": (_i, [_vp, _i, C.c_float, C.c_float, C.c_float, C.c_float]),
     "pgh_server_opt_commit": (_i, [_vp]),
     "pgh_server_opt_steps": (_i, [_vp, _P64]),

@@ -166,14 +166,15 @@ struct pgh_ctx {
     // (pgh_rules.cpp, pgh_serveropt.cpp) and by fold_launch's lines for the optimizer and noise tenants.  The
     // lifecycle files (pgh_api.cpp, pgh_ingest.cpp, pgh_slots.cpp, pgh_xfer.cpp, pgh_order.cpp) reach them
     // through rules_* and the fold plans below alone:
-    //   grep -n 'c->\(clip\|geo\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
-    pgh_detail::RowSums rowsums;   // K7's per-slot cache, the buffers of K7 and K12 (clip, geo)
+    //   grep -n 'c->\(clip\|geo\|krum\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
+    pgh_detail::RowSums rowsums;   // K7's per-slot cache, the buffers of K7, K12 and K13 (clip, geo, krum)
     pgh_detail::NegZeroPlane nz;   // the one plane of -0.0f (opt, noise, geo)
     pgh_detail::ClipState clip;
     pgh_detail::NoiseState noise;
     pgh_detail::TrimState trim;
     pgh_detail::MedianState med;
     pgh_detail::GeomedState geo;
+    pgh_detail::KrumState krum;
     pgh_detail::ServerOptState opt;
 
     bool streaming = false;

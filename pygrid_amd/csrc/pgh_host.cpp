@@ -209,6 +209,33 @@ bool geomed_step(const double* D, int64_t n, float nu, float* w, float* W, doubl
     return true;
 }
 
+int krum_select(const double* D, int n, int f, int m, int32_t* picked, int* n_picked, double* scores) {
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b)
+            if (a != b && !(D[(size_t)a * (size_t)n + (size_t)b] >= 0.0)) return -1;  // NaN or negative
+    if ((int64_t)n < 2 * (int64_t)f + 3) return -3;
+    const int k = n - f - 2, keep = m == 0 ? n - f : m;
+    std::vector<double> sc((size_t)n), row;
+    for (int a = 0; a < n; ++a) {
+        row.clear();
+        for (int b = 0; b < n; ++b)
+            if (b != a) row.push_back(D[(size_t)a * (size_t)n + (size_t)b]);
+        std::partial_sort(row.begin(), row.begin() + k, row.end());  // (no NaN: < is a strict weak order; equal values add alike)
+        double s = row[0];
+        for (int j = 1; j < k; ++j) s += row[(size_t)j];
+        sc[(size_t)a] = s;
+    }
+    if (scores) std::copy(sc.begin(), sc.end(), scores);
+    if (keep > n - f) return -3;
+    std::vector<int32_t> order((size_t)n);
+    for (int a = 0; a < n; ++a) order[(size_t)a] = a;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return sc[(size_t)x] < sc[(size_t)y]; });
+    std::sort(order.begin(), order.begin() + keep);  // the picked rows in list order
+    std::copy(order.begin(), order.begin() + keep, picked);
+    *n_picked = keep;
+    return 0;
+}
+
 }  // namespace pgh_detail
 
 namespace pgh_int {

@@ -204,4 +204,12 @@ inline double dp_sigma(float z, float c, int64_t n) { return ((double)z * (doubl
 // f64 left fold of the betas is 0 (every D non-finite): w and *W are not written then.
 bool geomed_step(const double* D, int64_t n, float nu, float* w, float* W, double* objective, float* max_w);
 
+// Steps 3 and 4 of the Multi-Krum selection (include/pgh_api.h, "Multi-Krum selection"): from the n x n matrix
+// of squared distances among the included rows, score[a] = the f64 left fold, in ascending order of value, of
+// the n - f - 2 smallest D[a][b], b != a; the m rows first in (score, position) order, reported as ascending
+// positions in picked[0, *n_picked).  m = 0 means n - f.  Returns 0, or -1 when an off-diagonal entry is NaN
+// or negative (an argument error), -3 when n < 2f + 3 or m > n - f (a state error); `scores` (n, nullable) is
+// written whenever the matrix was acceptable and n >= 2f + 3.
+int krum_select(const double* D, int n, int f, int m, int32_t* picked, int* n_picked, double* scores);
+
 }  // namespace pgh_detail

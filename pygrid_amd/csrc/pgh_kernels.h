@@ -219,6 +219,33 @@ struct DistsqArgs {
 };
 hipError_t launch_row_distsq(const DistsqArgs& a, const Rows& rows, hipStream_t s);
 
+// K13: Multi-Krum's pairwise squared distances (the definition is in include/pgh_api.h): for list indices
+// a < b of the n listed rows, K12's sum of row a against the point row b -- K7's sum, in K7's order, over
+// x = d_a[i] - d_b[i], one f32 subtraction per param.  List index k is slab row d_rows[k] (a device table of n
+// entries) or, without a table, row0 + k.  A workgroup owns one tile, PAIRDIST_RA anchors (their tile in
+// registers: 16 floats per lane and anchor) and PAIRDIST_RC of the rows after the block's first anchor, so the
+// slab is read n / PAIRDIST_RA times at most, not n times.  One launch takes the anchors [a0, a0 + na) against
+// every later row, writes part[((a - a0) * n + b) * ntiles + t] and then dist[a * n + b], b > a only: the
+// caller sizes `part` for na anchors and batches them; the lower triangle and the diagonal of `dist` are not
+// written.
+constexpr int PAIRDIST_RA = 8;
+constexpr int PAIRDIST_RC = 32;
+constexpr int PAIRDIST_MAX_ROWS = 1024;
+struct PairdistArgs {
+    const float* slab;       // the slab at row 0
+    SlabMap map;             // map.off = 0
+    int64_t p;               // params in the shard
+    int64_t ntiles;          // ceil(p / SUMSQ_TILE)
+    const int32_t* d_rows;   // [n] slab rows in list order, or null: row0 + k
+    int row0;
+    int n;                   // rows in the list
+    int a0, na;              // the launch's anchors
+    int nchunks;             // the launcher's: row chunks per anchor block in the grid
+    double* part;            // [na][n][ntiles]
+    double* dist;            // [n][n]
+};
+hipError_t launch_row_pairdist(const PairdistArgs& a, hipStream_t s);
+
 // K10: the server optimizer's step behind a FINAL fold (the definition is in include/pgh_api.h).  The
 // fold ran with ckpt = a plane of -0.0f and out = d, so d = (-0.0f) - g, which is -g bit for bit for
 // every non-NaN g: x - y = x + (-y) in IEEE 754, so d = (-0) + (-g); a finite non-zero or infinite

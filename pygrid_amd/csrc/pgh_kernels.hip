@@ -21,6 +21,8 @@
 //       DESIGN.md section 5); k_dp_normals returns the sampler's normals alone
 // K12 k_row_distsq             K7's sum over d_c[i] - v[i]: every row's squared distance to a moving point,
 //       a tile of the point held in registers over a chunk of rows; one tile body with K7, row_sq_tile
+// K13 k_row_pairdist           K12's sum for every pair of the listed rows (Multi-Krum): a block of anchor rows'
+//       tile held in registers while the later rows stream past; k_row_pairdist_fold finishes each pair
 //       (build-owned: PGH_GEOMETRIC_MEDIAN)
 //
 // Design (DESIGN.md "Kernels"): every kernel is a single streaming pass over the slab held in
@@ -1274,25 +1276,115 @@ __global__ __launch_bounds__(BLOCK) void k_row_distsq_rows(DistsqArgs d, RowTab 
 // them into LDS 1,024 at a time (coalesced) so the serial chain reads LDS, not HBM.
 constexpr int SUMSQ_FOLD_CHUNK = 4 * BLOCK;
 
-template <int SRC>
-__device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const Rows rows) {
+// (every lane returns; lane 0 holds the sum)
+__device__ __forceinline__ double tile_partials_fold(const double* part, int64_t ntiles) {
     __shared__ double buf[SUMSQ_FOLD_CHUNK];
-    const size_t row = row_at<SRC>(rows, (int)blockIdx.x);
-    const double* part = a.part + row * (size_t)a.ntiles;
     double acc = 0.0;  // + 0.0 + partial 0 is partial 0 (partials are never -0.0)
-    for (int64_t c0 = 0; c0 < a.ntiles; c0 += SUMSQ_FOLD_CHUNK) {
-        const int m = (int)min((int64_t)SUMSQ_FOLD_CHUNK, a.ntiles - c0);
+    for (int64_t c0 = 0; c0 < ntiles; c0 += SUMSQ_FOLD_CHUNK) {
+        const int m = (int)min((int64_t)SUMSQ_FOLD_CHUNK, ntiles - c0);
         for (int k = threadIdx.x; k < m; k += BLOCK) buf[k] = part[c0 + k];
         __syncthreads();
         if (threadIdx.x == 0)
             for (int k = 0; k < m; ++k) acc += buf[k];
         __syncthreads();
     }
+    return acc;
+}
+
+template <int SRC>
+__device__ __forceinline__ void row_sumsq_fold(const SumsqArgs& a, const Rows rows) {
+    const size_t row = row_at<SRC>(rows, (int)blockIdx.x);
+    const double acc = tile_partials_fold(a.part + row * (size_t)a.ntiles, a.ntiles);
     if (threadIdx.x == 0) a.sumsq[row] = acc;
 }
 
 __global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold(SumsqArgs a) { row_sumsq_fold<0>(a, Rows{nullptr, nullptr, a.row0}); }
 __global__ __launch_bounds__(BLOCK) void k_row_sumsq_fold_rows(SumsqArgs a, RowTab tab) { row_sumsq_fold<1>(a, Rows{&tab}); }
+
+// K13: every pairwise squared distance among the listed rows (Multi-Krum's scores), K12's sum for each pair.
+// A workgroup owns one tile, a block of PAIRDIST_RA anchor rows and a chunk of PAIRDIST_RC later rows of the
+// list: the anchors' tile comes into registers once (16 floats per lane and anchor; K12's nv[] is the
+// one-anchor case) and the chunk streams past in K7's row groups, every (anchor, streamed row) pair reduced on
+// its own in K7's order over x = anchor - row (one f32 subtraction; the square of the other way round is the
+// same, so one triangle serves both).  Only pairs with list index b > a are stored.  The workgroups of one tile
+// are neighbours in the grid (chunk fastest, then anchor block, then tile) and load plainly, so the tile of a
+// row is fetched from HBM about once and served from the caches to the other anchor blocks.  Addresses past
+// the shard clamp and mask as in K7; a short anchor block or row group repeats its last row.
+template <int SRC>
+__device__ __forceinline__ void row_pairdist_tile(const PairdistArgs& a) {
+    __shared__ double wsum[PAIRDIST_RA][PAIRDIST_RC][4];
+    const Rows rows{nullptr, a.d_rows, a.row0};
+    const int lane = threadIdx.x, wave = lane >> 6;
+    const int nabs = (a.na + PAIRDIST_RA - 1) / PAIRDIST_RA;
+    const int chunk = (int)(blockIdx.x % (unsigned)a.nchunks);
+    const int ab = (int)((blockIdx.x / (unsigned)a.nchunks) % (unsigned)nabs);
+    const int64_t t = blockIdx.x / ((unsigned)a.nchunks * (unsigned)nabs), base = t * SUMSQ_TILE;
+    const int ab0 = a.a0 + ab * PAIRDIST_RA;                 // the block's first anchor (list index)
+    const int nra = min(PAIRDIST_RA, a.a0 + a.na - ab0);
+    const int b0 = ab0 + 1 + chunk * PAIRDIST_RC;            // the chunk's first streamed row
+    const int nr = min(PAIRDIST_RC, a.n - b0);
+    if (nr <= 0) return;  // (uniform over the workgroup: the triangle leaves the later chunks of a late block empty)
+    const bool full = base + SUMSQ_TILE <= a.p;
+    const int64_t last4 = (a.p - 1) & ~int64_t(3);
+    int64_t idx[4], off[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        idx[j] = base + 4 * (lane + BLOCK * j);
+        off[j] = a.map.at(full ? idx[j] : min(idx[j], last4));
+    }
+    f32x4 av[PAIRDIST_RA][4];
+#pragma unroll
+    for (int ra = 0; ra < PAIRDIST_RA; ++ra) {
+        const size_t row = row_at<SRC>(rows, ab0 + min(ra, nra - 1));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) av[ra][j] = ld4<false>(a.slab + row * (size_t)a.map.ld + off[j]);
+    }
+#pragma unroll 1
+    for (int g = 0; g < nr; g += SUMSQ_RB) {
+        f32x4 v[SUMSQ_RB][4];
+#pragma unroll
+        for (int rr = 0; rr < SUMSQ_RB; ++rr) {
+            const size_t row = row_at<SRC>(rows, b0 + min(g + rr, nr - 1));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[rr][j] = ld4<false>(a.slab + row * (size_t)a.map.ld + off[j]);
+        }
+#pragma unroll
+        for (int ra = 0; ra < PAIRDIST_RA; ++ra)
+#pragma unroll
+            for (int rr = 0; rr < SUMSQ_RB; ++rr) {
+                double acc = 0.0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float xf = av[ra][j][e] - v[rr][j][e];
+                        const double x = (full || idx[j] + e < a.p) ? (double)xf : 0.0;
+                        acc = __builtin_fma(x, x, acc);
+                    }
+#pragma unroll
+                for (int h = 32; h >= 1; h >>= 1) acc += __shfl_down(acc, h, 64);
+                if ((lane & 63) == 0) wsum[ra][g + rr][wave] = acc;  // (g + rr < PAIRDIST_RC: a multiple of SUMSQ_RB)
+            }
+    }
+    __syncthreads();
+    const int ra = lane / PAIRDIST_RC, rr = lane % PAIRDIST_RC;  // one pair per lane
+    const int ia = ab0 + ra, ib = b0 + rr;
+    if (ra < nra && rr < nr && ib > ia)
+        a.part[((size_t)(ia - a.a0) * (size_t)a.n + (size_t)ib) * (size_t)a.ntiles + (size_t)t] =
+            ((wsum[ra][rr][0] + wsum[ra][rr][1]) + wsum[ra][rr][2]) + wsum[ra][rr][3];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_row_pairdist(PairdistArgs a) { row_pairdist_tile<0>(a); }
+__global__ __launch_bounds__(BLOCK) void k_row_pairdist_rows(PairdistArgs a) { row_pairdist_tile<2>(a); }
+
+// The pair's tile partials left to right, as a row's: workgroup (b, a - a0) of the launch's anchors.
+__global__ __launch_bounds__(BLOCK) void k_row_pairdist_fold(PairdistArgs a) {
+    const int ia = a.a0 + (int)blockIdx.y, ib = (int)blockIdx.x;
+    if (ib <= ia) return;  // (uniform over the workgroup)
+    const double acc =
+        tile_partials_fold(a.part + ((size_t)blockIdx.y * (size_t)a.n + (size_t)ib) * (size_t)a.ntiles, a.ntiles);
+    if (threadIdx.x == 0) a.dist[(size_t)ia * (size_t)a.n + (size_t)ib] = acc;
+}
 
 int cu_count() {
     static int cached[64] = {0};
@@ -1703,6 +1795,25 @@ static hipError_t launch_row_sq(const SumsqArgs& a, const float* negv, const Row
 
 hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s) { return launch_row_sq<SUMSQ_RB>(a, nullptr, rows, s); }
 hipError_t launch_row_distsq(const DistsqArgs& d, const Rows& rows, hipStream_t s) { return launch_row_sq<DISTSQ_RC>(d.s, d.negv, rows, s); }
+
+static_assert(PAIRDIST_RC % SUMSQ_RB == 0 && PAIRDIST_RA * PAIRDIST_RC == BLOCK, "K13: whole row groups, one lane per pair at the end");
+
+hipError_t launch_row_pairdist(const PairdistArgs& a, hipStream_t s) {
+    if (a.p <= 0 || a.n < 0 || a.n > PAIRDIST_MAX_ROWS || a.na < 0 || a.a0 < 0 || a.a0 + a.na > a.n || a.row0 < 0 ||
+        (a.d_rows && a.row0) || a.map.off != 0 || !valid_map(a.map, a.p) || a.ntiles != (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE)
+        return hipErrorInvalidValue;
+    if (a.na == 0 || a.n - a.a0 < 2) return hipSuccess;  // no pair with b > a
+    if (!a.slab || !a.part || !a.dist || !aligned16(a.slab)) return hipErrorInvalidValue;
+    PairdistArgs b = a;
+    b.nchunks = (a.n - a.a0 - 1 + PAIRDIST_RC - 1) / PAIRDIST_RC;  // of the launch's first anchor block: the most
+    const int64_t nabs = (a.na + PAIRDIST_RA - 1) / PAIRDIST_RA;
+    const int64_t grid = a.ntiles * nabs * (int64_t)b.nchunks;
+    if (a.ntiles > 0x7fffffff || grid > 0x7fffffff) return hipErrorInvalidValue;
+    if (a.d_rows) k_row_pairdist_rows<<<(unsigned)grid, BLOCK, 0, s>>>(b);
+    else k_row_pairdist<<<(unsigned)grid, BLOCK, 0, s>>>(b);
+    k_row_pairdist_fold<<<dim3((unsigned)a.n, (unsigned)a.na), BLOCK, 0, s>>>(b);
+    return hipGetLastError();
+}
 
 hipError_t launch_synth_shares(int64_t* out, const SlabMap& m, int64_t ncols, int n_clients, int n_parties,
                                int64_t p, uint64_t seed, int64_t client0, int64_t idx0, float enc_scale,

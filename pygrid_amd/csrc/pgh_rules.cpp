@@ -1,5 +1,5 @@
 // libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); the per-row
-// sums of squares and distances (RowSums: K7 with its host cache, K12); clipping's scales and tallies; the
+// sums of squares and distances (RowSums: K7 with its host cache, K12, K13) and the Multi-Krum selection over them; clipping's scales and tallies; the
 // Gaussian noise on the clipped close (K11 behind a FINAL launch, its plane, setting and entry points); the
 // trimmed mean's state planes (K8); the median's driver and row table (K9, K9p); the geometric median's included
 // rows, inner iterations and final weights (K12 between weighted folds); the context's -0 plane; what the rules'
@@ -70,6 +70,10 @@ int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
 bool rules_made(pgh_ctx* c) {
     if (const char* e = std::getenv("PGH_TRIM_VEC")) c->trim.vec = std::atoi(e) == 4 ? 4 : std::atoi(e) == 1 ? 1 : 0;
     if (const char* e = std::getenv("PGH_MEDIAN_PATH")) c->med.passes = std::strcmp(e, "passes") == 0;
+    if (const char* e = std::getenv("PGH_PAIRDIST_BUDGET")) {  // bytes of K13's tile partials per batch of anchors
+        const long long v = std::atoll(e);
+        if (v > 0 && (unsigned long long)v < c->rowsums.pair_budget) c->rowsums.pair_budget = (size_t)v;
+    }
     return c->rowsums.ev.make() == hipSuccess;
 }
 
@@ -77,6 +81,7 @@ void rules_slab_freed(pgh_ctx* c) {  // the streams are idle (free_slab synchron
     for (auto* v : {&c->trim.d_planes, &c->med.d_prefix, &c->med.d_rowidx, &c->geo.d_negv}) v->reset();
     c->rowsums.slab_freed();
     c->geo.forget();
+    c->krum.forget();
     c->clip.forget();
 }
 
@@ -96,6 +101,7 @@ void rules_reset(pgh_ctx* c) {
     c->rowsums.forget();
     c->clip.forget();
     c->geo.forget();
+    c->krum.forget();
 }
 
 void rules_slot_written(pgh_ctx* c, int slot, int n) {
@@ -281,6 +287,59 @@ int RowSums::distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* 
     RC(sums_d2h(c, slots.data(), slots.size(), h_dist.as<double>(), d_dist.as<double>(), s));
     CK(c, hipStreamSynchronize(s));
     for (size_t k = 0; k < slots.size(); ++k) D[k] = h_dist.as<double>()[slots[k]];
+    return PGH_OK;
+}
+
+// (K7's and K12's buffers are not touched: the cached sums stay what they were.)
+int RowSums::pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D) {
+    const size_t nn = (size_t)n * (size_t)n;
+    std::fill_n(D, nn, 0.0);  // the diagonal, and everything when n < 2
+    if (n < 2) return PGH_OK;
+    pgh::PairdistArgs a{};
+    a.slab = c->d_slab.as<float>();
+    a.map = slab_map(c);
+    a.p = c->pg;
+    a.ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
+    a.n = n;
+    // the anchors a batch takes: whole anchor blocks within the budget, or what fits of one
+    const size_t per_anchor = 8 * (size_t)n * (size_t)a.ntiles;
+    size_t batch = pair_budget / per_anchor;
+    if (batch == 0)
+        return fail(c, PGH_E_OOM, "pairwise distances: the tile partials of one row against %d (%zu bytes) exceed the budget of %zu", n, per_anchor, pair_budget);
+    if (batch > (size_t)pgh::PAIRDIST_RA) batch -= batch % (size_t)pgh::PAIRDIST_RA;
+    batch = std::min(batch, (size_t)n - 1);  // (the last row anchors nothing)
+    if (!d_pair_part.reserve(batch * per_anchor) || !d_pair.reserve(8 * nn) || !d_pair_rows.reserve(sizeof(int32_t) * (size_t)pgh::PAIRDIST_MAX_ROWS))
+        return fail(c, PGH_E_OOM, "allocation of the pairwise distances (%d rows, %zu anchors a batch) failed", n, batch);
+    a.part = d_pair_part.as<double>();
+    a.dist = d_pair.as<double>();
+    bool run = true;
+    for (int k = 0; k < n; ++k) run = run && slots[k] == slots[0] + k;
+    std::vector<int32_t> tab((size_t)n);
+    if (run) {
+        a.row0 = slots[0] * c->parties;
+    } else {
+        for (int k = 0; k < n; ++k) tab[(size_t)k] = slots[k] * c->parties;
+        // (an earlier K13 that read the table ran on this stream too)
+        CK(c, hipMemcpyAsync(d_pair_rows.as<int32_t>(), tab.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        CK(c, hipStreamSynchronize(s));  // tab is pageable: the copy has left it
+        a.d_rows = d_pair_rows.as<int32_t>();
+    }
+    for (int a0 = 0; a0 < n - 1; a0 += (int)batch) {
+        a.a0 = a0;
+        a.na = std::min((int)batch, n - 1 - a0);
+        // HBM bytes as issued, before the caches: every anchor block reads its own tile and the rows after it;
+        // the pairs' partials out and in again, the sums out
+        uint64_t rows_read = 0, pairs = 0;
+        for (int b0 = a0; b0 < a0 + a.na; b0 += pgh::PAIRDIST_RA) rows_read += (uint64_t)(std::min(pgh::PAIRDIST_RA, a0 + a.na - b0) + n - 1 - b0);
+        for (int k = a0; k < a0 + a.na; ++k) pairs += (uint64_t)(n - 1 - k);
+        const uint64_t bytes = rows_read * 4ull * (uint64_t)c->pg + pairs * (16ull * (uint64_t)a.ntiles + 8ull);
+        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_row_pairdist(a, s); }));
+    }
+    std::vector<double> h(nn);
+    CK(c, hipMemcpyAsync(h.data(), d_pair.as<double>(), 8 * nn, hipMemcpyDeviceToHost, s));
+    CK(c, hipStreamSynchronize(s));
+    for (int x = 0; x < n; ++x)
+        for (int y = x + 1; y < n; ++y) D[(size_t)x * n + y] = D[(size_t)y * n + x] = h[(size_t)x * n + y];
     return PGH_OK;
 }
 
@@ -570,6 +629,90 @@ int pgh_geomed_stats(pgh_ctx* c, int* iters, int64_t* n_rows, int64_t* n_exclude
     if (n_excluded) *n_excluded = c->geo.n_excluded;
     if (objective) *objective = c->geo.objective;
     if (max_weight) *max_weight = c->geo.max_weight;
+    return PGH_OK;
+}
+
+// ---- Multi-Krum selection: K13 alone, the host step alone, the selection, what the last one saw ----------------
+
+namespace {
+int check_pair_list(pgh_ctx* c, const char* what, const int32_t* slots, int n, bool no_twice) {
+    RC(check_clip_ctx(c, what));
+    RC(check_dtype(c, PGH_F32));
+    if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "%s: bad slot list (n=%d)", what, n);
+    if (n > PGH_KRUM_MAX_ROWS) return fail(c, PGH_E_UNSUPPORTED, "%s: %d rows, at most %d", what, n, PGH_KRUM_MAX_ROWS);
+    if (!no_twice) return check_slot_list(c, slots, n, false);  // (as pgh_row_distsq)
+    std::vector<char> seen((size_t)c->slots, 0);  // the selection: an unoccupied slot is an argument error too
+    for (int k = 0; k < n; ++k) {
+        const int32_t sl = slots[k];
+        if (sl < 0 || sl >= c->slots || c->slot_client[(size_t)sl] < 0 || seen[(size_t)sl])
+            return fail(c, PGH_E_ARG, "%s: slot %d is outside [0,%d), holds no diff or is listed twice", what, sl, c->slots);
+        seen[(size_t)sl] = 1;
+    }
+    return PGH_OK;
+}
+}  // namespace
+
+int pgh_row_pairdist(pgh_ctx* c, const int32_t* slots, int n, double* out) {
+    RC(check_pair_list(c, "pgh_row_pairdist", slots, n, false));
+    if (n > 0 && !out) return fail(c, PGH_E_ARG, "pgh_row_pairdist: out is NULL");
+    if (n == 0) return PGH_OK;
+    DeviceGuard g(c->device);
+    const hipStream_t s = c->stream;
+    RC(order_after_ingest(c, s));
+    return c->rowsums.pairdist(c, slots, n, s, out);
+}
+
+int pgh_krum_select_host(const double* dist, int n, int f, int m, int32_t* picked, int* n_picked, double* scores) {
+    if (n < 0 || f < 0 || m < 0 || (n > 0 && !dist) || !picked || !n_picked)
+        return fail(nullptr, PGH_E_ARG, "pgh_krum_select_host: bad arguments (n=%d, f=%d, m=%d)", n, f, m);
+    const int rc = krum_select(dist, n, f, m, picked, n_picked, scores);
+    if (rc == -1) return fail(nullptr, PGH_E_ARG, "Multi-Krum: a distance is NaN or negative");
+    if (rc == -3) return fail(nullptr, PGH_E_STATE, "Multi-Krum with f = %d, m = %d over %d rows: it needs at least 2f + 3 = %d rows and m <= n - f", f, m, n, 2 * f + 3);
+    return PGH_OK;
+}
+
+int pgh_krum_select(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
+    RC(check_pair_list(c, "pgh_krum_select", slots, n, true));
+    if (f < 0 || m < 0 || !picked || !n_picked) return fail(c, PGH_E_ARG, "pgh_krum_select: bad arguments (f=%d, m=%d)", f, m);
+    DeviceGuard g(c->device);
+    RC(c->rowsums.queue(c, slots, n));
+    RC(c->rowsums.wait(c));
+    std::vector<int32_t> inc;
+    for (int k = 0; k < n; ++k)
+        if (std::isfinite(c->rowsums.at(slots[k]))) inc.push_back(slots[k]);  // else excluded: no distance pass reads the row
+    const int ni = (int)inc.size();
+    if ((int64_t)ni < 2 * (int64_t)f + 3 || m > ni - f)  // (nothing is launched)
+        return fail(c, PGH_E_STATE, "Multi-Krum with f = %d, m = %d: %d of the %d diffs are finite, it needs at least 2f + 3 = %d and m <= n' - f", f, m, ni, n, 2 * f + 3);
+    const hipStream_t s = c->stream;
+    RC(order_after_ingest(c, s));
+    std::vector<double> D((size_t)ni * (size_t)ni), sc((size_t)ni);
+    RC(c->rowsums.pairdist(c, inc.data(), ni, s, D.data()));
+    std::vector<int32_t> pos((size_t)ni);
+    int np = 0;
+    const int rc = krum_select(D.data(), ni, f, m, pos.data(), &np, sc.data());
+    if (rc != 0) return fail(c, rc == -1 ? PGH_E_HIP : PGH_E_STATE, "Multi-Krum: the host step refused the distances (%d)", rc);
+    KrumState& ks = c->krum;
+    ks = KrumState{n, n - ni, np, 0.0, INFINITY};
+    std::vector<char> is((size_t)ni, 0);
+    for (int k = 0; k < np; ++k) {
+        picked[k] = inc[(size_t)pos[(size_t)k]];
+        is[(size_t)pos[(size_t)k]] = 1;
+        ks.max_picked_score = k == 0 ? sc[(size_t)pos[0]] : std::max(ks.max_picked_score, sc[(size_t)pos[(size_t)k]]);
+    }
+    for (int k = 0; k < ni; ++k)
+        if (!is[(size_t)k]) ks.min_dropped_score = std::min(ks.min_dropped_score, sc[(size_t)k]);
+    *n_picked = np;
+    return PGH_OK;
+}
+
+int pgh_krum_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_excluded, int64_t* n_picked, double* max_picked_score, double* min_dropped_score) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_krum_stats: group contexts select nothing");
+    if (n_rows) *n_rows = c->krum.n_rows;
+    if (n_excluded) *n_excluded = c->krum.n_excluded;
+    if (n_picked) *n_picked = c->krum.n_picked;
+    if (max_picked_score) *max_picked_score = c->krum.max_picked_score;
+    if (min_dropped_score) *min_dropped_score = c->krum.min_dropped_score;
     return PGH_OK;
 }
 

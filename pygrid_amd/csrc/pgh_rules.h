@@ -1,5 +1,5 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trim, med and opt, and what they share: the row
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, krum, trim, med and opt, and what they share: the row
 // sums (RowSums, rowsums), the fold's weights (FoldWeights, fw) and the -0 plane (NegZeroPlane, nz).  Their owners
 // release with the context.
 // The code that works on them: pgh_rules.cpp (clip, geo, trim, med and the lifecycle calls rules_*),
@@ -19,8 +19,8 @@ struct pgh_ctx;
 
 namespace pgh_detail {
 
-// What the row-wise rules share (clipping and the geometric median today): the per-slot cache of K7's sums of
-// squares and everything device-side that either row reduction (K7, K12) needs.  K7 (k_row_sumsq) runs on the
+// What the row-wise rules share (clipping, the geometric median and the Multi-Krum selection today): the per-slot cache of K7's sums of
+// squares and everything device-side that the row reductions (K7, K12, K13) need.  K7 (k_row_sumsq) runs on the
 // copy stream -- behind the row's ingest, ahead of any later overwrite of the slot -- and its sum comes back
 // through h_sq in a small D2H on the same stream, followed by ev.  K12 runs on the stream its caller gives and
 // its sums come back through h_dist behind a wait.  A slot's state: NONE (no sum of the slot's present diff),
@@ -35,6 +35,11 @@ struct RowSums {
     DeviceBuf d_sq, d_dist;         // double [slots]: K7's sums; K12's, by slab row
     PinnedBuf h_sq, h_dist;         // double [slots]
     Event ev;
+    // K13's (Multi-Krum's pairwise distances), allocated by the first pgh_row_pairdist / pgh_krum_select: the
+    // tile partials of one batch of anchors, at most pair_budget bytes whatever n and the model; the n x n
+    // matrix; the listed slab rows as a device table
+    DeviceBuf d_pair_part, d_pair, d_pair_rows;
+    size_t pair_budget = (size_t)1 << 30;  // PGH_PAIRDIST_BUDGET (bytes) lowers it, for tests of the batching
 
     double at(int slot) const { return value[(size_t)slot]; }  // after wait(): the sum of a slot queued before it
     void reserved(int slots) {  // pgh_reserve: the cache at its new length
@@ -49,7 +54,7 @@ struct RowSums {
         queued.clear();
     }
     void slab_freed() {  // the streams are idle: every buffer sized by the slab goes, and the cache
-        for (auto* v : {&d_part, &d_sq, &d_dist}) v->reset();
+        for (auto* v : {&d_part, &d_sq, &d_dist, &d_pair_part, &d_pair, &d_pair_rows}) v->reset();
         h_sq.reset();
         h_dist.reset();
         state.clear();
@@ -69,6 +74,9 @@ struct RowSums {
     // K12 over the listed slots against negv on stream s, the D2H of the sums and the wait: D[k] = the squared
     // distance of slots[k]
     int distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* negv, hipStream_t s, double* D);
+    // K13 over the listed slots (n <= PAIRDIST_MAX_ROWS) on stream s in batches of anchors, the D2H and the wait:
+    // D[a * n + b] = the squared distance of slots[a] to slots[b], symmetric, +0.0 on the diagonal
+    int pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D);
 };
 
 // The fold's per-client weights (fold order) and their device copy.  Three writers: the caller
@@ -186,6 +194,14 @@ struct GeomedState {
         nu = 0.f;
         forget();
     }
+};
+
+// Multi-Krum selection (pgh_krum_select): a call, not a setting -- what the last
+// selection saw, for pgh_krum_stats.  The sums and the distance matrix: RowSums.
+struct KrumState {
+    int64_t n_rows = 0, n_excluded = 0, n_picked = 0;
+    double max_picked_score = 0.0, min_dropped_score = 0.0;  // (min_dropped: +inf when nothing was dropped)
+    void forget() { *this = KrumState{}; }  // pgh_reset
 };
 
 // Trimmed-mean FedAvg (pgh_set_trim, PGH_TRIMMED_MEAN).  A fold that is a

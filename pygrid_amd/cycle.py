@@ -31,7 +31,7 @@ from .engine import ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
 from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, check_trim_count, clip_norm_of, failing_closed, median_of, \
     rule_of, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
-from . import serveropt
+from . import krum as krum_mod, serveropt
 from .dp import DpKeys
 from .serveropt import ServerOptStates
 from .settings import settings_of
@@ -328,7 +328,7 @@ class CycleAggregator:
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
                            plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
-                           dp_noise=UNSET, dp_round=None, geometric_median=UNSET) -> bytes:
+                           dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -338,12 +338,14 @@ class CycleAggregator:
         when the key is set); the step is committed once the new checkpoint bytes exist.  ``dp_noise`` /
         ``dp_round``: Gaussian noise on the clipped close (``dp.dp_noise_of``; default
         ``server_config["dp_noise"]``) and the round it is drawn for -- the cycle's id, required beside it;
-        the key not given in the setting is ``opt_key``'s in ``dp_keys``."""
+        the key not given in the setting is ``opt_key``'s in ``dp_keys``.  ``krum``: the Multi-Krum selection
+        (``krum.krum_of``; default ``server_config["diff_krum"]``): the cycle's mode then averages the picked
+        diffs alone, as if they were the only reports."""
         if framing not in ("fresh", "template"):
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum)
         with self._closing(server_config, given, avg_plan, weights, plan_key, lambda: _shapes_or_none(checkpoint),
                            lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round) as (settings, mode):
             return self._average_plan_diffs(checkpoint, diffs, weights, framing, settings, mode)
@@ -353,19 +355,29 @@ class CycleAggregator:
         """What both entry points do before their first ingest, and the fail-closed block they fold in:
         gives ``(settings, mode)`` with the engine laid out for ``numel_of()`` and ``n_diffs`` rows, the rule and the
         noise set and ``opt_key``'s moments bound.  ``given``: the caller's clip_norm, trim_count, median, dp_noise,
-        geometric_median."""
-        settings = settings_of(server_config, *given[:4], geometric_median=given[4])
+        geometric_median, krum."""
+        settings = settings_of(server_config, *given[:4], geometric_median=given[4], krum=given[5])
         with settings.fail_closed("the engine cannot average this cycle"):
             mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                                shapes=shapes, n_clients=n_diffs, **settings.rule_kwargs())
-            if settings.rule is not None and settings.rule.key == TRIM_KEY:
-                check_trim_count(settings.rule.value, n_diffs)
+            if settings.rule is not None and settings.rule.key == TRIM_KEY and settings.select is None:
+                check_trim_count(settings.rule.value, n_diffs)  # (under a selection: of the picked diffs, _finish_picked)
             numel = numel_of()
             self._prepare(numel, n_diffs)
             # before the first ingest: each diff's norm pass rides behind its copy
             settings.set_on_engine(self.engine, settings.noise_key(self.dp_keys, opt_key), dp_round)
             self.opt_states.bind(self.engine, opt_key, settings.opt, sum(numel))  # before the fold: its moments
             yield settings, mode
+
+    def _finish_picked(self, settings, mode, n_diffs, weights):
+        """Under a selection, after the ingests: the picked diffs alone are folded into the resident checkpoint,
+        in the cycle's order, in the cycle's mode."""
+        picked = krum_mod.select(self.engine, settings.select, range(n_diffs))
+        if settings.rule is not None and settings.rule.key == TRIM_KEY:
+            check_trim_count(settings.rule.value, len(picked))
+        if mode == WEIGHTED_MEAN:
+            self.engine.set_weights([weights[i] for i in picked])
+        self.engine.fold_slots_finish_resident(mode, picked)
 
     def _average_plan_diffs(self, checkpoint, diffs, weights, framing, settings, mode):
         if checkpoint is not self._resident or self.engine.ckpt_owner is not self:
@@ -376,13 +388,16 @@ class CycleAggregator:
             except StateParseError:
                 _decline_non_float32(d, f"diff {i}")
                 raise
-        if mode == WEIGHTED_MEAN:
+        if mode == WEIGHTED_MEAN and settings.select is None:
             self.engine.set_weights(weights)
         # From the fold on, HBM holds the NEW checkpoint: until its bytes exist, nobody may take the
         # resident copy for `checkpoint` (a retry after a failed patch would fold twice).
         self.engine.ckpt_owner = None
         self._resident = None
-        self.engine.fedavg_resident(mode)  # :252-296
+        if settings.select is not None:
+            self._finish_picked(settings, mode, len(diffs), weights)
+        else:
+            self.engine.fedavg_resident(mode)  # :252-296
         new = (state_codec.fresh_checkpoint(self.engine, checkpoint) if framing == "fresh"  # :303
                else self.engine.ckpt_patch_state(checkpoint))
         if settings.opt is not None:
@@ -396,23 +411,28 @@ class CycleAggregator:
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
                        weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
-                       dp_noise=UNSET, dp_round=None, geometric_median=UNSET) -> List[np.ndarray]:
+                       dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         shapes = [np.shape(p) for p in model_params]
         numel = [int(np.prod(s)) for s in shapes]
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum)
         with self._closing(server_config, given, avg_plan, weights, None, shapes, lambda: numel, len(diffs), opt_key,
                            dp_round) as (settings, mode):
             for i, d in enumerate(diffs):
                 if len(d) != len(numel):
                     raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
                 self.engine.ingest(i, np.concatenate([np.asarray(t, np.float32).reshape(-1) for t in d]))
-            if mode == WEIGHTED_MEAN:
-                self.engine.set_weights(weights)
             flat = np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in model_params])
             self._resident = None  # the host-buffer fold overwrites the resident checkpoint
-            out = self.engine.fedavg(mode, flat)
+            if settings.select is not None:  # the slot-list FINAL folds into the resident checkpoint
+                self.engine.ckpt_upload(flat)
+                self._finish_picked(settings, mode, len(diffs), weights)
+                out = self.engine.ckpt_download()
+            else:
+                if mode == WEIGHTED_MEAN:
+                    self.engine.set_weights(weights)
+                out = self.engine.fedavg(mode, flat)
             if settings.opt is not None:
                 self.opt_states.commit(self.engine)  # the new parameters are on the host: the step counts
             res, off = [], 0

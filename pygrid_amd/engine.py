@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -17,6 +17,7 @@ from .exceptions import AggregationError, EngineUnavailableError, StateParseErro
 
 MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN, GEOMETRIC_MEDIAN = 0, 1, 2, 3, 4, 5, 6
 GEOMED_MAX_ITERS = 16  # PGH_GEOMED_MAX_ITERS
+KRUM_MAX_ROWS = 1024   # PGH_KRUM_MAX_ROWS
 TRIM_MAX = 8  # PGH_TRIM_MAX
 MEDIAN_NCHIP = 1024  # PGH_MEDIAN_NCHIP: rows the on-chip median kernel takes
 STREAM_SECAGG = 16
@@ -377,6 +378,52 @@ class Engine:
                     "geomed_stats")
         return {"iterations": it.value, "rows": n.value, "excluded": x.value, "objective": o.value,
                 "max_weight": m.value}
+
+    # ---- Multi-Krum selection ahead of the average (kernel K13) ---------------------------------------
+    def row_pairdist(self, slots: Sequence[int]) -> np.ndarray:
+        """float64 [n][n] squared distances among the diffs in ``slots``: K13 alone; entry (a, b) is
+        ``row_distsq([slots[a]], diff of slots[b])`` bit for bit (tests, debugging)."""
+        a = np.ascontiguousarray(slots, dtype=np.int32)
+        out = np.empty((a.size, a.size), dtype=np.float64)
+        self._check(self._lib.pgh_row_pairdist(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
+                                               out.ctypes.data_as(C.POINTER(C.c_double))), "row_pairdist")
+        return out
+
+    def krum_select(self, slots: Sequence[int], f: int, m: int = 0) -> List[int]:
+        """The Multi-Krum selection (``include/pgh_api.h``) over the diffs in ``slots`` with ``f`` assumed
+        hostile: the ``m`` most central slots (0: all but f of the finite ones), in the order of ``slots``."""
+        a = np.ascontiguousarray(slots, dtype=np.int32)
+        picked, n = np.empty(max(a.size, 1), dtype=np.int32), C.c_int(0)
+        self._check(self._lib.pgh_krum_select(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, int(f), int(m),
+                                              picked.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "krum_select")
+        return [int(x) for x in picked[:n.value]]
+
+    @staticmethod
+    def krum_select_host(D, f: int, m: int = 0):
+        """``(picked positions, scores)`` of the selection's host step over the [n][n] squared distances ``D``
+        of the included rows (plain C++; no GPU)."""
+        lib = _lib.load()
+        d = np.ascontiguousarray(D, dtype=np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise AggregationError(f"krum_select_host: the distances must be [n][n], not {d.shape}")
+        n = d.shape[0]
+        picked, k, sc = np.empty(max(n, 1), dtype=np.int32), C.c_int(0), np.empty(n, dtype=np.float64)
+        rc = lib.pgh_krum_select_host(d.ctypes.data_as(C.POINTER(C.c_double)), n, int(f), int(m),
+                                      picked.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k),
+                                      sc.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise AggregationError(f"krum_select_host: {_lib.STATUS_NAMES.get(rc, rc)}: "
+                                   f"{lib.pgh_last_error(None).decode(errors='replace')}", status=rc)
+        return [int(x) for x in picked[:k.value]], sc
+
+    def krum_stats(self) -> dict:
+        """What the last ``krum_select`` saw: ``rows``, ``excluded`` (non-finite rows left out), ``picked``,
+        ``max_picked_score`` and ``min_dropped_score`` (inf when nothing was dropped)."""
+        n, x, k, a, b = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0), C.c_double(0)
+        self._check(self._lib.pgh_krum_stats(self._h, C.byref(n), C.byref(x), C.byref(k), C.byref(a), C.byref(b)),
+                    "krum_stats")
+        return {"rows": n.value, "excluded": x.value, "picked": k.value, "max_picked_score": a.value,
+                "min_dropped_score": b.value}
 
     # ---- coordinate-wise trimmed mean (TRIMMED_MEAN) ----------------------------------------------
     def set_trim(self, b: int):

@@ -69,6 +69,15 @@ class GeometricMedianUnavailableError(AggregationError):
     averaging takes no geometric median, so the close fails closed."""
 
 
+class KrumUnavailableError(AggregationError):
+    """The FL process asks for the Multi-Krum selection of its diffs (``server_config["diff_krum"]``) and the
+    engine cannot select this cycle: it declines the cycle (an unaccelerated plan, a non-float32 model), it has
+    no ``krum_select`` or answers PGH_E_UNSUPPORTED (a multi-GPU group, a sub-range shard, more than 1,024
+    diffs), ``dp_noise`` is set beside it, or fewer than ``2 f + 3`` finite diffs reached the close.  Like the
+    rules' errors it is NOT a ``PlanNotAcceleratedError``: the node's own averaging selects nothing, so the
+    close fails closed."""
+
+
 class ServerOptUnavailableError(AggregationError):
     """The FL process asks for a server optimizer (``server_config["server_optimizer"]``) and the
     engine cannot apply it this cycle: it declines the cycle (an unaccelerated plan, a non-float32

@@ -68,7 +68,7 @@ from . import state as state_codec
 from .cycle import _decline_non_float32
 from .engine import F32, MEAN, WEIGHTED_MEAN, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
-from . import dp, serveropt
+from . import dp, krum as krum_mod, serveropt
 from .robust import check_trim_count, failing_closed
 from .settings import CloseSettings, settings_of
 
@@ -87,10 +87,16 @@ class IncrementalCycle:
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
                  median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
-                 dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None):
+                 dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None, krum=None):
         """``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
-        ``median``, ``geometric_median``, ``server_opt`` and ``dp_noise`` below (both: an error); keys, round and
-        stores go beside either.
+        ``median``, ``geometric_median``, ``server_opt``, ``dp_noise`` and ``krum`` below (both: an error); keys,
+        round and stores go beside either.
+
+        ``krum``: the FL process's Multi-Krum selection (``krum.krum_of``: the setting's dict or its parsed form),
+        beside any ``mode``, weights or rule.  A selection needs every diff at once, so nothing is folded early and
+        the cycle takes at most as many diffs as slots, as under the median: the close selects over the held slots in
+        the close's order and finishes over the picked ones (their weights alone, a trim count checked against
+        their number), ``KrumUnavailableError`` where the engine cannot.
 
         ``geometric_median``: the FL process asks for the geometric median (``robust.geomed_of``: ``True``, the
         setting's dict or its parsed pair).  Wired like the median -- ``mode`` MEAN, no weights, no other rule,
@@ -131,8 +137,8 @@ class IncrementalCycle:
         self.mode = mode
         given = {k: v for k, v in dict(clip_norm=clip_norm, trim_count=trim_count, median=bool(median) or None,
                                        server_opt=server_opt, dp_noise=dp_noise,
-                                       geometric_median=None if geometric_median is False else geometric_median
-                                       ).items() if v is not None}
+                                       geometric_median=None if geometric_median is False else geometric_median,
+                                       krum=None if krum is False else krum).items() if v is not None}
         if settings is not None and given:
             raise AggregationError(f"settings= was given beside {', '.join(given)}")
         self._settings = settings = settings if settings is not None else settings_of({}, **given)
@@ -143,7 +149,8 @@ class IncrementalCycle:
         if rule is not None:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
         # a rule that needs every row of the cycle in one call: nothing folds early, no partial fold at the close
-        self._whole = bool(self.median) or self.geometric_median is not None
+        self._select = settings.select
+        self._whole = bool(self.median) or self.geometric_median is not None or self._select is not None
         self._fold_mode = rule.mode if rule else mode
         self._noise_args = (settings.noise_key(dp_keys if dp_keys is not None else dp.DpKeys(), opt_key), dp_round)
         self._opt_key = opt_key
@@ -207,7 +214,7 @@ class IncrementalCycle:
             try:
                 engine.ckpt_upload_state(checkpoint)
             except StateParseError:
-                with failing_closed(rule):
+                with krum_mod.failing_closed(self._select), failing_closed(rule):
                     _decline_non_float32(checkpoint, "the checkpoint")
                 raise
             engine.ckpt_owner = self
@@ -427,7 +434,7 @@ class IncrementalCycle:
                 raise AggregationError("cycle already closed")
             self._closed = True
             if self._declined:
-                with failing_closed(self._rule):
+                with krum_mod.failing_closed(self._select), failing_closed(self._rule):
                     raise ModelNotAcceleratedError(self._declined)
             if order is None:
                 if self._stale or self._bad:
@@ -445,8 +452,8 @@ class IncrementalCycle:
             if self.trim_count is not None:
                 check_trim_count(self.trim_count, len(order))
             if self._whole and len(order) > self.slots:  # every row at once: no partial fold, no slot given up
-                raise self._rule.refuse(f"is set and the cycle has {len(order)} diffs, the slab {self.slots} slots: a "
-                                        f"{'median' if self.median else 'geometric median'} needs every diff in HBM at once")
+                raise self._whole_refuse(f"is set and the cycle has {len(order)} diffs, the slab {self.slots} slots: "
+                                         f"{self._whole_name()} needs every diff in HBM at once")
             if self._weights_by_worker is not None:
                 missing = [w for w in order if w not in self._weights_by_worker]
                 if missing:
@@ -529,9 +536,27 @@ class IncrementalCycle:
             refold = self._stale or _common_prefix(self._folded, order) < len(self._folded)
             return self._fold_in_order(order if refold else order[len(self._folded):], None, dry=True)["db_rows"]
 
+    def _whole_name(self) -> str:
+        return "a median" if self.median else "a geometric median" if self.geometric_median is not None else "a selection"
+
+    def _whole_refuse(self, why: str) -> AggregationError:
+        """The refusal of whatever needs every row at once: the rule's, else the selection's."""
+        whole_rule = self._rule is not None and (self.median or self.geometric_median is not None)
+        return self._rule.refuse(why) if whole_rule else krum_mod.refuse(why)
+
     def _fold(self, ws: Sequence, final: bool, slot_of: dict, free: list, dry: bool):
         slots = [slot_of.pop(w) for w in ws]
-        if not dry:
+        if not dry and self._select is not None:
+            # (final, and every diff of the close: _whole folds nothing early and nothing partially)
+            picked = set(krum_mod.select(self.engine, self._select, slots))
+            ws_picked = [w for w, s in zip(ws, slots) if s in picked]
+            if self.trim_count is not None:
+                check_trim_count(self.trim_count, len(ws_picked))
+            if self.mode == WEIGHTED_MEAN and self._weights_by_worker is not None:
+                self._weights = [float(self._weights_by_worker[w]) for w in ws_picked]
+                self.engine.set_weights(self._weights)
+            self.engine.fold_slots_finish_resident(self._fold_mode, [s for s in slots if s in picked])
+        elif not dry:
             if self.mode == WEIGHTED_MEAN and self._weights_by_worker is not None and (ws or final):
                 self._weights.extend(float(self._weights_by_worker[w]) for w in ws)
                 if self._weights:
@@ -573,7 +598,7 @@ class IncrementalCycle:
             else:
                 from_host += 1
             if not free and self._whole:  # (seal refused a close with more diffs than slots)
-                raise self._rule.refuse("is set and no slot is free for a diff of the close")
+                raise self._whole_refuse("is set and no slot is free for a diff of the close")
             if not free:
                 if batch:
                     self._fold(batch, False, slot_of, free, dry)

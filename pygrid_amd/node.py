@@ -480,7 +480,7 @@ class NodeEngine:
                 self.stats["closes_close_time"] += 1
                 return close_time(cm, server_config, cycle)
             self.stats["closes_report_time"] += 1
-            if settings.rule is not None:
+            if settings.rule is not None or settings.select is not None:
                 log.info(settings.close_message(cycle.id, st.last_close))
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)

@@ -1,11 +1,12 @@
 """Everything an FL process can ask of a cycle's close in its ``server_config`` -- a robust-aggregation
 rule (``robust.py``), a server optimizer (``serveropt.py``), Gaussian noise beside the clip bound
-(``dp.py``) -- parsed once, by ``settings_of`` alone, into one ``CloseSettings``, which is what the call
+(``dp.py``), a Multi-Krum selection of the diffs ahead of the average (``krum.py``) -- parsed once, by ``settings_of`` alone, into one ``CloseSettings``, which is what the call
 sites hold: its ``fail_closed`` is the one fail-closed decision, ``refusing_original`` the one stand-in for
 the node's own averaging, ``set_on_engine`` the one way onto an engine, ``close_stats`` what ``last_close``
-says.  Of two things set together the noise speaks before the rule, the rule before the optimizer.
+says.  Of two things set together the noise speaks before the rule, the rule before the selection, the
+selection before the optimizer.
 
-Sits below ``cycle.py`` and ``incremental.py`` (it imports only those three, ``engine`` and ``exceptions``).
+Sits below ``cycle.py`` and ``incremental.py`` (it imports only those four, ``engine`` and ``exceptions``).
 """
 from __future__ import annotations
 
@@ -13,10 +14,11 @@ import contextlib
 import dataclasses
 from typing import Callable, Optional
 
-from . import dp, robust
+from . import dp, krum as krum_mod, robust
 from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
-from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, PlanNotAcceleratedError, \
-    ServerOptUnavailableError
+from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, KrumUnavailableError, \
+    PlanNotAcceleratedError, ServerOptUnavailableError
+from .krum import KRUM_KEY, KrumSpec, krum_of
 from .robust import CLIP_KEY, GEOMED_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
 
@@ -27,9 +29,10 @@ class CloseSettings:
     rule: Optional[Rule] = None
     opt: Optional[ServerOptSpec] = None
     noise: Optional[DpNoiseSpec] = None
+    select: Optional[KrumSpec] = None
 
     def __bool__(self) -> bool:
-        return self.rule is not None or self.opt is not None or self.noise is not None
+        return self.rule is not None or self.opt is not None or self.noise is not None or self.select is not None
 
     def rule_kwargs(self) -> dict:
         """The rule as the keyword argument that ``select_mode`` takes."""
@@ -40,9 +43,10 @@ class CloseSettings:
         """A ``PlanNotAcceleratedError`` (``ModelNotAcceleratedError`` included) raised in the block must not
         reach a caller that falls back to the node's own averaging, which clips, trims, steps and noises nothing.
         Under a rule it becomes the rule's error; under noise that error in turn, like the clip rule's own
-        refusal, a ``DpNoiseUnavailableError``; under an optimizer alone a ``ServerOptUnavailableError``."""
+        refusal, a ``DpNoiseUnavailableError``; under a selection without a rule a ``KrumUnavailableError``; under
+        an optimizer alone a ``ServerOptUnavailableError``."""
         try:
-            with robust.failing_closed(self.rule, what):
+            with krum_mod.failing_closed(self.select, what), robust.failing_closed(self.rule, what):
                 yield
         except (PlanNotAcceleratedError, ClipUnavailableError) as e:
             if self.noise is not None:
@@ -60,6 +64,8 @@ class CloseSettings:
             key, error, lacks = DP_KEY, DpNoiseUnavailableError, "adds no noise"
         elif self.rule is not None:
             key, error, lacks = self.rule.key, self.rule.error, self.rule.lacks
+        elif self.select is not None:
+            key, error, lacks = KRUM_KEY, KrumUnavailableError, "selects nothing"
         elif self.opt is not None:
             key, error, lacks = OPT_KEY, ServerOptUnavailableError, "applies no optimizer"
         else:
@@ -98,31 +104,43 @@ class CloseSettings:
             gs = engine.geomed_stats()
             stats["geometric_median"] = {"iterations": int(gs["iterations"]), "excluded": int(gs["excluded"]),
                                          "objective": float(gs["objective"]), "max_weight": float(gs["max_weight"])}
+        if self.select is not None:  # one more key, under a selection alone
+            stats["krum"] = krum_mod.close_stats(engine, self.select)
         return stats
 
     def close_message(self, cycle_id, last_close: dict) -> str:
-        """One log line on a close under a rule, from its ``last_close``."""
+        """One log line on a close under a rule or a selection, from its ``last_close``."""
+        kr = last_close.get("krum")
+        picked = "" if kr is None else "; %s picked %d of them (f = %d, %d excluded, largest picked score %s)" % (
+            KRUM_KEY, kr["picked"], kr["byzantine"], kr["excluded"], kr["max_picked_score"])
+        if self.rule is None:
+            return "cycle %s closed over %d diffs%s" % (cycle_id, last_close.get("n", 0), picked)
         noised = "" if self.noise is None else "; %s multiplier %s, noise std %s per parameter" % (
             DP_KEY, last_close.get("noise_multiplier"), last_close.get("noise_std"))
         gm = last_close.get("geometric_median")
         if gm is not None:
-            return "cycle %s closed with %s=%r over %d diffs (%d excluded, sum of distances %s, largest weight %s)" % (
+            return "cycle %s closed with %s=%r over %d diffs (%d excluded, sum of distances %s, largest weight %s)%s" % (
                 cycle_id, self.rule.key, self.rule.value, last_close.get("n", 0), gm["excluded"], gm["objective"],
-                gm["max_weight"])
-        return "cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)%s" % (
+                gm["max_weight"], picked)
+        return "cycle %s closed with %s=%r over %d diffs (%d clipped, max norm %s)%s%s" % (
             cycle_id, self.rule.key, self.rule.value, last_close.get("n", 0), last_close.get("clipped", 0),
-            last_close.get("max_norm"), noised)
+            last_close.get("max_norm"), noised, picked)
 
 
 def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
-                server_opt=UNSET, geometric_median=UNSET) -> CloseSettings:
+                server_opt=UNSET, geometric_median=UNSET, krum=UNSET) -> CloseSettings:
     """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
     ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
     malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
-    the earlier rule's error (``robust.KINDS``), noise without the clip bound ``DpNoiseUnavailableError``."""
+    the earlier rule's error (``robust.KINDS``), noise without the clip bound ``DpNoiseUnavailableError``, a
+    selection (``krum``: the setting's dict or its parsed form) beside noise ``KrumUnavailableError``."""
     rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median)
     if not isinstance(server_opt, ServerOptSpec):
         server_opt = server_opt_of(server_config if server_opt is UNSET else {OPT_KEY: server_opt})
     noise = dp_noise_of(server_config, dp_noise)
     dp.check_rule(noise, rule)
-    return CloseSettings(rule, server_opt, noise)
+    select = krum_of(server_config, krum)
+    if select is not None and noise is not None:
+        raise krum_mod.refuse(f"cannot be combined with {DP_KEY}: the clip-and-noise sensitivity argument does not "
+                              "cover a data-dependent selection of the diffs")
+    return CloseSettings(rule, server_opt, noise, select)
