@@ -56,7 +56,10 @@ typedef enum {
  * 2018; no parameter; no reference counterpart; defined below, before the reductions).
  * PGH_GEOMETRIC_MEDIAN: the smoothed Weiszfeld approximation of the geometric median of the N diffs
  * (Pillutla, Kakade, Harchaoui, "Robust Aggregation for Federated Learning"; settings from
- * pgh_set_geomed; no reference counterpart; defined below). */
+ * pgh_set_geomed; no reference counterpart; defined below).
+ * PGH_TRUSTED_MEAN: FLTrust (Cao, Fang, Liu, Gong, NDSS 2021): every diff rescaled to the norm of a server
+ * root update and weighted by its clipped cosine to it (pgh_set_trust, pgh_trust_root; no reference
+ * counterpart; defined below). */
 typedef enum {
     PGH_MEAN = 0,
     PGH_ITERATIVE_MEAN = 1,
@@ -64,7 +67,8 @@ typedef enum {
     PGH_CLIPPED_MEAN = 3,
     PGH_TRIMMED_MEAN = 4,
     PGH_MEDIAN = 5,
-    PGH_GEOMETRIC_MEDIAN = 6
+    PGH_GEOMETRIC_MEDIAN = 6,
+    PGH_TRUSTED_MEAN = PGH_GEOMETRIC_MEDIAN + 1 /* mode 7 */
 } pgh_mode;
 /* Stream kind for pgh_stream_begin besides the three averaging modes. */
 #define PGH_STREAM_SECAGG 16
@@ -381,6 +385,73 @@ int pgh_set_geomed(pgh_ctx* ctx, int iters, float nu);
 int pgh_row_distsq(pgh_ctx* ctx, const int32_t* slots, int n, const float* point, double* out);
 int pgh_geomed_stats(pgh_ctx* ctx, int* iters, int64_t* n_rows, int64_t* n_excluded, double* objective,
                      float* max_weight);
+
+/* ---- trust-bootstrapped FedAvg (PGH_TRUSTED_MEAN, FLTrust; kernel K14) ---------------------------
+ * Every other robust rule here assumes that the hostile workers are a minority.  This one does not: the
+ * server computes an update g0 of its own from a small clean root dataset and the cycle's checkpoint, and
+ * every reported diff is scored against it.  A diff pointing away from g0 gets trust 0; every other diff is
+ * rescaled to g0's norm and weighted by its cosine to g0.  The result stays inside the ball of radius |g0|
+ * whatever the number of hostile workers.  All arithmetic is IEEE, every operation rounded on its own (no
+ * FMA contraction); / and sqrt are correctly rounded; no libm call besides sqrt.  Rows d_0 .. d_{n-1} in
+ * fold order and the root g0 of P float32 (pgh_trust_root):
+ *   1. Root.  s0 = the sum of squares of g0 in the order of "clipped FedAvg" above (K7's exact order: the
+ *      same bits as pgh_row_sumsq of a slot holding g0).  s0 must be finite and > 0: a NaN, an infinity or an
+ *      all-zero root is PGH_E_ARG and no root is set.
+ *   2. Included rows.  s_c = K7's sum of row c, cached at ingest.  A row whose s_c is not finite is excluded,
+ *      as in the geometric median: no fold and no K14 pass of the close reads it.  The k-th included row is
+ *      fold client k.  No row included: PGH_E_STATE, nothing is launched, the context stays usable.
+ *   3. K14.  p_c = K7's sum in K7's exact order over (double)d_c[i] * (double)g0[i]: tiles of 4,096 params,
+ *      256 lane partials over j and e starting at +0.0, the shuffle tree per wave, ((w0 + w1) + w2) + w3, the
+ *      tile partials left to right.  The product of two f32 values is exact in f64, so fma(x, y, acc) is the
+ *      rounded add of the definition.  Params at or past P contribute +0.0 (the product is masked, not one
+ *      factor: 0 x NaN is NaN).  p_c is finite for every included row.
+ *   4. Weights, on the host in f64 unless said otherwise.  n0 = sqrt(s0), n_c = sqrt(s_c).
+ *        s_c > 0:  cos_c = p_c / (n0 * n_c);  ts_c = cos_c > 0 ? cos_c : 0.0;  a_c = ts_c * (n0 / n_c);
+ *        s_c == 0: ts_c = a_c = 0.0;
+ *        T = the left fold of ts_c in fold order; T == 0 is PGH_E_STATE (no row is trusted), nothing is folded;
+ *        w_c = (float)min(a_c / T, (double)FLT_MAX)  (the clamp keeps a hostile row of subnormal norm from
+ *        turning its rescale into +inf).
+ *   5. Fold and close.  acc = d_0 * w_0; acc = acc + d_c * w_c (the product rounded to f32, then the sum: the
+ *      weighted fold, with the divisor 1.0f); out = ckpt - acc; with a server optimizer K10 takes g = acc.
+ *      Rows of weight zero stay in the fold.
+ * The result is a function of the rows, their order and the root alone: not of the slots, the launch shape,
+ * the slab's block width, the range split or the entry point, nor of whether the dots were computed at
+ * ingest or at the close; a repeated close gives identical bits.
+ *
+ * pgh_set_trust: on != 0 switches the rule on, 0 off (always accepted).  PGH_E_UNSUPPORTED wherever
+ * pgh_set_clip_norm refuses (a group, a shard narrower than the layout, an int64 slab, a streaming
+ * context).  pgh_set_layout and pgh_set_shard clear the setting; pgh_reset and pgh_reserve keep it.  With the
+ * rule on every ingest queues the row's K7 behind its copy, as clipping does.
+ * pgh_trust_root: the cycle's root, P floats (nbytes = 4 P, else PGH_E_ARG), uploaded to a [P_shard] plane of
+ * its own; it needs the rule on (PGH_E_STATE).  The root belongs to the cycle: pgh_reset and pgh_reserve
+ * drop its validity (the plane stays), and a close without a root set since then is PGH_E_STATE.  A call
+ * that fails leaves no root set.  A new root makes the cached dots and the weights stale.  While a root is
+ * valid every ingest also queues the row's K14 behind its K7, so a report-time close is the host step plus
+ * one weighted fold; a close computes the dots still missing in one batch.
+ * The mode takes every row of the cycle in one call: pgh_fedavg, pgh_fedavg_device[_range],
+ * pgh_fedavg_resident and pgh_fold_slots_finish_resident (any slot list, no earlier slot fold in the cycle:
+ * PGH_E_STATE otherwise) accept it on one GPU holding whole rows; pgh_fold_slots, pgh_stream_begin, groups
+ * and narrower shards refuse it (PGH_E_UNSUPPORTED); the mode with the rule off or without a valid root is
+ * PGH_E_STATE, and so is the mode beside DP noise.  pgh_set_weights is not used (the close replaces the
+ * weights).  The weights are computed once per state of the slab and root: range calls and repeated closes
+ * reuse them.  pgh_effective_variant(ctx, PGH_TRUSTED_MEAN) reports what the weighted fold would run.
+ * pgh_row_dot: K14 alone against `point` (host, P floats), the counterpart of pgh_row_distsq: the n listed
+ * occupied slots' p_c into out (n doubles).  It does not sanitise, a slot may repeat, and it uses a scratch
+ * plane of its own: the root, the cached dots and K7's cache are untouched.
+ * pgh_trust_weights_host: steps 2 and 4 in plain C++, no context and no GPU: from s0 and the n rows' s_c and
+ * p_c (p_c is not read where s_c is not finite), the positions of the included rows into `included` and
+ * their w_c into `weights` (room for n each), their count and T.  s0 not finite or <= 0 is PGH_E_ARG; no row
+ * included or T == 0 is PGH_E_STATE (n_included and total_trust are written all the same).
+ * pgh_trust_stats: whether the rule is on and, of the last computation of the weights: the rows given, how
+ * many were excluded, how many had ts > 0, T, the largest w_c, and n0 of the valid root (0 without one).
+ * Each pointer may be NULL. */
+int pgh_set_trust(pgh_ctx* ctx, int on);
+int pgh_trust_root(pgh_ctx* ctx, const float* root, size_t nbytes);
+int pgh_row_dot(pgh_ctx* ctx, const int32_t* slots, int n, const float* point, double* out);
+int pgh_trust_weights_host(double s0, const double* sumsq, const double* dot, int n, float* weights,
+                           int32_t* included, int* n_included, double* total_trust);
+int pgh_trust_stats(pgh_ctx* ctx, int* on, int64_t* n_rows, int64_t* n_excluded, int64_t* n_trusted,
+                    double* total_trust, float* max_weight, double* root_norm);
 
 /* ---- Multi-Krum selection of diffs ahead of the average (Blanchard et al. 2017; kernel K13) --------
  * A stage, not an averaging mode: it decides WHICH diffs a cycle averages.  Each diff is scored by its

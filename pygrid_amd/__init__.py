@@ -19,9 +19,9 @@ from .exceptions import (AggregationError, ClipUnavailableError, DpNoiseUnavaila
                          KrumUnavailableError, MedianUnavailableError,
                          ModelNotAcceleratedError,
                          PlanNotAcceleratedError, PyGridError, ServerOptUnavailableError, StateParseError,
-                         TrimUnavailableError)
+                         TrimUnavailableError, TrustUnavailableError)
 from .engine import (CLIPPED_MEAN, F32, GEOMETRIC_MEDIAN, I64, ITERATIVE_MEAN, MEAN, MEDIAN, MEDIAN_NCHIP, MODE_NAMES, STREAM_SECAGG,
-                     TRIMMED_MEAN, TRIM_MAX,
+                     TRIMMED_MEAN, TRIM_MAX, TRUSTED_MEAN,
                      WEIGHTED_MEAN, Engine, PinnedBuffer, device_count)
 
 
@@ -44,7 +44,7 @@ __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
     "StateParseError", "TrimUnavailableError", "MedianUnavailableError", "ServerOptUnavailableError", "DpNoiseUnavailableError",
     "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
-    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "GEOMETRIC_MEDIAN", "GeometricMedianUnavailableError", "KrumUnavailableError", "MODE_NAMES", "F32", "I64",
+    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "GEOMETRIC_MEDIAN", "GeometricMedianUnavailableError", "KrumUnavailableError", "TRUSTED_MEAN", "TrustUnavailableError", "MODE_NAMES", "F32", "I64",
     "tune_process",
 ]
 __version__ = "0.3.0"

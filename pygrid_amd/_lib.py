@@ -112,6 +112,13 @@ SIGNATURES = {
     "pgh_set_geomed": (_i, [_vp, _i, C.c_float]),
     "pgh_row_distsq": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "pgh_geomed_stats": (_i, [_vp, C.POINTER(C.c_int), _P64, _P64, C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "pgh_set_trust": (_i, [_vp, _i]),
+    "pgh_trust_root": (_i, [_vp, C.POINTER(C.c_float), _sz]),
+    "pgh_row_dot": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "pgh_trust_weights_host": (_i, [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_float),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "pgh_trust_stats": (_i, [_vp, C.POINTER(C.c_int), _P64, _P64, _P64, C.POINTER(C.c_double), C.POINTER(C.c_float),
+                             C.POINTER(C.c_double)]),
     "pgh_row_pairdist": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
     "pgh_krum_select_host": (_i, [C.POINTER(C.c_double), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int),
                                   C.POINTER(C.c_double)]),

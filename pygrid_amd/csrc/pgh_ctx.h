@@ -15,7 +15,7 @@
 //   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: the row sums (RowSums:
 //                   K7 and its cache, K12), clipping (the scales, the tallies) and the Gaussian noise on the clipped
 //                   close (K11 behind a FINAL launch), trimming (K8's planes), the median (K9, K9p), the geometric
-//                   median (its weights); the -0 plane; the rules' lifecycle calls (rules_*), the fold plans the
+//                   median (its weights), the trust rule (its root, K14's cached dots, its weights); the -0 plane; the rules' lifecycle calls (rules_*), the fold plans the
 //                   two drivers ask for (rules_slot_plan, rules_resident_plan) and the entry points.  Their state:
 //                   pgh_rules.h
 //   pgh_serveropt.cpp  the server optimizer: K10 behind a FINAL launch, its planes, commit, download, upload
@@ -67,7 +67,8 @@ namespace pgh_detail {
 
 constexpr int KIND_SECAGG = PGH_STREAM_SECAGG;  // fold kind besides the pgh_mode values (none of which it equals)
 static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KIND_SECAGG != PGH_WEIGHTED_MEAN &&
-                  KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN && KIND_SECAGG != PGH_MEDIAN && KIND_SECAGG != PGH_GEOMETRIC_MEDIAN,
+                  KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN && KIND_SECAGG != PGH_MEDIAN && KIND_SECAGG != PGH_GEOMETRIC_MEDIAN &&
+                  KIND_SECAGG != PGH_TRUSTED_MEAN,
               "the secagg fold kind must not collide with an averaging mode");
 
 // CPUs on the GPU's own socket (its PCI device's local_cpulist) that this process may run on; empty
@@ -166,14 +167,15 @@ struct pgh_ctx {
     // (pgh_rules.cpp, pgh_serveropt.cpp) and by fold_launch's lines for the optimizer and noise tenants.  The
     // lifecycle files (pgh_api.cpp, pgh_ingest.cpp, pgh_slots.cpp, pgh_xfer.cpp, pgh_order.cpp) reach them
     // through rules_* and the fold plans below alone:
-    //   grep -n 'c->\(clip\|geo\|krum\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
-    pgh_detail::RowSums rowsums;   // K7's per-slot cache, the buffers of K7, K12 and K13 (clip, geo, krum)
+    //   grep -n 'c->\(clip\|geo\|trust\|krum\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
+    pgh_detail::RowSums rowsums;   // K7's and K14's per-slot caches, the buffers of K7, K12, K13 and K14 (clip, geo, krum, trust)
     pgh_detail::NegZeroPlane nz;   // the one plane of -0.0f (opt, noise, geo)
     pgh_detail::ClipState clip;
     pgh_detail::NoiseState noise;
     pgh_detail::TrimState trim;
     pgh_detail::MedianState med;
     pgh_detail::GeomedState geo;
+    pgh_detail::TrustState trust;
     pgh_detail::KrumState krum;
     pgh_detail::ServerOptState opt;
 
@@ -229,13 +231,16 @@ double now_ms();
 inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
 inline bool valid_mode(int m) {  // (pgh_effective_variant's alone: check_mode_use has its own switch)
     return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN ||
-           m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN || m == PGH_GEOMETRIC_MEDIAN;
+           m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN || m == PGH_GEOMETRIC_MEDIAN || m == PGH_TRUSTED_MEAN;
 }
+static_assert(PGH_TRUSTED_MEAN == 7, "the mode numbers are ABI: engine.py and every caller hold them as integers");
 static_assert(PGH_TRIMMED_MEAN == pgh::MODE_TRIMMED && PGH_TRIM_MAX == pgh::TRIM_MAX, "the kernels' numbering");
 static_assert(PGH_MEDIAN == pgh::MODE_MEDIAN && PGH_MEDIAN_NCHIP == pgh::MEDIAN_NCHIP, "the kernels' numbering");
 // The kernels' mode: a clipped mean is the weighted fold with the scales as weights, a geometric median the
-// weighted fold with the last Weiszfeld weights.
-inline int kernel_mode(int m) { return m == PGH_CLIPPED_MEAN || m == PGH_GEOMETRIC_MEDIAN ? PGH_WEIGHTED_MEAN : m; }
+// weighted fold with the last Weiszfeld weights, a trusted mean the weighted fold with the trust weights.
+inline int kernel_mode(int m) {
+    return m == PGH_CLIPPED_MEAN || m == PGH_GEOMETRIC_MEDIAN || m == PGH_TRUSTED_MEAN ? PGH_WEIGHTED_MEAN : m;
+}
 // May `mode` be folded this way on this context?  The one place that says so, in this order: an unknown
 // mode (PGH_E_ARG); a rule that the use or a group cannot serve -- a stream neither clips, trims nor
 // takes a median, a median folds nothing early, a group does not clip (PGH_E_UNSUPPORTED); a rule whose
@@ -385,7 +390,8 @@ int rules_row_ingested(pgh_ctx* c, int slot);   // the tail of an fp32 ingest: a
 // What a fold driver asks the rules before its launches: which rows the fold of `mode` takes and with what.
 // For PGH_MEAN, ITERATIVE, WEIGHTED, TRIMMED and MEDIAN (and a share sum) the plan is the input unchanged and
 // nothing is launched.  A clipped fold gets its scales as the weights (K7 for the sums still missing); a
-// geometric median its included rows, their final weights and W (the inner iterations are finished on return).
+// geometric median its included rows, their final weights and W (the inner iterations are finished on return); a
+// trusted mean its included rows, their trust weights and the divisor 1 (K7 and K14 for what is still missing).
 struct FoldPlan {
     const int32_t* slots = nullptr;  // the rows to fold, in order: the given ones or the included ones.
                                      // rules_resident_plan: null = clients [0, n) where the slab holds them
@@ -397,7 +403,7 @@ struct FoldPlan {
 };
 int rules_slot_plan(pgh_ctx* c, int mode, const int32_t* slots, int n, int64_t c0, FoldPlan* p);  // slot_fold
 int rules_resident_plan(pgh_ctx* c, int mode, int64_t c0, int64_t n, FoldPlan* p);                // fold_run
-// A rule that closes a cycle in one slot fold only (median, geometric median): its name for the refusal; else null.
+// A rule that closes a cycle in one slot fold only (median, geometric median, trusted mean): its name for the refusal; else null.
 const char* rules_one_fold_cycle(int mode);
 int trim_divisor(pgh_ctx* c, int64_t n, float* div);  // n - 2b; PGH_E_STATE with fewer than 2b + 1 diffs
 
@@ -425,8 +431,10 @@ float clip_scale_of(double sumsq, float c);
 
 // ---- geometric-median FedAvg (pgh_rules.cpp) ---------------------------------------------------------
 inline bool geomed_on(const pgh_ctx* c) { return c->geo.iters > 0 && c->dtype == PGH_F32 && !c->streaming; }
-// K7 behind every ingest: clipping or the geometric median is on
-inline bool norms_wanted(const pgh_ctx* c) { return clip_on(c) || geomed_on(c); }
+// ---- trust-bootstrapped FedAvg (pgh_rules.cpp) ---------------------------------------------------------
+inline bool trust_on(const pgh_ctx* c) { return c->trust.on && c->dtype == PGH_F32 && !c->streaming; }
+// K7 behind every ingest: clipping, the geometric median or the trust rule is on
+inline bool norms_wanted(const pgh_ctx* c) { return clip_on(c) || geomed_on(c) || trust_on(c); }
 
 // ---- Gaussian noise on the clipped close (pgh_rules.cpp) ---------------------------------------------
 inline bool noise_on(const pgh_ctx* c) { return c->noise.z > 0.f; }

@@ -7,6 +7,7 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -233,6 +234,76 @@ int krum_select(const double* D, int n, int f, int m, int32_t* picked, int* n_pi
     std::sort(order.begin(), order.begin() + keep);  // the picked rows in list order
     std::copy(order.begin(), order.begin() + keep, picked);
     *n_picked = keep;
+    return 0;
+}
+
+double row_dot_host(const float* x, const float* y, int64_t p) {
+    double row = 0.0;
+    for (int64_t base = 0; base < p || base == 0; base += 4096) {
+        double a[256];
+        for (int l = 0; l < 256; ++l) {
+            double acc = 0.0;
+            for (int j = 0; j < 4; ++j)
+                for (int e = 0; e < 4; ++e) {
+                    const int64_t i = base + 4 * (l + 256 * j) + e;
+                    // (the product of two f32 values is exact in f64: one rounded addition, as the kernels' fma)
+                    acc = acc + (i < p ? (double)x[i] * (double)y[i] : 0.0);
+                }
+            a[l] = acc;
+        }
+        double w[4];
+        for (int wv = 0; wv < 4; ++wv) {
+            double* v = a + 64 * wv;
+            for (int h = 32; h >= 1; h >>= 1)
+                for (int l = 0; l < h; ++l) v[l] = v[l] + v[l + h];
+            w[wv] = v[0];
+        }
+        row = row + (((w[0] + w[1]) + w[2]) + w[3]);
+    }
+    return row;
+}
+
+int trust_weights(double s0, const double* sumsq, const double* dot, int64_t n, float* w, int32_t* included,
+                  int64_t* n_included, double* T, int64_t* n_trusted, float* max_w) {
+    if (!(std::isfinite(s0) && s0 > 0.0)) return -1;
+    const double n0 = std::sqrt(s0);
+    std::vector<double> a;
+    double tot = 0.0;
+    int64_t ni = 0, nt = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const double sc = sumsq[k];
+        if (!std::isfinite(sc)) continue;  // excluded
+        double ts = 0.0, ac = 0.0;
+        if (sc > 0.0) {
+            const double nc = std::sqrt(sc);
+            const double den = n0 * nc;
+            const double cosc = dot[k] / den;
+            ts = cosc > 0.0 ? cosc : 0.0;
+            const double resc = n0 / nc;
+            ac = ts * resc;
+        }
+        included[ni] = (int32_t)k;
+        tot = ni == 0 ? ts : tot + ts;
+        a.push_back(ac);
+        nt += ts > 0.0 ? 1 : 0;
+        ++ni;
+    }
+    *n_included = ni;
+    if (n_trusted) *n_trusted = nt;
+    if (max_w) *max_w = 0.f;
+    if (ni == 0) {
+        *T = 0.0;
+        return -2;
+    }
+    *T = tot;
+    if (!(tot != 0.0)) return -3;
+    float mx = 0.f;
+    for (int64_t k = 0; k < ni; ++k) {
+        const double q = a[(size_t)k] / tot;
+        w[k] = (float)std::min(q, (double)FLT_MAX);
+        mx = w[k] > mx ? w[k] : mx;
+    }
+    if (max_w) *max_w = mx;
     return 0;
 }
 

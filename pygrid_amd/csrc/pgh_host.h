@@ -212,4 +212,18 @@ bool geomed_step(const double* D, int64_t n, float nu, float* w, float* W, doubl
 // written whenever the matrix was acceptable and n >= 2f + 3.
 int krum_select(const double* D, int n, int f, int m, int32_t* picked, int* n_picked, double* scores);
 
+// K7's sum in K7's exact order (pgh_kernels.h) over (double)x[i] * (double)y[i], i < p, on the host: what K14
+// returns for a row x against the plane y, and with y == x what K7 returns for x.  The trust root's s0 comes from
+// here (pgh_trust_root): the same bits as pgh_row_sumsq of a slot holding the root.
+double row_dot_host(const float* x, const float* y, int64_t p);
+
+// Steps 2 and 4 of trust-bootstrapped FedAvg (include/pgh_api.h, "Trust-bootstrapped FedAvg"): from the root's
+// sum of squares s0 and, per row in fold order, K7's sum sumsq[k] and K14's dot[k] (not read where sumsq[k] is
+// not finite), the positions of the included rows (included[0, *n_included)), their fold weights
+// (w[0, *n_included)) and T.  Returns 0, or -1 when s0 is not finite and > 0 (an argument error), -2 when no row
+// is included, -3 when T == 0 (state errors; *n_included and, for -3, `included` are written all the same).
+// n_trusted (rows with ts > 0) and max_w are nullable.
+int trust_weights(double s0, const double* sumsq, const double* dot, int64_t n, float* w, int32_t* included,
+                  int64_t* n_included, double* T, int64_t* n_trusted, float* max_w);
+
 }  // namespace pgh_detail

@@ -219,6 +219,13 @@ struct DistsqArgs {
 };
 hipError_t launch_row_distsq(const DistsqArgs& a, const Rows& rows, hipStream_t s);
 
+// K14: every row's inner product with a fixed vector (the trust root of PGH_TRUSTED_MEAN; the definition is in
+// include/pgh_api.h): K7's sum, in K7's order, over (double)d_c[i] * (double)g0[i] -- exact products, one rounded
+// f64 addition each.  K12's shape, tile body and launcher: `negv` holds g0 itself here (at least p floats rounded
+// up to 4, 16-byte aligned), params at or past p contribute +0.0 whatever either operand holds there, and the
+// launch writes s.part[row * ntiles + t] and then s.sumsq[row] (the dots' buffer).  A sum may be negative.
+hipError_t launch_row_dot(const DistsqArgs& a, const Rows& rows, hipStream_t s);
+
 // K13: Multi-Krum's pairwise squared distances (the definition is in include/pgh_api.h): for list indices
 // a < b of the n listed rows, K12's sum of row a against the point row b -- K7's sum, in K7's order, over
 // x = d_a[i] - d_b[i], one f32 subtraction per param.  List index k is slab row d_rows[k] (a device table of n

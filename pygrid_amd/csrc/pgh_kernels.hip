@@ -24,6 +24,8 @@
 // K13 k_row_pairdist           K12's sum for every pair of the listed rows (Multi-Krum): a block of anchor rows'
 //       tile held in registers while the later rows stream past; k_row_pairdist_fold finishes each pair
 //       (build-owned: PGH_GEOMETRIC_MEDIAN)
+// K14 k_row_dot                K7's sum over d_c[i] * g0[i]: every row's inner product with a fixed vector (the
+//       trust root), K12's shape and tile body (build-owned: PGH_TRUSTED_MEAN)
 //
 // Design (DESIGN.md "Kernels"): every kernel is a single streaming pass over the slab held in
 // HBM, column-blocked (SlabMap in pgh_kernels.h: blocks of ld columns, each block all rows,
@@ -1204,15 +1206,22 @@ __global__ __launch_bounds__(256) void k_varint_decode(const uint8_t* bytes, con
 // below is the rounded add of the definition.  Addresses past the shard clamp to its last column and are masked
 // to +0.0 (the slab's padding columns hold stale bytes); a chunk's last row group repeats its last row instead
 // of branching around the loads.  The wave sums of every row of the chunk meet in LDS behind one barrier.
-//   K7  (RC = SUMSQ_RB, DIST = false): x = d_c[i]; one row group per workgroup.
-//   K12 (RC = DISTSQ_RC, DIST = true): x = d_c[i] + negv[i] (one f32 addition; negv holds -v, so this is d - v).
+//   K7  (RC = SUMSQ_RB, OP = ROW_SQ): x = d_c[i]; one row group per workgroup.
+//   K12 (RC = DISTSQ_RC, OP = ROW_DIST): x = d_c[i] + negv[i] (one f32 addition; negv holds -v, so this is d - v).
 //       The workgroup brings its 16 KiB of the plane into registers once (16 floats per lane, plain loads: the
 //       workgroups of the other row chunks read the same tile; clamped like the rows: the plane is at least p
 //       long) and streams its rows past it, so the plane costs 1 / DISTSQ_RC of the slab's bytes instead of
 //       1 / SUMSQ_RB.  The tile partials go where K7's go and k_row_sumsq_fold[_rows] finishes the rows.
+//   K14 (RC = DISTSQ_RC, OP = ROW_DOT): the sum runs over (double)d_c[i] * (double)g0[i], the plane (`negv`) holding
+//       g0 itself: K12's shape with a convert of the plane's value in place of the f32 addition.  The product of
+//       two f32 values is exact in f64, so the fma is again the rounded add.  Past p both factors are masked: the
+//       product is +0.0 there, never 0 x NaN.  A tile partial may be negative, but not -0.0: a lane's sum starts
+//       at +0.0, and +0.0 + (-0.0) and every exact cancellation round to +0.0.
 constexpr int SUMSQ_RB = 4;
 
-template <int SRC, int RC, bool DIST>
+enum RowOp : int { ROW_SQ = 0, ROW_DIST = 1, ROW_DOT = 2 };
+
+template <int SRC, int RC, int OP>
 __device__ __forceinline__ void row_sq_tile(const SumsqArgs& a, const float* negv, const Rows rows) {
     __shared__ double wsum[RC][4];
     const int lane = threadIdx.x, wave = lane >> 6;
@@ -1228,7 +1237,7 @@ __device__ __forceinline__ void row_sq_tile(const SumsqArgs& a, const float* neg
         idx[j] = base + 4 * (lane + BLOCK * j);
         const int64_t i = full ? idx[j] : min(idx[j], last4);
         off[j] = a.map.at(i);
-        if constexpr (DIST) nv[j] = ld4<false>(negv + i);
+        if constexpr (OP != ROW_SQ) nv[j] = ld4<false>(negv + i);
     }
     const int ng = RC == SUMSQ_RB ? SUMSQ_RB : nr;  // (nr is uniform over the workgroup; K7: one trip)
 #pragma unroll 1
@@ -1248,9 +1257,19 @@ __device__ __forceinline__ void row_sq_tile(const SumsqArgs& a, const float* neg
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float xf = DIST ? v[rr][j][e] + nv[j][e] : v[rr][j][e];
-                    const double x = (full || idx[j] + e < a.p) ? (double)xf : 0.0;
-                    acc = __builtin_fma(x, x, acc);
+                    const bool in = full || idx[j] + e < a.p;
+                    const float xf = OP == ROW_DIST ? v[rr][j][e] + nv[j][e] : v[rr][j][e];
+                    const double x = in ? (double)xf : 0.0;
+                    double y = x;
+                    if constexpr (OP == ROW_DOT) {
+                        // K14: both factors masked, so the product past p is +0.0 whatever the padding holds.  The
+                        // plane's value is converted at each use: the empty asm keeps the compiler from holding the
+                        // tile as 16 doubles across the row loop, 32 VGPRs and one wave of occupancy more than K12.
+                        float yf = nv[j][e];
+                        asm volatile("" : "+v"(yf));
+                        y = in ? (double)yf : 0.0;
+                    }
+                    acc = __builtin_fma(x, y, acc);
                 }
 #pragma unroll
             for (int h = 32; h >= 1; h >>= 1) acc += __shfl_down(acc, h, 64);
@@ -1264,13 +1283,18 @@ __device__ __forceinline__ void row_sq_tile(const SumsqArgs& a, const float* neg
 }
 
 __global__ __launch_bounds__(BLOCK) void k_row_sumsq(SumsqArgs a) {
-    row_sq_tile<0, SUMSQ_RB, false>(a, nullptr, Rows{nullptr, nullptr, a.row0});
+    row_sq_tile<0, SUMSQ_RB, ROW_SQ>(a, nullptr, Rows{nullptr, nullptr, a.row0});
 }
-__global__ __launch_bounds__(BLOCK) void k_row_sumsq_rows(SumsqArgs a, RowTab tab) { row_sq_tile<1, SUMSQ_RB, false>(a, nullptr, Rows{&tab}); }
+__global__ __launch_bounds__(BLOCK) void k_row_sumsq_rows(SumsqArgs a, RowTab tab) { row_sq_tile<1, SUMSQ_RB, ROW_SQ>(a, nullptr, Rows{&tab}); }
 __global__ __launch_bounds__(BLOCK) void k_row_distsq(DistsqArgs d) {
-    row_sq_tile<0, DISTSQ_RC, true>(d.s, d.negv, Rows{nullptr, nullptr, d.s.row0});
+    row_sq_tile<0, DISTSQ_RC, ROW_DIST>(d.s, d.negv, Rows{nullptr, nullptr, d.s.row0});
 }
-__global__ __launch_bounds__(BLOCK) void k_row_distsq_rows(DistsqArgs d, RowTab tab) { row_sq_tile<1, DISTSQ_RC, true>(d.s, d.negv, Rows{&tab}); }
+__global__ __launch_bounds__(BLOCK) void k_row_distsq_rows(DistsqArgs d, RowTab tab) { row_sq_tile<1, DISTSQ_RC, ROW_DIST>(d.s, d.negv, Rows{&tab}); }
+__global__ __launch_bounds__(BLOCK) void k_row_dot(DistsqArgs d) {
+    row_sq_tile<0, DISTSQ_RC, ROW_DOT>(d.s, d.negv, Rows{nullptr, nullptr, d.s.row0});
+}
+// (K12's occupancy: without the hint the table form takes 101 VGPRs, 5 past the step to 4 waves per SIMD)
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5))) void k_row_dot_rows(DistsqArgs d, RowTab tab) { row_sq_tile<1, DISTSQ_RC, ROW_DOT>(d.s, d.negv, Rows{&tab}); }
 
 // The row's tile partials, left-folded in ascending tile order by one lane; the workgroup brings
 // them into LDS 1,024 at a time (coalesced) so the serial chain reads LDS, not HBM.
@@ -1279,7 +1303,7 @@ constexpr int SUMSQ_FOLD_CHUNK = 4 * BLOCK;
 // (every lane returns; lane 0 holds the sum)
 __device__ __forceinline__ double tile_partials_fold(const double* part, int64_t ntiles) {
     __shared__ double buf[SUMSQ_FOLD_CHUNK];
-    double acc = 0.0;  // + 0.0 + partial 0 is partial 0 (partials are never -0.0)
+    double acc = 0.0;  // + 0.0 + partial 0 is partial 0 (partials are never -0.0, K14's signed ones included)
     for (int64_t c0 = 0; c0 < ntiles; c0 += SUMSQ_FOLD_CHUNK) {
         const int m = (int)min((int64_t)SUMSQ_FOLD_CHUNK, ntiles - c0);
         for (int k = threadIdx.x; k < m; k += BLOCK) buf[k] = part[c0 + k];
@@ -1763,10 +1787,11 @@ hipError_t launch_dp_normals(uint64_t key, uint32_t round, int64_t i0, int64_t n
 
 static_assert(DISTSQ_RC % SUMSQ_RB == 0 && DISTSQ_RC <= BLOCK, "K12's row chunk: whole row groups, one lane per row at the end");
 
-// K7 (negv null) or K12 over the launch's rows, RC rows per workgroup, and the fold of the tile partials behind it.
-template <int RC>
+// K7 (negv null), K12 or K14 over the launch's rows, RC rows per workgroup, and the fold of the tile partials behind it.
+template <int OP>
 static hipError_t launch_row_sq(const SumsqArgs& a, const float* negv, const Rows& rows, hipStream_t s) {
-    constexpr bool DIST = RC == DISTSQ_RC;
+    constexpr bool DIST = OP != ROW_SQ;  // a plane beside the rows
+    constexpr int RC = DIST ? DISTSQ_RC : SUMSQ_RB;
     const RowTab* tab = rows.tab;
     if (!valid_rows(rows, a.n_rows, false, true) || a.p <= 0 || a.n_rows < 0 || a.map.off != 0 || !valid_map(a.map, a.p) ||
         a.ntiles != (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE || a.ntiles > 0x7fffffff)
@@ -1781,7 +1806,9 @@ static hipError_t launch_row_sq(const SumsqArgs& a, const float* negv, const Row
         b.row0 = rows.row0 + done;
         b.n_rows = std::min(max_rows, a.n_rows - done);
         const dim3 grid((unsigned)b.ntiles, (unsigned)((b.n_rows + RC - 1) / RC));
-        if (DIST && tab) k_row_distsq_rows<<<grid, BLOCK, 0, s>>>(DistsqArgs{b, negv}, *tab);
+        if (OP == ROW_DOT && tab) k_row_dot_rows<<<grid, BLOCK, 0, s>>>(DistsqArgs{b, negv}, *tab);
+        else if (OP == ROW_DOT) k_row_dot<<<grid, BLOCK, 0, s>>>(DistsqArgs{b, negv});
+        else if (DIST && tab) k_row_distsq_rows<<<grid, BLOCK, 0, s>>>(DistsqArgs{b, negv}, *tab);
         else if (DIST) k_row_distsq<<<grid, BLOCK, 0, s>>>(DistsqArgs{b, negv});
         else if (tab) k_row_sumsq_rows<<<grid, BLOCK, 0, s>>>(b, *tab);
         else k_row_sumsq<<<grid, BLOCK, 0, s>>>(b);
@@ -1793,8 +1820,9 @@ static hipError_t launch_row_sq(const SumsqArgs& a, const float* negv, const Row
     return hipSuccess;
 }
 
-hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s) { return launch_row_sq<SUMSQ_RB>(a, nullptr, rows, s); }
-hipError_t launch_row_distsq(const DistsqArgs& d, const Rows& rows, hipStream_t s) { return launch_row_sq<DISTSQ_RC>(d.s, d.negv, rows, s); }
+hipError_t launch_row_sumsq(const SumsqArgs& a, const Rows& rows, hipStream_t s) { return launch_row_sq<ROW_SQ>(a, nullptr, rows, s); }
+hipError_t launch_row_distsq(const DistsqArgs& d, const Rows& rows, hipStream_t s) { return launch_row_sq<ROW_DIST>(d.s, d.negv, rows, s); }
+hipError_t launch_row_dot(const DistsqArgs& d, const Rows& rows, hipStream_t s) { return launch_row_sq<ROW_DOT>(d.s, d.negv, rows, s); }
 
 static_assert(PAIRDIST_RC % SUMSQ_RB == 0 && PAIRDIST_RA * PAIRDIST_RC == BLOCK, "K13: whole row groups, one lane per pair at the end");
 

@@ -2,7 +2,8 @@
 // sums of squares and distances (RowSums: K7 with its host cache, K12, K13) and the Multi-Krum selection over them; clipping's scales and tallies; the
 // Gaussian noise on the clipped close (K11 behind a FINAL launch, its plane, setting and entry points); the
 // trimmed mean's state planes (K8); the median's driver and row table (K9, K9p); the geometric median's included
-// rows, inner iterations and final weights (K12 between weighted folds); the context's -0 plane; what the rules'
+// rows, inner iterations and final weights (K12 between weighted folds); the trust rule's root, cached dots (K14)
+// and weights; the context's -0 plane; what the rules'
 // state does at each lifecycle event of the context (rules_*: the one call each event's site makes) and what
 // they hand a fold driver before its launches (rules_slot_plan, rules_resident_plan).  The state itself:
 // pgh_rules.h.
@@ -59,6 +60,16 @@ int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
             return fail(c, PGH_E_UNSUPPORTED, "a geometric median needs whole rows: the shard [%lld,%lld) is narrower than the model", (long long)c->lo, (long long)c->hi);
         if (c->geo.iters == 0) return fail(c, PGH_E_STATE, "PGH_GEOMETRIC_MEDIAN needs its setting: call pgh_set_geomed first");
         return PGH_OK;
+    case PGH_TRUSTED_MEAN:  // as the geometric median: every row at once, the whole row of each
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no trusted mean: it needs every row at once");
+        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a trusted mean needs every row at once: nothing can be folded early");
+        if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts take no trusted mean: the shards each hold part of a row");
+        if (c->layout && c->pg != c->P)
+            return fail(c, PGH_E_UNSUPPORTED, "a trusted mean needs whole rows: the shard [%lld,%lld) is narrower than the model", (long long)c->lo, (long long)c->hi);
+        if (!c->trust.on) return fail(c, PGH_E_STATE, "PGH_TRUSTED_MEAN needs its setting: call pgh_set_trust first");
+        if (!c->trust.root_valid) return fail(c, PGH_E_STATE, "PGH_TRUSTED_MEAN needs the cycle's root: call pgh_trust_root (none set since pgh_reset / pgh_reserve)");
+        if (noise_on(c)) return fail(c, PGH_E_STATE, "DP noise is set (pgh_set_dp_noise): a trusted mean takes none");
+        return PGH_OK;
     default:
         return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);
     }
@@ -74,13 +85,14 @@ bool rules_made(pgh_ctx* c) {
         const long long v = std::atoll(e);
         if (v > 0 && (unsigned long long)v < c->rowsums.pair_budget) c->rowsums.pair_budget = (size_t)v;
     }
-    return c->rowsums.ev.make() == hipSuccess;
+    return c->rowsums.ev.make() == hipSuccess && c->rowsums.ev_dot.make() == hipSuccess;
 }
 
 void rules_slab_freed(pgh_ctx* c) {  // the streams are idle (free_slab synchronised them)
     for (auto* v : {&c->trim.d_planes, &c->med.d_prefix, &c->med.d_rowidx, &c->geo.d_negv}) v->reset();
     c->rowsums.slab_freed();
     c->geo.forget();
+    c->trust.forget();  // (the root's validity goes with the cycle; its plane is sized by the shard and stays)
     c->krum.forget();
     c->clip.forget();
 }
@@ -93,6 +105,7 @@ void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep
     if (!(same_shard && pvec == c->pvec)) c->nz.d.reset();     // (its tenants above and below are gone with it)
     if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
     c->geo.release();  // (free_slab has dropped the plane; the setting goes with the layout or shard)
+    c->trust.release();
 }
 
 void rules_reserved(pgh_ctx* c, int slots) { c->rowsums.reserved(slots); }
@@ -101,6 +114,7 @@ void rules_reset(pgh_ctx* c) {
     c->rowsums.forget();
     c->clip.forget();
     c->geo.forget();
+    c->trust.forget();
     c->krum.forget();
 }
 
@@ -120,11 +134,14 @@ void rules_cycle_finished(pgh_ctx* c, int mode) {
 int rules_row_ingested(pgh_ctx* c, int slot) {
     if (!norms_wanted(c)) return PGH_OK;
     const int32_t sl = slot;
-    return c->rowsums.queue(c, &sl, 1);
+    RC(c->rowsums.queue(c, &sl, 1));
+    // the trust rule with the cycle's root in place: the row's K14 behind its K7, both behind the next report's copy
+    if (trust_on(c) && c->trust.root_valid) RC(c->rowsums.queue_dots(c, &sl, 1, c->trust.d_root.as<float>()));
+    return PGH_OK;
 }
 
 const char* rules_one_fold_cycle(int mode) {
-    return mode == PGH_MEDIAN ? "a median" : mode == PGH_GEOMETRIC_MEDIAN ? "a geometric median" : nullptr;
+    return mode == PGH_MEDIAN ? "a median" : mode == PGH_GEOMETRIC_MEDIAN ? "a geometric median" : mode == PGH_TRUSTED_MEAN ? "a trusted mean" : nullptr;
 }
 
 int NegZeroPlane::ensure(pgh_ctx* c, hipStream_t s) {
@@ -260,18 +277,73 @@ int RowSums::queue(pgh_ctx* c, const int32_t* slots, int n) {
 }
 
 int RowSums::wait(pgh_ctx* c) {
-    if (queued.empty()) return PGH_OK;
-    CK(c, hipEventSynchronize(ev));
-    for (int32_t sl : queued)
-        if (state[(size_t)sl] == QUEUED) {
-            value[(size_t)sl] = h_sq.as<double>()[sl];
-            state[(size_t)sl] = VALID;
-        }
-    queued.clear();
+    if (!queued.empty()) {
+        CK(c, hipEventSynchronize(ev));
+        for (int32_t sl : queued)
+            if (state[(size_t)sl] == QUEUED) {
+                value[(size_t)sl] = h_sq.as<double>()[sl];
+                state[(size_t)sl] = VALID;
+            }
+        queued.clear();
+    }
+    if (!dot_queued.empty()) {
+        CK(c, hipEventSynchronize(ev_dot));
+        for (int32_t sl : dot_queued)
+            if (dot_state[(size_t)sl] == QUEUED) {
+                dot_value[(size_t)sl] = h_dot.as<double>()[sl];
+                dot_state[(size_t)sl] = VALID;
+            }
+        dot_queued.clear();
+    }
     return PGH_OK;
 }
 
-// (K7's tile partials are free: every queued K7 has been waited for.)
+// (on the copy stream like K7: the two share the tile partials, and one stream orders them)
+int RowSums::queue_dots(pgh_ctx* c, const int32_t* slots, int n, const float* root) {
+    std::vector<int32_t> todo;
+    for (int k = 0; k < n; ++k)
+        if (dot_state[(size_t)slots[k]] == NONE) todo.push_back(slots[k]);
+    if (todo.empty()) return PGH_OK;
+    RC(ensure(c));
+    if (!d_dot.reserve(8 * (size_t)c->slots) || !h_dot.reserve(8 * (size_t)c->slots))
+        return fail(c, PGH_E_OOM, "allocation of the trust rule's dots (%d rows) failed", c->slots);
+    pgh::DistsqArgs a{args(c, d_dot.as<double>()), root};
+    const hipStream_t s = c->copy;
+    // HBM bytes: the rows, the partials out and in again; the plane once per row chunk (from L2 mostly)
+    RC(for_row_runs(c, todo.data(), todo.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
+        a.s.n_rows = (int)m;
+        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
+        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_dot(a, rows, s); });
+    }));
+    RC(sums_d2h(c, todo.data(), todo.size(), h_dot.as<double>(), d_dot.as<double>(), s));
+    CK(c, hipEventRecord(ev_dot, s));
+    for (int32_t sl : todo) {
+        dot_state[(size_t)sl] = QUEUED;
+        dot_queued.push_back(sl);
+    }
+    return PGH_OK;
+}
+
+// (K7's and the cached K14's tile partials are free: everything queued has been waited for.  The sums go through
+// K12's buffers: neither cache is touched.)
+int RowSums::dots(pgh_ctx* c, const std::vector<int32_t>& slots, const float* plane, hipStream_t s, double* D) {
+    RC(wait(c));
+    RC(ensure(c));
+    if (!d_dist.reserve(8 * (size_t)c->slots) || !h_dist.reserve(8 * (size_t)c->slots))
+        return fail(c, PGH_E_OOM, "allocation of the row dots (%d rows) failed", c->slots);
+    pgh::DistsqArgs a{args(c, d_dist.as<double>()), plane};
+    RC(for_row_runs(c, slots.data(), slots.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
+        a.s.n_rows = (int)m;
+        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
+        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_dot(a, rows, s); });
+    }));
+    RC(sums_d2h(c, slots.data(), slots.size(), h_dist.as<double>(), d_dist.as<double>(), s));
+    CK(c, hipStreamSynchronize(s));
+    for (size_t k = 0; k < slots.size(); ++k) D[k] = h_dist.as<double>()[slots[k]];
+    return PGH_OK;
+}
+
+// (K7's tile partials are free: every queued K7 and K14 has been waited for.)
 int RowSums::distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* negv, hipStream_t s, double* D) {
     RC(wait(c));
     RC(ensure(c));
@@ -454,6 +526,65 @@ int geomed_resident_weights(pgh_ctx* c, int64_t n) {  // clients [0, n) in slots
     c->fw.validate(n);
     return PGH_OK;
 }
+
+// ---- trust-bootstrapped FedAvg: the included rows and their weights ---------------------------------------------
+
+// a float [pvec] plane of the trust rule at the context's present length, zeroed when it is (re)allocated
+int trust_plane(pgh_ctx* c, DeviceBuf* d, hipStream_t s) {
+    if (*d && c->trust.pvec == c->pvec) return PGH_OK;
+    if (c->trust.pvec != c->pvec) {  // (both planes are of one length)
+        c->trust.d_root.reset();
+        c->trust.d_point.reset();
+        c->trust.pvec = c->pvec;
+    }
+    if (!d->reserve(4 * (size_t)c->pvec)) return fail(c, PGH_E_OOM, "allocation of a trust plane (%zu bytes) failed", 4 * (size_t)c->pvec);
+    CK(c, hipMemsetAsync(d->as<void>(), 0, 4 * (size_t)c->pvec, s));
+    return PGH_OK;
+}
+
+// The weights of a close over slots[0, n) in fold order (the included rows into trust.rows, their weights into
+// the context's): K7 for the sums still missing, K14 for the included rows' dots still missing, the host step.
+// PGH_E_STATE with no row included or none trusted; no fold is launched then.
+int trust_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
+    TrustState& t = c->trust;
+    c->fw.stale();  // (the context's weights become this rule's, whatever happens below)
+    RC(c->rowsums.queue(c, slots, n));
+    RC(c->rowsums.wait(c));
+    std::vector<int32_t> inc;
+    std::vector<double> ss((size_t)n), dot((size_t)n, 0.0);
+    for (int k = 0; k < n; ++k) {
+        ss[(size_t)k] = c->rowsums.at(slots[k]);
+        if (std::isfinite(ss[(size_t)k])) inc.push_back(slots[k]);  // else excluded: no fold and no K14 pass of the close reads the row
+    }
+    if (inc.empty()) return fail(c, PGH_E_STATE, "trusted mean: none of the %d diffs is finite", n);
+    RC(c->rowsums.queue_dots(c, inc.data(), (int)inc.size(), t.d_root.as<float>()));
+    RC(c->rowsums.wait(c));
+    for (int k = 0; k < n; ++k)
+        if (std::isfinite(ss[(size_t)k])) dot[(size_t)k] = c->rowsums.dot_at(slots[k]);
+    std::vector<float> w(inc.size());
+    std::vector<int32_t> pos((size_t)n);
+    int64_t ni = 0, nt = 0;
+    double T = 0.0;
+    float mx = 0.f;
+    const int rc = trust_weights(t.s0, ss.data(), dot.data(), n, w.data(), pos.data(), &ni, &T, &nt, &mx);
+    t.n_rows = n;
+    t.n_excluded = n - ni;
+    t.n_trusted = nt;
+    t.total_trust = T;
+    t.max_weight = mx;
+    t.rows = inc;
+    if (rc == -3) return fail(c, PGH_E_STATE, "trusted mean: none of the %lld finite diffs points along the root (T = 0)", (long long)ni);
+    if (rc != 0) return fail(c, PGH_E_STATE, "trusted mean: the host step refused the sums (%d)", rc);
+    c->fw.replace(FoldWeights::TRUST) = w;
+    return PGH_OK;
+}
+
+int trust_resident_weights(pgh_ctx* c, int64_t n) {  // clients [0, n) in slots [0, n), once per slab state and root
+    if (c->fw.valid(FoldWeights::TRUST, n) && c->fw.v.size() == c->trust.rows.size()) return PGH_OK;
+    RC(trust_slot_weights(c, first_slots(n).data(), (int)n));
+    c->fw.validate(n);
+    return PGH_OK;
+}
 }  // namespace
 
 // ---- the fold plans: what the drivers ask before their launches ------------------------------------------------
@@ -465,6 +596,14 @@ void geomed_plan(pgh_ctx* c, FoldPlan* p) {  // the included rows alone, fold cl
     p->total = p->n;
     p->has_divisor = true;
     p->divisor = c->geo.W;
+    p->whole_rows = true;
+}
+void trust_plan(pgh_ctx* c, FoldPlan* p) {  // the included rows alone; the weights carry the normalisation
+    p->slots = c->trust.rows.data();
+    p->n = (int)c->trust.rows.size();
+    p->total = p->n;
+    p->has_divisor = true;
+    p->divisor = 1.0f;
     p->whole_rows = true;
 }
 }  // namespace
@@ -481,6 +620,10 @@ int rules_slot_plan(pgh_ctx* c, int mode, const int32_t* slots, int n, int64_t c
         RC(geomed_slot_weights(c, slots, n));
         geomed_plan(c, p);
     }
+    if (mode == PGH_TRUSTED_MEAN) {
+        RC(trust_slot_weights(c, slots, n));
+        trust_plan(c, p);
+    }
     return PGH_OK;
 }
 
@@ -494,6 +637,10 @@ int rules_resident_plan(pgh_ctx* c, int mode, int64_t c0, int64_t n, FoldPlan* p
     if (mode == PGH_GEOMETRIC_MEDIAN) {
         RC(geomed_resident_weights(c, n));
         geomed_plan(c, p);
+    }
+    if (mode == PGH_TRUSTED_MEAN) {
+        RC(trust_resident_weights(c, n));
+        trust_plan(c, p);
     }
     return PGH_OK;
 }
@@ -629,6 +776,90 @@ int pgh_geomed_stats(pgh_ctx* c, int* iters, int64_t* n_rows, int64_t* n_exclude
     if (n_excluded) *n_excluded = c->geo.n_excluded;
     if (objective) *objective = c->geo.objective;
     if (max_weight) *max_weight = c->geo.max_weight;
+    return PGH_OK;
+}
+
+// ---- trust-bootstrapped FedAvg: the setting, the root, K14 alone, the host step alone, what the last close saw ----
+
+int pgh_set_trust(pgh_ctx* c, int on) {
+    if (!c) return PGH_E_ARG;
+    if (!on) {  // off: always possible (the planes stay for the next trusted cycle of this shard)
+        if (c->grp) return PGH_OK;
+        c->trust.on = false;
+        c->trust.forget();
+        c->rowsums.dots_stale();
+        c->fw.stale(FoldWeights::TRUST);
+        return PGH_OK;
+    }
+    RC(check_clip_ctx(c, "pgh_set_trust"));
+    c->trust.on = true;
+    return PGH_OK;
+}
+
+int pgh_trust_root(pgh_ctx* c, const float* root, size_t nbytes) {
+    RC(check_clip_ctx(c, "pgh_trust_root"));
+    if (!c->trust.on) return fail(c, PGH_E_STATE, "pgh_trust_root: the rule is off, call pgh_set_trust first");
+    if (!root || nbytes != 4 * (size_t)c->P) return fail(c, PGH_E_ARG, "pgh_trust_root: the root must be %lld floats (%zu bytes given)", (long long)c->P, nbytes);
+    TrustState& t = c->trust;
+    // whatever happens below, the old root is gone: its dots and weights with it
+    t.root_valid = false;
+    c->rowsums.dots_stale();
+    c->fw.stale(FoldWeights::TRUST);
+    const double s0 = row_dot_host(root, root, c->P);
+    if (!(std::isfinite(s0) && s0 > 0.0))
+        return fail(c, PGH_E_ARG, "pgh_trust_root: the root's sum of squares is %g: it must be finite and > 0 (a NaN, an infinity or an all-zero root)", s0);
+    DeviceGuard g(c->device);
+    // the copy stream: every K14 that read the old root was issued there
+    const hipStream_t s = c->copy;
+    RC(trust_plane(c, &t.d_root, s));
+    CK(c, hipMemcpyAsync(t.d_root.as<float>(), root, nbytes, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // the caller's bytes are free on return
+    t.s0 = s0;
+    t.root_valid = true;
+    return PGH_OK;
+}
+
+int pgh_row_dot(pgh_ctx* c, const int32_t* slots, int n, const float* point, double* out) {
+    RC(check_clip_ctx(c, "pgh_row_dot"));
+    RC(check_dtype(c, PGH_F32));
+    if (n < 0 || (n > 0 && (!slots || !point || !out))) return fail(c, PGH_E_ARG, "bad slot list, point or out (n=%d)", n);
+    RC(check_slot_list(c, slots, n, false));
+    if (n == 0) return PGH_OK;
+    DeviceGuard g(c->device);
+    const hipStream_t s = c->stream;
+    RC(order_after_ingest(c, s));
+    RC(trust_plane(c, &c->trust.d_point, s));
+    CK(c, hipMemcpyAsync(c->trust.d_point.as<float>(), point, 4 * (size_t)c->pg, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // the caller's bytes are free on return
+    return c->rowsums.dots(c, std::vector<int32_t>(slots, slots + n), c->trust.d_point.as<float>(), s, out);
+}
+
+int pgh_trust_weights_host(double s0, const double* sumsq, const double* dot, int n, float* weights, int32_t* included,
+                           int* n_included, double* total_trust) {
+    if (n < 0 || (n > 0 && (!sumsq || !dot || !weights || !included)) || !n_included)
+        return fail(nullptr, PGH_E_ARG, "pgh_trust_weights_host: bad arguments (n=%d)", n);
+    int64_t ni = 0;
+    double T = 0.0;
+    const int rc = trust_weights(s0, sumsq, dot, n, weights, included, &ni, &T, nullptr, nullptr);
+    if (rc == -1) return fail(nullptr, PGH_E_ARG, "trusted mean: the root's sum of squares must be finite and > 0");
+    *n_included = (int)ni;
+    if (total_trust) *total_trust = T;
+    if (rc == -2) return fail(nullptr, PGH_E_STATE, "trusted mean: none of the %d diffs is finite", n);
+    if (rc == -3) return fail(nullptr, PGH_E_STATE, "trusted mean: none of the %lld finite diffs points along the root (T = 0)", (long long)ni);
+    return PGH_OK;
+}
+
+int pgh_trust_stats(pgh_ctx* c, int* on, int64_t* n_rows, int64_t* n_excluded, int64_t* n_trusted, double* total_trust, float* max_weight,
+                    double* root_norm) {
+    if (!c) return PGH_E_ARG;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_trust_stats: group contexts take no trusted mean");
+    if (on) *on = c->trust.on ? 1 : 0;
+    if (n_rows) *n_rows = c->trust.n_rows;
+    if (n_excluded) *n_excluded = c->trust.n_excluded;
+    if (n_trusted) *n_trusted = c->trust.n_trusted;
+    if (total_trust) *total_trust = c->trust.total_trust;
+    if (max_weight) *max_weight = c->trust.max_weight;
+    if (root_norm) *root_norm = c->trust.root_valid ? std::sqrt(c->trust.s0) : 0.0;
     return PGH_OK;
 }
 

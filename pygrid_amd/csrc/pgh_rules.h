@@ -1,5 +1,5 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, krum, trim, med and opt, and what they share: the row
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trust, krum, trim, med and opt, and what they share: the row
 // sums (RowSums, rowsums), the fold's weights (FoldWeights, fw) and the -0 plane (NegZeroPlane, nz).  Their owners
 // release with the context.
 // The code that works on them: pgh_rules.cpp (clip, geo, trim, med and the lifecycle calls rules_*),
@@ -40,26 +40,55 @@ struct RowSums {
     // matrix; the listed slab rows as a device table
     DeviceBuf d_pair_part, d_pair, d_pair_rows;
     size_t pair_budget = (size_t)1 << 30;  // PGH_PAIRDIST_BUDGET (bytes) lowers it, for tests of the batching
+    // K14's (the trust rule's inner products with the cycle's root): a second per-slot cache with K7's state
+    // machine.  A queued K14 runs on the copy stream behind the row's K7 -- it shares d_part, one stream orders
+    // the two -- and its dot comes back through h_dot, followed by ev_dot.  An ingest into the slot resets its
+    // entry (slot_written), a new root resets them all (dots_stale).  d_dot / h_dot are allocated by the first
+    // queue_dots.
+    std::vector<uint8_t> dot_state;
+    std::vector<double> dot_value;
+    std::vector<int32_t> dot_queued;
+    DeviceBuf d_dot;                // double [slots], by slab row
+    PinnedBuf h_dot;
+    Event ev_dot;
 
     double at(int slot) const { return value[(size_t)slot]; }  // after wait(): the sum of a slot queued before it
-    void reserved(int slots) {  // pgh_reserve: the cache at its new length
+    double dot_at(int slot) const { return dot_value[(size_t)slot]; }  // after wait(): the dot, likewise
+    void reserved(int slots) {  // pgh_reserve: the caches at their new length
         state.assign((size_t)slots, (uint8_t)NONE);
         value.assign((size_t)slots, 0.0);
+        dot_state.assign((size_t)slots, (uint8_t)NONE);
+        dot_value.assign((size_t)slots, 0.0);
     }
     // The diffs in slots [slot, slot + n) are being replaced: their cached sums were the old diffs'.  The one
     // place a sum goes to NONE slot by slot.
-    void slot_written(int slot, int n) { std::fill_n(state.begin() + slot, n, (uint8_t)NONE); }
+    void slot_written(int slot, int n) {
+        std::fill_n(state.begin() + slot, n, (uint8_t)NONE);
+        std::fill_n(dot_state.begin() + slot, n, (uint8_t)NONE);
+    }
+    // The root changed or went: every cached dot was the old root's.  A K14 still in flight is waited for first, so
+    // that "nothing queued" keeps meaning "nobody writes the shared tile partials" for wait()'s callers.
+    void dots_stale() {
+        if (!dot_queued.empty()) (void)hipEventSynchronize(ev_dot);
+        std::fill(dot_state.begin(), dot_state.end(), (uint8_t)NONE);
+        dot_queued.clear();
+    }
     void forget() {  // every slot back to NONE (pgh_reset)
         slot_written(0, (int)state.size());
         queued.clear();
+        dot_queued.clear();
     }
     void slab_freed() {  // the streams are idle: every buffer sized by the slab goes, and the cache
-        for (auto* v : {&d_part, &d_sq, &d_dist, &d_pair_part, &d_pair, &d_pair_rows}) v->reset();
+        for (auto* v : {&d_part, &d_sq, &d_dist, &d_pair_part, &d_pair, &d_pair_rows, &d_dot}) v->reset();
         h_sq.reset();
         h_dist.reset();
+        h_dot.reset();
         state.clear();
         value.clear();
         queued.clear();
+        dot_state.clear();
+        dot_value.clear();
+        dot_queued.clear();
     }
     // f(rows, k0, m) for each run of the listed slots a launch can take: all of them when they are consecutive,
     // else RowTabs of at most ROWTAB_MAX; k0 = the fold index of the run's first row.  (pgh_ctx.h)
@@ -70,7 +99,12 @@ struct RowSums {
     int ensure(pgh_ctx* c);  // the tile partials, the sums buffer and its pinned image: all three or none
     // K7 on the copy stream for those of `slots` that have no sum yet, and the D2H of the sums
     int queue(pgh_ctx* c, const int32_t* slots, int n);
-    int wait(pgh_ctx* c);  // the queued sums are in at() afterwards
+    int wait(pgh_ctx* c);  // the queued sums are in at() afterwards, the queued dots in dot_at()
+    // K14 against `root` on the copy stream for those of `slots` that have no dot yet, and the D2H of the dots
+    int queue_dots(pgh_ctx* c, const int32_t* slots, int n, const float* root);
+    // K14 over the listed slots against `plane` on stream s into K12's buffers (the caches stay as they are),
+    // the D2H and the wait: D[k] = the dot of slots[k]
+    int dots(pgh_ctx* c, const std::vector<int32_t>& slots, const float* plane, hipStream_t s, double* D);
     // K12 over the listed slots against negv on stream s, the D2H of the sums and the wait: D[k] = the squared
     // distance of slots[k]
     int distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* negv, hipStream_t s, double* D);
@@ -79,12 +113,12 @@ struct RowSums {
     int pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D);
 };
 
-// The fold's per-client weights (fold order) and their device copy.  Three writers: the caller
-// (pgh_set_weights), the clip scales, the geometric median's final weights.  A rule that wrote them for the
+// The fold's per-client weights (fold order) and their device copy.  Four writers: the caller
+// (pgh_set_weights), the clip scales, the geometric median's final weights, the trust rule's.  A rule that wrote them for the
 // resident slab as it is marks them valid for clients [0, n): range folds and repeated closes reuse them.
 // PGH_WEIGHTED_MEAN folds with whatever the vector holds, whoever wrote it.
 struct FoldWeights {
-    enum Writer : uint8_t { CALLER = 0, CLIP = 1, GEOMED = 2 };
+    enum Writer : uint8_t { CALLER = 0, CLIP = 1, GEOMED = 2, TRUST = 3 };
     std::vector<float> v;
     DeviceBuf d;             // float per client
     bool on_device = false;
@@ -192,6 +226,42 @@ struct GeomedState {
         d_negv.reset();
         iters = 0;
         nu = 0.f;
+        forget();
+    }
+};
+
+// Trust-bootstrapped FedAvg (pgh_set_trust, pgh_trust_root, PGH_TRUSTED_MEAN): FLTrust.
+// With the rule on every ingest queues K7 like clipping, and, while the cycle's root is valid, K14 behind it
+// (RowSums: the cached sums and dots).  A close computes what is missing in one batch, runs the host step
+// (trust_weights, pgh_host.cpp) and leaves the weights in the context's FoldWeights (writer TRUST, fold order of
+// the included rows) for the one FINAL fold, the weighted fold over `rows` with the divisor 1.  The root plane
+// is float [pvec], zero past the root, allocated by the first pgh_trust_root and kept over pgh_reset /
+// pgh_reserve (the validity is not); pgh_row_dot's scratch plane likewise, by its first call.
+struct TrustState {
+    bool on = false;
+    bool root_valid = false;        // a root set since pgh_reset / pgh_reserve
+    double s0 = 0.0;                // K7's sum of squares of the root
+    DeviceBuf d_root, d_point;      // float [pvec]
+    int64_t pvec = 0;               // the planes' length
+    std::vector<int32_t> rows;      // the included slots, in fold order
+    // what the last computation of the weights saw (pgh_trust_stats)
+    int64_t n_rows = 0, n_excluded = 0, n_trusted = 0;
+    double total_trust = 0.0;
+    float max_weight = 0.f;
+
+    void forget() {  // the cycle's root, the included rows and the tallies (pgh_reset, pgh_reserve); the setting stays
+        root_valid = false;
+        s0 = 0.0;
+        rows.clear();
+        n_rows = n_excluded = n_trusted = 0;
+        total_trust = 0.0;
+        max_weight = 0.f;
+    }
+    void release() {  // planes and setting; the caller has waited for the context's work
+        d_root.reset();
+        d_point.reset();
+        pvec = 0;
+        on = false;
         forget();
     }
 };

@@ -27,11 +27,11 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import state as state_codec
-from .engine import ITERATIVE_MEAN, MEAN, WEIGHTED_MEAN, F32, I64, Engine
+from .engine import ITERATIVE_MEAN, MEAN, TRUSTED_MEAN, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
 from .robust import CLIP_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, check_trim_count, clip_norm_of, failing_closed, median_of, \
     rule_of, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
-from . import krum as krum_mod, serveropt
+from . import krum as krum_mod, serveropt, trust as trust_mod
 from .dp import DpKeys
 from .serveropt import ServerOptStates
 from .settings import settings_of
@@ -184,15 +184,24 @@ def cached_mode(server_config: dict, plan_key, mean_plans: Optional[str] = None)
 
 def select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
                 mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None,
-                trim_count=None, median: bool = False, geometric_median=None) -> int:
+                trim_count=None, median: bool = False, geometric_median=None, trust=None) -> int:
     """The dispatch rule below; under a rule (``robust.rule_of`` of ``clip_norm``, ``trim_count``,
     ``median`` and ``geometric_median``, parsed values; ``server_config``'s own keys are not read): the rule's
     mode -- ``CLIPPED_MEAN``, ``TRIMMED_MEAN``, ``MEDIAN``, ``GEOMETRIC_MEDIAN`` -- exactly where the dispatch gives ``MEAN`` (no
     hosted plan, or a plan probed equal to the mean) and the rule's error everywhere else -- weights,
     the iterative plan, a plan the engine declines -- so that the caller cannot fall back to an
-    average that does not apply the rule."""
+    average that does not apply the rule.  ``trust`` (a parsed ``trust.TrustSpec``, without a rule): ``TRUSTED_MEAN``
+    in the same places and ``TrustUnavailableError`` everywhere else."""
     rule = rule_of(server_config, clip_norm=clip_norm, trim_count=trim_count, median=median,
                    geometric_median=geometric_median)
+    if rule is None and trust is not None:
+        if weights is not None:
+            raise trust_mod.refuse("cannot be combined with aggregation weights")
+        with trust_mod.failing_closed(trust, "the engine does not run this avg plan"):
+            mode = _select_mode(server_config, avg_plan, None, plan_key, mean_plans, shapes, n_clients)
+        if mode != MEAN:
+            raise trust_mod.refuse("is set but the hosted avg plan is the iterative mean, to which the engine does not apply it")
+        return TRUSTED_MEAN
     if rule is None:
         return _select_mode(server_config, avg_plan, weights, plan_key, mean_plans, shapes, n_clients)
     if weights is not None:
@@ -328,7 +337,8 @@ class CycleAggregator:
     def average_plan_diffs(self, server_config: dict, checkpoint: bytes, diffs: Sequence[bytes],
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
                            plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
-                           dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET) -> bytes:
+                           dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
+                           trust_root=None) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -340,26 +350,33 @@ class CycleAggregator:
         ``server_config["dp_noise"]``) and the round it is drawn for -- the cycle's id, required beside it;
         the key not given in the setting is ``opt_key``'s in ``dp_keys``.  ``krum``: the Multi-Krum selection
         (``krum.krum_of``; default ``server_config["diff_krum"]``): the cycle's mode then averages the picked
-        diffs alone, as if they were the only reports."""
+        diffs alone, as if they were the only reports.  ``trust``: the trust rule (``trust.trust_of``; default
+        ``server_config["diff_trust_root"]``) and ``trust_root``, the server's own update for this cycle (State bytes
+        shaped like a diff, a sequence of arrays or a flat array), required beside it: ``TrustUnavailableError``
+        without one."""
         if framing not in ("fresh", "template"):
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust)
         with self._closing(server_config, given, avg_plan, weights, plan_key, lambda: _shapes_or_none(checkpoint),
-                           lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round) as (settings, mode):
+                           lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round, trust_root) as (settings, mode):
             return self._average_plan_diffs(checkpoint, diffs, weights, framing, settings, mode)
 
     @contextlib.contextmanager
-    def _closing(self, server_config, given, avg_plan, weights, plan_key, shapes, numel_of, n_diffs, opt_key, dp_round):
+    def _closing(self, server_config, given, avg_plan, weights, plan_key, shapes, numel_of, n_diffs, opt_key, dp_round,
+                 trust_root=None):
         """What both entry points do before their first ingest, and the fail-closed block they fold in:
         gives ``(settings, mode)`` with the engine laid out for ``numel_of()`` and ``n_diffs`` rows, the rule and the
         noise set and ``opt_key``'s moments bound.  ``given``: the caller's clip_norm, trim_count, median, dp_noise,
-        geometric_median, krum."""
-        settings = settings_of(server_config, *given[:4], geometric_median=given[4], krum=given[5])
+        geometric_median, krum, trust.  Under the trust rule the cycle's ``trust_root`` goes onto the engine here too,
+        ahead of the ingests: each diff's inner product with it rides behind its copy."""
+        settings = settings_of(server_config, *given[:4], geometric_median=given[4], krum=given[5], trust=given[6])
         with settings.fail_closed("the engine cannot average this cycle"):
             mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
-                               shapes=shapes, n_clients=n_diffs, **settings.rule_kwargs())
+                               shapes=shapes, n_clients=n_diffs, trust=settings.trust, **settings.rule_kwargs())
+            if settings.trust is not None and trust_root is None:
+                raise trust_mod.refuse("is set but the close has no trust_root: the server's own update for this cycle")
             if settings.rule is not None and settings.rule.key == TRIM_KEY and settings.select is None:
                 check_trim_count(settings.rule.value, n_diffs)  # (under a selection: of the picked diffs, _finish_picked)
             numel = numel_of()
@@ -367,7 +384,10 @@ class CycleAggregator:
             # before the first ingest: each diff's norm pass rides behind its copy
             settings.set_on_engine(self.engine, settings.noise_key(self.dp_keys, opt_key), dp_round)
             self.opt_states.bind(self.engine, opt_key, settings.opt, sum(numel))  # before the fold: its moments
-            yield settings, mode
+            if settings.trust is not None:
+                trust_mod.set_root(self.engine, trust_root, numel)
+            with trust_mod.closing(settings.trust):
+                yield settings, mode
 
     def _finish_picked(self, settings, mode, n_diffs, weights):
         """Under a selection, after the ingests: the picked diffs alone are folded into the resident checkpoint,
@@ -411,14 +431,15 @@ class CycleAggregator:
     def average_params(self, server_config: dict, model_params: Sequence[np.ndarray],
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
                        weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
-                       dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET) -> List[np.ndarray]:
+                       dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
+                       trust_root=None) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         shapes = [np.shape(p) for p in model_params]
         numel = [int(np.prod(s)) for s in shapes]
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust)
         with self._closing(server_config, given, avg_plan, weights, None, shapes, lambda: numel, len(diffs), opt_key,
-                           dp_round) as (settings, mode):
+                           dp_round, trust_root) as (settings, mode):
             for i, d in enumerate(diffs):
                 if len(d) != len(numel):
                     raise AggregationError(f"diff {i} has {len(d)} tensors, model has {len(numel)}")
@@ -477,7 +498,8 @@ def _probed_plan(*_a, **_k):  # stands in for a hosted plan whose verdict is cac
 
 
 def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_manager, plan_manager,
-                            original: Callable, gate: Optional[Callable] = None, framing: str = "fresh") -> Callable:
+                            original: Callable, gate: Optional[Callable] = None, framing: str = "fresh",
+                            trust_root: Optional[Callable] = None) -> Callable:
     """Build a drop-in ``CycleManager._average_plan_diffs(self, server_config, cycle)``.
 
     DB I/O mirrors ``cycle_manager.py:234-245`` and ``:304-323``; the arithmetic slice
@@ -488,6 +510,8 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
     ``gate()``: a context manager held while the completed rows and their diffs are read (the
     node's report gate: a re-report's DB write lands wholly before or after that read).
     ``framing``: the new checkpoint's framing (``CycleAggregator.average_plan_diffs``).
+    ``trust_root(cycle, checkpoint_bytes)``: the server's own update for the cycle, asked for under
+    ``server_config["diff_trust_root"]`` alone; without one such a cycle fails closed (``TrustUnavailableError``).
     """
 
     def _average_plan_diffs(self, server_config: dict, cycle):
@@ -501,6 +525,10 @@ def make_average_plan_diffs(aggregator: CycleAggregator, model_manager, process_
         opt_kw = {"opt_key": cycle.fl_process_id} if settings.opt is not None or settings.noise is not None else {}
         if settings.noise is not None:
             opt_kw["dp_round"] = cycle.id  # the round the noise is drawn for: a retried close draws it again
+        if settings.trust is not None:
+            if trust_root is None:
+                raise trust_mod.refuse("is set but no root provider is registered (install(trust_root=fn))")
+            opt_kw["trust_root"] = trust_root(cycle, _checkpoint.value)
         try:
             # a plan whose cached verdict is a decline raises from hosted_plan already: under an optimizer,
             # a rule or noise that must fail the close too, not reach the fall-back below

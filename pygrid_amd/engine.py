@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .exceptions import AggregationError, EngineUnavailableError, StateParseError
 
-MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN, GEOMETRIC_MEDIAN = 0, 1, 2, 3, 4, 5, 6
+MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN, GEOMETRIC_MEDIAN, TRUSTED_MEAN = 0, 1, 2, 3, 4, 5, 6, 7
 GEOMED_MAX_ITERS = 16  # PGH_GEOMED_MAX_ITERS
 KRUM_MAX_ROWS = 1024   # PGH_KRUM_MAX_ROWS
 TRIM_MAX = 8  # PGH_TRIM_MAX
@@ -26,7 +26,7 @@ F32, I64 = 0, 1
 OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4  # pgh_server_opt
 MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
               CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean", MEDIAN: "median",
-              GEOMETRIC_MEDIAN: "geometric_median"}
+              GEOMETRIC_MEDIAN: "geometric_median", TRUSTED_MEAN: "trusted_mean"}
 
 
 def device_count() -> int:
@@ -378,6 +378,64 @@ class Engine:
                     "geomed_stats")
         return {"iterations": it.value, "rows": n.value, "excluded": x.value, "objective": o.value,
                 "max_weight": m.value}
+
+    # ---- trust-bootstrapped FedAvg (TRUSTED_MEAN, FLTrust; kernel K14) --------------------------------
+    def set_trust(self, on: bool = True):
+        """Switch the trust rule of later TRUSTED_MEAN closes (``include/pgh_api.h``).  With it on every ingest
+        queues the row's norm pass, and its inner product with the root while one is set.  Refused
+        (PGH_E_UNSUPPORTED) where ``set_clip_norm`` is; a new layout or shard clears it."""
+        self._check(self._lib.pgh_set_trust(self._h, 1 if on else 0), "set_trust")
+
+    def trust_root(self, root):
+        """The cycle's root update (P floats): needs the rule on; ``reset`` / ``reserve`` drop it.  A NaN, an
+        infinity or an all-zero root is refused (PGH_E_ARG) and leaves no root set."""
+        r = np.ascontiguousarray(root, dtype=np.float32).reshape(-1)
+        self._check(self._lib.pgh_trust_root(self._h, r.ctypes.data_as(C.POINTER(C.c_float)), r.nbytes), "trust_root")
+
+    def row_dot(self, slots: Sequence[int], point) -> np.ndarray:
+        """float64 inner products of the diffs in ``slots`` with ``point`` (P floats): K14 alone, in the
+        order of ``row_sumsq`` (tests, debugging, a cosine to any direction)."""
+        a = np.ascontiguousarray(slots, dtype=np.int32)
+        pt = np.ascontiguousarray(point, dtype=np.float32).reshape(-1)
+        if pt.size != self.P:
+            raise AggregationError(f"row_dot: the point has {pt.size} values, the model {self.P}")
+        out = np.empty(a.size, dtype=np.float64)
+        self._check(self._lib.pgh_row_dot(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
+                                          pt.ctypes.data_as(C.POINTER(C.c_float)),
+                                          out.ctypes.data_as(C.POINTER(C.c_double))), "row_dot")
+        return out
+
+    @staticmethod
+    def trust_weights_host(s0: float, sumsq, dot):
+        """``(weights f32, included positions, T)`` of the trust rule's host step over the rows' sums of squares
+        and inner products with the root (plain C++; no GPU)."""
+        lib = _lib.load()
+        ss = np.ascontiguousarray(sumsq, dtype=np.float64).reshape(-1)
+        dt = np.ascontiguousarray(dot, dtype=np.float64).reshape(-1)
+        if ss.size != dt.size:
+            raise AggregationError(f"trust_weights_host: {ss.size} sums beside {dt.size} dots")
+        n = ss.size
+        w, inc = np.empty(max(n, 1), dtype=np.float32), np.empty(max(n, 1), dtype=np.int32)
+        k, t = C.c_int(0), C.c_double(0)
+        rc = lib.pgh_trust_weights_host(C.c_double(float(s0)), ss.ctypes.data_as(C.POINTER(C.c_double)),
+                                        dt.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                        w.ctypes.data_as(C.POINTER(C.c_float)), inc.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        C.byref(k), C.byref(t))
+        if rc != 0:
+            raise AggregationError(f"trust_weights_host: {_lib.STATUS_NAMES.get(rc, rc)}: "
+                                   f"{lib.pgh_last_error(None).decode(errors='replace')}", status=rc)
+        return w[:k.value].copy(), [int(x) for x in inc[:k.value]], np.float64(t.value)
+
+    def trust_stats(self) -> dict:
+        """``on`` and what the last TRUSTED_MEAN close saw: ``rows``, ``excluded`` (non-finite rows left out),
+        ``trusted`` (rows of positive trust), ``total_trust``, ``max_weight`` and ``root_norm`` (0 without a
+        valid root)."""
+        on, n, x, k = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        t, m, r = C.c_double(0), C.c_float(0), C.c_double(0)
+        self._check(self._lib.pgh_trust_stats(self._h, C.byref(on), C.byref(n), C.byref(x), C.byref(k), C.byref(t),
+                                              C.byref(m), C.byref(r)), "trust_stats")
+        return {"on": bool(on.value), "rows": n.value, "excluded": x.value, "trusted": k.value,
+                "total_trust": t.value, "max_weight": m.value, "root_norm": r.value}
 
     # ---- Multi-Krum selection ahead of the average (kernel K13) ---------------------------------------
     def row_pairdist(self, slots: Sequence[int]) -> np.ndarray:

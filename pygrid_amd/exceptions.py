@@ -78,6 +78,16 @@ class KrumUnavailableError(AggregationError):
     close fails closed."""
 
 
+class TrustUnavailableError(AggregationError):
+    """The FL process asks for trust-bootstrapped averaging (``server_config["diff_trust_root"]``) and the engine
+    cannot apply it this cycle: no root provider is registered, the provider raised or returned ``None``, the
+    root is unusable (another layout, a NaN, an infinity, all zeros), a rule of ``robust.KINDS``, ``dp_noise``,
+    aggregation weights or the iterative plan stands beside it, the engine declines the cycle (an unaccelerated
+    plan, a non-float32 model), lacks ``set_trust`` or answers PGH_E_UNSUPPORTED (a multi-GPU group, a sub-range
+    shard), or no finite diff points along the root.  Like the rules' errors it is NOT a
+    ``PlanNotAcceleratedError``: the node's own averaging trusts every diff, so the close fails closed."""
+
+
 class ServerOptUnavailableError(AggregationError):
     """The FL process asks for a server optimizer (``server_config["server_optimizer"]``) and the
     engine cannot apply it this cycle: it declines the cycle (an unaccelerated plan, a non-float32

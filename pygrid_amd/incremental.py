@@ -66,9 +66,9 @@ from typing import Callable, Dict, Hashable, List, Optional, Sequence
 
 from . import state as state_codec
 from .cycle import _decline_non_float32
-from .engine import F32, MEAN, WEIGHTED_MEAN, Engine
+from .engine import F32, MEAN, TRUSTED_MEAN, WEIGHTED_MEAN, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
-from . import dp, krum as krum_mod, serveropt
+from . import dp, krum as krum_mod, serveropt, trust as trust_mod
 from .robust import check_trim_count, failing_closed
 from .settings import CloseSettings, settings_of
 
@@ -87,10 +87,19 @@ class IncrementalCycle:
                  weights_by_worker: Optional[Dict[object, float]] = None, checkpoint: Optional[bytes] = None,
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
                  median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
-                 dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None, krum=None):
+                 dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None, krum=None, trust=None,
+                 trust_root=None):
         """``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
         ``median``, ``geometric_median``, ``server_opt``, ``dp_noise`` and ``krum`` below (both: an error); keys,
         round and stores go beside either.
+
+        ``trust``: the FL process asks for trust-bootstrapped averaging (``trust.trust_of``: ``True`` or its parsed
+        form); ``trust_root``: the server's own update for this cycle (``trust.root_flat``), here or at ``finish``.
+        Given here, each diff's inner product with it rides behind its ingest; given at ``finish`` they are
+        computed in one batch at the close.  Wired like the geometric median -- ``mode`` MEAN, no weights, no rule,
+        nothing folded early, one TRUSTED_MEAN finish over every held slot (after a selection: over the picked
+        ones) in the close's order, at most as many diffs as slots -- with ``TrustUnavailableError`` where the
+        geometric median raises its own, and where the close has no usable root.
 
         ``krum``: the FL process's Multi-Krum selection (``krum.krum_of``: the setting's dict or its parsed form),
         beside any ``mode``, weights or rule.  A selection needs every diff at once, so nothing is folded early and
@@ -138,20 +147,25 @@ class IncrementalCycle:
         given = {k: v for k, v in dict(clip_norm=clip_norm, trim_count=trim_count, median=bool(median) or None,
                                        server_opt=server_opt, dp_noise=dp_noise,
                                        geometric_median=None if geometric_median is False else geometric_median,
-                                       krum=None if krum is False else krum).items() if v is not None}
+                                       krum=None if krum is False else krum,
+                                       trust=None if trust is False else trust).items() if v is not None}
         if settings is not None and given:
             raise AggregationError(f"settings= was given beside {', '.join(given)}")
         self._settings = settings = settings if settings is not None else settings_of({}, **given)
         self._rule = rule = settings.rule
         if rule is not None and (mode != MEAN or weights_by_worker is not None):
             raise rule.refuse("applies to the plain mean only (no weights, no iterative plan)")
+        self._trust = settings.trust
+        if self._trust is not None and (mode != MEAN or weights_by_worker is not None):
+            raise trust_mod.refuse("applies to the plain mean only (no weights, no iterative plan)")
         self.clip_norm, self.trim_count, self.median, self.geometric_median = None, None, False, None
         if rule is not None:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
         # a rule that needs every row of the cycle in one call: nothing folds early, no partial fold at the close
         self._select = settings.select
-        self._whole = bool(self.median) or self.geometric_median is not None or self._select is not None
-        self._fold_mode = rule.mode if rule else mode
+        self._whole = bool(self.median) or self.geometric_median is not None or self._select is not None \
+            or self._trust is not None
+        self._fold_mode = rule.mode if rule else TRUSTED_MEAN if self._trust is not None else mode
         self._noise_args = (settings.noise_key(dp_keys if dp_keys is not None else dp.DpKeys(), opt_key), dp_round)
         self._opt_key = opt_key
         self._opt_states = opt_states if opt_states is not None else serveropt.ServerOptStates()
@@ -203,6 +217,10 @@ class IncrementalCycle:
             # the close overlaps the tail of the last report's copy (pgh_set_ingest_ranges)
             engine.set_ingest_ranges(os.environ.get("PGH_INGEST_RANGES", "1") != "0")
         settings.set_on_engine(engine, *self._noise_args)  # (the engine was reset above: no slot folds under way)
+        self._has_root = False
+        if self._trust is not None and trust_root is not None:  # ahead of the reports: their dots ride behind them
+            trust_mod.set_root(engine, trust_root, self._numel)
+            self._has_root = True
         self._ckpt: Optional[bytes] = None  # checkpoint bytes whose payloads are resident in HBM
         if checkpoint is not None and getattr(engine, "ckpt_owner", None) is not None \
                 and getattr(engine, "ckpt_bytes", None) is checkpoint:
@@ -214,7 +232,7 @@ class IncrementalCycle:
             try:
                 engine.ckpt_upload_state(checkpoint)
             except StateParseError:
-                with krum_mod.failing_closed(self._select), failing_closed(rule):
+                with krum_mod.failing_closed(self._select), trust_mod.failing_closed(self._trust), failing_closed(rule):
                     _decline_non_float32(checkpoint, "the checkpoint")
                 raise
             engine.ckpt_owner = self
@@ -411,7 +429,7 @@ class IncrementalCycle:
 
     # ---- close (cycle_manager.py:217 -> _average_plan_diffs :240-303) ---------------------------
     def close(self, checkpoint: bytes, framing: str = "fresh", order: Optional[Sequence[Hashable]] = None,
-              fetch: Optional[Callable[[object], bytes]] = None) -> bytes:
+              fetch: Optional[Callable[[object], bytes]] = None, trust_root=None) -> bytes:
         """New checkpoint bytes (``cycle_manager.py:293-303``), framed like ``serialize_model_params``
         (``framing="fresh"``) or as the old checkpoint (``"template"``; see CycleAggregator).
 
@@ -420,7 +438,7 @@ class IncrementalCycle:
         Without ``order`` the assignment order of the reporters is taken as the query's.
         ``seal(order)`` then ``finish(checkpoint, ...)``."""
         self.seal(order)
-        return self.finish(checkpoint, framing=framing, fetch=fetch)
+        return self.finish(checkpoint, framing=framing, fetch=fetch, trust_root=trust_root)
 
     def seal(self, order: Optional[Sequence[Hashable]] = None) -> bool:
         """The close's snapshot (``cycle_manager.py:243-245``: the moment the reference's query reads
@@ -434,7 +452,7 @@ class IncrementalCycle:
                 raise AggregationError("cycle already closed")
             self._closed = True
             if self._declined:
-                with krum_mod.failing_closed(self._select), failing_closed(self._rule):
+                with krum_mod.failing_closed(self._select), trust_mod.failing_closed(self._trust), failing_closed(self._rule):
                     raise ModelNotAcceleratedError(self._declined)
             if order is None:
                 if self._stale or self._bad:
@@ -474,9 +492,15 @@ class IncrementalCycle:
         return any(w not in self._slot_of for w in order[common:])
 
     def finish(self, checkpoint: bytes, framing: str = "fresh",
-               fetch: Optional[Callable[[object], bytes]] = None) -> bytes:
-        """The rest of ``close`` after ``seal``: fold, FINAL pass, new checkpoint bytes."""
-        with self._lock:
+               fetch: Optional[Callable[[object], bytes]] = None, trust_root=None) -> bytes:
+        """The rest of ``close`` after ``seal``: fold, FINAL pass, new checkpoint bytes.  ``trust_root``: under the
+        trust rule, the cycle's root where the constructor was given none (or another one: it replaces it)."""
+        with self._lock, trust_mod.closing(self._trust):
+            if self._trust is not None and trust_root is not None:
+                trust_mod.set_root(self.engine, trust_root, self._numel)
+                self._has_root = True
+            if self._trust is not None and not self._has_root:
+                raise trust_mod.refuse("is set but the cycle has no trust_root: the server's own update for it")
             order = self._close_order
             if order is None:
                 raise AggregationError("finish() without a successful seal()")
@@ -537,11 +561,14 @@ class IncrementalCycle:
             return self._fold_in_order(order if refold else order[len(self._folded):], None, dry=True)["db_rows"]
 
     def _whole_name(self) -> str:
-        return "a median" if self.median else "a geometric median" if self.geometric_median is not None else "a selection"
+        return "a median" if self.median else "a geometric median" if self.geometric_median is not None else \
+            "a trusted mean" if self._trust is not None else "a selection"
 
     def _whole_refuse(self, why: str) -> AggregationError:
         """The refusal of whatever needs every row at once: the rule's, else the selection's."""
         whole_rule = self._rule is not None and (self.median or self.geometric_median is not None)
+        if not whole_rule and self._trust is not None:
+            return trust_mod.refuse(why)
         return self._rule.refuse(why) if whole_rule else krum_mod.refuse(why)
 
     def _fold(self, ws: Sequence, final: bool, slot_of: dict, free: list, dry: bool):

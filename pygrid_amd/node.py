@@ -127,7 +127,7 @@ class NodeEngine:
                  report_time: bool = True, close_trigger: str = "reference", deadline: bool = False,
                  keep_checkpoints: int = 4, slots: Optional[int] = None, fold_batch: int = 8,
                  mean_plans: Optional[str] = None, framing: str = "fresh", report_module=None,
-                 pinned_reports: int = 16):
+                 pinned_reports: int = 16, trust_root: Optional[Callable] = None):
         if close_trigger not in ("reference", "replay"):
             raise AggregationError(f"close_trigger must be 'reference' or 'replay', not {close_trigger!r}")
         if deadline and close_trigger != "replay":
@@ -145,6 +145,13 @@ class NodeEngine:
         self.slots = slots
         self.fold_batch = fold_batch
         self.framing = framing
+        # server_config["diff_trust_root"]: the operator's provider of the server's own update,
+        # fn(fl_process_id, cycle, checkpoint_bytes) -> State bytes shaped like a diff, arrays or a flat array.
+        # Asked once per close, before its FINAL pass; what it gave (or why it gave nothing) is kept while that close
+        # runs -- its report-time attempt and its fall-back to the close-time path share one answer -- and dropped when
+        # it ends, so a retried close asks again.
+        self.trust_root = trust_root
+        self._trust_roots: Dict[object, object] = {}
         self.store = CheckpointStore(keep=keep_checkpoints) if keep_checkpoints else None
         self.report_module = report_module
         self.pinned = None
@@ -186,6 +193,7 @@ class NodeEngine:
         orig_run = self.mod.run_task_once
         close_time = make_average_plan_diffs(self.aggregator, self.model_manager, self.process_manager,
                                              self.plan_manager, original=orig["_average_plan_diffs"],
+                                             trust_root=self._trust_root_for,
                                              gate=self._gate.exclusive, framing=self.framing)
 
         def assign(cm, worker, cycle, hash_key):
@@ -314,6 +322,33 @@ class NodeEngine:
         finally:
             self._engine_lock.release()
 
+    def _trust_root_for(self, cycle, checkpoint: bytes):
+        """The cycle's root update from the operator's provider, asked once per close (``average_plan_diffs`` drops the
+        answer when the close ends).  No provider, a provider that raises or returns None: ``TrustUnavailableError``,
+        again on every later call within that close: the cycle fails closed, since the node's own averaging trusts
+        every diff.  A retried close asks the provider again."""
+        from . import trust as trust_mod
+
+        with self._lock:
+            got = self._trust_roots.get(cycle.id, _MISSING)
+        if got is _MISSING:
+            if self.trust_root is None:
+                got = trust_mod.refuse("is set but no root provider is registered (install(trust_root=fn))")
+            else:
+                try:
+                    got = self.trust_root(cycle.fl_process_id, cycle, checkpoint)
+                    if got is None:
+                        got = trust_mod.refuse(f"is set but the root provider returned None for cycle {cycle.id}")
+                except Exception as e:  # noqa: BLE001 -- operator code: whatever it raises fails the cycle closed
+                    err = trust_mod.refuse(f"is set but the root provider raised for cycle {cycle.id}: {e!r}")
+                    err.__cause__ = e
+                    got = err
+            with self._lock:
+                self._trust_roots[cycle.id] = got  # (until the close ends: average_plan_diffs)
+        if isinstance(got, Exception):
+            raise got
+        return got
+
     def _new_cycle(self, cm, cycle, fresh: bool = False) -> IncrementalCycle:
         server_config, _ = self.process_manager.get_configs(id=cycle.fl_process_id)
         settings = settings_of(server_config)  # (a malformed setting, or noise without the clip bound, raises)
@@ -331,10 +366,10 @@ class NodeEngine:
         numel = checkpoint_numels(ckpt)
         # under a rule: the rule's mode where the plan dispatches to MEAN, the rule's error everywhere else
         mode = select_mode(server_config, avg_plan, plan_key=plan_key, mean_plans=self.aggregator.mean_plans,
-                           shapes=lambda: _shapes(ckpt), **settings.rule_kwargs())
+                           shapes=lambda: _shapes(ckpt), trust=settings.trust, **settings.rule_kwargs())
         self.aggregator._resident = None  # the report-time cycle takes over the engine's slab
         # the moments under the FL process's id, the noise for the cycle's id; the close-time path's stores
-        inc = IncrementalCycle(self.engine, numel, mode=MEAN if settings.rule else mode, slots=self.slots,
+        inc = IncrementalCycle(self.engine, numel, mode=MEAN if settings.rule or settings.trust else mode, slots=self.slots,
                                fold_batch=self.fold_batch, checkpoint=ckpt, settings=settings,
                                opt_key=cycle.fl_process_id, opt_states=self.aggregator.opt_states,
                                dp_round=cycle.id, dp_keys=self.aggregator.dp_keys)
@@ -415,6 +450,13 @@ class NodeEngine:
     def average_plan_diffs(self, cm, server_config, cycle, close_time: Callable, original: Callable):
         """The close (executor thread).  Holds the engine lock throughout, the report gate only for
         the snapshot of the completed rows (see the module docstring)."""
+        try:
+            return self._average_plan_diffs(cm, server_config, cycle, close_time, original)
+        finally:
+            with self._lock:
+                self._trust_roots.pop(cycle.id, None)  # the root (or its refusal) lives as long as the close
+
+    def _average_plan_diffs(self, cm, server_config, cycle, close_time: Callable, original: Callable):
         settings = settings_of(server_config)  # a malformed setting, or two rules at once, fails the close
         original = settings.refusing_original(cycle.id) or original  # fail closed: the node's applies none
         with self._engine_for_close():
@@ -460,7 +502,9 @@ class NodeEngine:
                     blobs = {rid: by_id[rid].diff for rid in st.fetch_plan()}
                 self._gate.release_exclusive()  # the fold needs no DB row beyond `blobs`
                 gated = False
-                new = st.finish(ckpt.value, framing=self.framing, fetch=_only(blobs))
+                # under the trust rule: the server's own update, asked for now (once; the gate is free again)
+                root_kw = {"trust_root": self._trust_root_for(cycle, ckpt.value)} if settings.trust is not None else {}
+                new = st.finish(ckpt.value, framing=self.framing, fetch=_only(blobs), **root_kw)
             except PlanNotAcceleratedError as e:  # incl. ModelNotAcceleratedError: a non-float32 diff
                 log.info("engine declined cycle %s (%s): running the reference averaging", cycle.id, e)
                 fallback = "original"
@@ -480,7 +524,7 @@ class NodeEngine:
                 self.stats["closes_close_time"] += 1
                 return close_time(cm, server_config, cycle)
             self.stats["closes_report_time"] += 1
-            if settings.rule is not None or settings.select is not None:
+            if settings.rule is not None or settings.select is not None or settings.trust is not None:
                 log.info(settings.close_message(cycle.id, st.last_close))
             self.stats["refolds"] += int(st.last_close.get("refold", False))
             self.stats["diffs_from_db"] += st.last_close.get("from_db", 0)

@@ -14,13 +14,14 @@ import contextlib
 import dataclasses
 from typing import Callable, Optional
 
-from . import dp, krum as krum_mod, robust
+from . import dp, krum as krum_mod, robust, trust as trust_mod
 from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
 from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, KrumUnavailableError, \
-    PlanNotAcceleratedError, ServerOptUnavailableError
+    PlanNotAcceleratedError, ServerOptUnavailableError, TrustUnavailableError
 from .krum import KRUM_KEY, KrumSpec, krum_of
 from .robust import CLIP_KEY, GEOMED_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
+from .trust import TRUST_KEY, TrustSpec, trust_of
 
 
 @dataclasses.dataclass(frozen=True)
@@ -30,9 +31,11 @@ class CloseSettings:
     opt: Optional[ServerOptSpec] = None
     noise: Optional[DpNoiseSpec] = None
     select: Optional[KrumSpec] = None
+    trust: Optional[TrustSpec] = None
 
     def __bool__(self) -> bool:
-        return self.rule is not None or self.opt is not None or self.noise is not None or self.select is not None
+        return self.rule is not None or self.opt is not None or self.noise is not None or self.select is not None \
+            or self.trust is not None
 
     def rule_kwargs(self) -> dict:
         """The rule as the keyword argument that ``select_mode`` takes."""
@@ -42,11 +45,12 @@ class CloseSettings:
     def fail_closed(self, what: str = "the engine does not average this cycle"):
         """A ``PlanNotAcceleratedError`` (``ModelNotAcceleratedError`` included) raised in the block must not
         reach a caller that falls back to the node's own averaging, which clips, trims, steps and noises nothing.
-        Under a rule it becomes the rule's error; under noise that error in turn, like the clip rule's own
+        Under a rule it becomes the rule's error, under the trust rule a ``TrustUnavailableError``; under noise that error in turn, like the clip rule's own
         refusal, a ``DpNoiseUnavailableError``; under a selection without a rule a ``KrumUnavailableError``; under
         an optimizer alone a ``ServerOptUnavailableError``."""
         try:
-            with krum_mod.failing_closed(self.select, what), robust.failing_closed(self.rule, what):
+            with krum_mod.failing_closed(self.select, what), trust_mod.failing_closed(self.trust, what), \
+                    robust.failing_closed(self.rule, what):
                 yield
         except (PlanNotAcceleratedError, ClipUnavailableError) as e:
             if self.noise is not None:
@@ -64,6 +68,8 @@ class CloseSettings:
             key, error, lacks = DP_KEY, DpNoiseUnavailableError, "adds no noise"
         elif self.rule is not None:
             key, error, lacks = self.rule.key, self.rule.error, self.rule.lacks
+        elif self.trust is not None:
+            key, error, lacks = TRUST_KEY, TrustUnavailableError, "trusts every diff"
         elif self.select is not None:
             key, error, lacks = KRUM_KEY, KrumUnavailableError, "selects nothing"
         elif self.opt is not None:
@@ -86,6 +92,7 @@ class CloseSettings:
         ``noise_only``: again right before a FINAL pass."""
         if not noise_only:
             robust.set_on_engine(engine, self.rule)
+            trust_mod.set_on_engine(engine, self.trust)  # (the cycle's root follows: trust.set_root)
         dp.set_on_engine(engine, self.noise, key, round)
 
     def _value(self, key: str, off=None):
@@ -106,6 +113,8 @@ class CloseSettings:
                                          "objective": float(gs["objective"]), "max_weight": float(gs["max_weight"])}
         if self.select is not None:  # one more key, under a selection alone
             stats["krum"] = krum_mod.close_stats(engine, self.select)
+        if self.trust is not None:  # one more key, under the trust rule alone
+            stats["trust"] = trust_mod.close_stats(engine)
         return stats
 
     def close_message(self, cycle_id, last_close: dict) -> str:
@@ -113,6 +122,11 @@ class CloseSettings:
         kr = last_close.get("krum")
         picked = "" if kr is None else "; %s picked %d of them (f = %d, %d excluded, largest picked score %s)" % (
             KRUM_KEY, kr["picked"], kr["byzantine"], kr["excluded"], kr["max_picked_score"])
+        tr = last_close.get("trust")
+        if tr is not None:
+            return "cycle %s closed with %s over %d diffs (%d trusted, %d excluded, total trust %s, largest weight %s, root norm %s)%s" % (
+                cycle_id, TRUST_KEY, last_close.get("n", 0), tr["trusted"], tr["excluded"], tr["total_trust"],
+                tr["max_weight"], tr["root_norm"], picked)
         if self.rule is None:
             return "cycle %s closed over %d diffs%s" % (cycle_id, last_close.get("n", 0), picked)
         noised = "" if self.noise is None else "; %s multiplier %s, noise std %s per parameter" % (
@@ -128,19 +142,26 @@ class CloseSettings:
 
 
 def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
-                server_opt=UNSET, geometric_median=UNSET, krum=UNSET) -> CloseSettings:
+                server_opt=UNSET, geometric_median=UNSET, krum=UNSET, trust=UNSET) -> CloseSettings:
     """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
     ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
     malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
     the earlier rule's error (``robust.KINDS``), noise without the clip bound ``DpNoiseUnavailableError``, a
-    selection (``krum``: the setting's dict or its parsed form) beside noise ``KrumUnavailableError``."""
+    selection (``krum``: the setting's dict or its parsed form) beside noise ``KrumUnavailableError``, the trust
+    rule (``trust``) beside any rule of ``robust.KINDS`` or beside noise ``TrustUnavailableError`` (weights and the
+    iterative plan are refused where the mode is chosen, ``cycle.select_mode``)."""
     rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median)
     if not isinstance(server_opt, ServerOptSpec):
         server_opt = server_opt_of(server_config if server_opt is UNSET else {OPT_KEY: server_opt})
     noise = dp_noise_of(server_config, dp_noise)
+    tr = trust_of(server_config, trust)
+    if tr is not None and rule is not None:
+        raise trust_mod.refuse(f"cannot be combined with {rule.key}: the trusted mean is the cycle's averaging rule")
+    if tr is not None and noise is not None:
+        raise trust_mod.refuse(f"cannot be combined with {DP_KEY}: the noise is calibrated to the clipped mean")
     dp.check_rule(noise, rule)
     select = krum_of(server_config, krum)
     if select is not None and noise is not None:
         raise krum_mod.refuse(f"cannot be combined with {DP_KEY}: the clip-and-noise sensitivity argument does not "
                               "cover a data-dependent selection of the diffs")
-    return CloseSettings(rule, server_opt, noise, select)
+    return CloseSettings(rule, server_opt, noise, select, tr)
