@@ -4,7 +4,8 @@
 // The context's code is split by what it does:
 //   pgh_api.cpp     lifecycle, errors and state checks, observability, the group driver's internals
 //   pgh_host.cpp    host code free of HIP (pgh_host.h): non-temporal copy, copy pool, pre-faulting, the walk over
-//                   host pieces (PieceCursor), the chunk arithmetic of ranged ingest, the geometric median's host step
+//                   host pieces (PieceCursor), the chunk arithmetic of ranged ingest, the rules' host steps; in the
+//                   header alone, the per-slot state machine of a cached row reduction (SlotCache)
 //   pgh_xfer.cpp    host <-> HBM: the pinned staging ring, the D2H rings, page-locked host blocks; the methods of
 //                   the transfer owners.  Their state: pgh_xfer.h
 //   pgh_order.cpp   which stream waits for what, and the timing events
@@ -12,20 +13,23 @@
 //   pgh_reduce.cpp  the one fp32 fold launch (fold_prepare, fold_launch), the fold over listed slots (fold_listed);
 //                   fold_run's ring walk and the share sum; the divisors; the weights' upload; RESIDENT and STREAM
 //                   entry points, the resident checkpoint
-//   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: the row sums (RowSums:
-//                   K7 and its cache, K12), clipping (the scales, the tallies) and the Gaussian noise on the clipped
-//                   close (K11 behind a FINAL launch), trimming (K8's planes), the median (K9, K9p), the geometric
-//                   median (its weights), the trust rule (its root, K14's cached dots, its weights); the -0 plane; the rules' lifecycle calls (rules_*), the fold plans the
-//                   two drivers ask for (rules_slot_plan, rules_resident_plan) and the entry points.  Their state:
-//                   pgh_rules.h
+//   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: the row reductions (RowSums:
+//                   K7 and K14 through their per-slot caches, K12 and K14 over listed rows, K13), clipping (the scales,
+//                   the tallies) and the Gaussian noise on the clipped close (K11 behind a FINAL launch), trimming
+//                   (K8's planes), the median (K9, K9p), the geometric median and the trust rule (the included rows
+//                   and resident weights they share; the iterations; the root), the Multi-Krum selection; the -0
+//                   plane; the rules' lifecycle calls (rules_*), the fold plans the two drivers ask for
+//                   (rules_slot_plan, rules_resident_plan) and the entry points.  Their state: pgh_rules.h
 //   pgh_serveropt.cpp  the server optimizer: K10 behind a FINAL launch, its planes, commit, download, upload
 //   pgh_slots.cpp   report-time slot folds (the certain prefix of the close-time order): slot_fold
 // A new averaging rule adds its state struct to pgh_rules.h (a member of pgh_ctx), its lines to the lifecycle
 // functions rules_* in pgh_rules.cpp -- the one call each event of the context makes: made, slab freed, shard
 // set, reserved, reset, slot written, row ingested, folds restarted, cycle finished -- and to the two plan
 // functions, and touches check_mode_use, fold_prepare and fold_launch; both fold drivers (fold_run, slot_fold)
-// ask for the plan and reach the kernels through the last two alone.  A row-wise rule takes its sums from RowSums,
-// writes its weights through FoldWeights::replace and folds against the one -0 plane (NegZeroPlane).  The server optimizer (pgh_set_server_opt) hangs on fold_launch too: a FINAL
+// ask for the plan and reach the kernels through the last two alone.  A row-wise rule takes its sums from RowSums
+// (a new cached value per slot is one more RowCache there and one RowOp in pgh_rules.cpp), its finite rows from
+// finite_rows into an IncludedRows, writes its weights through FoldWeights::replace and folds against the one -0
+// plane (NegZeroPlane).  The server optimizer (pgh_set_server_opt) hangs on fold_launch too: a FINAL
 // launch with one set is followed by K10 (server_opt_launch).  The noise (pgh_set_dp_noise) is a second tenant of
 // that mechanism: a clipped FINAL launch with it set is followed by K11 (dp_noise_launch), ahead of K10.
 // A new transfer feature adds its state struct to pgh_xfer.h (a member of pgh_ctx), its events and knobs to
@@ -168,7 +172,7 @@ struct pgh_ctx {
     // lifecycle files (pgh_api.cpp, pgh_ingest.cpp, pgh_slots.cpp, pgh_xfer.cpp, pgh_order.cpp) reach them
     // through rules_* and the fold plans below alone:
     //   grep -n 'c->\(clip\|geo\|trust\|krum\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
-    pgh_detail::RowSums rowsums;   // K7's and K14's per-slot caches, the buffers of K7, K12, K13 and K14 (clip, geo, krum, trust)
+    pgh_detail::RowSums rowsums;   // the per-slot caches sq (K7) and dot (K14), the tile partials and the buffers of K12 and K13 (clip, geo, krum, trust)
     pgh_detail::NegZeroPlane nz;   // the one plane of -0.0f (opt, noise, geo)
     pgh_detail::ClipState clip;
     pgh_detail::NoiseState noise;

@@ -1,6 +1,7 @@
 // HIP-free host code of libpygrid_hip (not installed): the non-temporal copy, the copy pool, the
 // scatter out of a landed piece, the walk over concatenated host pieces, the chunk arithmetic of ranged ingest,
-// page pre-faulting, the CPU count, the DP noise sampler's restatement, the geometric median's host step.
+// page pre-faulting, the CPU count, the DP noise sampler's restatement, the host steps of the geometric median,
+// the Multi-Krum selection and the trust rule, the per-slot state machine of a cached row reduction (SlotCache).
 // Nothing here may include HIP.
 #pragma once
 #include <algorithm>
@@ -225,5 +226,68 @@ double row_dot_host(const float* x, const float* y, int64_t p);
 // n_trusted (rows with ts > 0) and max_w are nullable.
 int trust_weights(double s0, const double* sumsq, const double* dot, int64_t n, float* w, int32_t* included,
                   int64_t* n_included, double* T, int64_t* n_trusted, float* max_w);
+
+// The host side of a per-slot cache of one f64 that a kernel computes from the slot's diff (K7's sum of squares,
+// K14's dot; RowCache in pgh_rules.h adds the buffers and the event).  A slot is NONE (no value of its present
+// diff), QUEUED (the kernel and the D2H of its value are issued: the value is in the host image once the
+// owner's event has passed) or VALID (at() holds it).  Whoever queues asks missing() first, launches, and
+// marks what it launched; whoever reads waits for the event and harvests first.
+struct SlotCache {
+    enum : uint8_t { NONE = 0, QUEUED = 1, VALID = 2 };
+    std::vector<uint8_t> state;   // per slot
+    std::vector<double> value;    // per slot: what at() returns for a VALID one
+    std::vector<int32_t> queued;  // the slots that went QUEUED since the last harvest
+
+    double at(int slot) const { return value[(size_t)slot]; }  // after a harvest: the value of a slot queued before it
+    bool anything_queued() const { return !queued.empty(); }
+    void reserved(int slots) {  // the slab at a new length: every slot NONE, nothing queued
+        state.assign((size_t)slots, (uint8_t)NONE);
+        value.assign((size_t)slots, 0.0);
+        queued.clear();
+    }
+    // The diffs in slots [slot, slot + n) are being replaced: their values were the old diffs'.  The one place a
+    // value goes to NONE slot by slot; one that is QUEUED stays in the queued list and its harvest skips it.
+    void written(int slot, int n) { std::fill_n(state.begin() + slot, n, (uint8_t)NONE); }
+    // those of slots[0, n) that are NONE: once each, in list order
+    std::vector<int32_t> missing(const int32_t* slots, int n) {
+        std::vector<int32_t> todo;
+        for (int k = 0; k < n; ++k)
+            if (state[(size_t)slots[k]] == NONE) {
+                todo.push_back(slots[k]);
+                state[(size_t)slots[k]] = QUEUED;  // (a slot listed twice is taken once; put back below)
+            }
+        for (int32_t sl : todo) state[(size_t)sl] = NONE;
+        return todo;
+    }
+    void mark_queued(const std::vector<int32_t>& todo) {  // their kernel and D2H are issued
+        for (int32_t sl : todo) {
+            state[(size_t)sl] = QUEUED;
+            queued.push_back(sl);
+        }
+    }
+    // The queued values have landed in host_image (indexed by slot): QUEUED -> VALID.  A slot that was written
+    // after it was queued is NONE (or QUEUED again, and then listed again behind this entry, its new value
+    // the one the image holds): its old value is never taken, a harvest resurrects nothing.
+    void harvest(const double* host_image) {
+        for (int32_t sl : queued)
+            if (state[(size_t)sl] == QUEUED) {
+                value[(size_t)sl] = host_image[sl];
+                state[(size_t)sl] = VALID;
+            }
+        queued.clear();
+    }
+    // Every slot back to NONE and nothing to harvest.  all_stale: what the values were computed against has
+    // changed (the owner has waited for what was in flight); forget: the diffs themselves are gone.
+    void all_stale() {
+        std::fill(state.begin(), state.end(), (uint8_t)NONE);
+        queued.clear();
+    }
+    void forget() { all_stale(); }
+    void clear() {  // the slab is freed: no slot at all
+        state.clear();
+        value.clear();
+        queued.clear();
+    }
+};
 
 }  // namespace pgh_detail

@@ -1,12 +1,13 @@
-// libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); the per-row
-// sums of squares and distances (RowSums: K7 with its host cache, K12, K13) and the Multi-Krum selection over them; clipping's scales and tallies; the
-// Gaussian noise on the clipped close (K11 behind a FINAL launch, its plane, setting and entry points); the
-// trimmed mean's state planes (K8); the median's driver and row table (K9, K9p); the geometric median's included
-// rows, inner iterations and final weights (K12 between weighted folds); the trust rule's root, cached dots (K14)
-// and weights; the context's -0 plane; what the rules'
-// state does at each lifecycle event of the context (rules_*: the one call each event's site makes) and what
-// they hand a fold driver before its launches (rules_slot_plan, rules_resident_plan).  The state itself:
-// pgh_rules.h.
+// libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); the row
+// reductions (RowSums: K7 and K14 through their per-slot caches, K12 and K14 over a listed set of rows, K13) and
+// the Multi-Krum selection over them; clipping's scales and tallies; the Gaussian noise on the clipped close (K11
+// behind a FINAL launch, its plane, setting and entry points); the trimmed mean's state planes (K8); the
+// median's driver and row table (K9, K9p); what the geometric median and the trust rule share (the finite rows
+// of a close, the resident weights, the plan over the included rows) and each one's own: the inner iterations
+// and final weights (K12 between weighted folds), the root and the weights from the cached dots; the context's
+// -0 plane; what the rules' state does at each lifecycle event of the context (rules_*: the one call each
+// event's site makes) and what they hand a fold driver before its launches (rules_slot_plan,
+// rules_resident_plan).  The state itself: pgh_rules.h.
 // (struct pgh_ctx and the shared helpers: pgh_ctx.h)
 #include "pgh_ctx.h"
 
@@ -20,6 +21,8 @@ namespace pgh_detail {
 
 namespace {
 int mode_use_rule(pgh_ctx* c, int mode, ModeUse use);
+int queue_sums(pgh_ctx* c, const int32_t* slots, int n);
+int queue_dots(pgh_ctx* c, const int32_t* slots, int n);
 }
 
 int check_mode_use(pgh_ctx* c, int mode, ModeUse use) {
@@ -35,6 +38,20 @@ int check_noise_final(pgh_ctx* c, int mode) {
 }
 
 namespace {
+// The rules that close a whole cycle in one fold (rules_one_fold_cycle, which has their names): every row at
+// once; with whole_rows the whole row of each, like clipping.
+int one_fold_cycle_use(pgh_ctx* c, int mode, ModeUse use, bool whole_rows) {
+    const char* a_rule = rules_one_fold_cycle(mode);  // "a median"
+    const char* rule = a_rule + 2;                    // "median"
+    if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no %s: it needs every row at once", rule);
+    if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "%s needs every row at once: nothing can be folded early", a_rule);
+    if (!whole_rows) return PGH_OK;
+    if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts take no %s: the shards each hold part of a row", rule);
+    if (c->layout && c->pg != c->P)
+        return fail(c, PGH_E_UNSUPPORTED, "%s needs whole rows: the shard [%lld,%lld) is narrower than the model", a_rule, (long long)c->lo, (long long)c->hi);
+    return PGH_OK;
+}
+
 int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
     switch (mode) {
     case PGH_MEAN: case PGH_ITERATIVE_MEAN: case PGH_WEIGHTED_MEAN:
@@ -48,24 +65,14 @@ int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
         if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use does not trim: fold a RESIDENT slab or slots");
         if (!c->grp && c->trim.b == 0) return fail(c, PGH_E_STATE, "PGH_TRIMMED_MEAN needs a trim count: call pgh_set_trim first");
         return PGH_OK;
-    case PGH_MEDIAN:  // it needs every row of the cycle at once
-        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no median: it needs every row at once");
-        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a median needs every row at once: nothing can be folded early");
-        return PGH_OK;
-    case PGH_GEOMETRIC_MEDIAN:  // every row at once like the median, the whole row of each like clipping
-        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no geometric median: it needs every row at once");
-        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a geometric median needs every row at once: nothing can be folded early");
-        if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts take no geometric median: the shards each hold part of a row");
-        if (c->layout && c->pg != c->P)
-            return fail(c, PGH_E_UNSUPPORTED, "a geometric median needs whole rows: the shard [%lld,%lld) is narrower than the model", (long long)c->lo, (long long)c->hi);
+    case PGH_MEDIAN:
+        return one_fold_cycle_use(c, mode, use, false);
+    case PGH_GEOMETRIC_MEDIAN:
+        RC(one_fold_cycle_use(c, mode, use, true));
         if (c->geo.iters == 0) return fail(c, PGH_E_STATE, "PGH_GEOMETRIC_MEDIAN needs its setting: call pgh_set_geomed first");
         return PGH_OK;
-    case PGH_TRUSTED_MEAN:  // as the geometric median: every row at once, the whole row of each
-        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no trusted mean: it needs every row at once");
-        if (use == USE_SLOT_EARLY) return fail(c, PGH_E_UNSUPPORTED, "a trusted mean needs every row at once: nothing can be folded early");
-        if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "group contexts take no trusted mean: the shards each hold part of a row");
-        if (c->layout && c->pg != c->P)
-            return fail(c, PGH_E_UNSUPPORTED, "a trusted mean needs whole rows: the shard [%lld,%lld) is narrower than the model", (long long)c->lo, (long long)c->hi);
+    case PGH_TRUSTED_MEAN:
+        RC(one_fold_cycle_use(c, mode, use, true));
         if (!c->trust.on) return fail(c, PGH_E_STATE, "PGH_TRUSTED_MEAN needs its setting: call pgh_set_trust first");
         if (!c->trust.root_valid) return fail(c, PGH_E_STATE, "PGH_TRUSTED_MEAN needs the cycle's root: call pgh_trust_root (none set since pgh_reset / pgh_reserve)");
         if (noise_on(c)) return fail(c, PGH_E_STATE, "DP noise is set (pgh_set_dp_noise): a trusted mean takes none");
@@ -85,7 +92,7 @@ bool rules_made(pgh_ctx* c) {
         const long long v = std::atoll(e);
         if (v > 0 && (unsigned long long)v < c->rowsums.pair_budget) c->rowsums.pair_budget = (size_t)v;
     }
-    return c->rowsums.ev.make() == hipSuccess && c->rowsums.ev_dot.make() == hipSuccess;
+    return c->rowsums.sq.ev.make() == hipSuccess && c->rowsums.dot.ev.make() == hipSuccess;
 }
 
 void rules_slab_freed(pgh_ctx* c) {  // the streams are idle (free_slab synchronised them)
@@ -134,9 +141,9 @@ void rules_cycle_finished(pgh_ctx* c, int mode) {
 int rules_row_ingested(pgh_ctx* c, int slot) {
     if (!norms_wanted(c)) return PGH_OK;
     const int32_t sl = slot;
-    RC(c->rowsums.queue(c, &sl, 1));
+    RC(queue_sums(c, &sl, 1));
     // the trust rule with the cycle's root in place: the row's K14 behind its K7, both behind the next report's copy
-    if (trust_on(c) && c->trust.root_valid) RC(c->rowsums.queue_dots(c, &sl, 1, c->trust.d_root.as<float>()));
+    if (trust_on(c) && c->trust.root_valid) RC(queue_dots(c, &sl, 1));
     return PGH_OK;
 }
 
@@ -217,13 +224,27 @@ void ClipState::count(const float* scales, const double* row_norms, int64_t n) {
     }
 }
 
-// ---- the row sums: K7 and its host cache, K12 (RowSums) -------------------------------------------------------
+// ---- the row reductions: K7 and K14 through their caches, K12 and K14 over listed rows (RowSums) ---------------
+
+// A row reduction against a plane: its launcher, the f64s it moves per tile and row (the partial out: K7; out and
+// in again: K12 and K14, whose plane comes once per row chunk, from L2 mostly) and what an allocation error
+// calls its sums.
+struct RowOp {
+    hipError_t (*launch)(const pgh::DistsqArgs&, const pgh::Rows&, hipStream_t);
+    uint64_t tile_bytes;
+    const char* what;
+};
+namespace {
+const RowOp ROW_SUMSQ{[](const pgh::DistsqArgs& a, const pgh::Rows& r, hipStream_t s) { return pgh::launch_row_sumsq(a.s, r, s); }, 8, "clipping sums"};
+const RowOp ROW_DISTSQ{pgh::launch_row_distsq, 16, "geometric median's distances"};
+const RowOp ROW_DOT{pgh::launch_row_dot, 16, "row dots"};
+}  // namespace
 
 int RowSums::ensure(pgh_ctx* c) {
     if (d_part) return PGH_OK;
     const size_t ntiles = (size_t)((c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE);
     const size_t rows = (size_t)c->slots;
-    if (!d_part.reserve(8 * rows * ntiles) || !d_sq.reserve(8 * rows) || !h_sq.reserve(8 * rows)) {
+    if (!d_part.reserve(8 * rows * ntiles) || !sq.alloc(rows)) {
         d_part.reset();  // (the test above: all three or none)
         return fail(c, PGH_E_OOM, "allocation of the clipping sums (%zu rows x %zu tiles) failed", rows, ntiles);
     }
@@ -241,6 +262,16 @@ pgh::SumsqArgs RowSums::args(pgh_ctx* c, double* sums) const {
     return a;
 }
 
+int RowSums::launch_rows(pgh_ctx* c, const RowOp& op, const float* plane, const int32_t* slots, size_t n, double* sums, hipStream_t s) {
+    pgh::DistsqArgs a{args(c, sums), plane};
+    // HBM bytes of a row: the row, its tile partials
+    const uint64_t row_bytes = 4ull * (uint64_t)c->pg + op.tile_bytes * (uint64_t)a.s.ntiles;
+    return for_row_runs(c, slots, n, [&](const pgh::Rows& rows, size_t, size_t m) {
+        a.s.n_rows = (int)m;
+        return timed_launch(c, s, m * row_bytes, [&] { return op.launch(a, rows, s); });
+    });
+}
+
 namespace {
 // sums[lo, hi] of the listed slots from the device to their pinned image on stream s.  Entries of other slots
 // inside [lo, hi] are rewritten with what the device holds for them: the same value an earlier copy brought
@@ -253,114 +284,52 @@ int sums_d2h(pgh_ctx* c, const int32_t* slots, size_t n, double* h, const double
 }
 }  // namespace
 
-int RowSums::queue(pgh_ctx* c, const int32_t* slots, int n) {
-    std::vector<int32_t> todo;
-    for (int k = 0; k < n; ++k)
-        if (state[(size_t)slots[k]] == NONE) todo.push_back(slots[k]);
+int RowSums::queue_cached(pgh_ctx* c, RowCache& cache, const RowOp& op, const float* plane, const int32_t* slots, int n) {
+    const std::vector<int32_t> todo = cache.missing(slots, n);
     if (todo.empty()) return PGH_OK;
     RC(ensure(c));
-    pgh::SumsqArgs a = args(c, d_sq.as<double>());
+    if (!cache.alloc((size_t)c->slots)) return fail(c, PGH_E_OOM, "allocation of the %s (%d rows) failed", cache.what, c->slots);
     const hipStream_t s = c->copy;
-    // HBM bytes: the rows, the tile partials out
-    RC(for_row_runs(c, todo.data(), todo.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
-        a.n_rows = (int)m;
-        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 8ull * (uint64_t)a.ntiles);
-        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_sumsq(a, rows, s); });
-    }));
-    RC(sums_d2h(c, todo.data(), todo.size(), h_sq.as<double>(), d_sq.as<double>(), s));
-    CK(c, hipEventRecord(ev, s));
-    for (int32_t sl : todo) {
-        state[(size_t)sl] = QUEUED;
-        queued.push_back(sl);
-    }
+    RC(launch_rows(c, op, plane, todo.data(), todo.size(), cache.d.as<double>(), s));
+    RC(sums_d2h(c, todo.data(), todo.size(), cache.h.as<double>(), cache.d.as<double>(), s));
+    CK(c, hipEventRecord(cache.ev, s));
+    cache.mark_queued(todo);
     return PGH_OK;
 }
 
 int RowSums::wait(pgh_ctx* c) {
-    if (!queued.empty()) {
-        CK(c, hipEventSynchronize(ev));
-        for (int32_t sl : queued)
-            if (state[(size_t)sl] == QUEUED) {
-                value[(size_t)sl] = h_sq.as<double>()[sl];
-                state[(size_t)sl] = VALID;
-            }
-        queued.clear();
-    }
-    if (!dot_queued.empty()) {
-        CK(c, hipEventSynchronize(ev_dot));
-        for (int32_t sl : dot_queued)
-            if (dot_state[(size_t)sl] == QUEUED) {
-                dot_value[(size_t)sl] = h_dot.as<double>()[sl];
-                dot_state[(size_t)sl] = VALID;
-            }
-        dot_queued.clear();
-    }
+    for (RowCache* r : {&sq, &dot})
+        if (r->anything_queued()) {
+            CK(c, hipEventSynchronize(r->ev));
+            r->harvest(r->h.as<double>());
+        }
     return PGH_OK;
 }
 
-// (on the copy stream like K7: the two share the tile partials, and one stream orders them)
-int RowSums::queue_dots(pgh_ctx* c, const int32_t* slots, int n, const float* root) {
-    std::vector<int32_t> todo;
-    for (int k = 0; k < n; ++k)
-        if (dot_state[(size_t)slots[k]] == NONE) todo.push_back(slots[k]);
-    if (todo.empty()) return PGH_OK;
-    RC(ensure(c));
-    if (!d_dot.reserve(8 * (size_t)c->slots) || !h_dot.reserve(8 * (size_t)c->slots))
-        return fail(c, PGH_E_OOM, "allocation of the trust rule's dots (%d rows) failed", c->slots);
-    pgh::DistsqArgs a{args(c, d_dot.as<double>()), root};
-    const hipStream_t s = c->copy;
-    // HBM bytes: the rows, the partials out and in again; the plane once per row chunk (from L2 mostly)
-    RC(for_row_runs(c, todo.data(), todo.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
-        a.s.n_rows = (int)m;
-        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
-        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_dot(a, rows, s); });
-    }));
-    RC(sums_d2h(c, todo.data(), todo.size(), h_dot.as<double>(), d_dot.as<double>(), s));
-    CK(c, hipEventRecord(ev_dot, s));
-    for (int32_t sl : todo) {
-        dot_state[(size_t)sl] = QUEUED;
-        dot_queued.push_back(sl);
-    }
-    return PGH_OK;
-}
-
-// (K7's and the cached K14's tile partials are free: everything queued has been waited for.  The sums go through
-// K12's buffers: neither cache is touched.)
-int RowSums::dots(pgh_ctx* c, const std::vector<int32_t>& slots, const float* plane, hipStream_t s, double* D) {
+// (The tile partials are free: everything queued has been waited for.  The sums go through d_dist / h_dist:
+// neither cache is touched.)
+int RowSums::run_listed(pgh_ctx* c, const RowOp& op, const std::vector<int32_t>& slots, const float* plane, hipStream_t s, double* D) {
     RC(wait(c));
     RC(ensure(c));
     if (!d_dist.reserve(8 * (size_t)c->slots) || !h_dist.reserve(8 * (size_t)c->slots))
-        return fail(c, PGH_E_OOM, "allocation of the row dots (%d rows) failed", c->slots);
-    pgh::DistsqArgs a{args(c, d_dist.as<double>()), plane};
-    RC(for_row_runs(c, slots.data(), slots.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
-        a.s.n_rows = (int)m;
-        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
-        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_dot(a, rows, s); });
-    }));
+        return fail(c, PGH_E_OOM, "allocation of the %s (%d rows) failed", op.what, c->slots);
+    RC(launch_rows(c, op, plane, slots.data(), slots.size(), d_dist.as<double>(), s));
     RC(sums_d2h(c, slots.data(), slots.size(), h_dist.as<double>(), d_dist.as<double>(), s));
     CK(c, hipStreamSynchronize(s));
     for (size_t k = 0; k < slots.size(); ++k) D[k] = h_dist.as<double>()[slots[k]];
     return PGH_OK;
 }
 
-// (K7's tile partials are free: every queued K7 and K14 has been waited for.)
-int RowSums::distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* negv, hipStream_t s, double* D) {
-    RC(wait(c));
-    RC(ensure(c));
-    if (!d_dist.reserve(8 * (size_t)c->slots) || !h_dist.reserve(8 * (size_t)c->slots))
-        return fail(c, PGH_E_OOM, "allocation of the geometric median's distances (%d rows) failed", c->slots);
-    pgh::DistsqArgs a{args(c, d_dist.as<double>()), negv};
-    // HBM bytes: the rows, the partials out and in again; the plane once per row chunk (from L2 mostly)
-    RC(for_row_runs(c, slots.data(), slots.size(), [&](const pgh::Rows& rows, size_t, size_t m) {
-        a.s.n_rows = (int)m;
-        const uint64_t bytes = m * (4ull * (uint64_t)c->pg + 16ull * (uint64_t)a.s.ntiles);
-        return timed_launch(c, s, bytes, [&] { return pgh::launch_row_distsq(a, rows, s); });
-    }));
-    RC(sums_d2h(c, slots.data(), slots.size(), h_dist.as<double>(), d_dist.as<double>(), s));
-    CK(c, hipStreamSynchronize(s));
-    for (size_t k = 0; k < slots.size(); ++k) D[k] = h_dist.as<double>()[slots[k]];
-    return PGH_OK;
+namespace {
+// K7 into its cache for those of `slots` that have no sum yet; K14 against the cycle's root, likewise (on the
+// copy stream like K7: the two share the tile partials, and one stream orders them)
+int queue_sums(pgh_ctx* c, const int32_t* slots, int n) {
+    return c->rowsums.queue_cached(c, c->rowsums.sq, ROW_SUMSQ, nullptr, slots, n);
 }
+int queue_dots(pgh_ctx* c, const int32_t* slots, int n) {
+    return c->rowsums.queue_cached(c, c->rowsums.dot, ROW_DOT, c->trust.d_root.as<float>(), slots, n);
+}
+}  // namespace
 
 // (K7's and K12's buffers are not touched: the cached sums stay what they were.)
 int RowSums::pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D) {
@@ -426,7 +395,7 @@ namespace {
 // weights[c0 + k] = the scale of slots[k] (K7 for the sums still missing in one batch, then the wait); norms
 // receives sqrt(sumsq) beside them
 int clip_set_scales(pgh_ctx* c, const int32_t* slots, int n, int64_t c0, std::vector<double>* norms) {
-    RC(c->rowsums.queue(c, slots, n));
+    RC(queue_sums(c, slots, n));
     RC(c->rowsums.wait(c));
     std::vector<float>& w = c->fw.replace(FoldWeights::CLIP);
     w.resize((size_t)(c0 + n));
@@ -456,7 +425,44 @@ int resident_clip_scales(pgh_ctx* c, int64_t n) {
     return PGH_OK;
 }
 
-// ---- geometric-median FedAvg: the included rows, the inner iterations, the final weights ---------------------
+// ---- what the geometric median, the trust rule and the Multi-Krum selection share ------------------------------
+
+// K7 for the sums of slots[0, n) still missing in one batch and the wait; then those of the slots whose sum is
+// finite, in list order, into *inc and (sums nullable) their sums beside them.  Every other row is excluded: no
+// fold and no later pass of the caller reads it.
+int finite_rows(pgh_ctx* c, const int32_t* slots, int n, std::vector<int32_t>* inc, std::vector<double>* sums) {
+    RC(queue_sums(c, slots, n));
+    RC(c->rowsums.wait(c));
+    for (int k = 0; k < n; ++k) {
+        const double ss = c->rowsums.at(slots[k]);
+        if (!std::isfinite(ss)) continue;
+        inc->push_back(slots[k]);
+        if (sums) sums->push_back(ss);
+    }
+    return PGH_OK;
+}
+
+// A resident fold of a rule that writes the included rows' weights: clients [0, n) in slots [0, n), computed
+// (compute = the rule's slot weights) once per state of the slab and of whatever else makes them stale.
+int resident_weights(pgh_ctx* c, FoldWeights::Writer writer, const IncludedRows& included, int64_t n,
+                     int (*compute)(pgh_ctx*, const int32_t*, int)) {
+    if (c->fw.valid(writer, n) && c->fw.v.size() == included.rows.size()) return PGH_OK;
+    RC(compute(c, first_slots(n).data(), (int)n));
+    c->fw.validate(n);
+    return PGH_OK;
+}
+
+// the included rows alone, fold client k = the k-th of them; the rule supplies the divisor
+void included_plan(FoldPlan* p, const IncludedRows& included, float divisor) {
+    p->slots = included.rows.data();
+    p->n = (int)included.rows.size();
+    p->total = p->n;
+    p->has_divisor = true;
+    p->divisor = divisor;
+    p->whole_rows = true;
+}
+
+// ---- geometric-median FedAvg: the inner iterations, the final weights -------------------------------------------
 
 int geomed_plane(pgh_ctx* c, hipStream_t s) {  // the iterate plane, -0 until something is written to it
     GeomedState& g = c->geo;
@@ -469,28 +475,21 @@ int geomed_plane(pgh_ctx* c, hipStream_t s) {  // the iterate plane, -0 until so
                : fail(c, PGH_E_HIP, "hipMemsetD32Async of the iterate plane failed");
 }
 
-// The final weights of a close over slots[0, n) in fold order (the included rows into geo.rows, their weights
+// The final weights of a close over slots[0, n) in fold order (the included rows into geo.inc, their weights
 // into the context's, W into geo.W): the inner iterations run whole-shard on the context's stream and are
 // finished when this returns.  PGH_E_STATE with no row included; nothing is launched then.
 int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
     GeomedState& g = c->geo;
     c->fw.stale();  // (the context's weights become this rule's, whatever happens below)
-    RC(c->rowsums.queue(c, slots, n));
-    RC(c->rowsums.wait(c));
     std::vector<int32_t> inc;
-    std::vector<double> D;
-    for (int k = 0; k < n; ++k) {
-        const double ss = c->rowsums.at(slots[k]);
-        if (!std::isfinite(ss)) continue;  // excluded: no fold and no distance pass reads the row
-        inc.push_back(slots[k]);
-        D.push_back(ss);
-    }
+    std::vector<double> D;  // iteration 0's squared distances: the sums
+    RC(finite_rows(c, slots, n, &inc, &D));
     if (inc.empty()) return fail(c, PGH_E_STATE, "geometric median: none of the %d diffs is finite", n);
     const hipStream_t s = c->stream;
     std::vector<float> w(inc.size());
     float W = 0.f, mx = 0.f;
     double obj = 0.0;
-    g.rows = inc;
+    g.inc.rows = inc;
     for (int t = 0;; ++t) {
         if (!geomed_step(D.data(), (int64_t)D.size(), g.nu, w.data(), &W, &obj, &mx))
             return fail(c, PGH_E_STATE, "geometric median: no finite distance in iteration %d", t);
@@ -510,24 +509,17 @@ int geomed_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
         fa.len = c->pg;
         fa.plain = true;
         RC(fold_listed(c, PGH_GEOMETRIC_MEDIAN, inc.data(), inc.size(), true, fa, s));
-        RC(c->rowsums.distsq(c, inc, g.d_negv.as<float>(), s, D.data()));
+        RC(c->rowsums.run_listed(c, ROW_DISTSQ, inc, g.d_negv.as<float>(), s, D.data()));
     }
     g.W = W;
-    g.n_rows = n;
-    g.n_excluded = n - (int64_t)inc.size();
+    g.inc.n_rows = n;
+    g.inc.n_excluded = n - (int64_t)inc.size();
+    g.inc.max_weight = mx;
     g.objective = obj;
-    g.max_weight = mx;
     return PGH_OK;
 }
 
-int geomed_resident_weights(pgh_ctx* c, int64_t n) {  // clients [0, n) in slots [0, n), once per slab state
-    if (c->fw.valid(FoldWeights::GEOMED, n) && c->fw.v.size() == c->geo.rows.size()) return PGH_OK;
-    RC(geomed_slot_weights(c, first_slots(n).data(), (int)n));
-    c->fw.validate(n);
-    return PGH_OK;
-}
-
-// ---- trust-bootstrapped FedAvg: the included rows and their weights ---------------------------------------------
+// ---- trust-bootstrapped FedAvg: the planes and the weights --------------------------------------------------------
 
 // a float [pvec] plane of the trust rule at the context's present length, zeroed when it is (re)allocated
 int trust_plane(pgh_ctx* c, DeviceBuf* d, hipStream_t s) {
@@ -542,71 +534,42 @@ int trust_plane(pgh_ctx* c, DeviceBuf* d, hipStream_t s) {
     return PGH_OK;
 }
 
-// The weights of a close over slots[0, n) in fold order (the included rows into trust.rows, their weights into
+// The weights of a close over slots[0, n) in fold order (the included rows into trust.inc, their weights into
 // the context's): K7 for the sums still missing, K14 for the included rows' dots still missing, the host step.
 // PGH_E_STATE with no row included or none trusted; no fold is launched then.
 int trust_slot_weights(pgh_ctx* c, const int32_t* slots, int n) {
     TrustState& t = c->trust;
     c->fw.stale();  // (the context's weights become this rule's, whatever happens below)
-    RC(c->rowsums.queue(c, slots, n));
-    RC(c->rowsums.wait(c));
     std::vector<int32_t> inc;
-    std::vector<double> ss((size_t)n), dot((size_t)n, 0.0);
-    for (int k = 0; k < n; ++k) {
-        ss[(size_t)k] = c->rowsums.at(slots[k]);
-        if (std::isfinite(ss[(size_t)k])) inc.push_back(slots[k]);  // else excluded: no fold and no K14 pass of the close reads the row
-    }
+    std::vector<double> ss;
+    RC(finite_rows(c, slots, n, &inc, &ss));
     if (inc.empty()) return fail(c, PGH_E_STATE, "trusted mean: none of the %d diffs is finite", n);
-    RC(c->rowsums.queue_dots(c, inc.data(), (int)inc.size(), t.d_root.as<float>()));
+    const int64_t ni = (int64_t)inc.size();
+    RC(queue_dots(c, inc.data(), (int)ni));
     RC(c->rowsums.wait(c));
-    for (int k = 0; k < n; ++k)
-        if (std::isfinite(ss[(size_t)k])) dot[(size_t)k] = c->rowsums.dot_at(slots[k]);
-    std::vector<float> w(inc.size());
-    std::vector<int32_t> pos((size_t)n);
-    int64_t ni = 0, nt = 0;
+    std::vector<double> dot((size_t)ni);
+    for (int64_t k = 0; k < ni; ++k) dot[(size_t)k] = c->rowsums.dot_at(inc[(size_t)k]);
+    // the host step over the included rows alone: it includes every one of them (pos = 0 .. ni - 1)
+    std::vector<float> w((size_t)ni);
+    std::vector<int32_t> pos((size_t)ni);
+    int64_t n_pos = 0, nt = 0;
     double T = 0.0;
     float mx = 0.f;
-    const int rc = trust_weights(t.s0, ss.data(), dot.data(), n, w.data(), pos.data(), &ni, &T, &nt, &mx);
-    t.n_rows = n;
-    t.n_excluded = n - ni;
+    const int rc = trust_weights(t.s0, ss.data(), dot.data(), ni, w.data(), pos.data(), &n_pos, &T, &nt, &mx);
+    t.inc.n_rows = n;
+    t.inc.n_excluded = n - ni;
+    t.inc.max_weight = mx;
+    t.inc.rows = inc;
     t.n_trusted = nt;
     t.total_trust = T;
-    t.max_weight = mx;
-    t.rows = inc;
     if (rc == -3) return fail(c, PGH_E_STATE, "trusted mean: none of the %lld finite diffs points along the root (T = 0)", (long long)ni);
     if (rc != 0) return fail(c, PGH_E_STATE, "trusted mean: the host step refused the sums (%d)", rc);
     c->fw.replace(FoldWeights::TRUST) = w;
     return PGH_OK;
 }
-
-int trust_resident_weights(pgh_ctx* c, int64_t n) {  // clients [0, n) in slots [0, n), once per slab state and root
-    if (c->fw.valid(FoldWeights::TRUST, n) && c->fw.v.size() == c->trust.rows.size()) return PGH_OK;
-    RC(trust_slot_weights(c, first_slots(n).data(), (int)n));
-    c->fw.validate(n);
-    return PGH_OK;
-}
 }  // namespace
 
 // ---- the fold plans: what the drivers ask before their launches ------------------------------------------------
-
-namespace {
-void geomed_plan(pgh_ctx* c, FoldPlan* p) {  // the included rows alone, fold client k = the k-th of them
-    p->slots = c->geo.rows.data();
-    p->n = (int)c->geo.rows.size();
-    p->total = p->n;
-    p->has_divisor = true;
-    p->divisor = c->geo.W;
-    p->whole_rows = true;
-}
-void trust_plan(pgh_ctx* c, FoldPlan* p) {  // the included rows alone; the weights carry the normalisation
-    p->slots = c->trust.rows.data();
-    p->n = (int)c->trust.rows.size();
-    p->total = p->n;
-    p->has_divisor = true;
-    p->divisor = 1.0f;
-    p->whole_rows = true;
-}
-}  // namespace
 
 int rules_slot_plan(pgh_ctx* c, int mode, const int32_t* slots, int n, int64_t c0, FoldPlan* p) {
     *p = FoldPlan{slots, n, c0 + n};
@@ -618,11 +581,11 @@ int rules_slot_plan(pgh_ctx* c, int mode, const int32_t* slots, int n, int64_t c
     }
     if (mode == PGH_GEOMETRIC_MEDIAN) {
         RC(geomed_slot_weights(c, slots, n));
-        geomed_plan(c, p);
+        included_plan(p, c->geo.inc, c->geo.W);
     }
-    if (mode == PGH_TRUSTED_MEAN) {
+    if (mode == PGH_TRUSTED_MEAN) {  // the weights carry the normalisation
         RC(trust_slot_weights(c, slots, n));
-        trust_plan(c, p);
+        included_plan(p, c->trust.inc, 1.0f);
     }
     return PGH_OK;
 }
@@ -635,12 +598,12 @@ int rules_resident_plan(pgh_ctx* c, int mode, int64_t c0, int64_t n, FoldPlan* p
         return resident_clip_scales(c, n);
     }
     if (mode == PGH_GEOMETRIC_MEDIAN) {
-        RC(geomed_resident_weights(c, n));
-        geomed_plan(c, p);
+        RC(resident_weights(c, FoldWeights::GEOMED, c->geo.inc, n, geomed_slot_weights));
+        included_plan(p, c->geo.inc, c->geo.W);
     }
     if (mode == PGH_TRUSTED_MEAN) {
-        RC(trust_resident_weights(c, n));
-        trust_plan(c, p);
+        RC(resident_weights(c, FoldWeights::TRUST, c->trust.inc, n, trust_slot_weights));
+        included_plan(p, c->trust.inc, 1.0f);
     }
     return PGH_OK;
 }
@@ -726,7 +689,7 @@ int pgh_row_sumsq(pgh_ctx* c, const int32_t* slots, int n, double* out) {
     if (n < 0 || (n > 0 && !slots)) return fail(c, PGH_E_ARG, "bad slot list (n=%d)", n);
     RC(check_slot_list(c, slots, n, false));
     DeviceGuard g(c->device);
-    RC(c->rowsums.queue(c, slots, n));
+    RC(queue_sums(c, slots, n));
     if (!out) return PGH_OK;
     RC(c->rowsums.wait(c));
     for (int k = 0; k < n; ++k) out[k] = c->rowsums.at(slots[k]);
@@ -751,8 +714,12 @@ int pgh_set_geomed(pgh_ctx* c, int iters, float nu) {
     return PGH_OK;
 }
 
-int pgh_row_distsq(pgh_ctx* c, const int32_t* slots, int n, const float* point, double* out) {
-    RC(check_clip_ctx(c, "pgh_row_distsq"));
+namespace {
+// pgh_row_distsq and pgh_row_dot: `op` over the listed slots against the caller's point, which goes -- negated
+// for K12, which adds -v -- into the plane that ensure_plane allocates and hands back.
+int row_op_against_point(pgh_ctx* c, const char* who, const RowOp& op, bool negate, int (*ensure_plane)(pgh_ctx*, hipStream_t, float**),
+                         const int32_t* slots, int n, const float* point, double* out) {
+    RC(check_clip_ctx(c, who));
     RC(check_dtype(c, PGH_F32));
     if (n < 0 || (n > 0 && (!slots || !point || !out))) return fail(c, PGH_E_ARG, "bad slot list, point or out (n=%d)", n);
     RC(check_slot_list(c, slots, n, false));
@@ -760,22 +727,35 @@ int pgh_row_distsq(pgh_ctx* c, const int32_t* slots, int n, const float* point, 
     DeviceGuard g(c->device);
     const hipStream_t s = c->stream;
     RC(order_after_ingest(c, s));
-    RC(geomed_plane(c, s));
-    std::vector<float> neg((size_t)c->pg);
-    for (int64_t i = 0; i < c->pg; ++i) neg[(size_t)i] = -point[i];
-    CK(c, hipMemcpyAsync(c->geo.d_negv.as<float>(), neg.data(), 4 * (size_t)c->pg, hipMemcpyHostToDevice, s));
-    CK(c, hipStreamSynchronize(s));  // neg is pageable: the copy has left it
-    return c->rowsums.distsq(c, std::vector<int32_t>(slots, slots + n), c->geo.d_negv.as<float>(), s, out);
+    float* plane = nullptr;
+    RC(ensure_plane(c, s, &plane));
+    std::vector<float> neg;
+    if (negate) {
+        neg.resize((size_t)c->pg);
+        for (int64_t i = 0; i < c->pg; ++i) neg[(size_t)i] = -point[i];
+    }
+    CK(c, hipMemcpyAsync(plane, negate ? neg.data() : point, 4 * (size_t)c->pg, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // neg is pageable and the caller's bytes are free on return: the copy has left them
+    return c->rowsums.run_listed(c, op, std::vector<int32_t>(slots, slots + n), plane, s, out);
+}
+}  // namespace
+
+int pgh_row_distsq(pgh_ctx* c, const int32_t* slots, int n, const float* point, double* out) {
+    return row_op_against_point(c, "pgh_row_distsq", ROW_DISTSQ, true, [](pgh_ctx* c, hipStream_t s, float** plane) {
+        RC(geomed_plane(c, s));
+        *plane = c->geo.d_negv.as<float>();
+        return (int)PGH_OK;
+    }, slots, n, point, out);
 }
 
 int pgh_geomed_stats(pgh_ctx* c, int* iters, int64_t* n_rows, int64_t* n_excluded, double* objective, float* max_weight) {
     if (!c) return PGH_E_ARG;
     if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_geomed_stats: group contexts take no geometric median");
     if (iters) *iters = c->geo.iters;
-    if (n_rows) *n_rows = c->geo.n_rows;
-    if (n_excluded) *n_excluded = c->geo.n_excluded;
+    if (n_rows) *n_rows = c->geo.inc.n_rows;
+    if (n_excluded) *n_excluded = c->geo.inc.n_excluded;
     if (objective) *objective = c->geo.objective;
-    if (max_weight) *max_weight = c->geo.max_weight;
+    if (max_weight) *max_weight = c->geo.inc.max_weight;
     return PGH_OK;
 }
 
@@ -820,18 +800,11 @@ int pgh_trust_root(pgh_ctx* c, const float* root, size_t nbytes) {
 }
 
 int pgh_row_dot(pgh_ctx* c, const int32_t* slots, int n, const float* point, double* out) {
-    RC(check_clip_ctx(c, "pgh_row_dot"));
-    RC(check_dtype(c, PGH_F32));
-    if (n < 0 || (n > 0 && (!slots || !point || !out))) return fail(c, PGH_E_ARG, "bad slot list, point or out (n=%d)", n);
-    RC(check_slot_list(c, slots, n, false));
-    if (n == 0) return PGH_OK;
-    DeviceGuard g(c->device);
-    const hipStream_t s = c->stream;
-    RC(order_after_ingest(c, s));
-    RC(trust_plane(c, &c->trust.d_point, s));
-    CK(c, hipMemcpyAsync(c->trust.d_point.as<float>(), point, 4 * (size_t)c->pg, hipMemcpyHostToDevice, s));
-    CK(c, hipStreamSynchronize(s));  // the caller's bytes are free on return
-    return c->rowsums.dots(c, std::vector<int32_t>(slots, slots + n), c->trust.d_point.as<float>(), s, out);
+    return row_op_against_point(c, "pgh_row_dot", ROW_DOT, false, [](pgh_ctx* c, hipStream_t s, float** plane) {
+        RC(trust_plane(c, &c->trust.d_point, s));
+        *plane = c->trust.d_point.as<float>();
+        return (int)PGH_OK;
+    }, slots, n, point, out);
 }
 
 int pgh_trust_weights_host(double s0, const double* sumsq, const double* dot, int n, float* weights, int32_t* included,
@@ -854,11 +827,11 @@ int pgh_trust_stats(pgh_ctx* c, int* on, int64_t* n_rows, int64_t* n_excluded, i
     if (!c) return PGH_E_ARG;
     if (c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_trust_stats: group contexts take no trusted mean");
     if (on) *on = c->trust.on ? 1 : 0;
-    if (n_rows) *n_rows = c->trust.n_rows;
-    if (n_excluded) *n_excluded = c->trust.n_excluded;
+    if (n_rows) *n_rows = c->trust.inc.n_rows;
+    if (n_excluded) *n_excluded = c->trust.inc.n_excluded;
     if (n_trusted) *n_trusted = c->trust.n_trusted;
     if (total_trust) *total_trust = c->trust.total_trust;
-    if (max_weight) *max_weight = c->trust.max_weight;
+    if (max_weight) *max_weight = c->trust.inc.max_weight;
     if (root_norm) *root_norm = c->trust.root_valid ? std::sqrt(c->trust.s0) : 0.0;
     return PGH_OK;
 }
@@ -906,11 +879,8 @@ int pgh_krum_select(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32
     RC(check_pair_list(c, "pgh_krum_select", slots, n, true));
     if (f < 0 || m < 0 || !picked || !n_picked) return fail(c, PGH_E_ARG, "pgh_krum_select: bad arguments (f=%d, m=%d)", f, m);
     DeviceGuard g(c->device);
-    RC(c->rowsums.queue(c, slots, n));
-    RC(c->rowsums.wait(c));
     std::vector<int32_t> inc;
-    for (int k = 0; k < n; ++k)
-        if (std::isfinite(c->rowsums.at(slots[k]))) inc.push_back(slots[k]);  // else excluded: no distance pass reads the row
+    RC(finite_rows(c, slots, n, &inc, nullptr));
     const int ni = (int)inc.size();
     if ((int64_t)ni < 2 * (int64_t)f + 3 || m > ni - f)  // (nothing is launched)
         return fail(c, PGH_E_STATE, "Multi-Krum with f = %d, m = %d: %d of the %d diffs are finite, it needs at least 2f + 3 = %d and m <= n' - f", f, m, ni, n, 2 * f + 3);

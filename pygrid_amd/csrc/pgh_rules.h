@@ -1,8 +1,9 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trust, krum, trim, med and opt, and what they share: the row
-// sums (RowSums, rowsums), the fold's weights (FoldWeights, fw) and the -0 plane (NegZeroPlane, nz).  Their owners
-// release with the context.
-// The code that works on them: pgh_rules.cpp (clip, geo, trim, med and the lifecycle calls rules_*),
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trust, krum, trim, med and opt, and what they share:
+// the row reductions and their two per-slot caches (RowSums, rowsums; a cache is a RowCache), the rows a
+// row-wise rule includes (IncludedRows, in geo and trust), the fold's weights (FoldWeights, fw) and the -0 plane
+// (NegZeroPlane, nz).  Their owners release with the context.
+// The code that works on them: pgh_rules.cpp (every rule, the noise and the lifecycle calls rules_*),
 // pgh_serveropt.cpp (opt).  Not installed.
 #pragma once
 #include <algorithm>
@@ -12,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "pgh_host.h"
 #include "pgh_kernels.h"
 #include "pgh_res.h"
 
@@ -19,95 +21,83 @@ struct pgh_ctx;
 
 namespace pgh_detail {
 
-// What the row-wise rules share (clipping, the geometric median and the Multi-Krum selection today): the per-slot cache of K7's sums of
-// squares and everything device-side that the row reductions (K7, K12, K13) need.  K7 (k_row_sumsq) runs on the
-// copy stream -- behind the row's ingest, ahead of any later overwrite of the slot -- and its sum comes back
-// through h_sq in a small D2H on the same stream, followed by ev.  K12 runs on the stream its caller gives and
-// its sums come back through h_dist behind a wait.  A slot's state: NONE (no sum of the slot's present diff),
-// QUEUED (K7 + D2H issued, the value lands in h_sq before the latest ev), VALID (at() holds it).  Any ingest
-// into a slot resets it.  The methods are in pgh_rules.cpp.
-struct RowSums {
-    enum : uint8_t { NONE = 0, QUEUED = 1, VALID = 2 };
-    std::vector<uint8_t> state;     // per slot
-    std::vector<double> value;      // per slot: the cached sum of squares
-    std::vector<int32_t> queued;    // slots that went QUEUED since the last harvest
-    DeviceBuf d_part;               // double [slots][ceil(pg / SUMSQ_TILE)] tile partials, K7's and K12's
-    DeviceBuf d_sq, d_dist;         // double [slots]: K7's sums; K12's, by slab row
-    PinnedBuf h_sq, h_dist;         // double [slots]
+// One per-slot cache of a row reduction: the state machine (SlotCache, pgh_host.h) with the device buffer its
+// kernel writes, by slab row, the pinned image the D2H behind the kernel fills, and the event recorded behind
+// that D2H.  `what` names the values in an allocation error.
+struct RowCache : SlotCache {
+    const char* what;
+    DeviceBuf d;   // double [slots]
+    PinnedBuf h;   // double [slots]
     Event ev;
+    explicit RowCache(const char* w) : what(w) {}
+    bool alloc(size_t slots) { return d.reserve(8 * slots) && h.reserve(8 * slots); }
+    // What the values were computed against changed or went.  A kernel still in flight is waited for first, so
+    // that "nothing queued" keeps meaning "nobody writes the shared tile partials" for RowSums::wait's callers.
+    void stale() {
+        if (anything_queued()) (void)hipEventSynchronize(ev);
+        all_stale();
+    }
+    void slab_freed() {  // the streams are idle
+        d.reset();
+        h.reset();
+        clear();
+    }
+};
+
+struct RowOp;  // a row reduction against a plane: its launcher and its bytes per tile (pgh_rules.cpp)
+
+// What the row-wise rules share (clipping, the geometric median, the Multi-Krum selection, the trust rule): two
+// per-slot caches -- `sq`, K7's sums of squares, and `dot`, K14's inner products with the cycle's trust root --
+// and everything device-side that the row reductions (K7, K12, K13, K14) need.  A cached reduction runs on the
+// copy stream (queue_cached): behind the row's ingest, ahead of any later overwrite of the slot, and K14 behind
+// the row's K7, since all of them write the one set of tile partials and one stream orders them.  Its values
+// come back through the cache's pinned image in a small D2H on the same stream, followed by the cache's event.
+// An ingest into a slot resets its entry in both caches (slot_written); a new root resets every dot
+// (dots_stale).  An uncached reduction (run_listed: K12, or K14 against another plane) runs on the stream its
+// caller gives, after a wait, and its sums come back through d_dist / h_dist: the caches stay as they are.
+// sq's buffers come with the tile partials, all three or none (ensure); dot's with the first queued K14.
+// The methods are in pgh_rules.cpp.
+struct RowSums {
+    RowCache sq{"clipping sums"}, dot{"trust rule's dots"};
+    DeviceBuf d_part;               // double [slots][ceil(pg / SUMSQ_TILE)] tile partials, K7's, K12's and K14's
+    DeviceBuf d_dist;               // double [slots]: an uncached reduction's sums, by slab row
+    PinnedBuf h_dist;
     // K13's (Multi-Krum's pairwise distances), allocated by the first pgh_row_pairdist / pgh_krum_select: the
     // tile partials of one batch of anchors, at most pair_budget bytes whatever n and the model; the n x n
     // matrix; the listed slab rows as a device table
     DeviceBuf d_pair_part, d_pair, d_pair_rows;
     size_t pair_budget = (size_t)1 << 30;  // PGH_PAIRDIST_BUDGET (bytes) lowers it, for tests of the batching
-    // K14's (the trust rule's inner products with the cycle's root): a second per-slot cache with K7's state
-    // machine.  A queued K14 runs on the copy stream behind the row's K7 -- it shares d_part, one stream orders
-    // the two -- and its dot comes back through h_dot, followed by ev_dot.  An ingest into the slot resets its
-    // entry (slot_written), a new root resets them all (dots_stale).  d_dot / h_dot are allocated by the first
-    // queue_dots.
-    std::vector<uint8_t> dot_state;
-    std::vector<double> dot_value;
-    std::vector<int32_t> dot_queued;
-    DeviceBuf d_dot;                // double [slots], by slab row
-    PinnedBuf h_dot;
-    Event ev_dot;
 
-    double at(int slot) const { return value[(size_t)slot]; }  // after wait(): the sum of a slot queued before it
-    double dot_at(int slot) const { return dot_value[(size_t)slot]; }  // after wait(): the dot, likewise
+    double at(int slot) const { return sq.at(slot); }       // after wait(): the sum of a slot queued before it
+    double dot_at(int slot) const { return dot.at(slot); }  // after wait(): the dot, likewise
     void reserved(int slots) {  // pgh_reserve: the caches at their new length
-        state.assign((size_t)slots, (uint8_t)NONE);
-        value.assign((size_t)slots, 0.0);
-        dot_state.assign((size_t)slots, (uint8_t)NONE);
-        dot_value.assign((size_t)slots, 0.0);
+        for (RowCache* r : {&sq, &dot}) r->reserved(slots);
     }
-    // The diffs in slots [slot, slot + n) are being replaced: their cached sums were the old diffs'.  The one
-    // place a sum goes to NONE slot by slot.
+    // the diffs in slots [slot, slot + n) are being replaced: their cached sums and dots were the old diffs'
     void slot_written(int slot, int n) {
-        std::fill_n(state.begin() + slot, n, (uint8_t)NONE);
-        std::fill_n(dot_state.begin() + slot, n, (uint8_t)NONE);
+        for (RowCache* r : {&sq, &dot}) r->written(slot, n);
     }
-    // The root changed or went: every cached dot was the old root's.  A K14 still in flight is waited for first, so
-    // that "nothing queued" keeps meaning "nobody writes the shared tile partials" for wait()'s callers.
-    void dots_stale() {
-        if (!dot_queued.empty()) (void)hipEventSynchronize(ev_dot);
-        std::fill(dot_state.begin(), dot_state.end(), (uint8_t)NONE);
-        dot_queued.clear();
-    }
+    void dots_stale() { dot.stale(); }  // the root changed or went: every cached dot was the old root's
     void forget() {  // every slot back to NONE (pgh_reset)
-        slot_written(0, (int)state.size());
-        queued.clear();
-        dot_queued.clear();
+        for (RowCache* r : {&sq, &dot}) r->forget();
     }
-    void slab_freed() {  // the streams are idle: every buffer sized by the slab goes, and the cache
-        for (auto* v : {&d_part, &d_sq, &d_dist, &d_pair_part, &d_pair, &d_pair_rows, &d_dot}) v->reset();
-        h_sq.reset();
+    void slab_freed() {  // the streams are idle: every buffer sized by the slab goes, and the caches
+        for (auto* v : {&d_part, &d_dist, &d_pair_part, &d_pair, &d_pair_rows}) v->reset();
         h_dist.reset();
-        h_dot.reset();
-        state.clear();
-        value.clear();
-        queued.clear();
-        dot_state.clear();
-        dot_value.clear();
-        dot_queued.clear();
+        for (RowCache* r : {&sq, &dot}) r->slab_freed();
     }
-    // f(rows, k0, m) for each run of the listed slots a launch can take: all of them when they are consecutive,
-    // else RowTabs of at most ROWTAB_MAX; k0 = the fold index of the run's first row.  (pgh_ctx.h)
-    template <class F>
-    static int for_runs(pgh_ctx* c, const int32_t* slots, size_t n, F&& f);
-    // the kernel arguments of either reduction from the context, the sums going to `sums`
+    // the kernel arguments of any of the reductions from the context, the sums going to `sums`
     pgh::SumsqArgs args(pgh_ctx* c, double* sums) const;
-    int ensure(pgh_ctx* c);  // the tile partials, the sums buffer and its pinned image: all three or none
-    // K7 on the copy stream for those of `slots` that have no sum yet, and the D2H of the sums
-    int queue(pgh_ctx* c, const int32_t* slots, int n);
-    int wait(pgh_ctx* c);  // the queued sums are in at() afterwards, the queued dots in dot_at()
-    // K14 against `root` on the copy stream for those of `slots` that have no dot yet, and the D2H of the dots
-    int queue_dots(pgh_ctx* c, const int32_t* slots, int n, const float* root);
-    // K14 over the listed slots against `plane` on stream s into K12's buffers (the caches stay as they are),
-    // the D2H and the wait: D[k] = the dot of slots[k]
-    int dots(pgh_ctx* c, const std::vector<int32_t>& slots, const float* plane, hipStream_t s, double* D);
-    // K12 over the listed slots against negv on stream s, the D2H of the sums and the wait: D[k] = the squared
-    // distance of slots[k]
-    int distsq(pgh_ctx* c, const std::vector<int32_t>& slots, const float* negv, hipStream_t s, double* D);
+    int ensure(pgh_ctx* c);  // the tile partials, sq's buffer and its pinned image: all three or none
+    // one launch of `op` per run of the listed slots (for_row_runs, pgh_ctx.h) on stream s, the sums to `sums`
+    int launch_rows(pgh_ctx* c, const RowOp& op, const float* plane, const int32_t* slots, size_t n, double* sums, hipStream_t s);
+    // `op` against `plane` (K7 reads none) on the copy stream for those of `slots` that `cache` has no value of
+    // yet, the D2H of the values and the cache's event
+    int queue_cached(pgh_ctx* c, RowCache& cache, const RowOp& op, const float* plane, const int32_t* slots, int n);
+    int wait(pgh_ctx* c);  // nothing is queued afterwards: the queued sums are in at(), the queued dots in dot_at()
+    // `op` over the listed slots against `plane` on stream s through d_dist / h_dist, the D2H and the wait:
+    // D[k] = the sum of slots[k]
+    int run_listed(pgh_ctx* c, const RowOp& op, const std::vector<int32_t>& slots, const float* plane, hipStream_t s, double* D);
     // K13 over the listed slots (n <= PAIRDIST_MAX_ROWS) on stream s in batches of anchors, the D2H and the wait:
     // D[a * n + b] = the squared distance of slots[a] to slots[b], symmetric, +0.0 on the diagonal
     int pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D);
@@ -198,29 +188,37 @@ struct NoiseState {
     }
 };
 
+// The rows of a close that a row-wise rule folds -- those whose K7 sum is finite, in fold order -- and what its
+// last computation of the weights saw of them (pgh_geomed_stats, pgh_trust_stats).
+struct IncludedRows {
+    std::vector<int32_t> rows;  // the included slots, in fold order
+    int64_t n_rows = 0, n_excluded = 0;
+    float max_weight = 0.f;
+    void forget() {
+        rows.clear();
+        n_rows = n_excluded = 0;
+        max_weight = 0.f;
+    }
+};
+
 // Geometric-median FedAvg (pgh_set_geomed, PGH_GEOMETRIC_MEDIAN): the smoothed
 // Weiszfeld iteration.  With the rule on every ingest queues K7 like clipping (RowSums: the cached sums are
 // iteration 0's squared distances and say which rows are excluded).  A close computes the final weights on the
 // context's stream -- per inner iteration a weighted fold against the -0 plane into d_negv (= -v), K12
 // against it, a D2H of the distances, the host step -- and leaves them in the context's FoldWeights (writer
-// GEOMED, fold order of the included rows) for the one FINAL fold, which is the weighted fold over `rows`.
+// GEOMED, fold order of the included rows) for the one FINAL fold, which is the weighted fold over `inc.rows`.
 // The iterate plane is float [pvec], allocated by the first close that iterates (iters >= 2) or by pgh_row_distsq.
 struct GeomedState {
     int iters = 0;                  // 0 = the rule is off
     float nu = 0.f;
-    std::vector<int32_t> rows;      // the included slots, in fold order
+    IncludedRows inc;
     float W = 0.f;                  // the f32 left fold of the final weights
     DeviceBuf d_negv;               // -v of the last inner iteration (or -point)
-    // what the last computation of the weights saw (pgh_geomed_stats)
-    int64_t n_rows = 0, n_excluded = 0;
-    double objective = 0.0;
-    float max_weight = 0.f;
+    double objective = 0.0;         // of the last computation of the weights (pgh_geomed_stats)
 
     void forget() {  // the included rows and the tallies (pgh_reset); the setting stays
-        rows.clear();
-        n_rows = n_excluded = 0;
+        inc.forget();
         objective = 0.0;
-        max_weight = 0.f;
     }
     void release() {  // plane and setting; the caller has waited for the context's work
         d_negv.reset();
@@ -234,7 +232,7 @@ struct GeomedState {
 // With the rule on every ingest queues K7 like clipping, and, while the cycle's root is valid, K14 behind it
 // (RowSums: the cached sums and dots).  A close computes what is missing in one batch, runs the host step
 // (trust_weights, pgh_host.cpp) and leaves the weights in the context's FoldWeights (writer TRUST, fold order of
-// the included rows) for the one FINAL fold, the weighted fold over `rows` with the divisor 1.  The root plane
+// the included rows) for the one FINAL fold, the weighted fold over `inc.rows` with the divisor 1.  The root plane
 // is float [pvec], zero past the root, allocated by the first pgh_trust_root and kept over pgh_reset /
 // pgh_reserve (the validity is not); pgh_row_dot's scratch plane likewise, by its first call.
 struct TrustState {
@@ -243,19 +241,16 @@ struct TrustState {
     double s0 = 0.0;                // K7's sum of squares of the root
     DeviceBuf d_root, d_point;      // float [pvec]
     int64_t pvec = 0;               // the planes' length
-    std::vector<int32_t> rows;      // the included slots, in fold order
-    // what the last computation of the weights saw (pgh_trust_stats)
-    int64_t n_rows = 0, n_excluded = 0, n_trusted = 0;
+    IncludedRows inc;
+    int64_t n_trusted = 0;          // of the last computation of the weights (pgh_trust_stats)
     double total_trust = 0.0;
-    float max_weight = 0.f;
 
     void forget() {  // the cycle's root, the included rows and the tallies (pgh_reset, pgh_reserve); the setting stays
         root_valid = false;
         s0 = 0.0;
-        rows.clear();
-        n_rows = n_excluded = n_trusted = 0;
+        inc.forget();
+        n_trusted = 0;
         total_trust = 0.0;
-        max_weight = 0.f;
     }
     void release() {  // planes and setting; the caller has waited for the context's work
         d_root.reset();

@@ -1,9 +1,11 @@
 """GPU: what the averaging rules' state does at each lifecycle event of a context -- a slot written, the
 weights replaced, a reset, a reserve, slot folds restarted, a shard set, the context made -- for clipping,
-trimming, the median and the geometric median, bit-exact against tests/clip_oracle.py, tests/trim_oracle.py,
-tests/median_oracle.py and tests/geomed_oracle.py; and what the rules share: the fold's weights as clipping, the
-caller and the geometric median write them in turn, and the one plane of -0.0f under the server optimizer, the
-noise (tests/serveropt_oracle.py, tests/dp_oracle.py) and the geometric median's inner folds.
+trimming, the median, the geometric median and the trust rule, bit-exact against tests/clip_oracle.py,
+tests/trim_oracle.py, tests/median_oracle.py, tests/geomed_oracle.py and tests/trust_oracle.py; and what the rules
+share: the two per-slot caches of K7's sums and K14's dots beside the uncached row calls (tests/krum_oracle.py for
+the pairwise distances), the fold's weights as clipping, the caller and the geometric median write them in turn,
+and the one plane of -0.0f under the server optimizer, the noise (tests/serveropt_oracle.py, tests/dp_oracle.py)
+and the geometric median's inner folds.
 (The server optimizer's events: test_gpu_serveropt.py::test_state_lifetime.)
 
     python tests/test_gpu_rule_lifecycle.py median | trimmed     (the child processes)
@@ -23,15 +25,17 @@ if str(ROOT) not in sys.path:
 import clip_oracle as CO  # noqa: E402
 import dp_oracle as DO  # noqa: E402
 import geomed_oracle as GO  # noqa: E402
+import krum_oracle as KO  # noqa: E402
 import median_oracle as MO  # noqa: E402
 import serveropt_oracle as SO  # noqa: E402
 import trim_oracle as TO  # noqa: E402
+import trust_oracle as TR  # noqa: E402
 from gen_trim_golden import special_rows  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-MEAN, WEIGHTED, CLIPPED, TRIMMED, MEDIAN, GEOMED = 0, 2, 3, 4, 5, 6
+MEAN, WEIGHTED, CLIPPED, TRIMMED, MEDIAN, GEOMED, TRUST = 0, 2, 3, 4, 5, 6, 7
 STATE, UNSUPPORTED = -3, -6
 P = 4101  # one full SUMSQ_TILE (4096) and a ragged tile of 5: not a multiple of 4
 BOUND = 1.0
@@ -261,6 +265,112 @@ def test_geomed_reset_reserve_shard(eng):
         assert np.array_equal(u32(eng.fedavg(GEOMED, ckpt)), u32(GO.fedavg_geomed(ckpt, diffs[:3], 2, NU)))
     finally:
         eng.set_layout([P])
+
+
+# ---- trust rule: a slot written, the root replaced; the uncached row calls beside the two caches ---------------------
+
+def trust_rows(n, p, seed):
+    """n rows of p floats of mixed length and angle to a root (about a third pointing away, row 1 among them; rows
+    0 and 2 along it), the root and a checkpoint."""
+    rng = np.random.default_rng(seed)
+    root = (rng.standard_normal(p) * 0.3).astype(F)
+    sign = np.where(rng.random(n) < 0.35, -1.0, 1.0)
+    sign[[0, 2]] = 1.0
+    sign[1] = -1.0
+    rows = np.stack([((sign[k] * root + rng.standard_normal(p) * 0.2) * 10.0 ** rng.integers(-1, 2)).astype(F) for k in range(n)])
+    return rows, root, rng.standard_normal(p).astype(F)
+
+
+def trust_saw(eng, rows, root):
+    """trust_stats() is what the oracle gives for these rows and this root: the counts, and T, the largest weight
+    and the root's norm by bits."""
+    st, t = eng.trust_stats(), TR.trust(rows, root)
+    return (st["on"] and st["rows"] == len(rows) and st["excluded"] == t["excluded"] and st["trusted"] == t["trusted"] and
+            u64([st["total_trust"]])[0] == u64([t["T"]])[0] and u32([st["max_weight"]])[0] == u32([t["max_weight"]])[0] and
+            u64([st["root_norm"]])[0] == u64([t["root_norm"]])[0])
+
+
+def test_trust_slot_written(eng):
+    diffs, root, ckpt = trust_rows(6, P, 50)
+    rng = np.random.default_rng(51)
+    other = ((root * F(0.5) + rng.standard_normal(P)) * F(3)).astype(F)  # another norm and angle than the row it replaces
+    diffs2 = diffs.copy()
+    diffs2[2] = other
+    diffs3 = diffs2.copy()
+    diffs3[4, 1234] = np.inf
+    diffs4 = diffs3.copy()
+    diffs4[1] = (root * F(2) - diffs[1]).astype(F)
+    root2 = (root[::-1] * F(0.7) + diffs[0] * F(0.1)).astype(F)
+    eng.set_layout([P])
+    eng.reserve(6)
+    eng.set_trust(True)
+    try:
+        eng.trust_root(root)  # ahead of the ingests: K14 is queued behind each of them
+        for k, d in enumerate(diffs):
+            eng.ingest(k, d)
+        assert np.array_equal(u32(eng.fedavg(TRUST, ckpt)), u32(TR.fedavg_trust(ckpt, diffs, root)))
+        assert trust_saw(eng, diffs, root)
+        # the slot's sum and dot went with its diff and the slab's weights are computed again
+        eng.ingest(2, other)
+        want2 = TR.fedavg_trust(ckpt, diffs2, root)
+        assert not np.array_equal(u32(want2), u32(TR.fedavg_trust(ckpt, diffs, root)))
+        assert np.array_equal(u32(eng.fedavg(TRUST, ckpt)), u32(want2))
+        assert trust_saw(eng, diffs2, root)
+        # a row with one inf: its sum says so, the row is excluded
+        eng.ingest(4, diffs3[4])
+        assert np.array_equal(u32(eng.fedavg(TRUST, ckpt)), u32(TR.fedavg_trust(ckpt, diffs3, root)))
+        assert eng.trust_stats()["excluded"] == 1 and trust_saw(eng, diffs3, root)
+        # the root replaced between a re-ingest and the close: the dot queued behind the ingest was the old root's
+        eng.ingest(1, diffs4[1])
+        eng.trust_root(root2)
+        want4 = TR.fedavg_trust(ckpt, diffs4, root2)
+        assert not np.array_equal(u32(want4), u32(TR.fedavg_trust(ckpt, diffs4, root)))
+        assert np.array_equal(u32(eng.fedavg(TRUST, ckpt)), u32(want4))
+        assert eng.trust_stats()["excluded"] == 1 and trust_saw(eng, diffs4, root2)
+    finally:
+        eng.set_trust(False)
+
+
+@pytest.mark.parametrize("slots", [list(range(33)), [5, 2, 7, 0, 3]], ids=["run33", "scattered5"])
+def test_row_calls_between_ingest_and_close(eng, slots):
+    """p = 4097, n = 33: one param past a tile, one row past a DISTSQ_RC chunk of 32; a scattered list goes to the
+    kernels as a row table.  The uncached calls share the tile partials with the queued K7 and K14 and leave both
+    caches as they were."""
+    p, n = 4097, len(slots)
+    rows, root, ckpt = trust_rows(n, p, 52 + n)
+    point = np.random.default_rng(53).standard_normal(p).astype(F)
+    t = TR.trust(rows, root)
+    want = (ckpt - t["acc"]).astype(F)
+
+    def ingest_all():
+        for k, d in enumerate(rows):
+            eng.ingest(slots[k], d)
+
+    def close():
+        if slots == list(range(n)):
+            return eng.fedavg(TRUST, ckpt)
+        eng.ckpt_upload(ckpt)
+        eng.fold_slots_finish_resident(TRUST, slots)
+        return eng.ckpt_download()
+
+    eng.set_layout([p])
+    eng.reserve(max(slots) + 1)
+    eng.set_trust(True)
+    try:
+        eng.trust_root(root)
+        ingest_all()  # K7 and K14 are queued behind each ingest, and nothing has waited for them
+        assert np.array_equal(u64(eng.row_dot(slots, point)), u64([TR.row_dot(r, point) for r in rows]))
+        assert np.array_equal(u64(eng.row_distsq(slots, point)), u64([GO.row_distsq(r, point) for r in rows]))
+        assert np.array_equal(u64(eng.row_pairdist(slots[:5])), u64(KO.pairdist(rows[:5])))
+        assert np.array_equal(u64(eng.row_sumsq(slots)), u64(t["sumsq"]))
+        assert np.array_equal(u32(close()), u32(want))
+        assert t["excluded"] == 0 and 0 < t["trusted"] < n and trust_saw(eng, rows, root)
+        if slots != list(range(n)):
+            ingest_all()  # (a slot fold frees its slots)
+        assert np.array_equal(u32(close()), u32(want))
+        assert trust_saw(eng, rows, root)
+    finally:
+        eng.set_trust(False)
 
 
 # ---- the fold's weights: clipping, the caller and the geometric median write them in turn ---------------------------
