@@ -59,7 +59,10 @@ typedef enum {
  * pgh_set_geomed; no reference counterpart; defined below).
  * PGH_TRUSTED_MEAN: FLTrust (Cao, Fang, Liu, Gong, NDSS 2021): every diff rescaled to the norm of a server
  * root update and weighted by its clipped cosine to it (pgh_set_trust, pgh_trust_root; no reference
- * counterpart; defined below). */
+ * counterpart; defined below).
+ * PGH_MEAN_AROUND_MEDIAN: per parameter, the mean of the N - c reported values nearest the median ("mean around
+ * the median", Xie, Koyejo, Gupta 2018; the second stage of Bulyan, El Mhamdi, Guerraoui, Rouault, ICML 2018; c
+ * from pgh_set_median_drop; no reference counterpart; defined below). */
 typedef enum {
     PGH_MEAN = 0,
     PGH_ITERATIVE_MEAN = 1,
@@ -70,6 +73,8 @@ typedef enum {
     PGH_GEOMETRIC_MEDIAN = 6,
     PGH_TRUSTED_MEAN = PGH_GEOMETRIC_MEDIAN + 1 /* mode 7 */
 } pgh_mode;
+/* One more averaging mode, taken wherever a pgh_mode is (the enum itself is as ABI 10 first had it). */
+#define PGH_MEAN_AROUND_MEDIAN 8
 /* Stream kind for pgh_stream_begin besides the three averaging modes. */
 #define PGH_STREAM_SECAGG 16
 
@@ -329,6 +334,42 @@ int pgh_set_trim(pgh_ctx* ctx, int b);
  * PGH_MEDIAN) reports 50 or 51 for the diffs currently held; pgh_set_variant does not affect
  * median folds. */
 #define PGH_MEDIAN_NCHIP 1024
+
+/* ---- mean around the median (PGH_MEAN_AROUND_MEDIAN, Bulyan's second stage; kernel K15) --------------
+ * Per parameter, the mean of the beta = N - c values closest to the median; rows x_0 .. x_{N-1} in fold order,
+ * c (the drop count) from pgh_set_median_drop:
+ *   1. m = the PGH_MEDIAN value of the parameter, exactly as defined above (the key order on bit patterns,
+ *      0.5f * a + 0.5f * b for an even N);
+ *   2. the distance key e_k = bits(x_k - m) & 0x7fffffff, compared as uint32: one f32 subtraction, rounded,
+ *      subnormals kept.  Finite distances order by size, +inf comes after them and every NaN (from x_k NaN, m
+ *      NaN or inf - inf) last.  Nothing is sanitised: a parameter whose median is not finite is already lost
+ *      to a hostile majority;
+ *   3. the kept positions are the beta smallest by (e_k, k): equal distances break towards the earlier fold
+ *      position, as Multi-Krum's ties do;
+ *   4. the sum, f64, in one fixed order: fold positions are cut into blocks of 64 (block g: positions 64 g ..
+ *      64 g + 63); s_g = the left fold from +0.0 of (double)x_k over the block's kept positions, ascending k;
+ *      S = the left fold of s_0, s_1, ... starting from s_0; mean = (float)(S / (double)beta), an IEEE f64
+ *      division rounded once more to f32; out = ckpt - mean, one f32 subtraction.  A server optimizer takes
+ *      g = mean.
+ * Example: the column (1, 2, 4, 5) with c = 1 has m = 3 and e = (2, 1, 1, 2) as distances; positions 1, 2 and 0
+ * are kept (0 wins the tie over 3), S = 1 + 2 + 4 and mean = (float)(7.0 / 3.0).
+ * The result is a function of the rows, their order and c alone: it does not depend on the slots, the launch
+ * shape, the slab's block width, the range split or the entry point.  Every kept value lies within the median
+ * +- the largest distance to the median among any N - c rows, so a c of at least the number of hostile rows, a
+ * minority, bounds the result by the spread of the honest rows.
+ *
+ * pgh_set_median_drop: c = 0 turns the setting off, c >= 1 turns it on, c < 0 is PGH_E_ARG; changing c while slot
+ * folds of a cycle are under way is PGH_E_STATE.  A group hands c to its children.  pgh_set_layout and
+ * pgh_set_shard clear the setting, pgh_reset and pgh_reserve keep it.
+ * The mode takes every row of the cycle in one call, like the median: pgh_fedavg, pgh_fedavg_device[_range],
+ * pgh_fedavg_resident and pgh_fold_slots_finish_resident accept it, on shards and groups too (nothing in it
+ * looks along a row); pgh_fold_slots and pgh_stream_begin refuse it (PGH_E_UNSUPPORTED).  The mode with the
+ * setting off is PGH_E_STATE, and so is a close of N <= c diffs, which leaves no value (nothing is launched; the
+ * context stays usable) and the mode beside pgh_set_dp_noise.  N > PGH_MEDIAN_NCHIP is PGH_E_UNSUPPORTED: the
+ * selection runs on chip only (K15).  pgh_effective_variant(ctx, PGH_MEAN_AROUND_MEDIAN) reports 60;
+ * pgh_set_variant does not affect the mode.  Behind pgh_krum_select with keep = n - 2f, c = 2f is Bulyan with
+ * the one-shot Multi-Krum selection as its first stage (not the paper's recursive one). */
+int pgh_set_median_drop(pgh_ctx* ctx, int c);
 
 /* ---- geometric-median FedAvg (PGH_GEOMETRIC_MEDIAN, RFA; kernel K12) ----------------------------
  * The geometric median of the diffs -- the point with the smallest sum of L2 distances to them --

@@ -72,7 +72,7 @@ namespace pgh_detail {
 constexpr int KIND_SECAGG = PGH_STREAM_SECAGG;  // fold kind besides the pgh_mode values (none of which it equals)
 static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KIND_SECAGG != PGH_WEIGHTED_MEAN &&
                   KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN && KIND_SECAGG != PGH_MEDIAN && KIND_SECAGG != PGH_GEOMETRIC_MEDIAN &&
-                  KIND_SECAGG != PGH_TRUSTED_MEAN,
+                  KIND_SECAGG != PGH_TRUSTED_MEAN && KIND_SECAGG != PGH_MEAN_AROUND_MEDIAN,
               "the secagg fold kind must not collide with an averaging mode");
 
 // CPUs on the GPU's own socket (its PCI device's local_cpulist) that this process may run on; empty
@@ -178,6 +178,7 @@ struct pgh_ctx {
     pgh_detail::NoiseState noise;
     pgh_detail::TrimState trim;
     pgh_detail::MedianState med;
+    pgh_detail::MedianMeanState mam;
     pgh_detail::GeomedState geo;
     pgh_detail::TrustState trust;
     pgh_detail::KrumState krum;
@@ -235,11 +236,15 @@ double now_ms();
 inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
 inline bool valid_mode(int m) {  // (pgh_effective_variant's alone: check_mode_use has its own switch)
     return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN ||
-           m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN || m == PGH_GEOMETRIC_MEDIAN || m == PGH_TRUSTED_MEAN;
+           m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN || m == PGH_GEOMETRIC_MEDIAN || m == PGH_TRUSTED_MEAN ||
+           m == PGH_MEAN_AROUND_MEDIAN;
 }
+// A coordinate rule that takes every row of the cycle in one launch: the median, the mean around it.
+inline bool whole_cycle_coordinate_rule(int m) { return m == PGH_MEDIAN || m == PGH_MEAN_AROUND_MEDIAN; }
 static_assert(PGH_TRUSTED_MEAN == 7, "the mode numbers are ABI: engine.py and every caller hold them as integers");
 static_assert(PGH_TRIMMED_MEAN == pgh::MODE_TRIMMED && PGH_TRIM_MAX == pgh::TRIM_MAX, "the kernels' numbering");
 static_assert(PGH_MEDIAN == pgh::MODE_MEDIAN && PGH_MEDIAN_NCHIP == pgh::MEDIAN_NCHIP, "the kernels' numbering");
+static_assert(PGH_MEAN_AROUND_MEDIAN == 8 && PGH_MEAN_AROUND_MEDIAN == pgh::MODE_MEAN_AROUND_MEDIAN, "the mode numbers are ABI; the kernels' numbering");
 // The kernels' mode: a clipped mean is the weighted fold with the scales as weights, a geometric median the
 // weighted fold with the last Weiszfeld weights, a trusted mean the weighted fold with the trust weights.
 inline int kernel_mode(int m) {
@@ -407,7 +412,7 @@ struct FoldPlan {
 };
 int rules_slot_plan(pgh_ctx* c, int mode, const int32_t* slots, int n, int64_t c0, FoldPlan* p);  // slot_fold
 int rules_resident_plan(pgh_ctx* c, int mode, int64_t c0, int64_t n, FoldPlan* p);                // fold_run
-// A rule that closes a cycle in one slot fold only (median, geometric median, trusted mean): its name for the refusal; else null.
+// A rule that closes a cycle in one slot fold only (median, mean around the median, geometric median, trusted mean): its name for the refusal; else null.
 const char* rules_one_fold_cycle(int mode);
 int trim_divisor(pgh_ctx* c, int64_t n, float* div);  // n - 2b; PGH_E_STATE with fewer than 2b + 1 diffs
 
@@ -475,6 +480,13 @@ int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hip
 // slots[k] * parties for k < n, uploaded to d_rowidx on stream s (waits for the copy)
 int median_row_table(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s);
 inline const int32_t* median_rows(const pgh_ctx* c) { return c->med.d_rowidx.as<int32_t>(); }  // that table
+
+// ---- mean around the median (pgh_rules.cpp) -----------------------------------------------------------
+// The whole fold of a filled FedavgArgs (diffs, map, n_rows, p, ckpt, out; every row of the cycle) on stream s:
+// K15's one launch over the n_rows - drop values nearest the median.
+int median_mean_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hipStream_t s);
+// n - drop as the FINAL divisor; PGH_E_STATE with n <= drop, PGH_E_UNSUPPORTED past PGH_MEDIAN_NCHIP rows
+int median_mean_divisor(pgh_ctx* c, int64_t n, float* div);
 
 // ---- server optimizer (pgh_serveropt.cpp) --------------------------------------------------------------
 struct FinalArgs;

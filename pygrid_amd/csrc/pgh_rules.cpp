@@ -2,7 +2,7 @@
 // reductions (RowSums: K7 and K14 through their per-slot caches, K12 and K14 over a listed set of rows, K13) and
 // the Multi-Krum selection over them; clipping's scales and tallies; the Gaussian noise on the clipped close (K11
 // behind a FINAL launch, its plane, setting and entry points); the trimmed mean's state planes (K8); the
-// median's driver and row table (K9, K9p); what the geometric median and the trust rule share (the finite rows
+// median's driver and row table (K9, K9p); the mean around the median's driver (K15); what the geometric median and the trust rule share (the finite rows
 // of a close, the resident weights, the plan over the included rows) and each one's own: the inner iterations
 // and final weights (K12 between weighted folds), the root and the weights from the cached dots; the context's
 // -0 plane; what the rules' state does at each lifecycle event of the context (rules_*: the one call each
@@ -67,6 +67,10 @@ int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
         return PGH_OK;
     case PGH_MEDIAN:
         return one_fold_cycle_use(c, mode, use, false);
+    case PGH_MEAN_AROUND_MEDIAN:
+        RC(one_fold_cycle_use(c, mode, use, false));
+        if (!c->grp && c->mam.drop == 0) return fail(c, PGH_E_STATE, "PGH_MEAN_AROUND_MEDIAN needs a drop count: call pgh_set_median_drop first");
+        return PGH_OK;
     case PGH_GEOMETRIC_MEDIAN:
         RC(one_fold_cycle_use(c, mode, use, true));
         if (c->geo.iters == 0) return fail(c, PGH_E_STATE, "PGH_GEOMETRIC_MEDIAN needs its setting: call pgh_set_geomed first");
@@ -112,6 +116,7 @@ void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep
     if (!(same_shard && pvec == c->pvec)) c->nz.d.reset();     // (its tenants above and below are gone with it)
     if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
     c->geo.release();  // (free_slab has dropped the plane; the setting goes with the layout or shard)
+    if (!keep_opt) c->mam.drop = 0;  // (a group's pgh_reserve lays its children out again: the setting stays)
     c->trust.release();
 }
 
@@ -148,7 +153,7 @@ int rules_row_ingested(pgh_ctx* c, int slot) {
 }
 
 const char* rules_one_fold_cycle(int mode) {
-    return mode == PGH_MEDIAN ? "a median" : mode == PGH_GEOMETRIC_MEDIAN ? "a geometric median" : mode == PGH_TRUSTED_MEAN ? "a trusted mean" : nullptr;
+    return mode == PGH_MEDIAN ? "a median" : mode == PGH_MEAN_AROUND_MEDIAN ? "a mean around the median" : mode == PGH_GEOMETRIC_MEDIAN ? "a geometric median" : mode == PGH_TRUSTED_MEAN ? "a trusted mean" : nullptr;
 }
 
 int NegZeroPlane::ensure(pgh_ctx* c, hipStream_t s) {
@@ -211,6 +216,33 @@ int median_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hip
         const uint64_t bytes = slab + (bit == 31 ? 0 : 4 * rp) + (bit == last ? 8 * rp : 4 * rp);
         RC(timed_launch(c, s, bytes, [&] { return pgh::launch_median_pass(m, rows, bit, s); }));
     }
+    return PGH_OK;
+}
+
+// ---- mean around the median: the fold's launch (K15) ---------------------------------------------------------
+
+int median_mean_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hipStream_t s) {
+    pgh::MedianMeanArgs m{};
+    m.diffs = a.diffs;
+    m.map = a.map;
+    m.n_rows = a.n_rows;
+    m.keep = a.n_rows - c->mam.drop;
+    m.p = a.p;
+    m.ckpt = a.ckpt;
+    m.out = a.out;
+    if (m.keep < 1 || a.n_rows > pgh::MEDIAN_NCHIP)  // (median_mean_divisor has refused both at the entry points)
+        return fail(c, PGH_E_STATE, "mean around the median: %d rows with a drop count of %d", a.n_rows, c->mam.drop);
+    // the slab once, ckpt in, out
+    return timed_launch(c, s, 4ull * (uint64_t)a.n_rows * (uint64_t)a.p + 8 * (uint64_t)a.p, [&] { return pgh::launch_median_mean(m, rows, s); });
+}
+
+int median_mean_divisor(pgh_ctx* c, int64_t n, float* div) {
+    if (n <= (int64_t)c->mam.drop)
+        return fail(c, PGH_E_STATE, "mean around the median with a drop count of %d needs at least %d diffs, have %lld", c->mam.drop,
+                    c->mam.drop + 1, (long long)n);
+    if (n > pgh::MEDIAN_NCHIP)
+        return fail(c, PGH_E_UNSUPPORTED, "mean around the median: %lld diffs, the on-chip kernel takes %d", (long long)n, pgh::MEDIAN_NCHIP);
+    *div = (float)(n - (int64_t)c->mam.drop);
     return PGH_OK;
 }
 
@@ -679,6 +711,17 @@ int pgh_set_trim(pgh_ctx* c, int b) {
         return fail(c, PGH_E_STATE, "trim count changed from %d to %d with %lld diffs of the cycle folded", c->trim.b, b,
                     (long long)c->folded);
     c->trim.b = b;
+    return PGH_OK;
+}
+
+int pgh_set_median_drop(pgh_ctx* c, int drop) {
+    if (!c) return PGH_E_ARG;
+    if (drop < 0) return fail(c, PGH_E_ARG, "drop count %d is negative", drop);
+    if (c->grp) return pgh_group_api::set_median_drop(c, drop);
+    if (drop != c->mam.drop && c->folded > 0 && !c->streaming)
+        return fail(c, PGH_E_STATE, "drop count changed from %d to %d with %lld diffs of the cycle folded", c->mam.drop, drop,
+                    (long long)c->folded);
+    c->mam.drop = drop;
     return PGH_OK;
 }
 

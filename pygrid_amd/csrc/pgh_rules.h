@@ -1,5 +1,5 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trust, krum, trim, med and opt, and what they share:
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trust, krum, trim, med, mam and opt, and what they share:
 // the row reductions and their two per-slot caches (RowSums, rowsums; a cache is a RowCache), the rows a
 // row-wise rule includes (IncludedRows, in geo and trust), the fold's weights (FoldWeights, fw) and the -0 plane
 // (NegZeroPlane, nz).  Their owners release with the context.
@@ -15,6 +15,7 @@
 
 #include "pgh_host.h"
 #include "pgh_kernels.h"
+#include "pgh_median_mean.h"
 #include "pgh_res.h"
 
 struct pgh_ctx;
@@ -286,6 +287,13 @@ struct MedianState {
     bool passes = false;  // PGH_MEDIAN_PATH=passes: K9p whatever the row count
     DeviceBuf d_prefix;   // uint32 [pvec]
     DeviceBuf d_rowidx;   // int32 [slots]
+};
+
+// Mean around the median (pgh_set_median_drop, PGH_MEAN_AROUND_MEDIAN): the drop count.
+// K15 keeps everything on chip; a slot list longer than a RowTab goes to it through the median's device table.
+// The setting belongs to the model: pgh_reset / pgh_reserve keep it, a new layout or shard clears it.
+struct MedianMeanState {
+    int drop = 0;  // values dropped per parameter, the farthest from the median; 0 = the rule is off
 };
 
 // Server optimizer (pgh_set_server_opt).  With one set, fold_launch runs every

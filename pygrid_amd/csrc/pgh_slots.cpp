@@ -21,7 +21,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
     const char* const one_fold = rules_one_fold_cycle(mode);
     if (one_fold && c->folded > 0)
         return fail(c, PGH_E_STATE, "%s closes a cycle without earlier slot folds (%lld diffs folded)", one_fold, (long long)c->folded);
-    const bool median = mode == PGH_MEDIAN;
+    const bool median = whole_cycle_coordinate_rule(mode);  // every row in one launch, through a device table past a RowTab
     const int64_t c0 = c->folded, total = c0 + n;
     FinalArgs fa;
     fa.ckpt = c->d_ckpt.as<float>();
@@ -61,7 +61,7 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         for (int k = 0; k < std::min(m, pgh::ROWTAB_MAX); ++k) tab.rows[k] = slots[done + k] * c->parties;
         const bool first = (c0 + done == 0), last = (done + m == n);
         const int flags = (first ? pgh::FL_FIRST : 0) | (final && last ? pgh::FL_FINAL : 0);
-        // (only a median comes with more rows than the table carries: they are in the device table then)
+        // (only a whole-cycle coordinate rule comes with more rows than the table carries: they are in the device table then)
         FoldRows rows{c->d_slab.as<float>(), m};
         if (m <= pgh::ROWTAB_MAX) rows.src.tab = &tab;
         else rows.src.d_rows = median_rows(c);

@@ -16,6 +16,7 @@ from . import _lib
 from .exceptions import AggregationError, EngineUnavailableError, StateParseError
 
 MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN, GEOMETRIC_MEDIAN, TRUSTED_MEAN = 0, 1, 2, 3, 4, 5, 6, 7
+MEAN_AROUND_MEDIAN = 8  # PGH_MEAN_AROUND_MEDIAN
 GEOMED_MAX_ITERS = 16  # PGH_GEOMED_MAX_ITERS
 KRUM_MAX_ROWS = 1024   # PGH_KRUM_MAX_ROWS
 TRIM_MAX = 8  # PGH_TRIM_MAX
@@ -26,7 +27,8 @@ F32, I64 = 0, 1
 OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4  # pgh_server_opt
 MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
               CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean", MEDIAN: "median",
-              GEOMETRIC_MEDIAN: "geometric_median", TRUSTED_MEAN: "trusted_mean"}
+              GEOMETRIC_MEDIAN: "geometric_median", TRUSTED_MEAN: "trusted_mean",
+              MEAN_AROUND_MEDIAN: "mean_around_median"}
 
 
 def device_count() -> int:
@@ -489,6 +491,13 @@ class Engine:
         trimming off.  Refused (PGH_E_STATE) while slot folds of a cycle are under way."""
         self._check(self._lib.pgh_set_trim(self._h, int(b)), "set_trim")
 
+    # ---- mean around the median (MEAN_AROUND_MEDIAN, Bulyan's second stage; kernel K15) --------------
+    def set_median_drop(self, c: int):
+        """Values dropped per parameter, the farthest from the median, by later MEAN_AROUND_MEDIAN closes
+        (``include/pgh_api.h``); 0 turns the setting off.  Refused (PGH_E_STATE) while slot folds of a cycle
+        are under way."""
+        self._check(self._lib.pgh_set_median_drop(self._h, int(c)), "set_median_drop")
+
     # ---- server optimizers (FedAvgM, FedAdagrad, FedAdam, FedYogi) ---------------------------------
     def set_server_opt(self, kind: int, lr: float = 0.0, beta1: float = 0.0, beta2: float = 0.0, tau: float = 0.0):
         """How later fp32 closes apply the average (``pgh_set_server_opt``): OPT_MOMENTUM .. OPT_YOGI,
@@ -689,7 +698,7 @@ class Engine:
     def effective_variant(self, mode: int = MEAN) -> int:
         """Kernel variant the next fold runs for ``mode`` (MEAN / ITERATIVE_MEAN / WEIGHTED_MEAN /
         STREAM_SECAGG; TRIMMED_MEAN: 40 for 16-byte columns, 41 for one parameter per lane; MEDIAN: 50
-        for the on-chip kernel, 51 for one pass per key bit, by the diffs held now)."""
+        for the on-chip kernel, 51 for one pass per key bit, by the diffs held now; MEAN_AROUND_MEDIAN: 60)."""
         v = self._lib.pgh_effective_variant(self._h, int(mode))
         self._check(min(v, 0), "effective_variant")
         return v

@@ -60,6 +60,15 @@ class MedianUnavailableError(AggregationError):
     no median, so the close fails closed."""
 
 
+class MeanAroundMedianUnavailableError(AggregationError):
+    """The FL process asks for the mean around the median (``server_config["diff_mean_around_median"]``, or
+    Bulyan, ``server_config["diff_bulyan"]``, which ends in it) and the engine cannot take it this cycle: a hosted
+    iterative or unaccelerated plan, a non-float32 model, aggregation weights or another rule given together
+    with it, more diffs at the close than the slab has slots or than the on-chip kernel takes (1,024), no more
+    diffs than the drop count, or, for Bulyan, fewer than ``4 f + 3`` diffs.  Like the other rules' errors it is
+    NOT a ``PlanNotAcceleratedError``: the node's own averaging drops nothing, so the close fails closed."""
+
+
 class GeometricMedianUnavailableError(AggregationError):
     """The FL process asks for the geometric median (``server_config["diff_geometric_median"]``) and the
     engine cannot take it this cycle: a hosted iterative or unaccelerated plan, a non-float32 model,

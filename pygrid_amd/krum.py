@@ -19,7 +19,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .exceptions import AggregationError, KrumUnavailableError, PlanNotAcceleratedError
+from .exceptions import AggregationError, KrumUnavailableError, MeanAroundMedianUnavailableError, \
+    PlanNotAcceleratedError
 from .robust import UNSET
 
 KRUM_KEY = "diff_krum"
@@ -31,6 +32,7 @@ class KrumSpec:
     """A parsed ``diff_krum`` setting: the assumed hostile count and the keep count (None: all but f)."""
     byzantine: int
     keep: Optional[int] = None
+    bulyan: bool = False  # ``settings.BULYAN_KEY``'s first stage: keep n - 2 f of n >= 4 f + 3 diffs
 
 
 def _count(name: str, v, least: int) -> int:
@@ -84,12 +86,22 @@ def failing_closed(spec: Optional[KrumSpec], what: str = "the engine does not av
 def select(engine, spec: KrumSpec, slots: Sequence[int]) -> List[int]:
     """The picked slots of ``slots`` (in their order).  An engine without ``krum_select``, one that answers
     PGH_E_UNSUPPORTED (a group, a sub-range shard, too many rows) or PGH_E_STATE (too few finite diffs for
-    ``f``, ``keep`` too large) fails the cycle with ``KrumUnavailableError``."""
+    ``f``, ``keep`` too large) fails the cycle with ``KrumUnavailableError``.  As Bulyan's first stage
+    (``spec.bulyan``) it keeps ``n - 2 f`` of the ``n`` diffs and needs ``n >= 4 f + 3``
+    (``MeanAroundMedianUnavailableError`` otherwise); the rows it excludes as non-finite count against ``f``: more than
+    ``f`` of them leave fewer finite diffs than the keep count allows, which the engine refuses."""
     fn = getattr(engine, "krum_select", None)
     if fn is None:
         raise refuse("is set but the engine has no krum_select")
+    keep = spec.keep or 0
+    if spec.bulyan:
+        f, n = spec.byzantine, len(slots)
+        if n < 4 * f + 3:
+            raise MeanAroundMedianUnavailableError(f"diff_bulyan with byzantine = {f} needs at least {4 * f + 3} diffs, "
+                                                   f"the close has {n}")
+        keep = n - 2 * f
     try:
-        return [int(s) for s in fn(list(slots), spec.byzantine, spec.keep or 0)]
+        return [int(s) for s in fn(list(slots), spec.byzantine, keep)]
     except KrumUnavailableError:
         raise
     except AggregationError as e:

@@ -1,8 +1,8 @@
 """The robust-aggregation rules an FL process can ask for in its ``server_config`` -- per-client L2
-clipping, the coordinate-wise trimmed mean, the coordinate-wise median, the geometric median (none has a
+clipping, the coordinate-wise trimmed mean, the coordinate-wise median, the mean around the median, the geometric median (none has a
 reference counterpart) -- and what the host layer does with them, once:
 
-* ``KINDS`` is the only place that ties a rule to its config key, the engine mode it turns ``MEAN``
+* ``KINDS`` (with ``LATER_KINDS``: ``ALL_KINDS``) is the only place that ties a rule to its config key, the engine mode it turns ``MEAN``
   into, its error class and its engine setter.  A new defence is a new row (and a new class in
   ``exceptions.py`` only if callers must tell its failures apart);
 * ``rule_of`` parses the settings and gives the single active ``Rule`` (or None).  At most one rule
@@ -23,9 +23,9 @@ from typing import Optional
 
 import numpy as np
 
-from .engine import CLIPPED_MEAN, GEOMED_MAX_ITERS, GEOMETRIC_MEDIAN, MEDIAN, TRIMMED_MEAN, TRIM_MAX
+from .engine import CLIPPED_MEAN, GEOMED_MAX_ITERS, GEOMETRIC_MEDIAN, MEAN_AROUND_MEDIAN, MEDIAN, TRIMMED_MEAN, TRIM_MAX
 from .exceptions import AggregationError, ClipUnavailableError, GeometricMedianUnavailableError, \
-    MedianUnavailableError, PlanNotAcceleratedError, TrimUnavailableError
+    MeanAroundMedianUnavailableError, MedianUnavailableError, PlanNotAcceleratedError, TrimUnavailableError
 
 CLIP_KEY = "diff_clip_norm"  # optional server_config key: the per-client L2 bound (no reference counterpart)
 
@@ -89,6 +89,40 @@ def median_of(server_config: dict) -> bool:
     if isinstance(m, (bool, np.bool_)):
         return bool(m)
     raise AggregationError(f"{MEDIAN_KEY} must be True or False, not {m!r}")
+
+
+MAM_KEY = "diff_mean_around_median"  # optional server_config key: the mean of the values nearest the median
+
+
+def count_of(key: str, field: str, cfg, least: int = 1) -> Optional[int]:
+    """``cfg[field]`` of a setting that is a dict with that one field, an int >= ``least``: None when ``cfg`` is
+    None or False.  Anything else -- another type, an unknown or missing field, a bool where the number belongs, a
+    float with a fraction, a smaller value -- raises ``AggregationError``."""
+    if cfg is None or (isinstance(cfg, (bool, np.bool_)) and not cfg):
+        return None
+    if not isinstance(cfg, dict) or list(cfg) != [field]:
+        raise AggregationError(f"{key} must be a dict of {field!r} alone, None or False, not {cfg!r}")
+    v = cfg[field]
+    bad = AggregationError(f"{key}[{field!r}] must be an integer >= {least}, not {v!r}")
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise bad
+    if isinstance(v, (float, np.floating)) and not (np.isfinite(v) and float(v) == int(v)):
+        raise bad
+    if int(v) < least:
+        raise bad
+    return int(v)
+
+
+def mean_around_median_of(server_config: dict) -> Optional[int]:
+    """The FL process's drop count c, ``server_config["diff_mean_around_median"] = {"drop": c}`` (an int >= 1):
+    per parameter the close averages the N - c values nearest the median.  Absent, ``None`` or ``False``: None."""
+    return count_of(MAM_KEY, "drop", server_config.get(MAM_KEY, None))
+
+
+def check_median_drop(drop: int, n_diffs: int):
+    """A close that drops c values per parameter needs more than c diffs."""
+    if n_diffs <= drop:
+        raise MeanAroundMedianUnavailableError(f"{MAM_KEY} drops {drop} values per parameter, the close has {n_diffs} diffs")
 
 
 GEOMED_KEY = "diff_geometric_median"  # optional server_config key: the geometric median, RFA (no reference counterpart)
@@ -157,21 +191,31 @@ KINDS = (
     Rule(TRIM_KEY, "trim_count", TRIMMED_MEAN, TrimUnavailableError, "does not trim", "set_trim", 0),
     Rule(CLIP_KEY, "clip_norm", CLIPPED_MEAN, ClipUnavailableError, "does not clip", "set_clip_norm", 0.0),
 )
+# the rules added since, behind the four above in precedence (callers and tests hold KINDS as those four)
+LATER_KINDS = (
+    Rule(MAM_KEY, "mean_around_median", MEAN_AROUND_MEDIAN, MeanAroundMedianUnavailableError,
+         "drops nothing around the median", "set_median_drop", 0),
+)
+ALL_KINDS = KINDS + LATER_KINDS
 
 UNSET = object()  # an argument left out: the setting comes from server_config
 
 
-def rule_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, geometric_median=UNSET) -> Optional[Rule]:
+def rule_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, geometric_median=UNSET,
+            mean_around_median=UNSET) -> Optional[Rule]:
     """The cycle's rule, or None.  An argument that is given overrides its ``server_config`` key
     (``None``: off).  Every setting is parsed, so a malformed one raises ``AggregationError`` even
-    beside a rule that would win; two valid ones raise the error of the rule earlier in ``KINDS``."""
+    beside a rule that would win; two valid ones raise the error of the rule earlier in ``ALL_KINDS``."""
     if isinstance(geometric_median, tuple):  # the parsed form (a Rule's value) back as the setting
         geometric_median = dict(zip(_GEOMED_FIELDS, geometric_median))
-    given = {CLIP_KEY: clip_norm, TRIM_KEY: trim_count, MEDIAN_KEY: median, GEOMED_KEY: geometric_median}
+    if isinstance(mean_around_median, int) and not isinstance(mean_around_median, bool):  # likewise
+        mean_around_median = {"drop": mean_around_median}
+    given = {CLIP_KEY: clip_norm, TRIM_KEY: trim_count, MEDIAN_KEY: median, GEOMED_KEY: geometric_median,
+             MAM_KEY: mean_around_median}
     cfg = {k: server_config.get(k, None) if v is UNSET else v for k, v in given.items()}
     values = {CLIP_KEY: clip_norm_of(cfg), TRIM_KEY: trim_count_of(cfg), MEDIAN_KEY: median_of(cfg) or None,
-              GEOMED_KEY: geomed_of(cfg)}
-    active = [dataclasses.replace(k, value=values[k.key]) for k in KINDS if values[k.key] is not None]
+              GEOMED_KEY: geomed_of(cfg), MAM_KEY: mean_around_median_of(cfg)}
+    active = [dataclasses.replace(k, value=values[k.key]) for k in ALL_KINDS if values[k.key] is not None]
     if len(active) > 1:
         raise active[0].refuse(f"cannot be combined with {active[1].key}")
     return active[0] if active else None
@@ -198,7 +242,7 @@ def set_on_engine(engine, rule: Optional[Rule]):
     def args(v):
         return v if isinstance(v, tuple) else (v,)
 
-    for kind in reversed(KINDS):  # the bound first, then the trim count, as engines have always been called
+    for kind in reversed(ALL_KINDS):  # the drop count, the bound, then the trim count, as engines have always been called
         if kind.setter is None:
             continue
         if rule is None or rule.key != kind.key:

@@ -17,11 +17,23 @@ from typing import Callable, Optional
 from . import dp, krum as krum_mod, robust, trust as trust_mod
 from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
 from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, KrumUnavailableError, \
-    PlanNotAcceleratedError, ServerOptUnavailableError, TrustUnavailableError
+    MeanAroundMedianUnavailableError, PlanNotAcceleratedError, ServerOptUnavailableError, TrustUnavailableError
 from .krum import KRUM_KEY, KrumSpec, krum_of
-from .robust import CLIP_KEY, GEOMED_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
+from .robust import CLIP_KEY, GEOMED_KEY, MAM_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
 from .trust import TRUST_KEY, TrustSpec, trust_of
+
+# Bulyan (El Mhamdi, Guerraoui, Rouault, ICML 2018), ``server_config["diff_bulyan"] = {"byzantine": f}``, f >= 1: a
+# shorthand for two settings -- the Multi-Krum stage with ``byzantine = f`` keeping ``n - 2 f`` of the close's n
+# diffs (n >= 4 f + 3), then the mean around the median with ``drop = 2 f`` over the picked ones.  Stage 1 is the
+# one-shot Multi-Krum selection the engine has, not the paper's recursive one.
+BULYAN_KEY = "diff_bulyan"
+
+
+def bulyan_of(server_config: dict, bulyan=UNSET) -> Optional[int]:
+    """The FL process's assumed hostile count f under ``diff_bulyan``, or None; ``bulyan`` given overrides the key
+    (``None``: off).  Parsed as strictly as ``diff_mean_around_median``."""
+    return robust.count_of(BULYAN_KEY, "byzantine", server_config.get(BULYAN_KEY, None) if bulyan is UNSET else bulyan)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -32,6 +44,7 @@ class CloseSettings:
     noise: Optional[DpNoiseSpec] = None
     select: Optional[KrumSpec] = None
     trust: Optional[TrustSpec] = None
+    bulyan: Optional[int] = None  # f of ``diff_bulyan``: ``rule`` and ``select`` are then its two stages
 
     def __bool__(self) -> bool:
         return self.rule is not None or self.opt is not None or self.noise is not None or self.select is not None \
@@ -111,6 +124,10 @@ class CloseSettings:
             gs = engine.geomed_stats()
             stats["geometric_median"] = {"iterations": int(gs["iterations"]), "excluded": int(gs["excluded"]),
                                          "objective": float(gs["objective"]), "max_weight": float(gs["max_weight"])}
+        if self._value(MAM_KEY) is not None:  # one more key, under this rule alone
+            stats["mean_around_median"] = {"drop": int(self._value(MAM_KEY))}
+            if self.bulyan is not None:
+                stats["mean_around_median"]["byzantine"] = int(self.bulyan)
         if self.select is not None:  # one more key, under a selection alone
             stats["krum"] = krum_mod.close_stats(engine, self.select)
         if self.trust is not None:  # one more key, under the trust rule alone
@@ -142,15 +159,18 @@ class CloseSettings:
 
 
 def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
-                server_opt=UNSET, geometric_median=UNSET, krum=UNSET, trust=UNSET) -> CloseSettings:
+                server_opt=UNSET, geometric_median=UNSET, krum=UNSET, trust=UNSET, mean_around_median=UNSET,
+                bulyan=UNSET) -> CloseSettings:
     """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
     ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
     malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
     the earlier rule's error (``robust.KINDS``), noise without the clip bound ``DpNoiseUnavailableError``, a
     selection (``krum``: the setting's dict or its parsed form) beside noise ``KrumUnavailableError``, the trust
     rule (``trust``) beside any rule of ``robust.KINDS`` or beside noise ``TrustUnavailableError`` (weights and the
-    iterative plan are refused where the mode is chosen, ``cycle.select_mode``)."""
-    rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median)
+    iterative plan are refused where the mode is chosen, ``cycle.select_mode``).  ``diff_bulyan`` (``bulyan``) beside
+    a selection, any rule, noise or the trust rule raises ``MeanAroundMedianUnavailableError``; alone it becomes the
+    mean around the median with ``drop = 2 f`` behind a selection that keeps ``n - 2 f`` diffs."""
+    rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median, mean_around_median)
     if not isinstance(server_opt, ServerOptSpec):
         server_opt = server_opt_of(server_config if server_opt is UNSET else {OPT_KEY: server_opt})
     noise = dp_noise_of(server_config, dp_noise)
@@ -164,4 +184,12 @@ def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=U
     if select is not None and noise is not None:
         raise krum_mod.refuse(f"cannot be combined with {DP_KEY}: the clip-and-noise sensitivity argument does not "
                               "cover a data-dependent selection of the diffs")
-    return CloseSettings(rule, server_opt, noise, select, tr)
+    f = bulyan_of(server_config, bulyan)
+    if f is not None:
+        beside = [k for k, v in ((KRUM_KEY, select), (rule and rule.key, rule), (DP_KEY, noise), (TRUST_KEY, tr)) if v is not None]
+        if beside:
+            raise MeanAroundMedianUnavailableError(f"{BULYAN_KEY} cannot be combined with {beside[0]}: it is a selection "
+                                                   "and an averaging rule of its own")
+        rule = rule_of({}, mean_around_median=2 * f)
+        select = KrumSpec(f, None, bulyan=True)
+    return CloseSettings(rule, server_opt, noise, select, tr, f)
