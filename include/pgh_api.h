@@ -342,8 +342,9 @@ int pgh_set_trim(pgh_ctx* ctx, int b);
  *      0.5f * a + 0.5f * b for an even N);
  *   2. the distance key e_k = bits(x_k - m) & 0x7fffffff, compared as uint32: one f32 subtraction, rounded,
  *      subnormals kept.  Finite distances order by size, +inf comes after them and every NaN (from x_k NaN, m
- *      NaN or inf - inf) last.  Nothing is sanitised: a parameter whose median is not finite is already lost
- *      to a hostile majority;
+ *      NaN or inf - inf) last.  The difference of two NaNs carries x_k's payload, quieted (a finite x_k gives
+ *      m's), so around a NaN median the NaN rows order by their own payloads.  Nothing is sanitised: a
+ *      parameter whose median is not finite is already lost to a hostile majority;
  *   3. the kept positions are the beta smallest by (e_k, k): equal distances break towards the earlier fold
  *      position, as Multi-Krum's ties do;
  *   4. the sum, f64, in one fixed order: fold positions are cut into blocks of 64 (block g: positions 64 g ..
