@@ -547,6 +547,39 @@ int pgh_krum_select(pgh_ctx* ctx, const int32_t* slots, int n, int f, int m, int
 int pgh_krum_stats(pgh_ctx* ctx, int64_t* n_rows, int64_t* n_excluded, int64_t* n_picked,
                    double* max_picked_score, double* min_dropped_score);
 
+/* ---- Gram distances: the selection's step 2 on the matrix cores (kernel K16) ------------------------
+ * An opt-in kind of the selection's distances, and the n x n matrix of inner products of the held diffs in
+ * its own right (cosine similarities).  The selection above ("exact", K13) is unchanged and the default.
+ * For the listed rows d_0 .. d_{n-1} (list order, slab rows of one GPU holding whole rows):
+ *   Gram entry.  G[a][b] = the sum over i < P of (double)d_a[i] * (double)d_b[i].  Every product is exact (two
+ *      f32 values); the products are accumulated in f64 by v_mfma_f64_16x16x4_f64 in an order the kernel fixes
+ *      as a function of (P, n, the list positions a and b) alone: not of the slots, of whether the list is a
+ *      contiguous run or goes through the device row table, of the batching of the workspace or of the
+ *      device's CU count.  A repeated call gives identical bits.
+ *   Padding.  Params at or past P contribute +0.0: the loaded value is clamped and masked as K7 does, never
+ *      0 x garbage.
+ *   Symmetry.  One triangle and the diagonal are computed and mirrored: G[a][b] and G[b][a] are one value.
+ *   No sanitising in the raw call: a NaN row gives NaN entries; a slot may repeat.
+ *   Accuracy.  With u = 2^-53, |G[a][b] - <d_a, d_b>| <= P u sum_i |d_a[i]| |d_b[i]|: the bound of a sum of P
+ *      exactly represented terms in any order, each accumulation step rounded once.
+ *   Gram distances.  D[a][b] = (s_a + s_b) - 2.0 * G[a][b] in f64 on the host, each operation rounded on its
+ *      own; s_c is K7's cached sum, the bits of pgh_row_sumsq.  A negative result becomes +0.0, a NaN
+ *      (inf - inf) becomes +inf, D[a][a] = +0.0; D is symmetric because G is.
+ *   Selection.  Steps 1, 3 and 4 of the Multi-Krum selection run unchanged over this D (no pass reads an
+ *      excluded row).  The selection is a function of the rows, their order, f and m alone.  It may differ
+ *      from the exact kind's only where two scores lie closer to each other than the accuracy bound above
+ *      (times the cancellation in s_a + s_b - 2 G) allows to tell apart.
+ * pgh_row_gram: K16 alone, the n x n matrix row-major over the listed occupied slots.
+ * pgh_gram_distances_host: the distances from a Gram matrix and the sums, no context and no GPU.
+ * pgh_krum_select_gram: pgh_krum_select with step 2 from K16; pgh_krum_stats reports it alike.
+ * Both context calls refuse what pgh_row_pairdist / pgh_krum_select refuse, with the same status, and use
+ * and fill K7's cache alike.  The partial blocks take at most the same 1 GiB (PGH_PAIRDIST_BUDGET lowers
+ * it): the block pairs go in batches, which changes no bit. */
+int pgh_row_gram(pgh_ctx* ctx, const int32_t* slots, int n, double* out);
+int pgh_gram_distances_host(const double* gram, const double* sumsq, int n, double* dist);
+int pgh_krum_select_gram(pgh_ctx* ctx, const int32_t* slots, int n, int f, int m, int32_t* picked,
+                         int* n_picked);
+
 /* ---- server optimizers: how the average is applied (FedAvgM, FedAdagrad, FedAdam, FedYogi) ------
  * Without one, a close writes out = ckpt - g, g being the cycle's average as its mode defines it
  * (acc / divisor; the iterative mean's acc; the trimmed mean; the median).  With one set, every

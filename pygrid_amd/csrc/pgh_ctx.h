@@ -14,7 +14,7 @@
 //                   fold_run's ring walk and the share sum; the divisors; the weights' upload; RESIDENT and STREAM
 //                   entry points, the resident checkpoint
 //   pgh_rules.cpp   what a mode may do (check_mode_use) and what the rules add to the fold: the row reductions (RowSums:
-//                   K7 and K14 through their per-slot caches, K12 and K14 over listed rows, K13), clipping (the scales,
+//                   K7 and K14 through their per-slot caches, K12 and K14 over listed rows, K13, K16), clipping (the scales,
 //                   the tallies) and the Gaussian noise on the clipped close (K11 behind a FINAL launch), trimming
 //                   (K8's planes), the median (K9, K9p), the geometric median and the trust rule (the included rows
 //                   and resident weights they share; the iterations; the root), the Multi-Krum selection; the -0
@@ -172,7 +172,7 @@ struct pgh_ctx {
     // lifecycle files (pgh_api.cpp, pgh_ingest.cpp, pgh_slots.cpp, pgh_xfer.cpp, pgh_order.cpp) reach them
     // through rules_* and the fold plans below alone:
     //   grep -n 'c->\(clip\|geo\|trust\|krum\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
-    pgh_detail::RowSums rowsums;   // the per-slot caches sq (K7) and dot (K14), the tile partials and the buffers of K12 and K13 (clip, geo, krum, trust)
+    pgh_detail::RowSums rowsums;   // the per-slot caches sq (K7) and dot (K14), the tile partials and the buffers of K12, K13 and K16 (clip, geo, krum, trust)
     pgh_detail::NegZeroPlane nz;   // the one plane of -0.0f (opt, noise, geo)
     pgh_detail::ClipState clip;
     pgh_detail::NoiseState noise;

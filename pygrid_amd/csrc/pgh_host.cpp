@@ -237,6 +237,15 @@ int krum_select(const double* D, int n, int f, int m, int32_t* picked, int* n_pi
     return 0;
 }
 
+void gram_distances(const double* G, const double* s, int n, double* D) {
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) {
+            const double sum = s[a] + s[b], twice = 2.0 * G[(size_t)a * (size_t)n + (size_t)b];
+            const double d = sum - twice;
+            D[(size_t)a * (size_t)n + (size_t)b] = a == b ? 0.0 : d != d ? (double)INFINITY : d < 0.0 ? 0.0 : d;
+        }
+}
+
 double row_dot_host(const float* x, const float* y, int64_t p) {
     double row = 0.0;
     for (int64_t base = 0; base < p || base == 0; base += 4096) {

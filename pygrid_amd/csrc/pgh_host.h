@@ -213,6 +213,11 @@ bool geomed_step(const double* D, int64_t n, float nu, float* w, float* W, doubl
 // written whenever the matrix was acceptable and n >= 2f + 3.
 int krum_select(const double* D, int n, int f, int m, int32_t* picked, int* n_picked, double* scores);
 
+// The "gram" kind's step 2 (include/pgh_api.h, "Gram distances"): from the n x n Gram matrix G of the included
+// rows and K7's sums s, D[a][b] = (s[a] + s[b]) - 2.0 * G[a][b], each operation rounded on its own; a negative
+// result becomes +0.0, a NaN (inf - inf) +inf; the diagonal is +0.0.  G symmetric gives D symmetric.
+void gram_distances(const double* G, const double* s, int n, double* D);
+
 // K7's sum in K7's exact order (pgh_kernels.h) over (double)x[i] * (double)y[i], i < p, on the host: what K14
 // returns for a row x against the plane y, and with y == x what K7 returns for x.  The trust root's s0 comes from
 // here (pgh_trust_root): the same bits as pgh_row_sumsq of a slot holding the root.

@@ -1,5 +1,5 @@
 // libpygrid_hip: the averaging rules on top of the fp32 fold -- what a mode may do (check_mode_use); the row
-// reductions (RowSums: K7 and K14 through their per-slot caches, K12 and K14 over a listed set of rows, K13) and
+// reductions (RowSums: K7 and K14 through their per-slot caches, K12 and K14 over a listed set of rows, K13, K16) and
 // the Multi-Krum selection over them; clipping's scales and tallies; the Gaussian noise on the clipped close (K11
 // behind a FINAL launch, its plane, setting and entry points); the trimmed mean's state planes (K8); the
 // median's driver and row table (K9, K9p); the mean around the median's driver (K15); what the geometric median and the trust rule share (the finite rows
@@ -363,6 +363,23 @@ int queue_dots(pgh_ctx* c, const int32_t* slots, int n) {
 }
 }  // namespace
 
+int RowSums::pair_rows(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, int* row0, const int32_t** d_rows) {
+    bool run = true;
+    for (int k = 0; k < n; ++k) run = run && slots[k] == slots[0] + k;
+    if (run) {
+        *row0 = slots[0] * c->parties;
+        return PGH_OK;
+    }
+    if (!d_pair_rows.reserve(sizeof(int32_t) * (size_t)pgh::PAIRDIST_MAX_ROWS)) return fail(c, PGH_E_OOM, "allocation of the pair list's row table failed");
+    std::vector<int32_t> tab((size_t)n);
+    for (int k = 0; k < n; ++k) tab[(size_t)k] = slots[k] * c->parties;
+    // (an earlier K13 or K16 that read the table ran on this stream too)
+    CK(c, hipMemcpyAsync(d_pair_rows.as<int32_t>(), tab.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // tab is pageable: the copy has left it
+    *d_rows = d_pair_rows.as<int32_t>();
+    return PGH_OK;
+}
+
 // (K7's and K12's buffers are not touched: the cached sums stay what they were.)
 int RowSums::pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D) {
     const size_t nn = (size_t)n * (size_t)n;
@@ -385,18 +402,7 @@ int RowSums::pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, do
         return fail(c, PGH_E_OOM, "allocation of the pairwise distances (%d rows, %zu anchors a batch) failed", n, batch);
     a.part = d_pair_part.as<double>();
     a.dist = d_pair.as<double>();
-    bool run = true;
-    for (int k = 0; k < n; ++k) run = run && slots[k] == slots[0] + k;
-    std::vector<int32_t> tab((size_t)n);
-    if (run) {
-        a.row0 = slots[0] * c->parties;
-    } else {
-        for (int k = 0; k < n; ++k) tab[(size_t)k] = slots[k] * c->parties;
-        // (an earlier K13 that read the table ran on this stream too)
-        CK(c, hipMemcpyAsync(d_pair_rows.as<int32_t>(), tab.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-        CK(c, hipStreamSynchronize(s));  // tab is pageable: the copy has left it
-        a.d_rows = d_pair_rows.as<int32_t>();
-    }
+    RC(pair_rows(c, slots, n, s, &a.row0, &a.d_rows));
     for (int a0 = 0; a0 < n - 1; a0 += (int)batch) {
         a.a0 = a0;
         a.na = std::min((int)batch, n - 1 - a0);
@@ -413,6 +419,41 @@ int RowSums::pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, do
     CK(c, hipStreamSynchronize(s));
     for (int x = 0; x < n; ++x)
         for (int y = x + 1; y < n; ++y) D[(size_t)x * n + y] = D[(size_t)y * n + x] = h[(size_t)x * n + y];
+    return PGH_OK;
+}
+
+// K16.  (Neither K7's nor K13's buffers are touched.)  The block pairs a batch takes are whole ones within the
+// budget; the chunks, and with them every entry's accumulation order, do not depend on the batching.
+int RowSums::gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* G) {
+    const size_t nn = (size_t)n * (size_t)n;
+    pgh::GramArgs a{};
+    a.slab = c->d_slab.as<float>();
+    a.map = slab_map(c);
+    a.p = c->pg;
+    a.n = n;
+    const int64_t ntiles = (c->pg + pgh::SUMSQ_TILE - 1) / pgh::SUMSQ_TILE;
+    a.chunk_tiles = pgh::gram_chunk_tiles(ntiles, n);
+    a.nchunks = (int)((ntiles + a.chunk_tiles - 1) / a.chunk_tiles);
+    const int nbp = pgh::gram_block_pairs(n);
+    const size_t per_pair = 8 * (size_t)pgh::GRAM_RB * (size_t)pgh::GRAM_RB * (size_t)a.nchunks;
+    const size_t batch = std::min(pair_budget / per_pair, (size_t)nbp);
+    if (batch == 0)
+        return fail(c, PGH_E_OOM, "Gram matrix: the partial blocks of one block pair (%zu bytes) exceed the budget of %zu", per_pair, pair_budget);
+    if (!d_gram_part.reserve(batch * per_pair) || !d_gram.reserve(8 * nn))
+        return fail(c, PGH_E_OOM, "allocation of the Gram matrix (%d rows, %zu block pairs a batch) failed", n, batch);
+    a.part = d_gram_part.as<double>();
+    a.gram = d_gram.as<double>();
+    RC(pair_rows(c, slots, n, s, &a.row0, &a.d_rows));
+    for (int q0 = 0; q0 < nbp; q0 += (int)batch) {
+        a.bp0 = q0;
+        a.nbp = std::min((int)batch, nbp - q0);
+        // the algorithmic bytes: the batch's share of the rows once; its entries' partials out and in, the matrix out
+        const uint64_t entries = (uint64_t)nn * (uint64_t)a.nbp / (uint64_t)nbp;
+        const uint64_t bytes = 4ull * (uint64_t)n * (uint64_t)c->pg * (uint64_t)a.nbp / (uint64_t)nbp + entries * (16ull * (uint64_t)a.nchunks + 8ull);
+        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_row_gram(a, s); }));
+    }
+    CK(c, hipMemcpyAsync(G, d_gram.as<double>(), 8 * nn, hipMemcpyDeviceToHost, s));
+    CK(c, hipStreamSynchronize(s));
     return PGH_OK;
 }
 
@@ -879,7 +920,7 @@ int pgh_trust_stats(pgh_ctx* c, int* on, int64_t* n_rows, int64_t* n_excluded, i
     return PGH_OK;
 }
 
-// ---- Multi-Krum selection: K13 alone, the host step alone, the selection, what the last one saw ----------------
+// ---- Multi-Krum selection: K13 and K16 alone, the host steps alone, the selection, what the last one saw -------
 
 namespace {
 int check_pair_list(pgh_ctx* c, const char* what, const int32_t* slots, int n, bool no_twice) {
@@ -918,19 +959,44 @@ int pgh_krum_select_host(const double* dist, int n, int f, int m, int32_t* picke
     return PGH_OK;
 }
 
-int pgh_krum_select(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
-    RC(check_pair_list(c, "pgh_krum_select", slots, n, true));
-    if (f < 0 || m < 0 || !picked || !n_picked) return fail(c, PGH_E_ARG, "pgh_krum_select: bad arguments (f=%d, m=%d)", f, m);
+int pgh_row_gram(pgh_ctx* c, const int32_t* slots, int n, double* out) {
+    RC(check_pair_list(c, "pgh_row_gram", slots, n, false));
+    if (n > 0 && !out) return fail(c, PGH_E_ARG, "pgh_row_gram: out is NULL");
+    if (n == 0) return PGH_OK;
+    DeviceGuard g(c->device);
+    const hipStream_t s = c->stream;
+    RC(order_after_ingest(c, s));
+    return c->rowsums.gram(c, slots, n, s, out);
+}
+
+int pgh_gram_distances_host(const double* gram, const double* sumsq, int n, double* dist) {
+    if (n < 0 || (n > 0 && (!gram || !sumsq || !dist))) return fail(nullptr, PGH_E_ARG, "pgh_gram_distances_host: bad arguments (n=%d)", n);
+    gram_distances(gram, sumsq, n, dist);
+    return PGH_OK;
+}
+
+namespace {
+// pgh_krum_select and pgh_krum_select_gram: steps 1 to 4, the distance matrix of step 2 from K13 or from K16
+int krum_select_ctx(pgh_ctx* c, const char* who, bool by_gram, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
+    RC(check_pair_list(c, who, slots, n, true));
+    if (f < 0 || m < 0 || !picked || !n_picked) return fail(c, PGH_E_ARG, "%s: bad arguments (f=%d, m=%d)", who, f, m);
     DeviceGuard g(c->device);
     std::vector<int32_t> inc;
-    RC(finite_rows(c, slots, n, &inc, nullptr));
+    std::vector<double> ss;
+    RC(finite_rows(c, slots, n, &inc, &ss));
     const int ni = (int)inc.size();
     if ((int64_t)ni < 2 * (int64_t)f + 3 || m > ni - f)  // (nothing is launched)
         return fail(c, PGH_E_STATE, "Multi-Krum with f = %d, m = %d: %d of the %d diffs are finite, it needs at least 2f + 3 = %d and m <= n' - f", f, m, ni, n, 2 * f + 3);
     const hipStream_t s = c->stream;
     RC(order_after_ingest(c, s));
     std::vector<double> D((size_t)ni * (size_t)ni), sc((size_t)ni);
-    RC(c->rowsums.pairdist(c, inc.data(), ni, s, D.data()));
+    if (by_gram) {
+        std::vector<double> G((size_t)ni * (size_t)ni);
+        RC(c->rowsums.gram(c, inc.data(), ni, s, G.data()));
+        gram_distances(G.data(), ss.data(), ni, D.data());
+    } else {
+        RC(c->rowsums.pairdist(c, inc.data(), ni, s, D.data()));
+    }
     std::vector<int32_t> pos((size_t)ni);
     int np = 0;
     const int rc = krum_select(D.data(), ni, f, m, pos.data(), &np, sc.data());
@@ -947,6 +1013,15 @@ int pgh_krum_select(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32
         if (!is[(size_t)k]) ks.min_dropped_score = std::min(ks.min_dropped_score, sc[(size_t)k]);
     *n_picked = np;
     return PGH_OK;
+}
+}  // namespace
+
+int pgh_krum_select(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
+    return krum_select_ctx(c, "pgh_krum_select", false, slots, n, f, m, picked, n_picked);
+}
+
+int pgh_krum_select_gram(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
+    return krum_select_ctx(c, "pgh_krum_select_gram", true, slots, n, f, m, picked, n_picked);
 }
 
 int pgh_krum_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_excluded, int64_t* n_picked, double* max_picked_score, double* min_dropped_score) {

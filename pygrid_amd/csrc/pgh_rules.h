@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pgh_host.h"
+#include "pgh_gram.h"
 #include "pgh_kernels.h"
 #include "pgh_median_mean.h"
 #include "pgh_res.h"
@@ -67,6 +68,9 @@ struct RowSums {
     // tile partials of one batch of anchors, at most pair_budget bytes whatever n and the model; the n x n
     // matrix; the listed slab rows as a device table
     DeviceBuf d_pair_part, d_pair, d_pair_rows;
+    // K16's (the Gram matrix), allocated by the first pgh_row_gram / pgh_krum_select_gram: the partial blocks of
+    // one batch of block pairs, within the same budget; the n x n matrix.  The row table is K13's.
+    DeviceBuf d_gram_part, d_gram;
     size_t pair_budget = (size_t)1 << 30;  // PGH_PAIRDIST_BUDGET (bytes) lowers it, for tests of the batching
 
     double at(int slot) const { return sq.at(slot); }       // after wait(): the sum of a slot queued before it
@@ -83,7 +87,7 @@ struct RowSums {
         for (RowCache* r : {&sq, &dot}) r->forget();
     }
     void slab_freed() {  // the streams are idle: every buffer sized by the slab goes, and the caches
-        for (auto* v : {&d_part, &d_dist, &d_pair_part, &d_pair, &d_pair_rows}) v->reset();
+        for (auto* v : {&d_part, &d_dist, &d_pair_part, &d_pair, &d_pair_rows, &d_gram_part, &d_gram}) v->reset();
         h_dist.reset();
         for (RowCache* r : {&sq, &dot}) r->slab_freed();
     }
@@ -102,6 +106,12 @@ struct RowSums {
     // K13 over the listed slots (n <= PAIRDIST_MAX_ROWS) on stream s in batches of anchors, the D2H and the wait:
     // D[a * n + b] = the squared distance of slots[a] to slots[b], symmetric, +0.0 on the diagonal
     int pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D);
+    // K16 over the listed slots (1 <= n <= PAIRDIST_MAX_ROWS) on stream s in batches of block pairs, the D2H and
+    // the wait: G[a * n + b] = the inner product of slots[a] and slots[b], symmetric
+    int gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* G);
+    // where the kernels of a pair list find its rows: *row0 for a contiguous run of slots, else the device table
+    // d_pair_rows, uploaded on stream s (complete on return)
+    int pair_rows(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, int* row0, const int32_t** d_rows);
 };
 
 // The fold's per-client weights (fold order) and their device copy.  Four writers: the caller

@@ -439,7 +439,7 @@ class Engine:
         return {"on": bool(on.value), "rows": n.value, "excluded": x.value, "trusted": k.value,
                 "total_trust": t.value, "max_weight": m.value, "root_norm": r.value}
 
-    # ---- Multi-Krum selection ahead of the average (kernel K13) ---------------------------------------
+    # ---- Multi-Krum selection ahead of the average (kernels K13, K16) ---------------------------------
     def row_pairdist(self, slots: Sequence[int]) -> np.ndarray:
         """float64 [n][n] squared distances among the diffs in ``slots``: K13 alone; entry (a, b) is
         ``row_distsq([slots[a]], diff of slots[b])`` bit for bit (tests, debugging)."""
@@ -449,13 +449,41 @@ class Engine:
                                                out.ctypes.data_as(C.POINTER(C.c_double))), "row_pairdist")
         return out
 
-    def krum_select(self, slots: Sequence[int], f: int, m: int = 0) -> List[int]:
+    def row_gram(self, slots: Sequence[int]) -> np.ndarray:
+        """float64 [n][n] inner products among the diffs in ``slots``: K16 alone, on the matrix cores
+        (``include/pgh_api.h``, "Gram distances"); symmetric, within P 2^-53 sum |a_i| |b_i| of the exact value."""
+        a = np.ascontiguousarray(slots, dtype=np.int32)
+        out = np.empty((a.size, a.size), dtype=np.float64)
+        self._check(self._lib.pgh_row_gram(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
+                                           out.ctypes.data_as(C.POINTER(C.c_double))), "row_gram")
+        return out
+
+    @staticmethod
+    def gram_distances_host(G, sumsq) -> np.ndarray:
+        """The "gram" kind's squared distances ``(s_a + s_b) - 2 G[a][b]`` (negative: +0, NaN: +inf, diagonal +0)
+        from the [n][n] Gram matrix and the n sums of squares (plain C++; no GPU)."""
+        lib = _lib.load()
+        g, s = np.ascontiguousarray(G, dtype=np.float64), np.ascontiguousarray(sumsq, dtype=np.float64)
+        if g.ndim != 2 or g.shape[0] != g.shape[1] or s.shape != (g.shape[0],):
+            raise AggregationError(f"gram_distances_host: G must be [n][n] and sumsq [n], not {g.shape} and {s.shape}")
+        out = np.empty_like(g)
+        rc = lib.pgh_gram_distances_host(g.ctypes.data_as(C.POINTER(C.c_double)), s.ctypes.data_as(C.POINTER(C.c_double)),
+                                         g.shape[0], out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise AggregationError(f"gram_distances_host: {_lib.STATUS_NAMES.get(rc, rc)}", status=rc)
+        return out
+
+    def krum_select(self, slots: Sequence[int], f: int, m: int = 0, distances: str = "exact") -> List[int]:
         """The Multi-Krum selection (``include/pgh_api.h``) over the diffs in ``slots`` with ``f`` assumed
-        hostile: the ``m`` most central slots (0: all but f of the finite ones), in the order of ``slots``."""
+        hostile: the ``m`` most central slots (0: all but f of the finite ones), in the order of ``slots``.
+        ``distances``: ``"exact"`` (K13's bit-reproducible sums) or ``"gram"`` (K16: from the Gram matrix)."""
+        if distances not in ("exact", "gram"):
+            raise AggregationError(f"krum_select: distances must be 'exact' or 'gram', not {distances!r}")
+        fn = self._lib.pgh_krum_select_gram if distances == "gram" else self._lib.pgh_krum_select
         a = np.ascontiguousarray(slots, dtype=np.int32)
         picked, n = np.empty(max(a.size, 1), dtype=np.int32), C.c_int(0)
-        self._check(self._lib.pgh_krum_select(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, int(f), int(m),
-                                              picked.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "krum_select")
+        self._check(fn(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, int(f), int(m),
+                       picked.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "krum_select")
         return [int(x) for x in picked[:n.value]]
 
     @staticmethod

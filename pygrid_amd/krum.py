@@ -1,10 +1,11 @@
 """Multi-Krum selection of a cycle's diffs ahead of its average (Blanchard et al. 2017; the arithmetic is
 defined in ``include/pgh_api.h``, the distances are kernel K13's).
 
-``server_config["diff_krum"] = {"byzantine": f, "keep": optional m}``: every diff is scored by its distance
+``server_config["diff_krum"] = {"byzantine": f, "keep": optional m, "distances": optional kind}``: every diff is scored by its distance
 to its ``n' - f - 2`` nearest neighbours among the ``n'`` finite diffs, the ``m`` most central ones
 (default ``n' - f``; 1 is Krum) are averaged and the others leave the cycle.  An absent key, ``None`` or
-``False`` selects nothing.
+``False`` selects nothing.  ``"distances"``: ``"exact"`` (the default: K13, bit-reproducible) or ``"gram"`` (K16:
+``s_a + s_b - 2 <d_a, d_b>`` from the Gram matrix on the matrix cores, for large cohorts).
 
 A selection is a stage, not an averaging rule (``robust.rule_of`` does not know it): the cycle's mode --
 the plain, iterative, weighted, clipped or trimmed mean, the median, the geometric median, with or without
@@ -24,7 +25,8 @@ from .exceptions import AggregationError, KrumUnavailableError, MeanAroundMedian
 from .robust import UNSET
 
 KRUM_KEY = "diff_krum"
-_FIELDS = ("byzantine", "keep")
+_FIELDS = ("byzantine", "keep", "distances")
+DISTANCES = ("exact", "gram")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -33,6 +35,14 @@ class KrumSpec:
     byzantine: int
     keep: Optional[int] = None
     bulyan: bool = False  # ``settings.BULYAN_KEY``'s first stage: keep n - 2 f of n >= 4 f + 3 diffs
+    distances: str = "exact"  # "exact": K13's bit-reproducible sums; "gram": from K16's Gram matrix
+
+
+def distances_of(key: str, v) -> str:
+    """The ``"distances"`` entry of ``key``'s setting: one of ``DISTANCES``."""
+    if not isinstance(v, str) or v not in DISTANCES:
+        raise AggregationError(f"{key}['distances'] must be one of {DISTANCES}, not {v!r}")
+    return v
 
 
 def _count(name: str, v, least: int) -> int:
@@ -48,7 +58,8 @@ def _count(name: str, v, least: int) -> int:
 
 def krum_of(server_config: dict, krum=UNSET) -> Optional[KrumSpec]:
     """The FL process's selection, or None.  ``krum`` given overrides the ``server_config`` key (``None``:
-    off).  ``{"byzantine": f}`` (an int >= 0) is required, ``"keep"`` (an int >= 1, or None) optional.
+    off).  ``{"byzantine": f}`` (an int >= 0) is required, ``"keep"`` (an int >= 1, or None) and ``"distances"``
+    (``"exact"`` or ``"gram"``) optional.
     Anything else -- another type, an unknown key, a bool where a number belongs, a float with a fraction, a
     negative count -- raises ``AggregationError``: a mistyped setting must not quietly mean "every diff"."""
     cfg = server_config.get(KRUM_KEY, None) if krum is UNSET else krum
@@ -64,7 +75,8 @@ def krum_of(server_config: dict, krum=UNSET) -> Optional[KrumSpec]:
     if "byzantine" not in cfg:
         raise AggregationError(f"{KRUM_KEY}['byzantine'] is required")
     keep = cfg.get("keep", None)
-    return KrumSpec(_count("byzantine", cfg["byzantine"], 0), None if keep is None else _count("keep", keep, 1))
+    return KrumSpec(_count("byzantine", cfg["byzantine"], 0), None if keep is None else _count("keep", keep, 1),
+                    distances=distances_of(KRUM_KEY, cfg.get("distances", "exact")))
 
 
 def refuse(why: str) -> KrumUnavailableError:
@@ -100,8 +112,9 @@ def select(engine, spec: KrumSpec, slots: Sequence[int]) -> List[int]:
             raise MeanAroundMedianUnavailableError(f"diff_bulyan with byzantine = {f} needs at least {4 * f + 3} diffs, "
                                                    f"the close has {n}")
         keep = n - 2 * f
+    kind = {} if spec.distances == "exact" else {"distances": spec.distances}
     try:
-        return [int(s) for s in fn(list(slots), spec.byzantine, keep)]
+        return [int(s) for s in fn(list(slots), spec.byzantine, keep, **kind)]
     except KrumUnavailableError:
         raise
     except AggregationError as e:
@@ -113,5 +126,8 @@ def select(engine, spec: KrumSpec, slots: Sequence[int]) -> List[int]:
 def close_stats(engine, spec: KrumSpec) -> dict:
     """The selection's entry of ``last_close``, read from the engine after the close."""
     ks = engine.krum_stats()
-    return {"byzantine": spec.byzantine, "picked": int(ks["picked"]), "excluded": int(ks["excluded"]),
-            "max_picked_score": float(ks["max_picked_score"])}
+    out = {"byzantine": spec.byzantine, "picked": int(ks["picked"]), "excluded": int(ks["excluded"]),
+           "max_picked_score": float(ks["max_picked_score"])}
+    if spec.distances != "exact":
+        out["distances"] = spec.distances
+    return out

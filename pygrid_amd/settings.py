@@ -23,7 +23,8 @@ from .robust import CLIP_KEY, GEOMED_KEY, MAM_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, 
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
 from .trust import TRUST_KEY, TrustSpec, trust_of
 
-# Bulyan (El Mhamdi, Guerraoui, Rouault, ICML 2018), ``server_config["diff_bulyan"] = {"byzantine": f}``, f >= 1: a
+# Bulyan (El Mhamdi, Guerraoui, Rouault, ICML 2018), ``server_config["diff_bulyan"] = {"byzantine": f}``, f >= 1
+# (and optionally ``"distances"``, stage 1's distance kind as in ``diff_krum``): a
 # shorthand for two settings -- the Multi-Krum stage with ``byzantine = f`` keeping ``n - 2 f`` of the close's n
 # diffs (n >= 4 f + 3), then the mean around the median with ``drop = 2 f`` over the picked ones.  Stage 1 is the
 # one-shot Multi-Krum selection the engine has, not the paper's recursive one.
@@ -33,7 +34,16 @@ BULYAN_KEY = "diff_bulyan"
 def bulyan_of(server_config: dict, bulyan=UNSET) -> Optional[int]:
     """The FL process's assumed hostile count f under ``diff_bulyan``, or None; ``bulyan`` given overrides the key
     (``None``: off).  Parsed as strictly as ``diff_mean_around_median``."""
-    return robust.count_of(BULYAN_KEY, "byzantine", server_config.get(BULYAN_KEY, None) if bulyan is UNSET else bulyan)
+    cfg = server_config.get(BULYAN_KEY, None) if bulyan is UNSET else bulyan
+    if isinstance(cfg, dict) and "distances" in cfg:  # (stage 1's optional kind: bulyan_distances_of)
+        cfg = {k: v for k, v in cfg.items() if k != "distances"}
+    return robust.count_of(BULYAN_KEY, "byzantine", cfg)
+
+
+def bulyan_distances_of(server_config: dict, bulyan=UNSET) -> str:
+    """The distance kind of ``diff_bulyan``'s first stage, its optional ``"distances"`` (``krum.DISTANCES``)."""
+    cfg = server_config.get(BULYAN_KEY, None) if bulyan is UNSET else bulyan
+    return krum_mod.distances_of(BULYAN_KEY, cfg["distances"]) if isinstance(cfg, dict) and "distances" in cfg else "exact"
 
 
 @dataclasses.dataclass(frozen=True)
@@ -191,5 +201,5 @@ def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=U
             raise MeanAroundMedianUnavailableError(f"{BULYAN_KEY} cannot be combined with {beside[0]}: it is a selection "
                                                    "and an averaging rule of its own")
         rule = rule_of({}, mean_around_median=2 * f)
-        select = KrumSpec(f, None, bulyan=True)
+        select = KrumSpec(f, None, bulyan=True, distances=bulyan_distances_of(server_config, bulyan))
     return CloseSettings(rule, server_opt, noise, select, tr, f)
