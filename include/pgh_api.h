@@ -62,7 +62,9 @@ typedef enum {
  * counterpart; defined below).
  * PGH_MEAN_AROUND_MEDIAN: per parameter, the mean of the N - c reported values nearest the median ("mean around
  * the median", Xie, Koyejo, Gupta 2018; the second stage of Bulyan, El Mhamdi, Guerraoui, Rouault, ICML 2018; c
- * from pgh_set_median_drop; no reference counterpart; defined below). */
+ * from pgh_set_median_drop; no reference counterpart; defined below).
+ * PGH_RANK_TRIMMED_MEAN: PGH_TRIMMED_MEAN's kept values, sort(values)[b : N - b], for any b with N >= 2b + 1 (b
+ * from pgh_set_rank_trim), summed in f64 in a fixed order of its own (no reference counterpart; defined below). */
 typedef enum {
     PGH_MEAN = 0,
     PGH_ITERATIVE_MEAN = 1,
@@ -75,6 +77,7 @@ typedef enum {
 } pgh_mode;
 /* One more averaging mode, taken wherever a pgh_mode is (the enum itself is as ABI 10 first had it). */
 #define PGH_MEAN_AROUND_MEDIAN 8
+#define PGH_RANK_TRIMMED_MEAN 9
 /* Stream kind for pgh_stream_begin besides the three averaging modes. */
 #define PGH_STREAM_SECAGG 16
 
@@ -371,6 +374,45 @@ int pgh_set_trim(pgh_ctx* ctx, int b);
  * pgh_set_variant does not affect the mode.  Behind pgh_krum_select with keep = n - 2f, c = 2f is Bulyan with
  * the one-shot Multi-Krum selection as its first stage (not the paper's recursive one). */
 int pgh_set_median_drop(pgh_ctx* ctx, int c);
+
+/* ---- rank-trimmed mean (PGH_RANK_TRIMMED_MEAN; kernel K17) ------------------------------------------------
+ * Per parameter, the mean of the reported values without the b largest and the b smallest, for any b -- a
+ * trim fraction of the cohort, where PGH_TRIMMED_MEAN stops at PGH_TRIM_MAX.  The kept values are those of
+ * PGH_TRIMMED_MEAN; the sum is not its f32 streaming chain but an f64 sum in one fixed order, so the two modes
+ * agree to rounding, not bit for bit.  Rows x_0 .. x_{N-1} in fold order, b from pgh_set_rank_trim, 1 <= b and
+ * N >= 2b + 1:
+ *   1. Order.  The total order on bit patterns of the trimmed mean and the median: key(x) above, compared as
+ *      u = key ^ 0x80000000, unsigned; equal keys are identical bits.
+ *   2. Selection.  s = sort(u), L = s[b], H = s[N - 1 - b]; the kept multiset is s[b : N - b].
+ *   3. Sum, f64, in one fixed order.  The interior is the positions k with L < u_k < H.  Fold positions are cut
+ *      into blocks of 64 (block g: positions 64 g .. 64 g + 63); s_g = the left fold from +0.0 of (double)x_k
+ *      over the block's interior positions, ascending k; S = the left fold of s_0, s_1, ... starting from s_0.
+ *      Then the two boundary values go in as products, which are exact (a count of at most 1,024 times an f32):
+ *        S = S + (double)kL * (double)unkey(L);  then, only if kH > 0,  S = S + (double)kH * (double)unkey(H);
+ *      for L < H: kL = #{u <= L} - b and kH = (N - b) - #{u < H};  for L == H: kL = N - 2b and kH = 0.
+ *   4. Close.  mean = (float)(S / (double)(N - 2b)), an IEEE f64 division rounded once more to f32;
+ *      out = ckpt - mean, one f32 subtraction.  A server optimizer takes g = mean.
+ * Equal keys are identical bits, so which of several rows equal to a boundary value is "kept" cannot matter:
+ * the definition needs no tie rule.
+ * Example: the column (5, 1, 4, 1, 2) with b = 1 has L = 1 and H = 4; the interior is (2), #{u <= L} = 2 and
+ * #{u < H} = 3 give kL = 1 and kH = 1, S = 2 + 1 * 1 + 1 * 4 and mean = (float)(7.0 / 3.0).
+ * The result is a function of the rows, their order and b alone: it does not depend on the slots, the launch
+ * shape, the slab's block width, the range split or the entry point.  Up to b rows of arbitrary content,
+ * non-finite ones included, cannot push a parameter outside the range of the others' values; more than b NaNs
+ * of one sign leave a NaN.
+ *
+ * pgh_set_rank_trim: b = 0 turns the setting off, b >= 1 turns it on, b < 0 is PGH_E_ARG; changing b while slot
+ * folds of a cycle are under way is PGH_E_STATE.  A group hands b to its children.  pgh_set_layout and
+ * pgh_set_shard clear the setting, pgh_reset and pgh_reserve keep it.  pgh_set_trim and PGH_TRIMMED_MEAN are
+ * not affected.
+ * The mode takes every row of the cycle in one call, like the median: pgh_fedavg, pgh_fedavg_device[_range],
+ * pgh_fedavg_resident and pgh_fold_slots_finish_resident accept it, on shards and groups too (nothing in it
+ * looks along a row); pgh_fold_slots and pgh_stream_begin refuse it (PGH_E_UNSUPPORTED).  The mode with the
+ * setting off is PGH_E_STATE, and so is a close of N < 2b + 1 diffs (nothing is launched; the context stays
+ * usable) and the mode beside pgh_set_dp_noise.  N > PGH_MEDIAN_NCHIP is PGH_E_UNSUPPORTED: the selection runs
+ * on chip only (K17).  pgh_effective_variant(ctx, PGH_RANK_TRIMMED_MEAN) reports 70; pgh_set_variant does not
+ * affect the mode. */
+int pgh_set_rank_trim(pgh_ctx* ctx, int b);
 
 /* ---- geometric-median FedAvg (PGH_GEOMETRIC_MEDIAN, RFA; kernel K12) ----------------------------
  * The geometric median of the diffs -- the point with the smallest sum of L2 distances to them --

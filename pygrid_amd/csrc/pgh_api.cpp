@@ -403,6 +403,7 @@ int pgh_effective_variant(pgh_ctx* c, int mode) {
         return median_variant(c, n);
     }
     if (mode == PGH_MEAN_AROUND_MEDIAN) return 60;  // K15, whatever pgh_set_variant says
+    if (mode == PGH_RANK_TRIMMED_MEAN) return 70;   // K17, likewise
     if (c->variant >= 0) return c->variant;
     if (mode == PGH_STREAM_SECAGG) return pgh::SECAGG_AUTO_VARIANT;
     if (!valid_mode(mode)) return fail(c, PGH_E_ARG, "unknown averaging mode %d", mode);

@@ -72,7 +72,7 @@ namespace pgh_detail {
 constexpr int KIND_SECAGG = PGH_STREAM_SECAGG;  // fold kind besides the pgh_mode values (none of which it equals)
 static_assert(KIND_SECAGG != PGH_MEAN && KIND_SECAGG != PGH_ITERATIVE_MEAN && KIND_SECAGG != PGH_WEIGHTED_MEAN &&
                   KIND_SECAGG != PGH_CLIPPED_MEAN && KIND_SECAGG != PGH_TRIMMED_MEAN && KIND_SECAGG != PGH_MEDIAN && KIND_SECAGG != PGH_GEOMETRIC_MEDIAN &&
-                  KIND_SECAGG != PGH_TRUSTED_MEAN && KIND_SECAGG != PGH_MEAN_AROUND_MEDIAN,
+                  KIND_SECAGG != PGH_TRUSTED_MEAN && KIND_SECAGG != PGH_MEAN_AROUND_MEDIAN && KIND_SECAGG != PGH_RANK_TRIMMED_MEAN,
               "the secagg fold kind must not collide with an averaging mode");
 
 // CPUs on the GPU's own socket (its PCI device's local_cpulist) that this process may run on; empty
@@ -179,6 +179,7 @@ struct pgh_ctx {
     pgh_detail::TrimState trim;
     pgh_detail::MedianState med;
     pgh_detail::MedianMeanState mam;
+    pgh_detail::RankTrimState rtrim;
     pgh_detail::GeomedState geo;
     pgh_detail::TrustState trust;
     pgh_detail::KrumState krum;
@@ -237,14 +238,16 @@ inline size_t esize(int dtype) { return dtype == PGH_F32 ? 4 : 8; }
 inline bool valid_mode(int m) {  // (pgh_effective_variant's alone: check_mode_use has its own switch)
     return m == PGH_MEAN || m == PGH_ITERATIVE_MEAN || m == PGH_WEIGHTED_MEAN || m == PGH_CLIPPED_MEAN ||
            m == PGH_TRIMMED_MEAN || m == PGH_MEDIAN || m == PGH_GEOMETRIC_MEDIAN || m == PGH_TRUSTED_MEAN ||
-           m == PGH_MEAN_AROUND_MEDIAN;
+           m == PGH_MEAN_AROUND_MEDIAN || m == PGH_RANK_TRIMMED_MEAN;
 }
-// A coordinate rule that takes every row of the cycle in one launch: the median, the mean around it.
-inline bool whole_cycle_coordinate_rule(int m) { return m == PGH_MEDIAN || m == PGH_MEAN_AROUND_MEDIAN; }
+// A coordinate rule that takes every row of the cycle in one launch: the median, the mean around it, the
+// rank-trimmed mean.
+inline bool whole_cycle_coordinate_rule(int m) { return m == PGH_MEDIAN || m == PGH_MEAN_AROUND_MEDIAN || m == PGH_RANK_TRIMMED_MEAN; }
 static_assert(PGH_TRUSTED_MEAN == 7, "the mode numbers are ABI: engine.py and every caller hold them as integers");
 static_assert(PGH_TRIMMED_MEAN == pgh::MODE_TRIMMED && PGH_TRIM_MAX == pgh::TRIM_MAX, "the kernels' numbering");
 static_assert(PGH_MEDIAN == pgh::MODE_MEDIAN && PGH_MEDIAN_NCHIP == pgh::MEDIAN_NCHIP, "the kernels' numbering");
 static_assert(PGH_MEAN_AROUND_MEDIAN == 8 && PGH_MEAN_AROUND_MEDIAN == pgh::MODE_MEAN_AROUND_MEDIAN, "the mode numbers are ABI; the kernels' numbering");
+static_assert(PGH_RANK_TRIMMED_MEAN == 9 && PGH_RANK_TRIMMED_MEAN == pgh::MODE_RANK_TRIMMED, "the mode numbers are ABI; the kernels' numbering");
 // The kernels' mode: a clipped mean is the weighted fold with the scales as weights, a geometric median the
 // weighted fold with the last Weiszfeld weights, a trusted mean the weighted fold with the trust weights.
 inline int kernel_mode(int m) {
@@ -487,6 +490,13 @@ inline const int32_t* median_rows(const pgh_ctx* c) { return c->med.d_rowidx.as<
 int median_mean_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hipStream_t s);
 // n - drop as the FINAL divisor; PGH_E_STATE with n <= drop, PGH_E_UNSUPPORTED past PGH_MEDIAN_NCHIP rows
 int median_mean_divisor(pgh_ctx* c, int64_t n, float* div);
+
+// ---- rank-trimmed mean (pgh_rules.cpp) -----------------------------------------------------------------
+// The whole fold of a filled FedavgArgs (diffs, map, n_rows, p, ckpt, out; every row of the cycle) on stream s:
+// K17's one launch over sort(values)[b : n_rows - b].
+int rank_trim_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hipStream_t s);
+// n - 2b as the FINAL divisor; PGH_E_STATE with n < 2b + 1, PGH_E_UNSUPPORTED past PGH_MEDIAN_NCHIP rows
+int rank_trim_divisor(pgh_ctx* c, int64_t n, float* div);
 
 // ---- server optimizer (pgh_serveropt.cpp) --------------------------------------------------------------
 struct FinalArgs;

@@ -730,6 +730,10 @@ int set_median_drop(pgh_ctx* c, int drop) {
     return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_median_drop(k, drop); }, (int)G(c)->kids.size());
 }
 
+int set_rank_trim(pgh_ctx* c, int b) {
+    return fan(c, [&](int, pgh_ctx* k) -> int { return pgh_set_rank_trim(k, b); }, (int)G(c)->kids.size());
+}
+
 // The server optimizer looks at one parameter at a time: every child runs it on its own shard.
 int set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2, float tau) {
     pgh_group* g = G(c);

@@ -64,6 +64,7 @@ int set_ingest_ranges(pgh_ctx* c, int on);
 int set_weights(pgh_ctx* c, const float* w, int n);
 int set_trim(pgh_ctx* c, int b);
 int set_median_drop(pgh_ctx* c, int drop);
+int set_rank_trim(pgh_ctx* c, int b);
 int set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2, float tau);
 int server_opt_commit(pgh_ctx* c);
 int server_opt_steps(pgh_ctx* c, int64_t* committed);

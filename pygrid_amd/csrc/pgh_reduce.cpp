@@ -107,6 +107,10 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
         RC(median_mean_fold(c, a, rows.src, s));
         return opt ? server_opt_launch(c, fa, s) : PGH_OK;
     }
+    if (mode == PGH_RANK_TRIMMED_MEAN) {  // (likewise)
+        RC(rank_trim_fold(c, a, rows.src, s));
+        return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+    }
     // HBM bytes: the rows; the running state in unless FIRST; the state out, or ckpt in and out when FINAL
     const uint64_t pg = (uint64_t)fa.len;
     uint64_t bytes = 4ull * (uint64_t)rows.n * pg + ((flags & pgh::FL_FIRST) ? 0 : 4 * pg) +
@@ -250,6 +254,8 @@ int fedavg_divisor(pgh_ctx* c, int mode, int64_t n, float* div) {
         RC(trim_divisor(c, n, div));
     } else if (mode == PGH_MEAN_AROUND_MEDIAN) {
         RC(median_mean_divisor(c, n, div));
+    } else if (mode == PGH_RANK_TRIMMED_MEAN) {
+        RC(rank_trim_divisor(c, n, div));
     } else if (mode == PGH_WEIGHTED_MEAN) {
         if ((int64_t)c->fw.v.size() < n)
             return fail(c, PGH_E_STATE, "weighted mean needs %lld weights, have %zu", (long long)n, c->fw.v.size());

@@ -2,7 +2,7 @@
 // reductions (RowSums: K7 and K14 through their per-slot caches, K12 and K14 over a listed set of rows, K13, K16) and
 // the Multi-Krum selection over them; clipping's scales and tallies; the Gaussian noise on the clipped close (K11
 // behind a FINAL launch, its plane, setting and entry points); the trimmed mean's state planes (K8); the
-// median's driver and row table (K9, K9p); the mean around the median's driver (K15); what the geometric median and the trust rule share (the finite rows
+// median's driver and row table (K9, K9p); the mean around the median's driver (K15); the rank-trimmed mean's (K17); what the geometric median and the trust rule share (the finite rows
 // of a close, the resident weights, the plan over the included rows) and each one's own: the inner iterations
 // and final weights (K12 between weighted folds), the root and the weights from the cached dots; the context's
 // -0 plane; what the rules' state does at each lifecycle event of the context (rules_*: the one call each
@@ -71,6 +71,10 @@ int mode_use_rule(pgh_ctx* c, int mode, ModeUse use) {
         RC(one_fold_cycle_use(c, mode, use, false));
         if (!c->grp && c->mam.drop == 0) return fail(c, PGH_E_STATE, "PGH_MEAN_AROUND_MEDIAN needs a drop count: call pgh_set_median_drop first");
         return PGH_OK;
+    case PGH_RANK_TRIMMED_MEAN:
+        RC(one_fold_cycle_use(c, mode, use, false));
+        if (!c->grp && c->rtrim.b == 0) return fail(c, PGH_E_STATE, "PGH_RANK_TRIMMED_MEAN needs a trim count: call pgh_set_rank_trim first");
+        return PGH_OK;
     case PGH_GEOMETRIC_MEDIAN:
         RC(one_fold_cycle_use(c, mode, use, true));
         if (c->geo.iters == 0) return fail(c, PGH_E_STATE, "PGH_GEOMETRIC_MEDIAN needs its setting: call pgh_set_geomed first");
@@ -116,7 +120,7 @@ void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep
     if (!(same_shard && pvec == c->pvec)) c->nz.d.reset();     // (its tenants above and below are gone with it)
     if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
     c->geo.release();  // (free_slab has dropped the plane; the setting goes with the layout or shard)
-    if (!keep_opt) c->mam.drop = 0;  // (a group's pgh_reserve lays its children out again: the setting stays)
+    if (!keep_opt) c->mam.drop = c->rtrim.b = 0;  // (a group's pgh_reserve lays its children out again: the settings stay)
     c->trust.release();
 }
 
@@ -153,7 +157,7 @@ int rules_row_ingested(pgh_ctx* c, int slot) {
 }
 
 const char* rules_one_fold_cycle(int mode) {
-    return mode == PGH_MEDIAN ? "a median" : mode == PGH_MEAN_AROUND_MEDIAN ? "a mean around the median" : mode == PGH_GEOMETRIC_MEDIAN ? "a geometric median" : mode == PGH_TRUSTED_MEAN ? "a trusted mean" : nullptr;
+    return mode == PGH_MEDIAN ? "a median" : mode == PGH_MEAN_AROUND_MEDIAN ? "a mean around the median" : mode == PGH_RANK_TRIMMED_MEAN ? "a rank-trimmed mean" : mode == PGH_GEOMETRIC_MEDIAN ? "a geometric median" : mode == PGH_TRUSTED_MEAN ? "a trusted mean" : nullptr;
 }
 
 int NegZeroPlane::ensure(pgh_ctx* c, hipStream_t s) {
@@ -243,6 +247,33 @@ int median_mean_divisor(pgh_ctx* c, int64_t n, float* div) {
     if (n > pgh::MEDIAN_NCHIP)
         return fail(c, PGH_E_UNSUPPORTED, "mean around the median: %lld diffs, the on-chip kernel takes %d", (long long)n, pgh::MEDIAN_NCHIP);
     *div = (float)(n - (int64_t)c->mam.drop);
+    return PGH_OK;
+}
+
+// ---- rank-trimmed mean: the fold's launch (K17) -----------------------------------------------------------------
+
+int rank_trim_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, hipStream_t s) {
+    pgh::RankTrimArgs m{};
+    m.diffs = a.diffs;
+    m.map = a.map;
+    m.n_rows = a.n_rows;
+    m.b = c->rtrim.b;
+    m.p = a.p;
+    m.ckpt = a.ckpt;
+    m.out = a.out;
+    if (m.b < 1 || a.n_rows < 2 * (int64_t)m.b + 1 || a.n_rows > pgh::MEDIAN_NCHIP)  // (rank_trim_divisor has refused all at the entry points)
+        return fail(c, PGH_E_STATE, "rank-trimmed mean: %d rows with a trim count of %d", a.n_rows, m.b);
+    // the slab once, ckpt in, out
+    return timed_launch(c, s, 4ull * (uint64_t)a.n_rows * (uint64_t)a.p + 8 * (uint64_t)a.p, [&] { return pgh::launch_rank_trim(m, rows, s); });
+}
+
+int rank_trim_divisor(pgh_ctx* c, int64_t n, float* div) {
+    if (n < 2 * (int64_t)c->rtrim.b + 1)
+        return fail(c, PGH_E_STATE, "rank-trimmed mean with a trim count of %d needs at least %lld diffs, have %lld", c->rtrim.b,
+                    2 * (long long)c->rtrim.b + 1, (long long)n);
+    if (n > pgh::MEDIAN_NCHIP)
+        return fail(c, PGH_E_UNSUPPORTED, "rank-trimmed mean: %lld diffs, the on-chip kernel takes %d", (long long)n, pgh::MEDIAN_NCHIP);
+    *div = (float)(n - 2 * (int64_t)c->rtrim.b);
     return PGH_OK;
 }
 
@@ -763,6 +794,17 @@ int pgh_set_median_drop(pgh_ctx* c, int drop) {
         return fail(c, PGH_E_STATE, "drop count changed from %d to %d with %lld diffs of the cycle folded", c->mam.drop, drop,
                     (long long)c->folded);
     c->mam.drop = drop;
+    return PGH_OK;
+}
+
+int pgh_set_rank_trim(pgh_ctx* c, int b) {
+    if (!c) return PGH_E_ARG;
+    if (b < 0) return fail(c, PGH_E_ARG, "trim count %d is negative", b);
+    if (c->grp) return pgh_group_api::set_rank_trim(c, b);
+    if (b != c->rtrim.b && c->folded > 0 && !c->streaming)
+        return fail(c, PGH_E_STATE, "trim count changed from %d to %d with %lld diffs of the cycle folded", c->rtrim.b, b,
+                    (long long)c->folded);
+    c->rtrim.b = b;
     return PGH_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "pgh_gram.h"
 #include "pgh_kernels.h"
 #include "pgh_median_mean.h"
+#include "pgh_rank_trim.h"
 #include "pgh_res.h"
 
 struct pgh_ctx;
@@ -304,6 +305,13 @@ struct MedianState {
 // The setting belongs to the model: pgh_reset / pgh_reserve keep it, a new layout or shard clears it.
 struct MedianMeanState {
     int drop = 0;  // values dropped per parameter, the farthest from the median; 0 = the rule is off
+};
+
+// Rank-trimmed mean (pgh_set_rank_trim, PGH_RANK_TRIMMED_MEAN): the trim count.  K17 keeps
+// everything on chip; a slot list longer than a RowTab goes to it through the median's device table.  The setting
+// belongs to the model, as the mean around the median's does.
+struct RankTrimState {
+    int b = 0;  // values dropped per side and parameter; 0 = the rule is off
 };
 
 // Server optimizer (pgh_set_server_opt).  With one set, fold_launch runs every

@@ -29,9 +29,9 @@ import numpy as np
 from . import state as state_codec
 from .engine import ITERATIVE_MEAN, MEAN, TRUSTED_MEAN, WEIGHTED_MEAN, F32, I64, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
-from .robust import CLIP_KEY, MAM_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, check_median_drop, check_trim_count, clip_norm_of, failing_closed, median_of, \
+from .robust import CLIP_KEY, MAM_KEY, MEDIAN_KEY, RANK_TRIM_KEY, TRIM_KEY, UNSET, check_median_drop, check_trim_count, clip_norm_of, failing_closed, median_of, \
     rule_of, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
-from . import krum as krum_mod, serveropt, trust as trust_mod
+from . import krum as krum_mod, robust, serveropt, trust as trust_mod
 from .dp import DpKeys
 from .serveropt import ServerOptStates
 from .settings import settings_of
@@ -185,16 +185,16 @@ def cached_mode(server_config: dict, plan_key, mean_plans: Optional[str] = None)
 def select_mode(server_config: dict, avg_plan: Optional[Callable] = None, weights=None, plan_key=None,
                 mean_plans: Optional[str] = None, shapes=None, n_clients=None, clip_norm=None,
                 trim_count=None, median: bool = False, geometric_median=None, trust=None,
-                mean_around_median=None) -> int:
+                mean_around_median=None, rank_trim=None) -> int:
     """The dispatch rule below; under a rule (``robust.rule_of`` of ``clip_norm``, ``trim_count``,
-    ``median``, ``geometric_median`` and ``mean_around_median``, parsed values; ``server_config``'s own keys are not read): the rule's
+    ``median``, ``geometric_median``, ``mean_around_median`` and ``rank_trim``, parsed values; ``server_config``'s own keys are not read): the rule's
     mode -- ``CLIPPED_MEAN``, ``TRIMMED_MEAN``, ``MEDIAN``, ``GEOMETRIC_MEDIAN`` -- exactly where the dispatch gives ``MEAN`` (no
     hosted plan, or a plan probed equal to the mean) and the rule's error everywhere else -- weights,
     the iterative plan, a plan the engine declines -- so that the caller cannot fall back to an
     average that does not apply the rule.  ``trust`` (a parsed ``trust.TrustSpec``, without a rule): ``TRUSTED_MEAN``
     in the same places and ``TrustUnavailableError`` everywhere else."""
     rule = rule_of(server_config, clip_norm=clip_norm, trim_count=trim_count, median=median,
-                   geometric_median=geometric_median, mean_around_median=mean_around_median)
+                   geometric_median=geometric_median, mean_around_median=mean_around_median, rank_trim=rank_trim)
     if rule is None and trust is not None:
         if weights is not None:
             raise trust_mod.refuse("cannot be combined with aggregation weights")
@@ -339,7 +339,7 @@ class CycleAggregator:
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
                            plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
                            dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
-                           trust_root=None, mean_around_median=UNSET, bulyan=UNSET) -> bytes:
+                           trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -356,12 +356,13 @@ class CycleAggregator:
         shaped like a diff, a sequence of arrays or a flat array), required beside it: ``TrustUnavailableError``
         without one.  ``mean_around_median`` / ``bulyan``: the mean of the values nearest the median
         (``robust.mean_around_median_of``; default ``server_config["diff_mean_around_median"]``) and the Bulyan shorthand
-        (``settings.bulyan_of``; default ``server_config["diff_bulyan"]``)."""
+        (``settings.bulyan_of``; default ``server_config["diff_bulyan"]``).  ``rank_trim``: the trimmed mean by rank, any
+        trim count or a trim fraction (``robust.rank_trim_of``; default ``server_config["diff_trimmed_mean"]``)."""
         if framing not in ("fresh", "template"):
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim)
         with self._closing(server_config, given, avg_plan, weights, plan_key, lambda: _shapes_or_none(checkpoint),
                            lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round, trust_root) as (settings, mode):
             return self._average_plan_diffs(checkpoint, diffs, weights, framing, settings, mode)
@@ -372,10 +373,10 @@ class CycleAggregator:
         """What both entry points do before their first ingest, and the fail-closed block they fold in:
         gives ``(settings, mode)`` with the engine laid out for ``numel_of()`` and ``n_diffs`` rows, the rule and the
         noise set and ``opt_key``'s moments bound.  ``given``: the caller's clip_norm, trim_count, median, dp_noise,
-        geometric_median, krum, trust, mean_around_median, bulyan.  Under the trust rule the cycle's ``trust_root`` goes onto the engine here too,
+        geometric_median, krum, trust, mean_around_median, bulyan, rank_trim.  Under the trust rule the cycle's ``trust_root`` goes onto the engine here too,
         ahead of the ingests: each diff's inner product with it rides behind its copy."""
         settings = settings_of(server_config, *given[:4], geometric_median=given[4], krum=given[5], trust=given[6],
-                               mean_around_median=given[7], bulyan=given[8])
+                               mean_around_median=given[7], bulyan=given[8], rank_trim=given[9])
         with settings.fail_closed("the engine cannot average this cycle"):
             mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                                shapes=shapes, n_clients=n_diffs, trust=settings.trust, **settings.rule_kwargs())
@@ -385,10 +386,15 @@ class CycleAggregator:
                 check_trim_count(settings.rule.value, n_diffs)  # (under a selection: of the picked diffs, _finish_picked)
             if settings.rule is not None and settings.rule.key == MAM_KEY and settings.select is None:
                 check_median_drop(settings.rule.value, n_diffs)
+            rank_trim = settings.rule is not None and settings.rule.key == RANK_TRIM_KEY and settings.select is None
+            if rank_trim:
+                robust.rank_trim_count(settings.rule.value, n_diffs)  # (refused before anything is ingested)
             numel = numel_of()
             self._prepare(numel, n_diffs)
             # before the first ingest: each diff's norm pass rides behind its copy
             settings.set_on_engine(self.engine, settings.noise_key(self.dp_keys, opt_key), dp_round)
+            if rank_trim:  # N is known: the resolved b (under a selection: of the picked diffs, _finish_picked)
+                robust.set_rank_trim(self.engine, settings.rule.value, n_diffs)
             self.opt_states.bind(self.engine, opt_key, settings.opt, sum(numel))  # before the fold: its moments
             if settings.trust is not None:
                 trust_mod.set_root(self.engine, trust_root, numel)
@@ -403,6 +409,8 @@ class CycleAggregator:
             check_trim_count(settings.rule.value, len(picked))
         if settings.rule is not None and settings.rule.key == MAM_KEY:
             check_median_drop(settings.rule.value, len(picked))
+        if settings.rule is not None and settings.rule.key == RANK_TRIM_KEY:
+            robust.set_rank_trim(self.engine, settings.rule.value, len(picked))
         if mode == WEIGHTED_MEAN:
             self.engine.set_weights([weights[i] for i in picked])
         self.engine.fold_slots_finish_resident(mode, picked)
@@ -440,12 +448,12 @@ class CycleAggregator:
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
                        weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
                        dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
-                       trust_root=None, mean_around_median=UNSET, bulyan=UNSET) -> List[np.ndarray]:
+                       trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         shapes = [np.shape(p) for p in model_params]
         numel = [int(np.prod(s)) for s in shapes]
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim)
         with self._closing(server_config, given, avg_plan, weights, None, shapes, lambda: numel, len(diffs), opt_key,
                            dp_round, trust_root) as (settings, mode):
             for i, d in enumerate(diffs):

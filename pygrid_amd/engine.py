@@ -17,6 +17,7 @@ from .exceptions import AggregationError, EngineUnavailableError, StateParseErro
 
 MEAN, ITERATIVE_MEAN, WEIGHTED_MEAN, CLIPPED_MEAN, TRIMMED_MEAN, MEDIAN, GEOMETRIC_MEDIAN, TRUSTED_MEAN = 0, 1, 2, 3, 4, 5, 6, 7
 MEAN_AROUND_MEDIAN = 8  # PGH_MEAN_AROUND_MEDIAN
+RANK_TRIMMED_MEAN = 9   # PGH_RANK_TRIMMED_MEAN
 GEOMED_MAX_ITERS = 16  # PGH_GEOMED_MAX_ITERS
 KRUM_MAX_ROWS = 1024   # PGH_KRUM_MAX_ROWS
 TRIM_MAX = 8  # PGH_TRIM_MAX
@@ -28,7 +29,7 @@ OPT_NONE, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 0, 1, 2, 3, 4  # pgh_s
 MODE_NAMES = {MEAN: "mean", ITERATIVE_MEAN: "iterative_mean", WEIGHTED_MEAN: "weighted_mean",
               CLIPPED_MEAN: "clipped_mean", TRIMMED_MEAN: "trimmed_mean", MEDIAN: "median",
               GEOMETRIC_MEDIAN: "geometric_median", TRUSTED_MEAN: "trusted_mean",
-              MEAN_AROUND_MEDIAN: "mean_around_median"}
+              MEAN_AROUND_MEDIAN: "mean_around_median", RANK_TRIMMED_MEAN: "rank_trimmed_mean"}
 
 
 def device_count() -> int:
@@ -526,6 +527,13 @@ class Engine:
         are under way."""
         self._check(self._lib.pgh_set_median_drop(self._h, int(c)), "set_median_drop")
 
+    # ---- rank-trimmed mean (RANK_TRIMMED_MEAN; kernel K17) ---------------------------------------------
+    def set_rank_trim(self, b: int):
+        """Values dropped per side and parameter by later RANK_TRIMMED_MEAN closes, any b >= 1 with
+        N >= 2 b + 1 (``include/pgh_api.h``); 0 turns the setting off.  Refused (PGH_E_STATE) while slot folds
+        of a cycle are under way.  ``set_trim`` and TRIMMED_MEAN are not affected."""
+        self._check(self._lib.pgh_set_rank_trim(self._h, int(b)), "set_rank_trim")
+
     # ---- server optimizers (FedAvgM, FedAdagrad, FedAdam, FedYogi) ---------------------------------
     def set_server_opt(self, kind: int, lr: float = 0.0, beta1: float = 0.0, beta2: float = 0.0, tau: float = 0.0):
         """How later fp32 closes apply the average (``pgh_set_server_opt``): OPT_MOMENTUM .. OPT_YOGI,
@@ -726,7 +734,7 @@ class Engine:
     def effective_variant(self, mode: int = MEAN) -> int:
         """Kernel variant the next fold runs for ``mode`` (MEAN / ITERATIVE_MEAN / WEIGHTED_MEAN /
         STREAM_SECAGG; TRIMMED_MEAN: 40 for 16-byte columns, 41 for one parameter per lane; MEDIAN: 50
-        for the on-chip kernel, 51 for one pass per key bit, by the diffs held now; MEAN_AROUND_MEDIAN: 60)."""
+        for the on-chip kernel, 51 for one pass per key bit, by the diffs held now; MEAN_AROUND_MEDIAN: 60; RANK_TRIMMED_MEAN: 70)."""
         v = self._lib.pgh_effective_variant(self._h, int(mode))
         self._check(min(v, 0), "effective_variant")
         return v

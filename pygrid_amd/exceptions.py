@@ -69,6 +69,15 @@ class MeanAroundMedianUnavailableError(AggregationError):
     NOT a ``PlanNotAcceleratedError``: the node's own averaging drops nothing, so the close fails closed."""
 
 
+class RankTrimUnavailableError(AggregationError):
+    """The FL process asks for the rank-trimmed mean (``server_config["diff_trimmed_mean"]``: a trim count of any
+    size or a trim fraction) and the engine cannot take it this cycle: a hosted iterative or unaccelerated plan, a
+    non-float32 model, aggregation weights or another rule given together with it, more diffs at the close than
+    the slab has slots or than the on-chip kernel takes (1,024), or fewer than ``2 b + 1`` diffs.  Like the other
+    rules' errors it is NOT a ``PlanNotAcceleratedError``: the node's own averaging trims nothing, so the close
+    fails closed."""
+
+
 class GeometricMedianUnavailableError(AggregationError):
     """The FL process asks for the geometric median (``server_config["diff_geometric_median"]``) and the
     engine cannot take it this cycle: a hosted iterative or unaccelerated plan, a non-float32 model,

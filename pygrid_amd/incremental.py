@@ -69,7 +69,7 @@ from .cycle import _decline_non_float32
 from .engine import F32, MEAN, TRUSTED_MEAN, WEIGHTED_MEAN, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
 from . import dp, krum as krum_mod, serveropt, trust as trust_mod
-from .robust import check_median_drop, check_trim_count, failing_closed
+from .robust import check_median_drop, check_trim_count, failing_closed, rank_trim_count, set_rank_trim
 from .settings import CloseSettings, settings_of
 
 DEFAULT_HBM_BUDGET = 64 << 30  # bytes of diffs kept in HBM per cycle when `slots` is not given
@@ -88,7 +88,7 @@ class IncrementalCycle:
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
                  median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
                  dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None, krum=None, trust=None,
-                 trust_root=None, mean_around_median=None, bulyan=None):
+                 trust_root=None, mean_around_median=None, bulyan=None, rank_trim=None):
         """``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
         ``median``, ``geometric_median``, ``server_opt``, ``dp_noise`` and ``krum`` below (both: an error); keys,
         round and stores go beside either.
@@ -119,6 +119,12 @@ class IncrementalCycle:
         MEAN_AROUND_MEDIAN finish over every held (or picked) slot in the close's order, at most as many diffs as
         slots -- with ``MeanAroundMedianUnavailableError`` where the median raises its own, and at a close of no
         more diffs than c.
+
+        ``rank_trim``: the FL process's trimmed mean by rank (``robust.rank_trim_of``: the setting's dict or its parsed
+        form), any trim count or a trim fraction.  Wired like the median -- ``mode`` MEAN, no weights, no other rule,
+        nothing folded early, one RANK_TRIMMED_MEAN finish over every held (or picked) slot in the close's order, at
+        most as many diffs as slots; b resolves at the close, from the number of diffs it folds -- with
+        ``RankTrimUnavailableError`` where the median raises its own, and at a close of fewer than ``2 b + 1`` diffs.
 
         ``dp_noise``: the FL process's noise setting (``dp.dp_noise_of``; it needs ``clip_norm``), drawn for
         ``dp_round`` (the cycle's id) from the key it names or ``opt_key``'s in ``dp_keys`` (share the
@@ -157,7 +163,8 @@ class IncrementalCycle:
                                        krum=None if krum is False else krum,
                                        trust=None if trust is False else trust,
                                        mean_around_median=None if mean_around_median is False else mean_around_median,
-                                       bulyan=None if bulyan is False else bulyan).items() if v is not None}
+                                       bulyan=None if bulyan is False else bulyan,
+                                       rank_trim=None if rank_trim is False else rank_trim).items() if v is not None}
         if settings is not None and given:
             raise AggregationError(f"settings= was given beside {', '.join(given)}")
         self._settings = settings = settings if settings is not None else settings_of({}, **given)
@@ -168,13 +175,13 @@ class IncrementalCycle:
         if self._trust is not None and (mode != MEAN or weights_by_worker is not None):
             raise trust_mod.refuse("applies to the plain mean only (no weights, no iterative plan)")
         self.clip_norm, self.trim_count, self.median, self.geometric_median = None, None, False, None
-        self.mean_around_median = None
+        self.mean_around_median, self.rank_trim = None, None
         if rule is not None:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
         # a rule that needs every row of the cycle in one call: nothing folds early, no partial fold at the close
         self._select = settings.select
         self._whole = bool(self.median) or self.geometric_median is not None or self._select is not None \
-            or self.mean_around_median is not None \
+            or self.mean_around_median is not None or self.rank_trim is not None \
             or self._trust is not None
         self._fold_mode = rule.mode if rule else TRUSTED_MEAN if self._trust is not None else mode
         self._noise_args = (settings.noise_key(dp_keys if dp_keys is not None else dp.DpKeys(), opt_key), dp_round)
@@ -482,6 +489,8 @@ class IncrementalCycle:
                 check_trim_count(self.trim_count, len(order))
             if self.mean_around_median is not None and self._select is None:
                 check_median_drop(self.mean_around_median, len(order))
+            if self.rank_trim is not None and self._select is None:
+                rank_trim_count(self.rank_trim, len(order))
             if self._whole and len(order) > self.slots:  # every row at once: no partial fold, no slot given up
                 raise self._whole_refuse(f"is set and the cycle has {len(order)} diffs, the slab {self.slots} slots: "
                                          f"{self._whole_name()} needs every diff in HBM at once")
@@ -575,13 +584,14 @@ class IncrementalCycle:
 
     def _whole_name(self) -> str:
         return "a median" if self.median else "a mean around the median" if self.mean_around_median is not None else \
+            "a rank-trimmed mean" if self.rank_trim is not None else \
             "a geometric median" if self.geometric_median is not None else \
             "a trusted mean" if self._trust is not None else "a selection"
 
     def _whole_refuse(self, why: str) -> AggregationError:
         """The refusal of whatever needs every row at once: the rule's, else the selection's."""
         whole_rule = self._rule is not None and (self.median or self.geometric_median is not None
-                                                 or self.mean_around_median is not None)
+                                                 or self.mean_around_median is not None or self.rank_trim is not None)
         if not whole_rule and self._trust is not None:
             return trust_mod.refuse(why)
         return self._rule.refuse(why) if whole_rule else krum_mod.refuse(why)
@@ -596,6 +606,8 @@ class IncrementalCycle:
                 check_trim_count(self.trim_count, len(ws_picked))
             if self.mean_around_median is not None:
                 check_median_drop(self.mean_around_median, len(ws_picked))
+            if self.rank_trim is not None:
+                set_rank_trim(self.engine, self.rank_trim, len(ws_picked))
             if self.mode == WEIGHTED_MEAN and self._weights_by_worker is not None:
                 self._weights = [float(self._weights_by_worker[w]) for w in ws_picked]
                 self.engine.set_weights(self._weights)
@@ -605,6 +617,8 @@ class IncrementalCycle:
                 self._weights.extend(float(self._weights_by_worker[w]) for w in ws)
                 if self._weights:
                     self.engine.set_weights(self._weights)
+            if final and self.rank_trim is not None:  # (every diff of the close: _whole) b for their number
+                set_rank_trim(self.engine, self.rank_trim, len(slots))
             if final:
                 self.engine.fold_slots_finish_resident(self._fold_mode, slots)
             else:

@@ -1,5 +1,6 @@
 """The robust-aggregation rules an FL process can ask for in its ``server_config`` -- per-client L2
-clipping, the coordinate-wise trimmed mean, the coordinate-wise median, the mean around the median, the geometric median (none has a
+clipping, the coordinate-wise trimmed mean (by a small count, or by rank for any count or fraction), the coordinate-wise median, the mean around
+the median, the geometric median (none has a
 reference counterpart) -- and what the host layer does with them, once:
 
 * ``KINDS`` (with ``LATER_KINDS``: ``ALL_KINDS``) is the only place that ties a rule to its config key, the engine mode it turns ``MEAN``
@@ -19,13 +20,16 @@ from __future__ import annotations
 
 import contextlib
 import dataclasses
+import fractions
+import math
 from typing import Optional
 
 import numpy as np
 
-from .engine import CLIPPED_MEAN, GEOMED_MAX_ITERS, GEOMETRIC_MEDIAN, MEAN_AROUND_MEDIAN, MEDIAN, TRIMMED_MEAN, TRIM_MAX
+from .engine import CLIPPED_MEAN, GEOMED_MAX_ITERS, GEOMETRIC_MEDIAN, MEAN_AROUND_MEDIAN, MEDIAN, RANK_TRIMMED_MEAN, TRIMMED_MEAN, \
+    TRIM_MAX
 from .exceptions import AggregationError, ClipUnavailableError, GeometricMedianUnavailableError, \
-    MeanAroundMedianUnavailableError, MedianUnavailableError, PlanNotAcceleratedError, TrimUnavailableError
+    MeanAroundMedianUnavailableError, MedianUnavailableError, PlanNotAcceleratedError, RankTrimUnavailableError, TrimUnavailableError
 
 CLIP_KEY = "diff_clip_norm"  # optional server_config key: the per-client L2 bound (no reference counterpart)
 
@@ -125,6 +129,58 @@ def check_median_drop(drop: int, n_diffs: int):
         raise MeanAroundMedianUnavailableError(f"{MAM_KEY} drops {drop} values per parameter, the close has {n_diffs} diffs")
 
 
+RANK_TRIM_KEY = "diff_trimmed_mean"  # optional server_config key: the trimmed mean by rank, any trim count or a fraction
+
+
+@dataclasses.dataclass(frozen=True)
+class RankTrim:
+    """The parsed ``diff_trimmed_mean``: exactly one of ``count`` (b itself) and ``fraction`` (beta, 0 < beta < 0.5)."""
+    count: Optional[int] = None
+    fraction: Optional[float] = None
+
+    def setting(self) -> dict:
+        return {"count": self.count} if self.count is not None else {"fraction": self.fraction}
+
+
+def rank_trim_of(server_config: dict) -> Optional[RankTrim]:
+    """The FL process's rank-trimmed mean, ``server_config["diff_trimmed_mean"]``: ``{"count": b}`` (an int >= 1)
+    or ``{"fraction": beta}`` (a float, 0 < beta < 0.5).  Absent, ``None`` or ``False``: None.  Anything else --
+    another type, both fields, neither, an unknown one, a bool or an int where the fraction belongs, a value out of
+    range -- raises ``AggregationError``: a mistyped setting must not quietly mean "the plain mean"."""
+    cfg = server_config.get(RANK_TRIM_KEY, None)
+    if isinstance(cfg, RankTrim):  # the parsed form (a Rule's value) back as the setting
+        cfg = cfg.setting()
+    if cfg is None or (isinstance(cfg, (bool, np.bool_)) and not cfg):
+        return None
+    if not isinstance(cfg, dict) or list(cfg) not in (["count"], ["fraction"]):
+        raise AggregationError(f"{RANK_TRIM_KEY} must be a dict of 'count' or of 'fraction' alone, None or False, not {cfg!r}")
+    if "count" in cfg:
+        return RankTrim(count=count_of(RANK_TRIM_KEY, "count", cfg))
+    beta = cfg["fraction"]
+    if not isinstance(beta, (float, np.floating)) or not 0.0 < float(beta) < 0.5:  # (a NaN compares false)
+        raise AggregationError(f"{RANK_TRIM_KEY}['fraction'] must be a float with 0 < fraction < 0.5, not {beta!r}")
+    return RankTrim(fraction=float(beta))
+
+
+def rank_trim_count(trim: RankTrim, n_diffs: int) -> int:
+    """b of a close of ``n_diffs`` diffs.  A fraction resolves here, when N is known, as Krum's keep count does:
+    ``ceil(N * beta)`` with beta the decimal the operator wrote (0.1 of 1,000 is 100, not the 101 that the
+    nearest double of 0.1 would give) -- the ceiling, so that a set rule never silently trims nothing.  The close
+    needs ``2 b + 1`` diffs (one value must be left per parameter): ``RankTrimUnavailableError`` otherwise."""
+    b = trim.count if trim.count is not None else math.ceil(n_diffs * fractions.Fraction(str(trim.fraction)))
+    if n_diffs < 2 * b + 1:
+        raise RankTrimUnavailableError(f"{RANK_TRIM_KEY} = {trim.setting()!r} trims {b} values per side and needs at "
+                                       f"least {2 * b + 1} diffs, the close has {n_diffs}")
+    return b
+
+
+def set_rank_trim(engine, trim: RankTrim, n_diffs: int) -> int:
+    """Right before the closing fold of ``n_diffs`` diffs: the resolved b, checked, onto the engine."""
+    b = rank_trim_count(trim, n_diffs)
+    engine.set_rank_trim(b)
+    return b
+
+
 GEOMED_KEY = "diff_geometric_median"  # optional server_config key: the geometric median, RFA (no reference counterpart)
 GEOMED_DEFAULTS = (3, 1e-6)  # (iterations, smoothing): the RFA paper's
 _GEOMED_FIELDS = ("iterations", "smoothing")
@@ -177,6 +233,9 @@ class Rule:
     setter: Optional[str] = None
     off: object = None            # what that method takes for "no rule"
     value: object = None          # the parsed setting
+    # the engine's value resolves at the close, which knows N (a trim fraction): until then the setter is given
+    # ``off``, and a closing fold that came without the resolved value is refused by the engine (PGH_E_STATE)
+    at_close: bool = False
 
     def refuse(self, why: str) -> AggregationError:
         """The rule's error, to raise: ``<key> <why>``."""
@@ -195,6 +254,8 @@ KINDS = (
 LATER_KINDS = (
     Rule(MAM_KEY, "mean_around_median", MEAN_AROUND_MEDIAN, MeanAroundMedianUnavailableError,
          "drops nothing around the median", "set_median_drop", 0),
+    Rule(RANK_TRIM_KEY, "rank_trim", RANK_TRIMMED_MEAN, RankTrimUnavailableError, "does not trim", "set_rank_trim", 0,
+         at_close=True),
 )
 ALL_KINDS = KINDS + LATER_KINDS
 
@@ -202,7 +263,7 @@ UNSET = object()  # an argument left out: the setting comes from server_config
 
 
 def rule_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, geometric_median=UNSET,
-            mean_around_median=UNSET) -> Optional[Rule]:
+            mean_around_median=UNSET, rank_trim=UNSET) -> Optional[Rule]:
     """The cycle's rule, or None.  An argument that is given overrides its ``server_config`` key
     (``None``: off).  Every setting is parsed, so a malformed one raises ``AggregationError`` even
     beside a rule that would win; two valid ones raise the error of the rule earlier in ``ALL_KINDS``."""
@@ -211,10 +272,10 @@ def rule_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET
     if isinstance(mean_around_median, int) and not isinstance(mean_around_median, bool):  # likewise
         mean_around_median = {"drop": mean_around_median}
     given = {CLIP_KEY: clip_norm, TRIM_KEY: trim_count, MEDIAN_KEY: median, GEOMED_KEY: geometric_median,
-             MAM_KEY: mean_around_median}
+             MAM_KEY: mean_around_median, RANK_TRIM_KEY: rank_trim}
     cfg = {k: server_config.get(k, None) if v is UNSET else v for k, v in given.items()}
     values = {CLIP_KEY: clip_norm_of(cfg), TRIM_KEY: trim_count_of(cfg), MEDIAN_KEY: median_of(cfg) or None,
-              GEOMED_KEY: geomed_of(cfg), MAM_KEY: mean_around_median_of(cfg)}
+              GEOMED_KEY: geomed_of(cfg), MAM_KEY: mean_around_median_of(cfg), RANK_TRIM_KEY: rank_trim_of(cfg)}
     active = [dataclasses.replace(k, value=values[k.key]) for k in ALL_KINDS if values[k.key] is not None]
     if len(active) > 1:
         raise active[0].refuse(f"cannot be combined with {active[1].key}")
@@ -250,7 +311,7 @@ def set_on_engine(engine, rule: Optional[Rule]):
                 getattr(engine, kind.setter)(*args(kind.off))
             continue
         try:
-            getattr(engine, kind.setter)(*args(rule.value))
+            getattr(engine, kind.setter)(*args(kind.off if kind.at_close else rule.value))
         except AttributeError as e:
             raise rule.refuse(f"is set but the engine has no {kind.setter}") from e
         except AggregationError as e:

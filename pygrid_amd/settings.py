@@ -19,7 +19,7 @@ from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
 from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, KrumUnavailableError, \
     MeanAroundMedianUnavailableError, PlanNotAcceleratedError, ServerOptUnavailableError, TrustUnavailableError
 from .krum import KRUM_KEY, KrumSpec, krum_of
-from .robust import CLIP_KEY, GEOMED_KEY, MAM_KEY, MEDIAN_KEY, TRIM_KEY, UNSET, Rule, rule_of
+from .robust import CLIP_KEY, GEOMED_KEY, MAM_KEY, MEDIAN_KEY, RANK_TRIM_KEY, TRIM_KEY, UNSET, Rule, rule_of
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
 from .trust import TRUST_KEY, TrustSpec, trust_of
 
@@ -138,6 +138,8 @@ class CloseSettings:
             stats["mean_around_median"] = {"drop": int(self._value(MAM_KEY))}
             if self.bulyan is not None:
                 stats["mean_around_median"]["byzantine"] = int(self.bulyan)
+        if self._value(RANK_TRIM_KEY) is not None:  # one more key, under this rule alone: the setting as parsed
+            stats["trimmed_mean"] = self._value(RANK_TRIM_KEY).setting()
         if self.select is not None:  # one more key, under a selection alone
             stats["krum"] = krum_mod.close_stats(engine, self.select)
         if self.trust is not None:  # one more key, under the trust rule alone
@@ -170,7 +172,7 @@ class CloseSettings:
 
 def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
                 server_opt=UNSET, geometric_median=UNSET, krum=UNSET, trust=UNSET, mean_around_median=UNSET,
-                bulyan=UNSET) -> CloseSettings:
+                bulyan=UNSET, rank_trim=UNSET) -> CloseSettings:
     """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
     ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
     malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
@@ -180,7 +182,7 @@ def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=U
     iterative plan are refused where the mode is chosen, ``cycle.select_mode``).  ``diff_bulyan`` (``bulyan``) beside
     a selection, any rule, noise or the trust rule raises ``MeanAroundMedianUnavailableError``; alone it becomes the
     mean around the median with ``drop = 2 f`` behind a selection that keeps ``n - 2 f`` diffs."""
-    rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median, mean_around_median)
+    rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median, mean_around_median, rank_trim)
     if not isinstance(server_opt, ServerOptSpec):
         server_opt = server_opt_of(server_config if server_opt is UNSET else {OPT_KEY: server_opt})
     noise = dp_noise_of(server_config, dp_noise)
