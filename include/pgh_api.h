@@ -671,6 +671,49 @@ int pgh_server_opt_steps(pgh_ctx* ctx, int64_t* committed);
 int pgh_server_opt_download(pgh_ctx* ctx, float* m, float* v);
 int pgh_server_opt_upload(pgh_ctx* ctx, const float* m, const float* v, size_t nbytes);
 
+/* ---- top-k sparsified update (SparseFed, Panda et al., AISTATS 2022; kernel K18) --------------------------
+ * After the diffs are averaged (and, with pgh_set_clip_norm, clipped), only the k coordinates of the update that
+ * are largest in magnitude are applied; the rest is kept in a server-side error memory and added back at the
+ * next close.  The rule bounds the support of the applied update; it does not filter values.  With the setting on
+ * every fp32 FINAL fold of the whole shard, in any averaging mode, is followed by K18 on the same stream, ahead
+ * of K10 when a server optimizer is set.  All arithmetic is IEEE f32, each operation rounded on its own, no FMA:
+ *   g      the average exactly as the cycle's mode produces it without the setting;
+ *   e      the committed error memory, [P] floats, +0.0f after pgh_set_topk and after a layout change;
+ *   u_i    = g_i + e_i, one addition; without an error memory (error_feedback = 0) no addition is made: u_i = g_i,
+ *          bit for bit;
+ *   key_i  = bits(u_i) & 0x7fffffff, the magnitude's bit pattern, ordered as an unsigned integer -- a NaN ranks
+ *          above every finite magnitude, is kept and stays visible;
+ *   tau    = the k-th largest of the P keys, 1 <= k <= P;  keep_i = key_i >= tau.  Ties at tau are all kept: the
+ *          kept count is >= k and is reported.  Nothing depends on the index order, the launch shape or the order
+ *          in which partial counts were merged (every count is an integer);
+ *   s_i    = keep_i ? u_i : +0.0f;      e'_i = keep_i ? +0.0f : u_i, the pending error memory;
+ *   out    = ckpt - s, one subtraction; a server optimizer takes s where its formulas take g.
+ * With k = P and no error memory the close gives the bits of the same close without the setting.
+ * Example: g = (0.5, -3, 0.25, 3, -1), e = +0, k = 2: the keys of -3 and 3 tie at tau = bits(3.0f), kept = 2,
+ * s = (0, -3, 0, 3, 0) and e' = (0.5, 0, 0.25, 0, -1).
+ *
+ * pgh_set_topk: k = 0 turns the setting off and frees its planes (always possible, on a group too, where it is
+ * never on); k < 0 or k > P is PGH_E_ARG; it needs a layout
+ * (PGH_E_STATE).  The same k and error_feedback again keep the error memory; any change starts it at +0.0f.
+ * PGH_E_UNSUPPORTED on a group (a global k would need the histograms all-reduced), on a shard narrower than the
+ * layout, beside an int64 slab and on a streaming context.  The planes are [P] float vectors in HBM: -0, a work
+ * plane, and e twice with an error memory.  The setting belongs to the model: pgh_reset and pgh_reserve keep it
+ * and the memory, pgh_set_layout and pgh_set_shard clear both.
+ * With the setting on, a FINAL over a proper sub-range of the shard (pgh_fedavg_device_range), pgh_stream_begin
+ * and a close beside pgh_set_dp_noise are PGH_E_UNSUPPORTED: nothing is launched and the context stays usable.
+ * pgh_fedavg_resident and pgh_fold_slots_finish_resident issue their FINAL pass as one whole-range launch.
+ * A FINAL never updates e in place: it reads the committed plane and writes a pending one, so a repeated FINAL
+ * gives identical bits.  pgh_topk_commit makes the pending memory the committed one (a pointer swap);
+ * PGH_E_STATE when no FINAL has run since the last commit or upload.  The library never commits by itself.
+ * pgh_topk_download copies the committed memory out (P floats), pgh_topk_upload replaces it (nbytes = 4 P) and
+ * clears anything pending; both are PGH_E_STATE without an error memory.  pgh_topk_stats waits for the last
+ * FINAL's stream work and reports k, tau's bits and the kept count of that close (0 and 0 before the first). */
+int pgh_set_topk(pgh_ctx* ctx, int64_t k, int error_feedback);
+int pgh_topk_commit(pgh_ctx* ctx);
+int pgh_topk_download(pgh_ctx* ctx, float* e);
+int pgh_topk_upload(pgh_ctx* ctx, const float* e, size_t nbytes);
+int pgh_topk_stats(pgh_ctx* ctx, int64_t* k, uint32_t* tau_bits, int64_t* kept);
+
 /* ---- reduction ----------------------------------------------------------------------------
  * out = ckpt - avg(diffs), over this context's shard.  Host pointers, P_shard floats each. */
 int pgh_fedavg(pgh_ctx* ctx, int mode, const float* ckpt, float* out);

@@ -134,6 +134,11 @@ SIGNATURES = {
     "pgh_server_opt_steps": (_i, [_vp, _P64]),
     "pgh_server_opt_download": (_i, [_vp, _vp, _vp]),
     "pgh_server_opt_upload": (_i, [_vp, _vp, _vp, _sz]),
+    "pgh_set_topk": (_i, [_vp, C.c_int64, _i]),
+    "pgh_topk_commit": (_i, [_vp]),
+    "pgh_topk_download": (_i, [_vp, _vp]),
+    "pgh_topk_upload": (_i, [_vp, _vp, _sz]),
+    "pgh_topk_stats": (_i, [_vp, _P64, C.POINTER(C.c_uint32), _P64]),
     "pgh_fedavg": (_i, [_vp, _i, _vp, _vp]),
     "pgh_fedavg_device": (_i, [_vp, _i, _vp, _vp, _vp]),
     "pgh_fedavg_device_range": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp]),

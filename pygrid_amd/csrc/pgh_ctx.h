@@ -184,6 +184,7 @@ struct pgh_ctx {
     pgh_detail::TrustState trust;
     pgh_detail::KrumState krum;
     pgh_detail::ServerOptState opt;
+    pgh_detail::TopkState topk;
 
     bool streaming = false;
     int slot_mode = -1;  // pgh_fold_slots: averaging mode of the cycle being folded slot by slot
@@ -498,9 +499,23 @@ int rank_trim_fold(pgh_ctx* c, const pgh::FedavgArgs& a, const pgh::Rows& rows, 
 // n - 2b as the FINAL divisor; PGH_E_STATE with n < 2b + 1, PGH_E_UNSUPPORTED past PGH_MEDIAN_NCHIP rows
 int rank_trim_divisor(pgh_ctx* c, int64_t n, float* div);
 
+// ---- top-k sparsified update (pgh_sparsify.cpp) ----------------------------------------------------------
+inline bool topk_on(const pgh_ctx* c) { return c->topk.k > 0; }
+// A FINAL fp32 fold over [off, off + len) of the shard (len < 0: to its end) is about to be issued with the
+// setting on: the selection needs every coordinate in one launch and takes no noise beside it
+// (PGH_E_UNSUPPORTED before anything is launched; the context stays usable).
+int check_topk_final(pgh_ctx* c, int64_t off, int64_t len);
+// K18 behind a FINAL launch over the whole shard on stream s, ahead of K10.  into_opt: the fold wrote the server
+// optimizer's delta plane and K10 follows -- the apply pass writes -s there; else the fold wrote the work plane
+// and the apply pass writes the real out = ckpt - s.
+int topk_launch(pgh_ctx* c, const FinalArgs& fa, bool into_opt, hipStream_t s);
+
 // ---- server optimizer (pgh_serveropt.cpp) --------------------------------------------------------------
 struct FinalArgs;
 int server_opt_launch(pgh_ctx* c, const FinalArgs& fa, hipStream_t s);  // K10 behind a FINAL launch (fold_launch)
+// Every launch that reads or writes the model's planes (the optimizer's, the error memory) has finished: the
+// context's reduction streams and the folds issued on callers' streams.
+int folds_quiesce(pgh_ctx* c);
 // pgh_set_shard; keep_opt (rules_shard_set): a group's pgh_reserve lays its children's shards out again
 int set_shard(pgh_ctx* c, int64_t lo, int64_t hi, bool keep_opt);
 

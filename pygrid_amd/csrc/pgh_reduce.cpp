@@ -89,27 +89,36 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     const bool noise = noise_on(c) && (flags & pgh::FL_FINAL) && !fa.plain;
     if (noise) RC(check_noise_final(c, mode));  // (the entry points have checked: nothing was launched)
     if (noise && (!fa.ckpt || !fa.out)) return fail(c, PGH_E_ARG, "a noised FINAL fold needs ckpt and out");
-    if (opt || noise) {  // (the lines that name the two tenants' delta planes: fold_launch's own)
+    // Top-k sparsification: a third tenant.  K18 follows the FINAL launch of any mode, reads the delta plane and
+    // writes -s into it ahead of K10, or, without an optimizer, the real out from the work plane of its own.
+    const bool topk = topk_on(c) && (flags & pgh::FL_FINAL) && !fa.plain;
+    if (topk) RC(check_topk_final(c, fa.off, fa.len));  // (the entry points have checked: nothing was launched)
+    if (topk && (!fa.ckpt || !fa.out)) return fail(c, PGH_E_ARG, "a sparsified FINAL fold needs ckpt and out");
+    if (opt || noise || topk) {  // (the lines that name the three tenants' delta planes: fold_launch's own)
         RC(c->nz.ensure(c, s));
-        if (!opt) RC(noise_plane(c));
+        if (!opt && noise) RC(noise_plane(c));
         a.ckpt = c->nz.get() + off;
-        a.out = (opt ? c->opt.d_d : c->noise.d_d).as<float>() + off;
+        a.out = (opt ? c->opt.d_d : noise ? c->noise.d_d : c->topk.d_u).as<float>() + off;
     }
     a.divisor = fa.divisor;
     a.flags = flags;
     a.mode = kernel_mode(mode);
     a.variant = c->variant;
+    const auto behind = [&]() -> int {  // what follows the FINAL launch of a rule that noise never accompanies
+        if (topk) RC(topk_launch(c, fa, opt, s));
+        return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+    };
     if (mode == PGH_MEDIAN) {  // (its own launches and bytes)
         RC(median_fold(c, a, rows.src, s));
-        return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+        return behind();
     }
     if (mode == PGH_MEAN_AROUND_MEDIAN) {  // (likewise)
         RC(median_mean_fold(c, a, rows.src, s));
-        return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+        return behind();
     }
     if (mode == PGH_RANK_TRIMMED_MEAN) {  // (likewise)
         RC(rank_trim_fold(c, a, rows.src, s));
-        return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+        return behind();
     }
     // HBM bytes: the rows; the running state in unless FIRST; the state out, or ckpt in and out when FINAL
     const uint64_t pg = (uint64_t)fa.len;
@@ -121,7 +130,7 @@ int fold_launch(pgh_ctx* c, int mode, const FoldRows& rows, int64_t client0, int
     }
     RC(timed_launch(c, s, bytes, [&] { return pgh::launch_fedavg(a, rows.src, s); }));
     if (noise) RC(dp_noise_launch(c, fa, client0 + rows.n, opt, s));  // the FINAL launch ends the cycle's N rows
-    return opt ? server_opt_launch(c, fa, s) : PGH_OK;
+    return behind();
 }
 
 int fold_listed(pgh_ctx* c, int mode, const int32_t* slots, size_t n, bool final, const FinalArgs& fa, hipStream_t s) {
@@ -281,6 +290,7 @@ int pgh_fedavg_device_range(pgh_ctx* c, int mode, int64_t off, int64_t len, cons
     if (c && c->grp) return fail(c, PGH_E_UNSUPPORTED, "pgh_fedavg_device* takes device pointers, which name one GPU: call it on pgh_group_child");
     RC(check_dtype(c, PGH_F32));
     RC(check_mode_use(c, mode, USE_RESIDENT));
+    if (topk_on(c)) RC(check_topk_final(c, off, len));  // a proper sub-range cannot select: nothing is launched
     if (!d_ckpt || !d_out) return fail(c, PGH_E_ARG, "d_ckpt / d_out is NULL");
     if (((uintptr_t)d_ckpt | (uintptr_t)d_out) & 15) return fail(c, PGH_E_ARG, "device buffers must be 16-byte aligned");
     DeviceGuard g(c->device);
@@ -359,7 +369,7 @@ int pgh_fedavg_resident(pgh_ctx* c, int mode) {
     DeviceGuard g(c->device);
     const double t0 = now_ms();
     clear_final_marks(c);
-    const int K = final_ranges(c);
+    const int K = topk_on(c) ? 1 : final_ranges(c);  // (the selection needs every coordinate: one whole-range FINAL)
     if (K == 1) {
         RC(pgh_fedavg_device(c, mode, c->d_ckpt.as<float>(), c->d_out.as<float>(), c->stream));
     } else {  // the same fold as K range launches, each followed by its mark (pipelined close)

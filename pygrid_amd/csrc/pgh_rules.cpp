@@ -27,6 +27,10 @@ int queue_dots(pgh_ctx* c, const int32_t* slots, int n);
 
 int check_mode_use(pgh_ctx* c, int mode, ModeUse use) {
     RC(mode_use_rule(c, mode, use));
+    if (topk_on(c)) {  // (never on for a group: pgh_set_topk refuses one)
+        if (use == USE_STREAM) return fail(c, PGH_E_UNSUPPORTED, "STREAM use takes no top-k (pgh_set_topk): the selection follows a RESIDENT or slot close");
+        if (use == USE_RESIDENT || use == USE_SLOT_FINAL) RC(check_topk_final(c, 0, -1));
+    }
     // a RESIDENT fold and a closing slot fold end in a FINAL launch (noise is never on for a group or a stream)
     return use == USE_RESIDENT || use == USE_SLOT_FINAL ? check_noise_final(c, mode) : PGH_OK;
 }
@@ -117,6 +121,7 @@ void rules_shard_set(pgh_ctx* c, int64_t lo, int64_t hi, int64_t pvec, bool keep
     const bool same = keep_opt && same_shard;
     if (!(same && pvec == c->opt.pvec)) c->opt.release();
     if (!(same && pvec == c->noise.pvec)) c->noise.release();  // (free_slab has synchronised the streams)
+    if (!(same && pvec == c->topk.pvec)) c->topk.release();
     if (!(same_shard && pvec == c->pvec)) c->nz.d.reset();     // (its tenants above and below are gone with it)
     if (hi - lo != c->P) c->clip.c = 0.f;  // a norm needs the whole row (pgh_set_clip_norm refuses too)
     c->geo.release();  // (free_slab has dropped the plane; the setting goes with the layout or shard)

@@ -1,10 +1,10 @@
 // What each averaging rule and the server optimizer keep in a single-GPU context: one struct per feature,
-// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trust, krum, trim, med, mam and opt, and what they share:
+// members of struct pgh_ctx (pgh_ctx.h) as clip, noise, geo, trust, krum, trim, med, mam, topk and opt, and what they share:
 // the row reductions and their two per-slot caches (RowSums, rowsums; a cache is a RowCache), the rows a
 // row-wise rule includes (IncludedRows, in geo and trust), the fold's weights (FoldWeights, fw) and the -0 plane
 // (NegZeroPlane, nz).  Their owners release with the context.
 // The code that works on them: pgh_rules.cpp (every rule, the noise and the lifecycle calls rules_*),
-// pgh_serveropt.cpp (opt).  Not installed.
+// pgh_serveropt.cpp (opt), pgh_sparsify.cpp (topk).  Not installed.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -19,6 +19,7 @@
 #include "pgh_median_mean.h"
 #include "pgh_rank_trim.h"
 #include "pgh_res.h"
+#include "pgh_topk.h"
 
 struct pgh_ctx;
 
@@ -312,6 +313,32 @@ struct MedianMeanState {
 // belongs to the model, as the mean around the median's does.
 struct RankTrimState {
     int b = 0;  // values dropped per side and parameter; 0 = the rule is off
+};
+
+// Top-k sparsification of the averaged update (pgh_set_topk; SparseFed): a modifier behind
+// any averaging mode, like the noise, not a rule of its own.  With k > 0 fold_launch runs every fp32 FINAL against
+// the context's -0 plane into a delta plane -- the server optimizer's when one is set, else the work plane here --
+// and K18 behind it, ahead of K10: three histogram passes and their picks, then the apply pass, which reads the
+// committed error memory's sum u from the work plane and writes the pending memory; pgh_topk_commit swaps the
+// two.  All planes are float [pvec] and belong to the model: pgh_reset / pgh_reserve keep them, a new layout or
+// shard drops them and the setting (rules_shard_set -> release).  The code: pgh_sparsify.cpp.
+struct TopkState {
+    int64_t k = 0;                // coordinates applied per close; 0 = off
+    bool feedback = false;        // an error memory is kept
+    DeviceBuf d_u;                // the work plane: d = -g of a FINAL without an optimizer, then u = g + e
+    DeviceBuf d_e, d_e2;          // committed; pending: written by K18's apply pass, committed by the swap
+    DeviceBuf d_blk;              // pgh::TopkBlock: the histogram and the selection's state
+    bool blk_clean = false;       // the histogram holds zeros (the last pick of a close leaves it so)
+    bool pending = false;         // a FINAL has run since the last commit / upload / (re)initialisation
+    bool ran = false;             // the state block holds a close's tau and counts (pgh_topk_stats)
+    int64_t pvec = 0;             // the planes' length (pvec when they were allocated)
+
+    void release() {  // planes and setting; the caller has waited for the context's work
+        for (auto* v : {&d_u, &d_e, &d_e2, &d_blk}) v->reset();
+        k = 0;
+        feedback = blk_clean = pending = ran = false;
+        pvec = 0;
+    }
 };
 
 // Server optimizer (pgh_set_server_opt).  With one set, fold_launch runs every

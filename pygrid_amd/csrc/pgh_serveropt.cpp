@@ -45,15 +45,14 @@ void ServerOptState::release() {
     pvec = 0;
 }
 
-namespace {
-// Every launch that reads or writes the planes has finished: the context's reduction stream and the
-// folds issued on callers' streams.
-int opt_quiesce(pgh_ctx* c) {
+int folds_quiesce(pgh_ctx* c) {
     CK(c, hipStreamSynchronize(c->stream));
     CK(c, hipStreamSynchronize(c->aux));
     for (auto& fe : c->fold_evs) CK(c, hipEventSynchronize(fe.second));
     return PGH_OK;
 }
+
+namespace {
 
 // m = +0, v = tau * tau in the committed planes; nothing pending, no step counted.
 int opt_init_state(pgh_ctx* c) {
@@ -100,7 +99,7 @@ int pgh_set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2,
     if (kind == PGH_OPT_NONE) {
         if (so.kind == PGH_OPT_NONE) return PGH_OK;
         DeviceGuard g(c->device);
-        RC(opt_quiesce(c));
+        RC(folds_quiesce(c));
         so.release();
         return PGH_OK;
     }
@@ -108,7 +107,7 @@ int pgh_set_server_opt(pgh_ctx* c, int kind, float lr, float beta1, float beta2,
     if (kind == so.kind && lr == so.lr && beta1 == so.beta1 && beta2 == so.beta2 && tau == so.tau)
         return PGH_OK;  // the same again: the state stays
     DeviceGuard g(c->device);
-    RC(opt_quiesce(c));
+    RC(folds_quiesce(c));
     so.release();
     const size_t bytes = 4 * (size_t)c->pvec;
     const bool adaptive = kind != PGH_OPT_MOMENTUM;
@@ -181,7 +180,7 @@ int pgh_server_opt_download(pgh_ctx* c, float* m, float* v) {
     const bool adaptive = c->opt.kind != PGH_OPT_MOMENTUM;
     if (!m || (adaptive && !v)) return fail(c, PGH_E_ARG, "m / v is NULL");
     DeviceGuard g(c->device);
-    RC(opt_quiesce(c));
+    RC(folds_quiesce(c));
     const size_t bytes = 4 * (size_t)c->pg;
     CK(c, hipMemcpy(m, c->opt.d_m.as<float>(), bytes, hipMemcpyDeviceToHost));
     if (adaptive) CK(c, hipMemcpy(v, c->opt.d_v.as<float>(), bytes, hipMemcpyDeviceToHost));
@@ -198,7 +197,7 @@ int pgh_server_opt_upload(pgh_ctx* c, const float* m, const float* v, size_t nby
     RC(shard_start(c, "optimizer state", nbytes, 4, &skip));
     const size_t shard = 4 * (size_t)c->pg;
     DeviceGuard g(c->device);
-    RC(opt_quiesce(c));
+    RC(folds_quiesce(c));
     CK(c, hipMemcpy(c->opt.d_m.as<float>(), m + skip, shard, hipMemcpyHostToDevice));
     if (adaptive) CK(c, hipMemcpy(c->opt.d_v.as<float>(), v + skip, shard, hipMemcpyHostToDevice));
     c->opt.nothing_pending();

@@ -72,7 +72,8 @@ int slot_fold(pgh_ctx* c, int mode, const int32_t* slots, int n, bool final) {
         // alternating over two streams (profiles/r04m/: 2.04 vs 2.19 ms, close start -> new
         // checkpoint bytes); a mark (a system-scope release) only where a piece ends (r05).
         const int64_t RF = (int64_t)(D2H_PIECE / 8);
-        const int K = (flags & pgh::FL_FINAL) && c->pg >= (1 << 20) ? (int)((c->pg + RF - 1) / RF) : 1;
+        // (with top-k set the selection needs every coordinate: one whole-range FINAL)
+        const int K = (flags & pgh::FL_FINAL) && c->pg >= (1 << 20) && !topk_on(c) ? (int)((c->pg + RF - 1) / RF) : 1;
         if (flags & pgh::FL_FINAL) clear_final_marks(c);
         // the new checkpoint's D2H starts here: after each mark, the pieces whose ranges have
         // finished go out while the later ranges are still being issued (stage_d2h_pieces adopts the

@@ -339,7 +339,7 @@ class CycleAggregator:
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
                            plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
                            dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
-                           trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET) -> bytes:
+                           trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET, top_k=UNSET) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -362,7 +362,7 @@ class CycleAggregator:
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim, top_k)
         with self._closing(server_config, given, avg_plan, weights, plan_key, lambda: _shapes_or_none(checkpoint),
                            lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round, trust_root) as (settings, mode):
             return self._average_plan_diffs(checkpoint, diffs, weights, framing, settings, mode)
@@ -376,7 +376,7 @@ class CycleAggregator:
         geometric_median, krum, trust, mean_around_median, bulyan, rank_trim.  Under the trust rule the cycle's ``trust_root`` goes onto the engine here too,
         ahead of the ingests: each diff's inner product with it rides behind its copy."""
         settings = settings_of(server_config, *given[:4], geometric_median=given[4], krum=given[5], trust=given[6],
-                               mean_around_median=given[7], bulyan=given[8], rank_trim=given[9])
+                               mean_around_median=given[7], bulyan=given[8], rank_trim=given[9], top_k=given[10])
         with settings.fail_closed("the engine cannot average this cycle"):
             mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                                shapes=shapes, n_clients=n_diffs, trust=settings.trust, **settings.rule_kwargs())
@@ -438,6 +438,8 @@ class CycleAggregator:
                else self.engine.ckpt_patch_state(checkpoint))
         if settings.opt is not None:
             self.opt_states.commit(self.engine)  # the new checkpoint's bytes exist: the step counts
+        if settings.top_k is not None:
+            self.engine.topk_commit()  # (likewise: the error memory this close wrote is the committed one)
         self.engine.ckpt_owner = self
         self.engine.ckpt_bytes = new  # the bytes whose params are resident (IncrementalCycle reuses them)
         self._resident = new
@@ -448,12 +450,12 @@ class CycleAggregator:
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
                        weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
                        dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
-                       trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET) -> List[np.ndarray]:
+                       trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET, top_k=UNSET) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         shapes = [np.shape(p) for p in model_params]
         numel = [int(np.prod(s)) for s in shapes]
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim, top_k)
         with self._closing(server_config, given, avg_plan, weights, None, shapes, lambda: numel, len(diffs), opt_key,
                            dp_round, trust_root) as (settings, mode):
             for i, d in enumerate(diffs):
@@ -472,6 +474,8 @@ class CycleAggregator:
                 out = self.engine.fedavg(mode, flat)
             if settings.opt is not None:
                 self.opt_states.commit(self.engine)  # the new parameters are on the host: the step counts
+            if settings.top_k is not None:
+                self.engine.topk_commit()
             res, off = [], 0
             for s, n in zip(shapes, numel):
                 res.append(out[off:off + n].reshape(s))

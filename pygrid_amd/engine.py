@@ -572,6 +572,38 @@ class Engine:
         self._check(self._lib.pgh_server_opt_upload(self._h, _ptr(a), _ptr(b) if b is not None else None, a.nbytes),
                     "server_opt_upload")
 
+    # ---- top-k sparsified update (SparseFed; kernel K18) ---------------------------------------------
+    def set_topk(self, k: int, error_feedback: bool = True):
+        """Later fp32 closes apply only the ``k`` coordinates of the averaged update that are largest in magnitude
+        (``pgh_set_topk``; the definition is in ``include/pgh_api.h``); with ``error_feedback`` the rest is kept in
+        an error memory in HBM and added back at the next close.  0 turns the setting off.  The same ``k`` and
+        ``error_feedback`` again keep the memory; any change starts it at zero."""
+        self._check(self._lib.pgh_set_topk(self._h, int(k), int(bool(error_feedback))), "set_topk")
+
+    def topk_commit(self):
+        """Make the error memory the last close wrote the committed one: once per close, when its result is
+        safe.  Until then a repeated close gives the same bits."""
+        self._check(self._lib.pgh_topk_commit(self._h), "topk_commit")
+
+    def topk_stats(self) -> dict:
+        """What the last close selected: ``k``, the threshold ``tau_bits`` (the k-th largest magnitude's bit
+        pattern; ``threshold`` is that magnitude) and ``kept`` (>= k: ties at the threshold are all kept)."""
+        k, tau, kept = C.c_int64(0), C.c_uint32(0), C.c_int64(0)
+        self._check(self._lib.pgh_topk_stats(self._h, C.byref(k), C.byref(tau), C.byref(kept)), "topk_stats")
+        return {"k": k.value, "tau_bits": tau.value, "kept": kept.value,
+                "threshold": float(np.array([tau.value], np.uint32).view(np.float32)[0])}
+
+    def topk_state(self) -> np.ndarray:
+        """The committed error memory (``pgh_topk_download``)."""
+        e = np.empty(self.p_shard, dtype=np.float32)
+        self._check(self._lib.pgh_topk_download(self._h, _ptr(e)), "topk_download")
+        return e
+
+    def load_topk_state(self, e: np.ndarray):
+        """Replace the committed error memory (``pgh_topk_upload``); drops a pending one."""
+        a = np.ascontiguousarray(e, dtype=np.float32).reshape(-1)
+        self._check(self._lib.pgh_topk_upload(self._h, _ptr(a), a.nbytes), "topk_upload")
+
     # ---- reduction -----------------------------------------------------------------------------
     def fedavg(self, mode: int, ckpt: np.ndarray) -> np.ndarray:
         """``ckpt - avg(diffs)`` over this shard (host arrays of p_shard floats)."""

@@ -78,6 +78,13 @@ class RankTrimUnavailableError(AggregationError):
     fails closed."""
 
 
+class TopKUnavailableError(AggregationError):
+    """The FL process asks for a top-k sparsified update (``server_config["update_top_k"]``) and the engine cannot
+    take it this cycle: a hosted unaccelerated plan, a non-float32 model, ``dp_noise`` beside it, a group of GPUs
+    or a shard (a global k needs every coordinate on one GPU), or a count larger than the model.  It is NOT a
+    ``PlanNotAcceleratedError``: the node's own averaging applies the dense update, so the close fails closed."""
+
+
 class GeometricMedianUnavailableError(AggregationError):
     """The FL process asks for the geometric median (``server_config["diff_geometric_median"]``) and the
     engine cannot take it this cycle: a hosted iterative or unaccelerated plan, a non-float32 model,

@@ -88,7 +88,7 @@ class IncrementalCycle:
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
                  median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
                  dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None, krum=None, trust=None,
-                 trust_root=None, mean_around_median=None, bulyan=None, rank_trim=None):
+                 trust_root=None, mean_around_median=None, bulyan=None, rank_trim=None, top_k=None):
         """``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
         ``median``, ``geometric_median``, ``server_opt``, ``dp_noise`` and ``krum`` below (both: an error); keys,
         round and stores go beside either.
@@ -125,6 +125,12 @@ class IncrementalCycle:
         nothing folded early, one RANK_TRIMMED_MEAN finish over every held (or picked) slot in the close's order, at
         most as many diffs as slots; b resolves at the close, from the number of diffs it folds -- with
         ``RankTrimUnavailableError`` where the median raises its own, and at a close of fewer than ``2 b + 1`` diffs.
+
+        ``top_k``: the FL process's top-k sparsified update (``sparsify.top_k_of``: the setting's dict or its parsed
+        form), behind any ``mode``, rule or selection and ahead of ``server_opt``, not beside ``dp_noise``.  Early
+        folds do not involve it: K18 follows the close's FINAL pass alone, which is then issued as one whole-range
+        launch; the error memory is committed beside the optimizer's step.  ``last_close`` reports ``top_k``,
+        ``top_k_kept`` and ``top_k_threshold``; ``TopKUnavailableError`` where the engine cannot.
 
         ``dp_noise``: the FL process's noise setting (``dp.dp_noise_of``; it needs ``clip_norm``), drawn for
         ``dp_round`` (the cycle's id) from the key it names or ``opt_key``'s in ``dp_keys`` (share the
@@ -164,7 +170,7 @@ class IncrementalCycle:
                                        trust=None if trust is False else trust,
                                        mean_around_median=None if mean_around_median is False else mean_around_median,
                                        bulyan=None if bulyan is False else bulyan,
-                                       rank_trim=None if rank_trim is False else rank_trim).items() if v is not None}
+                                       rank_trim=None if rank_trim is False else rank_trim, top_k=top_k).items() if v is not None}
         if settings is not None and given:
             raise AggregationError(f"settings= was given beside {', '.join(given)}")
         self._settings = settings = settings if settings is not None else settings_of({}, **given)
@@ -567,6 +573,8 @@ class IncrementalCycle:
                    else self.engine.ckpt_patch_state(checkpoint))
             if self._settings.opt is not None:
                 self._opt_states.commit(self.engine)  # the new checkpoint's bytes exist: the step counts
+            if self._settings.top_k is not None:
+                self.engine.topk_commit()  # (likewise: the error memory this close wrote is the committed one)
             self.engine.ckpt_owner = self
             self.engine.ckpt_bytes = new
             return new

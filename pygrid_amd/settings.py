@@ -14,10 +14,12 @@ import contextlib
 import dataclasses
 from typing import Callable, Optional
 
-from . import dp, krum as krum_mod, robust, trust as trust_mod
+from . import dp, krum as krum_mod, robust, sparsify, trust as trust_mod
 from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
 from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, KrumUnavailableError, \
-    MeanAroundMedianUnavailableError, PlanNotAcceleratedError, ServerOptUnavailableError, TrustUnavailableError
+    MeanAroundMedianUnavailableError, PlanNotAcceleratedError, ServerOptUnavailableError, TopKUnavailableError, \
+    TrustUnavailableError
+from .sparsify import TOPK_KEY, TopKSpec, top_k_of
 from .krum import KRUM_KEY, KrumSpec, krum_of
 from .robust import CLIP_KEY, GEOMED_KEY, MAM_KEY, MEDIAN_KEY, RANK_TRIM_KEY, TRIM_KEY, UNSET, Rule, rule_of
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
@@ -55,10 +57,11 @@ class CloseSettings:
     select: Optional[KrumSpec] = None
     trust: Optional[TrustSpec] = None
     bulyan: Optional[int] = None  # f of ``diff_bulyan``: ``rule`` and ``select`` are then its two stages
+    top_k: Optional[TopKSpec] = None  # a modifier behind the averaging, like the noise: not a rule
 
     def __bool__(self) -> bool:
         return self.rule is not None or self.opt is not None or self.noise is not None or self.select is not None \
-            or self.trust is not None
+            or self.trust is not None or self.top_k is not None
 
     def rule_kwargs(self) -> dict:
         """The rule as the keyword argument that ``select_mode`` takes."""
@@ -79,6 +82,9 @@ class CloseSettings:
             if self.noise is not None:
                 raise DpNoiseUnavailableError(f"{DP_KEY} is set but the engine does not average this cycle ({e}); "
                                               "the node's own averaging adds no noise") from e
+            if self.top_k is not None and isinstance(e, PlanNotAcceleratedError):
+                raise TopKUnavailableError(f"{TOPK_KEY} is set but the engine does not average this cycle ({e}); "
+                                           "the node's own averaging applies the dense update") from e
             if self.opt is not None and isinstance(e, PlanNotAcceleratedError):
                 raise ServerOptUnavailableError(f"{OPT_KEY} is set but the engine does not average this cycle ({e}); "
                                                 "the node's own averaging applies no optimizer") from e
@@ -95,6 +101,8 @@ class CloseSettings:
             key, error, lacks = TRUST_KEY, TrustUnavailableError, "trusts every diff"
         elif self.select is not None:
             key, error, lacks = KRUM_KEY, KrumUnavailableError, "selects nothing"
+        elif self.top_k is not None:
+            key, error, lacks = TOPK_KEY, TopKUnavailableError, "applies the dense update"
         elif self.opt is not None:
             key, error, lacks = OPT_KEY, ServerOptUnavailableError, "applies no optimizer"
         else:
@@ -116,6 +124,7 @@ class CloseSettings:
         if not noise_only:
             robust.set_on_engine(engine, self.rule)
             trust_mod.set_on_engine(engine, self.trust)  # (the cycle's root follows: trust.set_root)
+            sparsify.set_on_engine(engine, self.top_k)  # (the engine is laid out: k resolves against its model)
         dp.set_on_engine(engine, self.noise, key, round)
 
     def _value(self, key: str, off=None):
@@ -144,6 +153,8 @@ class CloseSettings:
             stats["krum"] = krum_mod.close_stats(engine, self.select)
         if self.trust is not None:  # one more key, under the trust rule alone
             stats["trust"] = trust_mod.close_stats(engine)
+        if self.top_k is not None:  # three more keys, under the top-k setting alone
+            stats.update(sparsify.close_stats(engine))
         return stats
 
     def close_message(self, cycle_id, last_close: dict) -> str:
@@ -172,7 +183,7 @@ class CloseSettings:
 
 def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
                 server_opt=UNSET, geometric_median=UNSET, krum=UNSET, trust=UNSET, mean_around_median=UNSET,
-                bulyan=UNSET, rank_trim=UNSET) -> CloseSettings:
+                bulyan=UNSET, rank_trim=UNSET, top_k=UNSET) -> CloseSettings:
     """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
     ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
     malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
@@ -204,4 +215,7 @@ def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=U
                                                    "and an averaging rule of its own")
         rule = rule_of({}, mean_around_median=2 * f)
         select = KrumSpec(f, None, bulyan=True, distances=bulyan_distances_of(server_config, bulyan))
-    return CloseSettings(rule, server_opt, noise, select, tr, f)
+    tk = top_k_of(server_config, top_k)
+    if tk is not None and noise is not None:
+        raise sparsify.refuse(f"cannot be combined with {DP_KEY}: the noise is calibrated to the dense clipped mean")
+    return CloseSettings(rule, server_opt, noise, select, tr, f, tk)
