@@ -622,6 +622,41 @@ int pgh_gram_distances_host(const double* gram, const double* sumsq, int n, doub
 int pgh_krum_select_gram(pgh_ctx* ctx, const int32_t* slots, int n, int f, int m, int32_t* picked,
                          int* n_picked);
 
+/* ---- Row mixing: Y = W X ahead of the average, nearest-neighbour mixing (kernel K19) -------------------
+ * A stage, not an averaging mode, and a call, not a setting: it REPLACES diffs by weighted sums of diffs.
+ * Nearest-neighbour mixing (Allouah et al., "Fixing by Mixing", AISTATS 2023) replaces every diff by the mean
+ * of its n - f nearest diffs before a robust rule runs; with another W the same call is bucketing,
+ * median-of-means or any other linear pre-aggregation.  For source slots src[0, n), destination slots
+ * dst[0, m) and the m x n row-major f64 matrix w, destination list position i < m and param q < P:
+ *   out[dst[i]][q] = (float) S,
+ *   S = the f64 sum over k = 0 .. n-1, in increasing k, of w[i*n + k] * (double) x[src[k]][q].
+ *   Accumulation.  By v_mfma_f64_16x16x4_f64 from +0.0, four consecutive k at a time (the instruction's own
+ *      order within the four), the groups in increasing k.  There is no split over k and no partial sums are
+ *      combined, so the accumulation order of an element depends on (n, k) alone: not on m, P, the slots, the
+ *      slab's block layout or the device's CU count.  A repeated call gives identical bits.
+ *   IEEE.  Nothing is sanitised: a zero weight does not hide a NaN or an infinity in a listed source row.
+ *   Padding.  Source places at or past n and weight places at or past n or m are masked to +0.0 before they
+ *      reach the MFMA -- masked, not clamped to a neighbour: padding never injects a non-finite value.
+ *   Rounding.  One rounding to f32 at the store (round to nearest even).
+ *   Accuracy.  With u = 2^-53, |S - sum_k w_ik x_kq| <= n u sum_k |w_ik| |x_kq| (first order).
+ * pgh_mix_rows: copies w and the two slot lists to the device, queues K19 on the context's stream and returns;
+ * a later fold or row reduction on the context is ordered behind it.  It returns before K19 has run, but not
+ * before the copies of w and the lists have left the caller's memory: those are ordered behind every ingest
+ * queued so far, so the call blocks the host until the pending ingests have landed.  Afterwards the dst slots
+ * hold diffs (occupied, as after an ingest) and whatever was cached for them (K7's sums, K14's dots) is dropped;
+ * a dst slot that still held an unfolded diff is overwritten, exactly as an ingest into it would (a free slot
+ * of a report-time cycle may hold a diff that the close left out); the src slots are untouched.  PGH_E_ARG: a NULL pointer, n or m < 1, a slot outside the reserved range, a slot twice
+ * in dst, a slot in both lists.  PGH_E_UNSUPPORTED: n or m > PGH_KRUM_MAX_ROWS, and every context
+ * pgh_krum_select refuses (a group, a shard narrower than the layout, an int64 slab).  PGH_E_STATE: a src slot
+ * that holds no diff, a streaming context, slot folds of an open cycle.
+ * pgh_nnm_weights_host: the mixing matrix of nearest-neighbour mixing, no context and no GPU.  From the n x n
+ * matrix dist (no NaN) and 0 <= f < n: row i of w (n x n) holds 1.0 / (double)(n - f) at the n - f positions j
+ * with the smallest dist[i*n + j], ties towards the smaller j (Krum's rule), and +0.0 elsewhere; with
+ * dist[i*n + i] = 0 < every other entry of the row, i is among its own neighbours.  *n_neighbours (nullable) = n - f.
+ * Anything else is PGH_E_ARG. */
+int pgh_mix_rows(pgh_ctx* ctx, const int32_t* src, int n, const int32_t* dst, int m, const double* w);
+int pgh_nnm_weights_host(const double* dist, int n, int f, double* w, int32_t* n_neighbours);
+
 /* ---- server optimizers: how the average is applied (FedAvgM, FedAdagrad, FedAdam, FedYogi) ------
  * Without one, a close writes out = ckpt - g, g being the cycle's average as its mode defines it
  * (acc / divisor; the iterative mean's acc; the trimmed mean; the median).  With one set, every

@@ -17,7 +17,7 @@ thresholds for 47 MB buffers).
 """
 from .exceptions import (AggregationError, ClipUnavailableError, DpNoiseUnavailableError, EngineUnavailableError, GeometricMedianUnavailableError,
                          KrumUnavailableError, MeanAroundMedianUnavailableError, MedianUnavailableError,
-                         ModelNotAcceleratedError,
+                         ModelNotAcceleratedError, NnmUnavailableError,
                          PlanNotAcceleratedError, PyGridError, RankTrimUnavailableError, ServerOptUnavailableError, StateParseError,
                          TopKUnavailableError, TrimUnavailableError, TrustUnavailableError)
 from .engine import (CLIPPED_MEAN, F32, GEOMETRIC_MEDIAN, I64, ITERATIVE_MEAN, MEAN, MEAN_AROUND_MEDIAN, MEDIAN, MEDIAN_NCHIP, MODE_NAMES, RANK_TRIMMED_MEAN, STREAM_SECAGG,
@@ -44,7 +44,7 @@ __all__ = [
     "AggregationError", "ClipUnavailableError", "EngineUnavailableError", "ModelNotAcceleratedError", "PlanNotAcceleratedError", "PyGridError",
     "StateParseError", "TrimUnavailableError", "MedianUnavailableError", "ServerOptUnavailableError", "DpNoiseUnavailableError",
     "Engine", "PinnedBuffer", "device_count", "STREAM_SECAGG", "MEAN", "ITERATIVE_MEAN", "WEIGHTED_MEAN", "CLIPPED_MEAN", "TRIMMED_MEAN",
-    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "MEAN_AROUND_MEDIAN", "MeanAroundMedianUnavailableError", "RANK_TRIMMED_MEAN", "RankTrimUnavailableError", "GEOMETRIC_MEDIAN", "GeometricMedianUnavailableError", "KrumUnavailableError", "TRUSTED_MEAN", "TrustUnavailableError", "TopKUnavailableError", "MODE_NAMES", "F32", "I64",
+    "TRIM_MAX", "MEDIAN", "MEDIAN_NCHIP", "MEAN_AROUND_MEDIAN", "MeanAroundMedianUnavailableError", "RANK_TRIMMED_MEAN", "RankTrimUnavailableError", "GEOMETRIC_MEDIAN", "GeometricMedianUnavailableError", "KrumUnavailableError", "NnmUnavailableError", "TRUSTED_MEAN", "TrustUnavailableError", "TopKUnavailableError", "MODE_NAMES", "F32", "I64",
     "tune_process",
 ]
 __version__ = "0.3.0"

@@ -172,7 +172,7 @@ struct pgh_ctx {
     // lifecycle files (pgh_api.cpp, pgh_ingest.cpp, pgh_slots.cpp, pgh_xfer.cpp, pgh_order.cpp) reach them
     // through rules_* and the fold plans below alone:
     //   grep -n 'c->\(clip\|geo\|trust\|krum\|noise\|trim\|med\|opt\)\.' of those five files finds nothing.
-    pgh_detail::RowSums rowsums;   // the per-slot caches sq (K7) and dot (K14), the tile partials and the buffers of K12, K13 and K16 (clip, geo, krum, trust)
+    pgh_detail::RowSums rowsums;   // the per-slot caches sq (K7) and dot (K14), the tile partials and the buffers of K12, K13, K16 and K19 (clip, geo, krum, trust, the row mix)
     pgh_detail::NegZeroPlane nz;   // the one plane of -0.0f (opt, noise, geo)
     pgh_detail::ClipState clip;
     pgh_detail::NoiseState noise;

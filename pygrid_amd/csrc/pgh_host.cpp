@@ -246,6 +246,25 @@ void gram_distances(const double* G, const double* s, int n, double* D) {
         }
 }
 
+bool nnm_weights(const double* D, int n, int f, double* w) {
+    if (n < 1 || f < 0 || f >= n) return false;
+    const size_t nn = (size_t)n * (size_t)n;
+    for (size_t e = 0; e < nn; ++e)
+        if (D[e] != D[e]) return false;
+    const int keep = n - f;
+    const double each = 1.0 / (double)keep;
+    std::fill_n(w, nn, 0.0);
+    std::vector<int32_t> order((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const double* row = D + (size_t)i * (size_t)n;
+        for (int j = 0; j < n; ++j) order[(size_t)j] = j;
+        // (no NaN: < is a strict weak order; the stable sort keeps equal distances in position order)
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return row[x] < row[y]; });
+        for (int j = 0; j < keep; ++j) w[(size_t)i * (size_t)n + (size_t)order[(size_t)j]] = each;
+    }
+    return true;
+}
+
 double row_dot_host(const float* x, const float* y, int64_t p) {
     double row = 0.0;
     for (int64_t base = 0; base < p || base == 0; base += 4096) {

@@ -218,6 +218,11 @@ int krum_select(const double* D, int n, int f, int m, int32_t* picked, int* n_pi
 // result becomes +0.0, a NaN (inf - inf) +inf; the diagonal is +0.0.  G symmetric gives D symmetric.
 void gram_distances(const double* G, const double* s, int n, double* D);
 
+// The mixing matrix of nearest-neighbour mixing (include/pgh_api.h, "Row mixing"): row i of the n x n matrix w
+// holds 1.0 / (double)(n - f) at the n - f positions j with the smallest D[i][j] (ties towards the smaller j)
+// and +0.0 elsewhere.  False when n < 1, f < 0, f >= n or an entry of D is NaN: w is not written then.
+bool nnm_weights(const double* D, int n, int f, double* w);
+
 // K7's sum in K7's exact order (pgh_kernels.h) over (double)x[i] * (double)y[i], i < p, on the host: what K14
 // returns for a row x against the plane y, and with y == x what K7 returns for x.  The trust root's s0 comes from
 // here (pgh_trust_root): the same bits as pgh_row_sumsq of a slot holding the root.

@@ -493,6 +493,32 @@ int RowSums::gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double
     return PGH_OK;
 }
 
+// K19.  (No other kernel's buffers are touched.)  An earlier K19 that read the tables and w ran on this stream too.
+int RowSums::mix(pgh_ctx* c, const int32_t* src, int n, const int32_t* dst, int m, const double* w, hipStream_t s) {
+    constexpr size_t TAB = (size_t)pgh::PAIRDIST_MAX_ROWS;
+    const size_t wbytes = 8 * (size_t)m * (size_t)n;
+    if (!d_mix_w.reserve(wbytes) || !d_mix_rows.reserve(sizeof(int32_t) * 2 * TAB))
+        return fail(c, PGH_E_OOM, "allocation of the row mix's weights (%d x %d) failed", m, n);
+    std::vector<int32_t> tab(2 * TAB, 0);
+    for (int k = 0; k < n; ++k) tab[(size_t)k] = src[k] * c->parties;
+    for (int i = 0; i < m; ++i) tab[TAB + (size_t)i] = dst[i] * c->parties;
+    CK(c, hipMemcpyAsync(d_mix_rows.as<int32_t>(), tab.data(), sizeof(int32_t) * 2 * TAB, hipMemcpyHostToDevice, s));
+    CK(c, hipMemcpyAsync(d_mix_w.as<double>(), w, wbytes, hipMemcpyHostToDevice, s));
+    CK(c, hipStreamSynchronize(s));  // tab and w are pageable: the copies have left them
+    pgh::MixArgs a{};
+    a.slab = c->d_slab.as<float>();
+    a.map = slab_map(c);
+    a.p = c->pg;
+    a.d_src = d_mix_rows.as<int32_t>();
+    a.n = n;
+    a.d_dst = d_mix_rows.as<int32_t>() + TAB;
+    a.m = m;
+    a.w = d_mix_w.as<double>();
+    // the algorithmic bytes: the sources once, the destinations out, the weights once
+    const uint64_t bytes = 4ull * (uint64_t)(n + m) * (uint64_t)c->pg + (uint64_t)wbytes;
+    return timed_launch(c, s, bytes, [&] { return pgh::launch_mix_rows(a, s); });
+}
+
 // ---- clipped FedAvg: the scales and the tallies ------------------------------------------------------------
 
 float clip_scale_of(double sumsq, float c) {
@@ -1069,6 +1095,60 @@ int pgh_krum_select(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32
 
 int pgh_krum_select_gram(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
     return krum_select_ctx(c, "pgh_krum_select_gram", true, slots, n, f, m, picked, n_picked);
+}
+
+// ---- row mixing ahead of the average: K19, the nearest-neighbour weights on the host ----------------------------
+
+int pgh_mix_rows(pgh_ctx* c, const int32_t* src, int n, const int32_t* dst, int m, const double* w) {
+    if (!c) return fail(nullptr, PGH_E_ARG, "null context");
+    if (!src || !dst || !w || n < 1 || m < 1) return fail(c, PGH_E_ARG, "pgh_mix_rows: bad lists or weights (n=%d, m=%d)", n, m);
+    if (c->streaming || c->folded > 0 || c->slot_mode >= 0)
+        return fail(c, PGH_E_STATE, "pgh_mix_rows: a stream or the slot folds of a cycle are open (%lld diffs folded)", (long long)c->folded);
+    RC(check_clip_ctx(c, "pgh_mix_rows"));
+    RC(check_dtype(c, PGH_F32));
+    if (n > PGH_KRUM_MAX_ROWS || m > PGH_KRUM_MAX_ROWS)
+        return fail(c, PGH_E_UNSUPPORTED, "pgh_mix_rows: %d sources and %d destinations, at most %d each", n, m, PGH_KRUM_MAX_ROWS);
+    std::vector<char> seen((size_t)c->slots, 0);  // 1: a source, 2: a destination
+    for (int k = 0; k < n; ++k) {
+        if (src[k] < 0 || src[k] >= c->slots) return fail(c, PGH_E_ARG, "pgh_mix_rows: source slot %d outside [0,%d)", src[k], c->slots);
+        seen[(size_t)src[k]] = 1;
+    }
+    for (int i = 0; i < m; ++i) {
+        if (dst[i] < 0 || dst[i] >= c->slots || seen[(size_t)dst[i]])
+            return fail(c, PGH_E_ARG, "pgh_mix_rows: destination slot %d is outside [0,%d), listed twice or a source too", dst[i], c->slots);
+        seen[(size_t)dst[i]] = 2;
+    }
+    RC(check_slot_list(c, src, n, false));  // (a source that holds no diff: PGH_E_STATE)
+    DeviceGuard g(c->device);
+    const hipStream_t s = c->stream;
+    // behind every ingest and cached row reduction (the copy stream) and every fold that may still read a destination
+    RC(order_after_ingest(c, s));
+    for (auto* evs : {&c->fold_evs, &c->slab_evs})
+        for (auto& fe : *evs)
+            if (fe.first != s) CK(c, hipStreamWaitEvent(s, fe.second, 0));
+    RC(c->rowsums.mix(c, src, n, dst, m, w, s));
+    // a later ingest into any of these slots waits for the kernel (order_slot_overwrite), and so does whatever the
+    // copy stream runs next: a cached row reduction of a destination reads the mixed row
+    std::vector<int32_t> all(src, src + n);
+    all.insert(all.end(), dst, dst + m);
+    RC(record_slot_fold(c, all.data(), (int)all.size()));
+    CK(c, hipStreamWaitEvent(c->copy, c->slot_ring.back().second, 0));
+    // the destinations hold diffs now, as after an ingest (a diff one still held is replaced, as an ingest would:
+    // a report-time cycle's free slots may hold diffs its close left out); nothing cached is theirs
+    for (int i = 0; i < m; ++i) {
+        c->rowsums.slot_written(dst[i], 1);
+        if (c->slot_client[(size_t)dst[i]] != dst[i]) c->st.n_clients += 1;
+        c->slot_client[(size_t)dst[i]] = dst[i];
+    }
+    c->fw.stale();
+    return PGH_OK;
+}
+
+int pgh_nnm_weights_host(const double* dist, int n, int f, double* w, int32_t* n_neighbours) {
+    if (!dist || !w || !nnm_weights(dist, n, f, w))
+        return fail(nullptr, PGH_E_ARG, "pgh_nnm_weights_host: bad arguments (n=%d, f=%d) or a NaN distance", n, f);
+    if (n_neighbours) *n_neighbours = n - f;
+    return PGH_OK;
 }
 
 int pgh_krum_stats(pgh_ctx* c, int64_t* n_rows, int64_t* n_excluded, int64_t* n_picked, double* max_picked_score, double* min_dropped_score) {

@@ -15,6 +15,7 @@
 
 #include "pgh_host.h"
 #include "pgh_gram.h"
+#include "pgh_mix.h"
 #include "pgh_kernels.h"
 #include "pgh_median_mean.h"
 #include "pgh_rank_trim.h"
@@ -73,6 +74,9 @@ struct RowSums {
     // K16's (the Gram matrix), allocated by the first pgh_row_gram / pgh_krum_select_gram: the partial blocks of
     // one batch of block pairs, within the same budget; the n x n matrix.  The row table is K13's.
     DeviceBuf d_gram_part, d_gram;
+    // K19's (the row mix), allocated by the first pgh_mix_rows: the m x n weight matrix, and the source and the
+    // destination slab rows as one device table ([2][PAIRDIST_MAX_ROWS])
+    DeviceBuf d_mix_w, d_mix_rows;
     size_t pair_budget = (size_t)1 << 30;  // PGH_PAIRDIST_BUDGET (bytes) lowers it, for tests of the batching
 
     double at(int slot) const { return sq.at(slot); }       // after wait(): the sum of a slot queued before it
@@ -89,7 +93,7 @@ struct RowSums {
         for (RowCache* r : {&sq, &dot}) r->forget();
     }
     void slab_freed() {  // the streams are idle: every buffer sized by the slab goes, and the caches
-        for (auto* v : {&d_part, &d_dist, &d_pair_part, &d_pair, &d_pair_rows, &d_gram_part, &d_gram}) v->reset();
+        for (auto* v : {&d_part, &d_dist, &d_pair_part, &d_pair, &d_pair_rows, &d_gram_part, &d_gram, &d_mix_w, &d_mix_rows}) v->reset();
         h_dist.reset();
         for (RowCache* r : {&sq, &dot}) r->slab_freed();
     }
@@ -111,6 +115,9 @@ struct RowSums {
     // K16 over the listed slots (1 <= n <= PAIRDIST_MAX_ROWS) on stream s in batches of block pairs, the D2H and
     // the wait: G[a * n + b] = the inner product of slots[a] and slots[b], symmetric
     int gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* G);
+    // K19 on stream s: w ([m][n], host) and the two slot lists go to the device (complete on return: the
+    // caller's bytes are free), then the kernel is queued
+    int mix(pgh_ctx* c, const int32_t* src, int n, const int32_t* dst, int m, const double* w, hipStream_t s);
     // where the kernels of a pair list find its rows: *row0 for a contiguous run of slots, else the device table
     // d_pair_rows, uploaded on stream s (complete on return)
     int pair_rows(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, int* row0, const int32_t** d_rows);

@@ -31,7 +31,7 @@ from .engine import ITERATIVE_MEAN, MEAN, TRUSTED_MEAN, WEIGHTED_MEAN, F32, I64,
 from .exceptions import AggregationError, ModelNotAcceleratedError, PlanNotAcceleratedError, StateParseError
 from .robust import CLIP_KEY, MAM_KEY, MEDIAN_KEY, RANK_TRIM_KEY, TRIM_KEY, UNSET, check_median_drop, check_trim_count, clip_norm_of, failing_closed, median_of, \
     rule_of, trim_count_of  # noqa: F401 -- the keys and parsers are re-exported here
-from . import krum as krum_mod, robust, serveropt, trust as trust_mod
+from . import krum as krum_mod, nnm as nnm_mod, robust, serveropt, trust as trust_mod
 from .dp import DpKeys
 from .serveropt import ServerOptStates
 from .settings import settings_of
@@ -339,7 +339,7 @@ class CycleAggregator:
                            avg_plan: Optional[Callable] = None, weights=None, framing: str = "fresh",
                            plan_key=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
                            dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
-                           trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET, top_k=UNSET) -> bytes:
+                           trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET, top_k=UNSET, nnm=UNSET) -> bytes:
         """New checkpoint bytes.  ``framing="fresh"`` (default) frames them like the reference's
         ``serialize_model_params`` (model_manager.py:82-90: new placeholder / tensor ids, plain
         torch_tensor entries, no tags); ``"template"`` keeps the old checkpoint's framing byte for
@@ -357,12 +357,14 @@ class CycleAggregator:
         without one.  ``mean_around_median`` / ``bulyan``: the mean of the values nearest the median
         (``robust.mean_around_median_of``; default ``server_config["diff_mean_around_median"]``) and the Bulyan shorthand
         (``settings.bulyan_of``; default ``server_config["diff_bulyan"]``).  ``rank_trim``: the trimmed mean by rank, any
-        trim count or a trim fraction (``robust.rank_trim_of``; default ``server_config["diff_trimmed_mean"]``)."""
+        trim count or a trim fraction (``robust.rank_trim_of``; default ``server_config["diff_trimmed_mean"]``).
+        ``nnm``: nearest-neighbour mixing ahead of the rule (``nnm.nnm_of``; default ``server_config["diff_nnm"]``): the
+        engine is laid out for twice the diffs, the mixed ones taking the second half of the slots."""
         if framing not in ("fresh", "template"):
             raise AggregationError(f"unknown checkpoint framing {framing!r}")
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim, top_k)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim, top_k, nnm)
         with self._closing(server_config, given, avg_plan, weights, plan_key, lambda: _shapes_or_none(checkpoint),
                            lambda: checkpoint_numels(checkpoint), len(diffs), opt_key, dp_round, trust_root) as (settings, mode):
             return self._average_plan_diffs(checkpoint, diffs, weights, framing, settings, mode)
@@ -376,24 +378,30 @@ class CycleAggregator:
         geometric_median, krum, trust, mean_around_median, bulyan, rank_trim.  Under the trust rule the cycle's ``trust_root`` goes onto the engine here too,
         ahead of the ingests: each diff's inner product with it rides behind its copy."""
         settings = settings_of(server_config, *given[:4], geometric_median=given[4], krum=given[5], trust=given[6],
-                               mean_around_median=given[7], bulyan=given[8], rank_trim=given[9], top_k=given[10])
+                               mean_around_median=given[7], bulyan=given[8], rank_trim=given[9], top_k=given[10],
+                               nnm=given[11])
         with settings.fail_closed("the engine cannot average this cycle"):
             mode = select_mode(server_config, avg_plan, weights, plan_key=plan_key, mean_plans=self.mean_plans,
                                shapes=shapes, n_clients=n_diffs, trust=settings.trust, **settings.rule_kwargs())
             if settings.trust is not None and trust_root is None:
                 raise trust_mod.refuse("is set but the close has no trust_root: the server's own update for this cycle")
-            if settings.rule is not None and settings.rule.key == TRIM_KEY and settings.select is None:
-                check_trim_count(settings.rule.value, n_diffs)  # (under a selection: of the picked diffs, _finish_picked)
-            if settings.rule is not None and settings.rule.key == MAM_KEY and settings.select is None:
+            if settings.nnm is not None:  # refused before anything is ingested, the engine untouched
+                nnm_mod.check_mode(mode, weights)
+                nnm_mod.check_engine(self.engine)
+            staged = settings.select is not None or settings.nnm is not None  # the rule's counts: of the rows it folds, _finish_staged
+            if settings.rule is not None and settings.rule.key == TRIM_KEY and not staged:
+                check_trim_count(settings.rule.value, n_diffs)
+            if settings.rule is not None and settings.rule.key == MAM_KEY and not staged:
                 check_median_drop(settings.rule.value, n_diffs)
-            rank_trim = settings.rule is not None and settings.rule.key == RANK_TRIM_KEY and settings.select is None
+            rank_trim = settings.rule is not None and settings.rule.key == RANK_TRIM_KEY and not staged
             if rank_trim:
                 robust.rank_trim_count(settings.rule.value, n_diffs)  # (refused before anything is ingested)
             numel = numel_of()
-            self._prepare(numel, n_diffs)
+            # under the mixing stage the mixed diffs take slots of their own: n_diffs .. 2 n_diffs - 1
+            self._prepare(numel, 2 * n_diffs if settings.nnm is not None else n_diffs)
             # before the first ingest: each diff's norm pass rides behind its copy
             settings.set_on_engine(self.engine, settings.noise_key(self.dp_keys, opt_key), dp_round)
-            if rank_trim:  # N is known: the resolved b (under a selection: of the picked diffs, _finish_picked)
+            if rank_trim:  # N is known: the resolved b (under a stage: of the rows it folds, _finish_staged)
                 robust.set_rank_trim(self.engine, settings.rule.value, n_diffs)
             self.opt_states.bind(self.engine, opt_key, settings.opt, sum(numel))  # before the fold: its moments
             if settings.trust is not None:
@@ -401,10 +409,14 @@ class CycleAggregator:
             with trust_mod.closing(settings.trust):
                 yield settings, mode
 
-    def _finish_picked(self, settings, mode, n_diffs, weights):
+    def _finish_staged(self, settings, mode, n_diffs, weights):
         """Under a selection, after the ingests: the picked diffs alone are folded into the resident checkpoint,
-        in the cycle's order, in the cycle's mode."""
-        picked = krum_mod.select(self.engine, settings.select, range(n_diffs))
+        in the cycle's order, in the cycle's mode.  Under the mixing stage: the mixed diffs, which K19 wrote to the
+        slots behind the reports'."""
+        if settings.nnm is not None:
+            picked, _ = nnm_mod.mix(self.engine, settings.nnm, range(n_diffs), range(n_diffs, 2 * n_diffs))
+        else:
+            picked = krum_mod.select(self.engine, settings.select, range(n_diffs))
         if settings.rule is not None and settings.rule.key == TRIM_KEY:
             check_trim_count(settings.rule.value, len(picked))
         if settings.rule is not None and settings.rule.key == MAM_KEY:
@@ -430,8 +442,8 @@ class CycleAggregator:
         # resident copy for `checkpoint` (a retry after a failed patch would fold twice).
         self.engine.ckpt_owner = None
         self._resident = None
-        if settings.select is not None:
-            self._finish_picked(settings, mode, len(diffs), weights)
+        if settings.select is not None or settings.nnm is not None:
+            self._finish_staged(settings, mode, len(diffs), weights)
         else:
             self.engine.fedavg_resident(mode)  # :252-296
         new = (state_codec.fresh_checkpoint(self.engine, checkpoint) if framing == "fresh"  # :303
@@ -450,12 +462,12 @@ class CycleAggregator:
                        diffs: Sequence[Sequence[np.ndarray]], avg_plan: Optional[Callable] = None,
                        weights=None, clip_norm=UNSET, trim_count=UNSET, median=UNSET, opt_key=None,
                        dp_noise=UNSET, dp_round=None, geometric_median=UNSET, krum=UNSET, trust=UNSET,
-                       trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET, top_k=UNSET) -> List[np.ndarray]:
+                       trust_root=None, mean_around_median=UNSET, bulyan=UNSET, rank_trim=UNSET, top_k=UNSET, nnm=UNSET) -> List[np.ndarray]:
         if len(diffs) == 0:
             raise AggregationError("no diffs to average")
         shapes = [np.shape(p) for p in model_params]
         numel = [int(np.prod(s)) for s in shapes]
-        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim, top_k)
+        given = (clip_norm, trim_count, median, dp_noise, geometric_median, krum, trust, mean_around_median, bulyan, rank_trim, top_k, nnm)
         with self._closing(server_config, given, avg_plan, weights, None, shapes, lambda: numel, len(diffs), opt_key,
                            dp_round, trust_root) as (settings, mode):
             for i, d in enumerate(diffs):
@@ -464,9 +476,9 @@ class CycleAggregator:
                 self.engine.ingest(i, np.concatenate([np.asarray(t, np.float32).reshape(-1) for t in d]))
             flat = np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in model_params])
             self._resident = None  # the host-buffer fold overwrites the resident checkpoint
-            if settings.select is not None:  # the slot-list FINAL folds into the resident checkpoint
+            if settings.select is not None or settings.nnm is not None:  # the slot-list FINAL folds into the resident checkpoint
                 self.engine.ckpt_upload(flat)
-                self._finish_picked(settings, mode, len(diffs), weights)
+                self._finish_staged(settings, mode, len(diffs), weights)
                 out = self.engine.ckpt_download()
             else:
                 if mode == WEIGHTED_MEAN:

@@ -514,6 +514,37 @@ class Engine:
         return {"rows": n.value, "excluded": x.value, "picked": k.value, "max_picked_score": a.value,
                 "min_dropped_score": b.value}
 
+    # ---- row mixing ahead of the average: nearest-neighbour mixing (kernel K19) ------------------------
+    def mix_rows(self, src: Sequence[int], dst: Sequence[int], weights) -> None:
+        """K19 (``include/pgh_api.h``, "Row mixing"): slot ``dst[i]`` becomes ``sum_k weights[i][k] * diff of
+        src[k]``, accumulated in f64 on the matrix cores in increasing k and rounded once to f32.  ``weights``:
+        float64 ``[len(dst)][len(src)]``.  The two lists share no slot; the sources stay as they are.  Queued on
+        the engine's stream, ahead of any later fold."""
+        s, d = np.ascontiguousarray(src, dtype=np.int32), np.ascontiguousarray(dst, dtype=np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if s.ndim != 1 or d.ndim != 1 or w.shape != (d.size, s.size):
+            raise AggregationError(f"mix_rows: weights must be [{d.size}][{s.size}] (destinations x sources), not {w.shape}")
+        self._check(self._lib.pgh_mix_rows(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.size,
+                                           d.ctypes.data_as(C.POINTER(C.c_int32)), d.size,
+                                           w.ctypes.data_as(C.POINTER(C.c_double))), "mix_rows")
+
+    @staticmethod
+    def nnm_weights(dist, f: int) -> np.ndarray:
+        """The float64 ``[n][n]`` mixing matrix of nearest-neighbour mixing over the ``[n][n]`` distances ``dist``:
+        row i holds ``1 / (n - f)`` at its ``n - f`` nearest rows (ties to the earlier row) and 0 elsewhere (plain
+        C++; no GPU)."""
+        lib = _lib.load()
+        d = np.ascontiguousarray(dist, dtype=np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise AggregationError(f"nnm_weights: the distances must be [n][n], not {d.shape}")
+        w, k = np.empty_like(d), C.c_int32(0)
+        rc = lib.pgh_nnm_weights_host(d.ctypes.data_as(C.POINTER(C.c_double)), d.shape[0], int(f),
+                                      w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(k))
+        if rc != 0:
+            raise AggregationError(f"nnm_weights: {_lib.STATUS_NAMES.get(rc, rc)}: "
+                                   f"{lib.pgh_last_error(None).decode(errors='replace')}", status=rc)
+        return w
+
     # ---- coordinate-wise trimmed mean (TRIMMED_MEAN) ----------------------------------------------
     def set_trim(self, b: int):
         """Values dropped per side and parameter by later TRIMMED_MEAN folds (1 .. TRIM_MAX); 0 turns

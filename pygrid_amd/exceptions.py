@@ -103,6 +103,16 @@ class KrumUnavailableError(AggregationError):
     close fails closed."""
 
 
+class NnmUnavailableError(AggregationError):
+    """The FL process asks for nearest-neighbour mixing of its diffs (``server_config["diff_nnm"]``) and the engine
+    cannot mix this cycle: a selection, Bulyan, the trust rule, clipping, noise, the geometric median, aggregation
+    weights or the iterative plan stands beside it, the engine declines the cycle (an unaccelerated plan, a
+    non-float32 model), has no ``mix_rows`` or answers PGH_E_UNSUPPORTED (a multi-GPU group, a sub-range shard, more
+    than 1,024 diffs), the slab has fewer free slots than diffs to mix, or no more than ``2 f`` finite diffs reached
+    the close.  Like the rules' errors it is NOT a ``PlanNotAcceleratedError``: the node's own averaging mixes
+    nothing, so the close fails closed."""
+
+
 class TrustUnavailableError(AggregationError):
     """The FL process asks for trust-bootstrapped averaging (``server_config["diff_trust_root"]``) and the engine
     cannot apply it this cycle: no root provider is registered, the provider raised or returned ``None``, the

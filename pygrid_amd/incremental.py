@@ -68,7 +68,7 @@ from . import state as state_codec
 from .cycle import _decline_non_float32
 from .engine import F32, MEAN, TRUSTED_MEAN, WEIGHTED_MEAN, Engine
 from .exceptions import AggregationError, ModelNotAcceleratedError, StateParseError
-from . import dp, krum as krum_mod, serveropt, trust as trust_mod
+from . import dp, krum as krum_mod, nnm as nnm_mod, serveropt, trust as trust_mod
 from .robust import check_median_drop, check_trim_count, failing_closed, rank_trim_count, set_rank_trim
 from .settings import CloseSettings, settings_of
 
@@ -88,8 +88,15 @@ class IncrementalCycle:
                  early_fold: bool = True, clip_norm: Optional[float] = None, trim_count: Optional[int] = None,
                  median: bool = False, server_opt=None, opt_key=None, opt_states=None, dp_noise=None, dp_round=None,
                  dp_keys=None, settings: Optional[CloseSettings] = None, geometric_median=None, krum=None, trust=None,
-                 trust_root=None, mean_around_median=None, bulyan=None, rank_trim=None, top_k=None):
-        """``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
+                 trust_root=None, mean_around_median=None, bulyan=None, rank_trim=None, top_k=None, nnm=None):
+        """``nnm``: the FL process's nearest-neighbour mixing (``nnm.nnm_of``: the setting's dict or its parsed form), in
+        front of the plain mean, a trimmed mean, the median or the mean around the median; anything else beside it
+        raises ``NnmUnavailableError`` here, before the engine is touched.  Like a selection it needs every diff at once:
+        nothing folds early, and the close mixes the finite held diffs into FREE slots of the cycle -- give the cycle
+        twice as many slots as diffs -- and finishes over the mixed ones.  A close with fewer free slots than diffs to
+        mix raises ``NnmUnavailableError``; it never closes unmixed.
+
+        ``settings``: the FL process's parsed ``settings.CloseSettings``, instead of ``clip_norm``, ``trim_count``,
         ``median``, ``geometric_median``, ``server_opt``, ``dp_noise`` and ``krum`` below (both: an error); keys,
         round and stores go beside either.
 
@@ -170,7 +177,8 @@ class IncrementalCycle:
                                        trust=None if trust is False else trust,
                                        mean_around_median=None if mean_around_median is False else mean_around_median,
                                        bulyan=None if bulyan is False else bulyan,
-                                       rank_trim=None if rank_trim is False else rank_trim, top_k=top_k).items() if v is not None}
+                                       rank_trim=None if rank_trim is False else rank_trim, top_k=top_k,
+                                       nnm=None if nnm is False else nnm).items() if v is not None}
         if settings is not None and given:
             raise AggregationError(f"settings= was given beside {', '.join(given)}")
         self._settings = settings = settings if settings is not None else settings_of({}, **given)
@@ -186,10 +194,15 @@ class IncrementalCycle:
             setattr(self, rule.arg, rule.value)  # the one that is set; the rules' real differences branch on these
         # a rule that needs every row of the cycle in one call: nothing folds early, no partial fold at the close
         self._select = settings.select
+        self._nnm = settings.nnm
+        self._nnm_stats: Optional[dict] = None  # what the close's nnm.mix returned beside the slots
         self._whole = bool(self.median) or self.geometric_median is not None or self._select is not None \
             or self.mean_around_median is not None or self.rank_trim is not None \
-            or self._trust is not None
+            or self._trust is not None or self._nnm is not None
         self._fold_mode = rule.mode if rule else TRUSTED_MEAN if self._trust is not None else mode
+        if self._nnm is not None:  # refused before anything is ingested, the engine untouched
+            nnm_mod.check_mode(self._fold_mode, weights_by_worker)
+            nnm_mod.check_engine(engine)
         self._noise_args = (settings.noise_key(dp_keys if dp_keys is not None else dp.DpKeys(), opt_key), dp_round)
         self._opt_key = opt_key
         self._opt_states = opt_states if opt_states is not None else serveropt.ServerOptStates()
@@ -256,7 +269,8 @@ class IncrementalCycle:
             try:
                 engine.ckpt_upload_state(checkpoint)
             except StateParseError:
-                with krum_mod.failing_closed(self._select), trust_mod.failing_closed(self._trust), failing_closed(rule):
+                with nnm_mod.failing_closed(self._nnm), krum_mod.failing_closed(self._select), \
+                        trust_mod.failing_closed(self._trust), failing_closed(rule):
                     _decline_non_float32(checkpoint, "the checkpoint")
                 raise
             engine.ckpt_owner = self
@@ -476,7 +490,8 @@ class IncrementalCycle:
                 raise AggregationError("cycle already closed")
             self._closed = True
             if self._declined:
-                with krum_mod.failing_closed(self._select), trust_mod.failing_closed(self._trust), failing_closed(self._rule):
+                with nnm_mod.failing_closed(self._nnm), krum_mod.failing_closed(self._select), \
+                        trust_mod.failing_closed(self._trust), failing_closed(self._rule):
                     raise ModelNotAcceleratedError(self._declined)
             if order is None:
                 if self._stale or self._bad:
@@ -493,9 +508,9 @@ class IncrementalCycle:
                 raise AggregationError("no diffs to average")
             if self.trim_count is not None:
                 check_trim_count(self.trim_count, len(order))
-            if self.mean_around_median is not None and self._select is None:
+            if self.mean_around_median is not None and self._select is None and self._nnm is None:
                 check_median_drop(self.mean_around_median, len(order))
-            if self.rank_trim is not None and self._select is None:
+            if self.rank_trim is not None and self._select is None and self._nnm is None:
                 rank_trim_count(self.rank_trim, len(order))
             if self._whole and len(order) > self.slots:  # every row at once: no partial fold, no slot given up
                 raise self._whole_refuse(f"is set and the cycle has {len(order)} diffs, the slab {self.slots} slots: "
@@ -567,7 +582,7 @@ class IncrementalCycle:
             del stats["db_rows"]
             stats.update(refold=bool(refold), reason=refold or None, early=k, n=len(order),
                          folded_before_close=folded_before)
-            stats.update(self._settings.close_stats(self.engine))
+            stats.update(self._settings.close_stats(self.engine, nnm=self._nnm_stats))
             self.last_close = stats
             new = (state_codec.fresh_checkpoint(self.engine, checkpoint, prepared=prep) if framing == "fresh"
                    else self.engine.ckpt_patch_state(checkpoint))
@@ -594,19 +609,31 @@ class IncrementalCycle:
         return "a median" if self.median else "a mean around the median" if self.mean_around_median is not None else \
             "a rank-trimmed mean" if self.rank_trim is not None else \
             "a geometric median" if self.geometric_median is not None else \
-            "a trusted mean" if self._trust is not None else "a selection"
+            "a trusted mean" if self._trust is not None else "a mixing" if self._nnm is not None else "a selection"
 
     def _whole_refuse(self, why: str) -> AggregationError:
         """The refusal of whatever needs every row at once: the rule's, else the selection's."""
         whole_rule = self._rule is not None and (self.median or self.geometric_median is not None
                                                  or self.mean_around_median is not None or self.rank_trim is not None)
+        if self._nnm is not None:  # (the stage speaks before the rule behind it: what fails is the mixing)
+            return nnm_mod.refuse(why)
         if not whole_rule and self._trust is not None:
             return trust_mod.refuse(why)
         return self._rule.refuse(why) if whole_rule else krum_mod.refuse(why)
 
     def _fold(self, ws: Sequence, final: bool, slot_of: dict, free: list, dry: bool):
         slots = [slot_of.pop(w) for w in ws]
-        if not dry and self._select is not None:
+        if not dry and self._nnm is not None:
+            # (final, and every diff of the close: _whole) the finite diffs mixed into free slots, the rule over those
+            mixed, self._nnm_stats = nnm_mod.mix(self.engine, self._nnm, slots, list(reversed(free)))
+            if self.trim_count is not None:
+                check_trim_count(self.trim_count, len(mixed))
+            if self.mean_around_median is not None:
+                check_median_drop(self.mean_around_median, len(mixed))
+            if self.rank_trim is not None:
+                set_rank_trim(self.engine, self.rank_trim, len(mixed))
+            self.engine.fold_slots_finish_resident(self._fold_mode, mixed)
+        elif not dry and self._select is not None:
             # (final, and every diff of the close: _whole folds nothing early and nothing partially)
             picked = set(krum_mod.select(self.engine, self._select, slots))
             ws_picked = [w for w, s in zip(ws, slots) if s in picked]

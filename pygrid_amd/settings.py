@@ -14,13 +14,14 @@ import contextlib
 import dataclasses
 from typing import Callable, Optional
 
-from . import dp, krum as krum_mod, robust, sparsify, trust as trust_mod
+from . import dp, krum as krum_mod, nnm as nnm_mod, robust, sparsify, trust as trust_mod
 from .dp import DP_KEY, DpNoiseSpec, dp_noise_of
 from .exceptions import ClipUnavailableError, DpNoiseUnavailableError, KrumUnavailableError, \
-    MeanAroundMedianUnavailableError, PlanNotAcceleratedError, ServerOptUnavailableError, TopKUnavailableError, \
+    MeanAroundMedianUnavailableError, NnmUnavailableError, PlanNotAcceleratedError, ServerOptUnavailableError, TopKUnavailableError, \
     TrustUnavailableError
 from .sparsify import TOPK_KEY, TopKSpec, top_k_of
 from .krum import KRUM_KEY, KrumSpec, krum_of
+from .nnm import NNM_KEY, NnmSpec, nnm_of
 from .robust import CLIP_KEY, GEOMED_KEY, MAM_KEY, MEDIAN_KEY, RANK_TRIM_KEY, TRIM_KEY, UNSET, Rule, rule_of
 from .serveropt import OPT_KEY, ServerOptSpec, server_opt_of
 from .trust import TRUST_KEY, TrustSpec, trust_of
@@ -58,10 +59,11 @@ class CloseSettings:
     trust: Optional[TrustSpec] = None
     bulyan: Optional[int] = None  # f of ``diff_bulyan``: ``rule`` and ``select`` are then its two stages
     top_k: Optional[TopKSpec] = None  # a modifier behind the averaging, like the noise: not a rule
+    nnm: Optional[NnmSpec] = None  # a stage ahead of the averaging, like ``select``: the rule runs over the mixed diffs
 
     def __bool__(self) -> bool:
         return self.rule is not None or self.opt is not None or self.noise is not None or self.select is not None \
-            or self.trust is not None or self.top_k is not None
+            or self.trust is not None or self.top_k is not None or self.nnm is not None
 
     def rule_kwargs(self) -> dict:
         """The rule as the keyword argument that ``select_mode`` takes."""
@@ -75,8 +77,8 @@ class CloseSettings:
         refusal, a ``DpNoiseUnavailableError``; under a selection without a rule a ``KrumUnavailableError``; under
         an optimizer alone a ``ServerOptUnavailableError``."""
         try:
-            with krum_mod.failing_closed(self.select, what), trust_mod.failing_closed(self.trust, what), \
-                    robust.failing_closed(self.rule, what):
+            with nnm_mod.failing_closed(self.nnm, what), krum_mod.failing_closed(self.select, what), \
+                    trust_mod.failing_closed(self.trust, what), robust.failing_closed(self.rule, what):
                 yield
         except (PlanNotAcceleratedError, ClipUnavailableError) as e:
             if self.noise is not None:
@@ -101,6 +103,8 @@ class CloseSettings:
             key, error, lacks = TRUST_KEY, TrustUnavailableError, "trusts every diff"
         elif self.select is not None:
             key, error, lacks = KRUM_KEY, KrumUnavailableError, "selects nothing"
+        elif self.nnm is not None:
+            key, error, lacks = NNM_KEY, NnmUnavailableError, "mixes nothing"
         elif self.top_k is not None:
             key, error, lacks = TOPK_KEY, TopKUnavailableError, "applies the dense update"
         elif self.opt is not None:
@@ -130,9 +134,10 @@ class CloseSettings:
     def _value(self, key: str, off=None):
         return self.rule.value if self.rule is not None and self.rule.key == key else off
 
-    def close_stats(self, engine) -> dict:
+    def close_stats(self, engine, nnm: Optional[dict] = None) -> dict:
         """The rule's and the noise's entries of ``last_close``, read from the engine after the FINAL pass (it
-        was reset when the cycle took it: the clip counters are this cycle's rows only; ``noise_std`` is z C / N)."""
+        was reset when the cycle took it: the clip counters are this cycle's rows only; ``noise_std`` is z C / N).
+        ``nnm``: under the mixing stage, what this close's ``nnm.mix`` returned beside the slots."""
         cs = engine.clip_stats() if self._value(CLIP_KEY) is not None else None
         ns = engine.dp_stats() if self.noise is not None else None
         stats = {"clipped": int(cs["clipped"]) if cs else 0, "max_norm": float(cs["max_norm"]) if cs else None,
@@ -153,6 +158,8 @@ class CloseSettings:
             stats["krum"] = krum_mod.close_stats(engine, self.select)
         if self.trust is not None:  # one more key, under the trust rule alone
             stats["trust"] = trust_mod.close_stats(engine)
+        if self.nnm is not None:  # one more key, under the mixing stage alone: what this close's nnm.mix returned
+            stats["nnm"] = dict(nnm)
         if self.top_k is not None:  # three more keys, under the top-k setting alone
             stats.update(sparsify.close_stats(engine))
         return stats
@@ -162,6 +169,10 @@ class CloseSettings:
         kr = last_close.get("krum")
         picked = "" if kr is None else "; %s picked %d of them (f = %d, %d excluded, largest picked score %s)" % (
             KRUM_KEY, kr["picked"], kr["byzantine"], kr["excluded"], kr["max_picked_score"])
+        nn = last_close.get("nnm")  # (never beside a selection: the suffix is the one or the other)
+        if nn is not None:
+            picked = "; %s mixed each of them over its %d nearest first (f = %d, %d excluded)" % (
+                NNM_KEY, nn["neighbours"], nn["byzantine"], nn["excluded"])
         tr = last_close.get("trust")
         if tr is not None:
             return "cycle %s closed with %s over %d diffs (%d trusted, %d excluded, total trust %s, largest weight %s, root norm %s)%s" % (
@@ -183,7 +194,7 @@ class CloseSettings:
 
 def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=UNSET, dp_noise=UNSET,
                 server_opt=UNSET, geometric_median=UNSET, krum=UNSET, trust=UNSET, mean_around_median=UNSET,
-                bulyan=UNSET, rank_trim=UNSET, top_k=UNSET) -> CloseSettings:
+                bulyan=UNSET, rank_trim=UNSET, top_k=UNSET, nnm=UNSET) -> CloseSettings:
     """The cycle's settings.  An argument that is given overrides its ``server_config`` key (``None``: off);
     ``server_opt`` and ``dp_noise`` take the setting's dict or its parsed form.  Every setting is parsed, so a
     malformed one raises ``AggregationError`` even beside one that would speak first; two rules at once raise
@@ -192,7 +203,9 @@ def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=U
     rule (``trust``) beside any rule of ``robust.KINDS`` or beside noise ``TrustUnavailableError`` (weights and the
     iterative plan are refused where the mode is chosen, ``cycle.select_mode``).  ``diff_bulyan`` (``bulyan``) beside
     a selection, any rule, noise or the trust rule raises ``MeanAroundMedianUnavailableError``; alone it becomes the
-    mean around the median with ``drop = 2 f`` behind a selection that keeps ``n - 2 f`` diffs."""
+    mean around the median with ``drop = 2 f`` behind a selection that keeps ``n - 2 f`` diffs.  ``diff_nnm`` (``nnm``)
+    beside a selection, Bulyan, the trust rule, the clip bound, noise or the geometric median raises
+    ``NnmUnavailableError``: the row-wise rules would need per-row sums of the mixed rows."""
     rule = rule_of(server_config, clip_norm, trim_count, median, geometric_median, mean_around_median, rank_trim)
     if not isinstance(server_opt, ServerOptSpec):
         server_opt = server_opt_of(server_config if server_opt is UNSET else {OPT_KEY: server_opt})
@@ -218,4 +231,12 @@ def settings_of(server_config: dict, clip_norm=UNSET, trim_count=UNSET, median=U
     tk = top_k_of(server_config, top_k)
     if tk is not None and noise is not None:
         raise sparsify.refuse(f"cannot be combined with {DP_KEY}: the noise is calibrated to the dense clipped mean")
-    return CloseSettings(rule, server_opt, noise, select, tr, f, tk)
+    mixing = nnm_of(server_config, nnm)
+    if mixing is not None:
+        row_wise = rule if rule is not None and rule.key in (CLIP_KEY, GEOMED_KEY) else None
+        beside = [k for k, v in ((BULYAN_KEY, f), (KRUM_KEY, select), (TRUST_KEY, tr), (DP_KEY, noise),
+                                 (rule and rule.key, row_wise)) if v is not None]
+        if beside:
+            raise nnm_mod.refuse(f"cannot be combined with {beside[0]}: behind the mixing run the plain mean, the "
+                                 "trimmed means, the median and the mean around the median")
+    return CloseSettings(rule, server_opt, noise, select, tr, f, tk, mixing)
