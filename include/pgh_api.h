@@ -622,6 +622,45 @@ int pgh_gram_distances_host(const double* gram, const double* sumsq, int n, doub
 int pgh_krum_select_gram(pgh_ctx* ctx, const int32_t* slots, int n, int f, int m, int32_t* picked,
                          int* n_picked);
 
+/* ---- Split-bf16 Gram: the same matrix from bf16 products on the matrix cores (kernel K20) -----------
+ * A second opt-in kind of the selection's distances: K16's matrix at close to f32 accuracy instead of f64, from
+ * the bf16 matrix instruction, which has well over ten times the peak of the f64 one.  Enough to rank
+ * neighbours; "exact" stays the default and the "gram" kind above is unchanged.  For the listed rows
+ * d_0 .. d_{n-1} and K7's sums s_a (the bits of pgh_row_sumsq, on the device before the kernel runs):
+ *   1. Row scale.  e_a = the integer with 2^e_a <= sqrt(s_a) < 2^(e_a + 1), taken from the exponent field of
+ *      the f64 sum (the floor of half the unbiased exponent); e_a = 0 where s_a is 0 or not finite.
+ *      x_a[i] = d_a[i] * 2^-e_a in f32 (ldexp: exact except where it underflows).  Then |x_a[i]| < 2 and the
+ *      norm of x_a lies in [1, 2): a hostile row of 1e30s cannot overflow an f32 accumulator.  (Unscaled, an
+ *      overflowed G = +inf would give D = -inf, which pgh_gram_distances_host turns into +0.0: that row would
+ *      be everybody's nearest neighbour.)
+ *   2. Split.  h = x rounded to nearest-even bf16; where that rounding would turn a finite x into an infinity
+ *      (only an unscaled row can hold such a value), h is the largest finite bf16 of x's sign.  m = bf16_rn(x - h)
+ *      and l = bf16_rn((x - h) - m), both subtractions in f32 and exact.  For finite x above the underflow
+ *      range h + m + l == x: 8 + 8 + 8 significand bits.
+ *   3. Products.  x_a[i] x_b[i] is taken as the six terms hh, hm, mh, mm, hl, lh, each a bf16 x bf16 product
+ *      and exact in f32.  The dropped terms ml, lm and ll total less than 2^-25 |x_a[i] x_b[i]|.
+ *   4. Accumulation.  v_mfma_f32_32x32x16_bf16 accumulates the terms in f32 over runs of PGH_GRAM_BF16_RUN
+ *      params (per 16 params: lh, hl, mm, mh, hm, hh); each run's f32 result is added to an f64 accumulator;
+ *      the chunks of P are finished in f64 by K16's partial fold in its fixed order, giving G'[a][b], and
+ *      G[a][b] = ldexp(G'[a][b], e_a + e_b).
+ *   5. Order.  A function of (P, n, a, b) alone, as for K16: not of the slots, of a contiguous run versus the
+ *      device row table, of the batching under PGH_PAIRDIST_BUDGET or of the CU count; a repeated call gives
+ *      identical bits.  One triangle and the diagonal are computed and mirrored.
+ *   6. Padding.  Params at or past P contribute +0.0: masked before they are split and reach LDS.
+ *   7. No sanitising in the raw call: a non-finite row gives NaN entries; the selection never reads one.
+ *   8. Accuracy, first order.  With R = PGH_GRAM_BF16_RUN and S = sum_i |d_a[i]| |d_b[i]|,
+ *      |G[a][b] - <d_a, d_b>| <= ((6 R + 2) 2^-24 + P 2^-53) S: 6 R f32 additions a run, the dropped terms
+ *      and the conversion (2 2^-24 together), the f64 additions of the runs and the chunks.  The selection may
+ *      differ from the exact kind's only where two scores lie closer to each other than this bound (times the
+ *      cancellation in s_a + s_b - 2 G) allows to tell apart.
+ * pgh_row_gram_bf16: K20 alone, as pgh_row_gram.  pgh_krum_select_gram_bf16: pgh_krum_select with step 2
+ * from K20 through pgh_gram_distances_host; pgh_krum_stats reports it alike.  Both refuse what their K16 twins
+ * refuse, with the same status, use and fill K7's cache alike, and share K16's workspace and batching. */
+#define PGH_GRAM_BF16_RUN 128
+int pgh_row_gram_bf16(pgh_ctx* ctx, const int32_t* slots, int n, double* out);
+int pgh_krum_select_gram_bf16(pgh_ctx* ctx, const int32_t* slots, int n, int f, int m, int32_t* picked,
+                              int* n_picked);
+
 /* ---- Row mixing: Y = W X ahead of the average, nearest-neighbour mixing (kernel K19) -------------------
  * A stage, not an averaging mode, and a call, not a setting: it REPLACES diffs by weighted sums of diffs.
  * Nearest-neighbour mixing (Allouah et al., "Fixing by Mixing", AISTATS 2023) replaces every diff by the mean

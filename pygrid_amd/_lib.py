@@ -129,6 +129,8 @@ SIGNATURES = {
     "pgh_row_gram": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
     "pgh_gram_distances_host": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double)]),
     "pgh_krum_select_gram": (_i, [_vp, C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "pgh_row_gram_bf16": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
+    "pgh_krum_select_gram_bf16": (_i, [_vp, C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "pgh_mix_rows": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double)]),
     "pgh_nnm_weights_host": (_i, [C.POINTER(C.c_double), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "pgh_set_server_opt": (_i, [_vp, _i, C.c_float, C.c_float, C.c_float, C.c_float]),

@@ -16,11 +16,11 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpygrid_hip.so"
-SOURCES = [CSRC / "pgh_kernels.hip", CSRC / "pgh_median_mean.hip", CSRC / "pgh_rank_trim.hip", CSRC / "pgh_gram.hip", CSRC / "pgh_mix.hip", CSRC / "pgh_topk.hip", CSRC / "pgh_api.cpp", CSRC / "pgh_host.cpp", CSRC / "pgh_xfer.cpp",
+SOURCES = [CSRC / "pgh_kernels.hip", CSRC / "pgh_median_mean.hip", CSRC / "pgh_rank_trim.hip", CSRC / "pgh_gram.hip", CSRC / "pgh_gram_bf16.hip", CSRC / "pgh_mix.hip", CSRC / "pgh_topk.hip", CSRC / "pgh_api.cpp", CSRC / "pgh_host.cpp", CSRC / "pgh_xfer.cpp",
            CSRC / "pgh_order.cpp", CSRC / "pgh_ingest.cpp", CSRC / "pgh_reduce.cpp", CSRC / "pgh_rules.cpp",
            CSRC / "pgh_serveropt.cpp", CSRC / "pgh_sparsify.cpp", CSRC / "pgh_slots.cpp", CSRC / "pgh_group.cpp", CSRC / "pgh_state.cpp",
            CSRC / "pgh_b64.cpp"]
-HEADERS = [CSRC / "pgh_kernels.h", CSRC / "pgh_median_mean.h", CSRC / "pgh_rank_trim.h", CSRC / "pgh_gram.h", CSRC / "pgh_mix.h", CSRC / "pgh_topk.h", CSRC / "pgh_variants.def", CSRC / "pgh_state.h", CSRC / "pgh_internal.h", CSRC / "pgh_ctx.h",
+HEADERS = [CSRC / "pgh_kernels.h", CSRC / "pgh_median_mean.h", CSRC / "pgh_rank_trim.h", CSRC / "pgh_gram.h", CSRC / "pgh_gram_bf16.h", CSRC / "pgh_mix.h", CSRC / "pgh_topk.h", CSRC / "pgh_variants.def", CSRC / "pgh_state.h", CSRC / "pgh_internal.h", CSRC / "pgh_ctx.h",
            CSRC / "pgh_rules.h", CSRC / "pgh_xfer.h", CSRC / "pgh_res.h", CSRC / "pgh_host.h", ROOT / "include" / "pgh_api.h"]
 ARCH = os.environ.get("PGH_OFFLOAD_ARCH", "gfx950")
 # Per-source flags.  K15 derives x - m per key and bit: it is compiled without the packed fp32 instructions,

@@ -38,8 +38,42 @@ struct GramArgs {
     int nchunks;             // ceil(ntiles / chunk_tiles)
     double* part;            // [nchunks][nbp][GRAM_RB * GRAM_RB]
     double* gram;            // [n][n]
+    const double* sums;      // K20 alone: K7's sums by slab row, the row scales (gram_row_exp); null for K16
 };
 hipError_t launch_row_gram(const GramArgs& a, hipStream_t s);
+// What both Gram kernels (K16; K20, pgh_gram_bf16.hip) share: the check of a launch's arguments, and the fold of
+// the launch's partial blocks over the chunks in chunk order into both triangles of `gram`.  With a.sums the
+// folded entry is scaled by 2^(e_a + e_b) first (K20's row scales); without, it is stored as it is.
+hipError_t check_row_gram(const GramArgs& a);
+hipError_t launch_row_gram_fold(const GramArgs& a, hipStream_t s);
 bool valid_map(const SlabMap& m, int64_t p);  // the geometry a kernel may rely on (pgh_kernels.hip)
+
+#ifdef __HIP__
+// slab row of list position k (SRC 2: through the device table)
+template <int SRC>
+__device__ __forceinline__ size_t gram_row_at(const GramArgs& a, int k) {
+    if constexpr (SRC == 2) return (size_t)(uint32_t)a.d_rows[k];
+    else return (size_t)(a.row0 + k);
+}
+
+// block pair q of nblk blocks -> (A, B), A-major (uniform: a short scalar loop)
+__device__ __forceinline__ void gram_pair(int q, int nblk, int* A, int* B) {
+    int x = 0;
+    while (q >= nblk - x) {
+        q -= nblk - x;
+        ++x;
+    }
+    *A = x;
+    *B = x + q;
+}
+
+// K20's row scale: the integer e with 2^e <= sqrt(s) < 2^(e + 1) from the exponent field of the f64 sum of
+// squares s (floor of half the unbiased exponent); 0 where s is 0 or not finite.  (A sum of squares of f32 values
+// is never subnormal in f64: an exponent field of 0 is the zero.)
+__device__ __forceinline__ int gram_row_exp(double s) {
+    const int be = (int)(((uint64_t)__double_as_longlong(s) >> 52) & 0x7ffu);
+    return be == 0 || be == 0x7ff ? 0 : (be - 1023) >> 1;
+}
+#endif
 
 }  // namespace pgh

@@ -39,24 +39,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 static_assert(GRAM_RB == 128 && GRAM_KSTEP == 32 && BLOCK == 256, "K16: 4 waves of 64 x 64, 8 lanes a row, 4 rows a lane");
 static_assert(SUMSQ_TILE % GRAM_KSTEP == 0, "K16: a chunk is whole steps");
 
-// slab row of list position k
-template <int SRC>
-__device__ __forceinline__ size_t gram_row_at(const GramArgs& a, int k) {
-    if constexpr (SRC == 2) return (size_t)(uint32_t)a.d_rows[k];
-    else return (size_t)(a.row0 + k);
-}
-
-// block pair q of nblk blocks -> (A, B), A-major (uniform: a short scalar loop)
-__device__ __forceinline__ void gram_pair(int q, int nblk, int* A, int* B) {
-    int x = 0;
-    while (q >= nblk - x) {
-        q -= nblk - x;
-        ++x;
-    }
-    *A = x;
-    *B = x + q;
-}
-
 template <int SRC>
 __global__ __launch_bounds__(BLOCK) void k_row_gram(GramArgs a) {
     __shared__ __attribute__((aligned(16))) float sA[2][GRAM_RB][GRAM_LD];
@@ -200,13 +182,17 @@ __global__ __launch_bounds__(BLOCK) void k_row_gram_fold(GramArgs a) {
     const size_t stride = (size_t)a.nbp * GRAM_BLK;
     double acc = p[0];
     for (int c = 1; c < a.nchunks; ++c) acc += p[(size_t)c * stride];
+    if (a.sums) {  // K20: the entry of the scaled rows back to the rows' own scale (exact unless it overflows)
+        const size_t ra = a.d_rows ? gram_row_at<2>(a, ia) : gram_row_at<0>(a, ia), rb = a.d_rows ? gram_row_at<2>(a, ib) : gram_row_at<0>(a, ib);
+        acc = ldexp(acc, gram_row_exp(a.sums[ra]) + gram_row_exp(a.sums[rb]));
+    }
     a.gram[(size_t)ia * (size_t)a.n + (size_t)ib] = acc;
     a.gram[(size_t)ib * (size_t)a.n + (size_t)ia] = acc;
 }
 
 }  // namespace
 
-hipError_t launch_row_gram(const GramArgs& a, hipStream_t s) {
+hipError_t check_row_gram(const GramArgs& a) {
     const int64_t ntiles = (a.p + SUMSQ_TILE - 1) / SUMSQ_TILE;
     if (a.p <= 0 || a.n < 1 || a.n > PAIRDIST_MAX_ROWS || a.row0 < 0 || (a.d_rows && a.row0) || a.map.off != 0 || !valid_map(a.map, a.p) ||
         a.bp0 < 0 || a.nbp < 1 || a.bp0 + a.nbp > gram_block_pairs(a.n) || a.chunk_tiles != gram_chunk_tiles(ntiles, a.n) ||
@@ -215,10 +201,20 @@ hipError_t launch_row_gram(const GramArgs& a, hipStream_t s) {
     if (!a.slab || !a.part || !a.gram || (reinterpret_cast<uintptr_t>(a.slab) & 15)) return hipErrorInvalidValue;
     const int64_t grid = (int64_t)a.nchunks * a.nbp;
     if (grid > 0x7fffffff) return hipErrorInvalidValue;
-    if (a.d_rows) k_row_gram<2><<<(unsigned)grid, BLOCK, 0, s>>>(a);
-    else k_row_gram<0><<<(unsigned)grid, BLOCK, 0, s>>>(a);
+    return hipSuccess;
+}
+
+hipError_t launch_row_gram_fold(const GramArgs& a, hipStream_t s) {
     k_row_gram_fold<<<(unsigned)(a.nbp * (GRAM_BLK / BLOCK)), BLOCK, 0, s>>>(a);
     return hipGetLastError();
+}
+
+hipError_t launch_row_gram(const GramArgs& a, hipStream_t s) {
+    if (check_row_gram(a) != hipSuccess || a.sums) return hipErrorInvalidValue;  // (K16 scales nothing)
+    const int64_t grid = (int64_t)a.nchunks * a.nbp;
+    if (a.d_rows) k_row_gram<2><<<(unsigned)grid, BLOCK, 0, s>>>(a);
+    else k_row_gram<0><<<(unsigned)grid, BLOCK, 0, s>>>(a);
+    return launch_row_gram_fold(a, s);
 }
 
 }  // namespace pgh

@@ -460,9 +460,16 @@ int RowSums::pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, do
 
 // K16.  (Neither K7's nor K13's buffers are touched.)  The block pairs a batch takes are whole ones within the
 // budget; the chunks, and with them every entry's accumulation order, do not depend on the batching.
-int RowSums::gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* G) {
+// K20 takes the same batches of the same workspace; its row scales are K7's sums, which it reads from the cache's
+// device buffer: whatever of them is missing is computed now and waited for (the copy stream), ahead of the launch.
+int RowSums::gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* G, bool bf16) {
     const size_t nn = (size_t)n * (size_t)n;
     pgh::GramArgs a{};
+    if (bf16) {
+        RC(queue_sums(c, slots, n));
+        RC(wait(c));
+        a.sums = sq.d.as<double>();
+    }
     a.slab = c->d_slab.as<float>();
     a.map = slab_map(c);
     a.p = c->pg;
@@ -486,7 +493,7 @@ int RowSums::gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double
         // the algorithmic bytes: the batch's share of the rows once; its entries' partials out and in, the matrix out
         const uint64_t entries = (uint64_t)nn * (uint64_t)a.nbp / (uint64_t)nbp;
         const uint64_t bytes = 4ull * (uint64_t)n * (uint64_t)c->pg * (uint64_t)a.nbp / (uint64_t)nbp + entries * (16ull * (uint64_t)a.nchunks + 8ull);
-        RC(timed_launch(c, s, bytes, [&] { return pgh::launch_row_gram(a, s); }));
+        RC(timed_launch(c, s, bytes, [&] { return bf16 ? pgh::launch_row_gram_bf16(a, s) : pgh::launch_row_gram(a, s); }));
     }
     CK(c, hipMemcpyAsync(G, d_gram.as<double>(), 8 * nn, hipMemcpyDeviceToHost, s));
     CK(c, hipStreamSynchronize(s));
@@ -1032,15 +1039,21 @@ int pgh_krum_select_host(const double* dist, int n, int f, int m, int32_t* picke
     return PGH_OK;
 }
 
-int pgh_row_gram(pgh_ctx* c, const int32_t* slots, int n, double* out) {
-    RC(check_pair_list(c, "pgh_row_gram", slots, n, false));
-    if (n > 0 && !out) return fail(c, PGH_E_ARG, "pgh_row_gram: out is NULL");
+namespace {
+int row_gram_ctx(pgh_ctx* c, const char* who, bool bf16, const int32_t* slots, int n, double* out) {
+    RC(check_pair_list(c, who, slots, n, false));
+    if (n > 0 && !out) return fail(c, PGH_E_ARG, "%s: out is NULL", who);
     if (n == 0) return PGH_OK;
     DeviceGuard g(c->device);
     const hipStream_t s = c->stream;
     RC(order_after_ingest(c, s));
-    return c->rowsums.gram(c, slots, n, s, out);
+    return c->rowsums.gram(c, slots, n, s, out, bf16);
 }
+}  // namespace
+
+int pgh_row_gram(pgh_ctx* c, const int32_t* slots, int n, double* out) { return row_gram_ctx(c, "pgh_row_gram", false, slots, n, out); }
+
+int pgh_row_gram_bf16(pgh_ctx* c, const int32_t* slots, int n, double* out) { return row_gram_ctx(c, "pgh_row_gram_bf16", true, slots, n, out); }
 
 int pgh_gram_distances_host(const double* gram, const double* sumsq, int n, double* dist) {
     if (n < 0 || (n > 0 && (!gram || !sumsq || !dist))) return fail(nullptr, PGH_E_ARG, "pgh_gram_distances_host: bad arguments (n=%d)", n);
@@ -1049,8 +1062,9 @@ int pgh_gram_distances_host(const double* gram, const double* sumsq, int n, doub
 }
 
 namespace {
-// pgh_krum_select and pgh_krum_select_gram: steps 1 to 4, the distance matrix of step 2 from K13 or from K16
-int krum_select_ctx(pgh_ctx* c, const char* who, bool by_gram, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
+// pgh_krum_select and its _gram and _gram_bf16 twins: steps 1 to 4, the distance matrix of step 2 from K13
+// (by_gram 0), from K16 (1) or from K20 (2)
+int krum_select_ctx(pgh_ctx* c, const char* who, int by_gram, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
     RC(check_pair_list(c, who, slots, n, true));
     if (f < 0 || m < 0 || !picked || !n_picked) return fail(c, PGH_E_ARG, "%s: bad arguments (f=%d, m=%d)", who, f, m);
     DeviceGuard g(c->device);
@@ -1065,7 +1079,7 @@ int krum_select_ctx(pgh_ctx* c, const char* who, bool by_gram, const int32_t* sl
     std::vector<double> D((size_t)ni * (size_t)ni), sc((size_t)ni);
     if (by_gram) {
         std::vector<double> G((size_t)ni * (size_t)ni);
-        RC(c->rowsums.gram(c, inc.data(), ni, s, G.data()));
+        RC(c->rowsums.gram(c, inc.data(), ni, s, G.data(), by_gram == 2));
         gram_distances(G.data(), ss.data(), ni, D.data());
     } else {
         RC(c->rowsums.pairdist(c, inc.data(), ni, s, D.data()));
@@ -1090,11 +1104,15 @@ int krum_select_ctx(pgh_ctx* c, const char* who, bool by_gram, const int32_t* sl
 }  // namespace
 
 int pgh_krum_select(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
-    return krum_select_ctx(c, "pgh_krum_select", false, slots, n, f, m, picked, n_picked);
+    return krum_select_ctx(c, "pgh_krum_select", 0, slots, n, f, m, picked, n_picked);
 }
 
 int pgh_krum_select_gram(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
-    return krum_select_ctx(c, "pgh_krum_select_gram", true, slots, n, f, m, picked, n_picked);
+    return krum_select_ctx(c, "pgh_krum_select_gram", 1, slots, n, f, m, picked, n_picked);
+}
+
+int pgh_krum_select_gram_bf16(pgh_ctx* c, const int32_t* slots, int n, int f, int m, int32_t* picked, int* n_picked) {
+    return krum_select_ctx(c, "pgh_krum_select_gram_bf16", 2, slots, n, f, m, picked, n_picked);
 }
 
 // ---- row mixing ahead of the average: K19, the nearest-neighbour weights on the host ----------------------------

@@ -15,6 +15,7 @@
 
 #include "pgh_host.h"
 #include "pgh_gram.h"
+#include "pgh_gram_bf16.h"
 #include "pgh_mix.h"
 #include "pgh_kernels.h"
 #include "pgh_median_mean.h"
@@ -114,7 +115,9 @@ struct RowSums {
     int pairdist(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* D);
     // K16 over the listed slots (1 <= n <= PAIRDIST_MAX_ROWS) on stream s in batches of block pairs, the D2H and
     // the wait: G[a * n + b] = the inner product of slots[a] and slots[b], symmetric
-    int gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* G);
+    // With bf16, K20 instead (pgh_gram_bf16.h): the same workspace and batches; the listed slots' sums are brought
+    // into K7's cache on the device first (its row scales)
+    int gram(pgh_ctx* c, const int32_t* slots, int n, hipStream_t s, double* G, bool bf16 = false);
     // K19 on stream s: w ([m][n], host) and the two slot lists go to the device (complete on return: the
     // caller's bytes are free), then the kernel is queued
     int mix(pgh_ctx* c, const int32_t* src, int n, const int32_t* dst, int m, const double* w, hipStream_t s);

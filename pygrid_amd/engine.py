@@ -20,6 +20,7 @@ MEAN_AROUND_MEDIAN = 8  # PGH_MEAN_AROUND_MEDIAN
 RANK_TRIMMED_MEAN = 9   # PGH_RANK_TRIMMED_MEAN
 GEOMED_MAX_ITERS = 16  # PGH_GEOMED_MAX_ITERS
 KRUM_MAX_ROWS = 1024   # PGH_KRUM_MAX_ROWS
+GRAM_BF16_RUN = 128    # PGH_GRAM_BF16_RUN: params K20 accumulates in f32 before the sum joins an f64 one
 TRIM_MAX = 8  # PGH_TRIM_MAX
 MEDIAN_NCHIP = 1024  # PGH_MEDIAN_NCHIP: rows the on-chip median kernel takes
 STREAM_SECAGG = 16
@@ -450,13 +451,17 @@ class Engine:
                                                out.ctypes.data_as(C.POINTER(C.c_double))), "row_pairdist")
         return out
 
-    def row_gram(self, slots: Sequence[int]) -> np.ndarray:
-        """float64 [n][n] inner products among the diffs in ``slots``: K16 alone, on the matrix cores
-        (``include/pgh_api.h``, "Gram distances"); symmetric, within P 2^-53 sum |a_i| |b_i| of the exact value."""
+    def row_gram(self, slots: Sequence[int], kind: str = "f64") -> np.ndarray:
+        """float64 [n][n] inner products among the diffs in ``slots``, on the matrix cores; symmetric.  ``kind``
+        ``"f64"``: K16 alone (``include/pgh_api.h``, "Gram distances"), within P 2^-53 sum |a_i| |b_i| of the exact
+        value.  ``"bf16"``: K20 alone ("Split-bf16 Gram"), within ((6 GRAM_BF16_RUN + 2) 2^-24 + P 2^-53) of it."""
+        if kind not in ("f64", "bf16"):
+            raise AggregationError(f"row_gram: kind must be 'f64' or 'bf16', not {kind!r}")
+        fn = self._lib.pgh_row_gram_bf16 if kind == "bf16" else self._lib.pgh_row_gram
         a = np.ascontiguousarray(slots, dtype=np.int32)
         out = np.empty((a.size, a.size), dtype=np.float64)
-        self._check(self._lib.pgh_row_gram(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
-                                           out.ctypes.data_as(C.POINTER(C.c_double))), "row_gram")
+        self._check(fn(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, out.ctypes.data_as(C.POINTER(C.c_double))),
+                    "row_gram")
         return out
 
     @staticmethod
@@ -477,10 +482,12 @@ class Engine:
     def krum_select(self, slots: Sequence[int], f: int, m: int = 0, distances: str = "exact") -> List[int]:
         """The Multi-Krum selection (``include/pgh_api.h``) over the diffs in ``slots`` with ``f`` assumed
         hostile: the ``m`` most central slots (0: all but f of the finite ones), in the order of ``slots``.
-        ``distances``: ``"exact"`` (K13's bit-reproducible sums) or ``"gram"`` (K16: from the Gram matrix)."""
-        if distances not in ("exact", "gram"):
-            raise AggregationError(f"krum_select: distances must be 'exact' or 'gram', not {distances!r}")
-        fn = self._lib.pgh_krum_select_gram if distances == "gram" else self._lib.pgh_krum_select
+        ``distances``: ``"exact"`` (K13's bit-reproducible sums), ``"gram"`` (K16: from the f64 Gram matrix) or
+        ``"gram_bf16"`` (K20: from the split-bf16 one)."""
+        fns = {"exact": "pgh_krum_select", "gram": "pgh_krum_select_gram", "gram_bf16": "pgh_krum_select_gram_bf16"}
+        if not isinstance(distances, str) or distances not in fns:
+            raise AggregationError(f"krum_select: distances must be one of {tuple(fns)}, not {distances!r}")
+        fn = getattr(self._lib, fns[distances])
         a = np.ascontiguousarray(slots, dtype=np.int32)
         picked, n = np.empty(max(a.size, 1), dtype=np.int32), C.c_int(0)
         self._check(fn(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, int(f), int(m),

@@ -5,7 +5,8 @@ defined in ``include/pgh_api.h``, the distances are kernel K13's).
 to its ``n' - f - 2`` nearest neighbours among the ``n'`` finite diffs, the ``m`` most central ones
 (default ``n' - f``; 1 is Krum) are averaged and the others leave the cycle.  An absent key, ``None`` or
 ``False`` selects nothing.  ``"distances"``: ``"exact"`` (the default: K13, bit-reproducible) or ``"gram"`` (K16:
-``s_a + s_b - 2 <d_a, d_b>`` from the Gram matrix on the matrix cores, for large cohorts).
+``s_a + s_b - 2 <d_a, d_b>`` from the Gram matrix on the matrix cores, for large cohorts) or ``"gram_bf16"`` (K20: the
+same matrix from split-bf16 products, close to f32 accuracy, for the largest ones).
 
 A selection is a stage, not an averaging rule (``robust.rule_of`` does not know it): the cycle's mode --
 the plain, iterative, weighted, clipped or trimmed mean, the median, the geometric median, with or without
@@ -26,7 +27,7 @@ from .robust import UNSET
 
 KRUM_KEY = "diff_krum"
 _FIELDS = ("byzantine", "keep", "distances")
-DISTANCES = ("exact", "gram")
+DISTANCES = ("exact", "gram", "gram_bf16")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -35,7 +36,7 @@ class KrumSpec:
     byzantine: int
     keep: Optional[int] = None
     bulyan: bool = False  # ``settings.BULYAN_KEY``'s first stage: keep n - 2 f of n >= 4 f + 3 diffs
-    distances: str = "exact"  # "exact": K13's bit-reproducible sums; "gram": from K16's Gram matrix
+    distances: str = "exact"  # "exact": K13's bit-reproducible sums; "gram" / "gram_bf16": from K16's / K20's Gram matrix
 
 
 def distances_of(key: str, v) -> str:
@@ -59,7 +60,7 @@ def _count(name: str, v, least: int) -> int:
 def krum_of(server_config: dict, krum=UNSET) -> Optional[KrumSpec]:
     """The FL process's selection, or None.  ``krum`` given overrides the ``server_config`` key (``None``:
     off).  ``{"byzantine": f}`` (an int >= 0) is required, ``"keep"`` (an int >= 1, or None) and ``"distances"``
-    (``"exact"`` or ``"gram"``) optional.
+    (one of ``DISTANCES``) optional.
     Anything else -- another type, an unknown key, a bool where a number belongs, a float with a fraction, a
     negative count -- raises ``AggregationError``: a mistyped setting must not quietly mean "every diff"."""
     cfg = server_config.get(KRUM_KEY, None) if krum is UNSET else krum

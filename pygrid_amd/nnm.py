@@ -5,7 +5,7 @@
 mean of its ``n' - f`` nearest diffs among the ``n'`` finite ones (itself included), and the cycle's rule then runs
 over the mixed diffs exactly as if they were the only reports.  With non-iid clients the honest diffs are spread
 out and the coordinate-wise rules lose their guarantees; the mixing restores them.  An absent key, ``None`` or
-``False`` mixes nothing.  ``"distances"``: ``"exact"`` (the default: K13) or ``"gram"`` (K16), as under ``diff_krum``.
+``False`` mixes nothing.  ``"distances"``: ``"exact"`` (the default: K13), ``"gram"`` (K16) or ``"gram_bf16"`` (K20), as under ``diff_krum``.
 
 A mixing is a stage, not an averaging rule (``robust.rule_of`` does not know it).  The mixed diffs are new rows:
 they go into slots of their own, so the stage DOUBLES the slab's slot count (n diffs take 2 n slots).  Behind it run
@@ -121,8 +121,9 @@ def mix(engine, spec: NnmSpec, slots: Sequence[int], free: Sequence[int]) -> Tup
         if len(free) < n:
             raise refuse(f"is set and the slab has {len(free)} free slots for {n} mixed diffs: the stage doubles the "
                          "slot count")
-        if spec.distances == "gram":
-            dist = engine.gram_distances_host(engine.row_gram(inc), sums[np.isfinite(sums)])
+        if spec.distances != "exact":  # K16's matrix, or K20's: the kind reaches the engine by keyword
+            kind = {"kind": "bf16"} if spec.distances == "gram_bf16" else {}
+            dist = engine.gram_distances_host(engine.row_gram(inc, **kind), sums[np.isfinite(sums)])
         else:
             dist = engine.row_pairdist(inc)
         dst = [int(s) for s in free[:n]]
